@@ -14,7 +14,12 @@ with the backward), global-norm clip, fused AdamW.  W warm-up steps, then EXACTL
 pairs, max over ranks; `value` = samples of ALL ranks per second.  Synthetic data, N(0, 0.02) weights.  At N > 1 the line also
 carries `exposed_allreduce_ms` (the step timed again with the collective stubbed) and `rccl_ranks`.
 
-Named legs on the same JSON line (same inputs, each with its own warm-up and barrier-bracketed timing):
+A plain run sets up, warms up, times the headline step (the `lora` leg; `forward` with --no-train) and prints the line.  --full runs
+every leg below (core legs at N > 1), the roofline, the CPU baseline and the DP-8 wire prediction as well; --legs picks legs by name.
+--dump-outputs DIR writes what the headline step computed in its last timed step as DIR/<name>.npy: for a training step `loss` and
+`trainable_params_sample` (sample_flat: a fixed, seeded sample of the updated trainable parameters), for the forward step `logits`.
+
+Named legs on the same JSON line with --full (same inputs, each with its own warm-up and barrier-bracketed timing):
   forward        configs[1]: the inference forward (prefill) step, samples/s and fraction of the MFMA peak
   decode         greedy decode model step (tok/s, HBM roofline); generate = MetaModel.generate() END TO END (tokenise ... stop match)
   decode_fp8     configs[4] semantics on the base plugin: weight-only fp8 decode, W8A8 prefill
@@ -63,7 +68,12 @@ def parse():
     ap.add_argument("--decode-steps", type=int, default=32)
     ap.add_argument("--gen-len", type=int, default=64, help="new tokens of the end-to-end generate() leg")
     ap.add_argument("--model", default="7b", choices=["7b", "13b", "tiny"])
-    ap.add_argument("--legs", default=None, help="comma list of " + ",".join(ALL_LEGS) + " (default: all at 1 GPU, core legs at N > 1)")
+    ap.add_argument("--legs", default=None, help="comma list of " + ",".join(ALL_LEGS) + " (default: the headline leg `lora`; with --full all "
+                                                 "at 1 GPU, core legs at N > 1)")
+    ap.add_argument("--full", action="store_true", help="every leg, the roofline, the CPU baseline and the DP-8 wire prediction (without it: "
+                                                        "set up, warm up, time the headline step, print the line)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the headline step computed in its "
+                                                                        "last step as DIR/<name>.npy (float32 / float64, <= 64 MB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-train", action="store_true", help="skip the fine-tuning legs (profiling runs); the headline is then the forward step")
     ap.add_argument("--train-steps", type=int, default=None, help="(deprecated) the training legs use --steps / --warmup")
@@ -365,7 +375,45 @@ def _exposed_allreduce(one, red, sec, steps, timer):  # noqa: D401
             "bucket_bytes_on_wire": int(red.wire_bytes_last_step)}
 
 
-def train_leg(m, B, T, image, tokens, steps, warmup, timer, recompute=None):
+DUMP_MAX_BYTES = 64 * 2 ** 20        # --dump-outputs: all arrays together
+DUMP_SAMPLE = 4 * 2 ** 20            # entries of the trainable-parameter sample (16 MB of fp32)
+
+
+def sample_flat(tensors, k, seed=0):
+    """float32 host copy of k entries of the concatenation of ``tensors`` (each flattened, in order) at sorted positions drawn with
+    replacement from a generator seeded with ``seed``: the same positions for the same sizes, whatever the build.  All entries when
+    there are at most k."""
+    sizes = [t.numel() for t in tensors]
+    n = sum(sizes)
+    idx = torch.arange(n) if n <= k else torch.randint(0, n, (k,), generator=torch.Generator().manual_seed(seed)).sort().values
+    out, lo = [], 0
+    for t, s in zip(tensors, sizes):
+        a, b = torch.searchsorted(idx, torch.tensor([lo, lo + s])).tolist()
+        if b > a:
+            out.append(t.detach().reshape(-1)[(idx[a:b] - lo).to(t.device)].float().cpu())
+        lo += s
+    return torch.cat(out).numpy()
+
+
+def train_step_outputs(one, params):
+    """What a caller of the training step holds after its last call: the loss it returned and the trainable parameters it updated
+    (a fixed sample of them, see sample_flat)."""
+    import numpy as np
+    return {"loss": np.array([float(one.loss)], dtype=np.float64), "trainable_params_sample": sample_flat(params, DUMP_SAMPLE)}
+
+
+def write_outputs(arrays, path):
+    import numpy as np
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError(f"bench.py --dump-outputs: {total} bytes, more than {DUMP_MAX_BYTES}")
+    os.makedirs(path, exist_ok=True)
+    for name, v in arrays.items():
+        assert v.dtype in (np.float32, np.float64), (name, v.dtype)
+        np.save(os.path.join(path, name + ".npy"), v)
+
+
+def train_leg(m, B, T, image, tokens, steps, warmup, timer, recompute=None, dump=None):
     """Full fine-tune step on this rank's micro-batch: fp32 masters for the trainables (decoder + projector), frozen bf16 ViT,
     bf16 GEMMs, AdamW(0.9, 0.95), clip 8; with N > 1 the per-layer gradient buckets are averaged over RCCL (bf16 on the wire =
     the reference's FSDP reduce_dtype, main_finetune.py:251-255) on a side stream while earlier layers still back-propagate.
@@ -389,6 +437,8 @@ def train_leg(m, B, T, image, tokens, steps, warmup, timer, recompute=None):
     labels[:, :T // 2] = 0
     one = _train_step_fn(eng, opt, red, params, tokens, labels, image)
     sec = timer(one, steps, max(1, warmup))
+    if dump is not None:
+        dump["train"] = train_step_outputs(one, params)
     train_leg.exposed = _exposed_allreduce(one, red, sec, steps, timer)
     return sec, float(one.loss), torch.cuda.max_memory_allocated() / 2 ** 30, sum(p.numel() for p in params), bool(eng.recompute)
 
@@ -469,7 +519,7 @@ def zero1_leg(m, B, T, image, tokens, steps, warmup, timer, shard_of=8, recomput
     return out
 
 
-def lora_leg(m, args, B, T, image, tokens, steps, warmup, timer, dev, rank=16):
+def lora_leg(m, args, B, T, image, tokens, steps, warmup, timer, dev, rank=16, dump=None):
     """configs[2]: LoRA fine-tune step (rank-16 adapters on the seven decoder linears of every block + norms + projector
     trainable, base matrices frozen in bf16) on this rank's micro-batch; adapter plugin built around the SAME base parameters."""
     import dataclasses
@@ -493,6 +543,8 @@ def lora_leg(m, args, B, T, image, tokens, steps, warmup, timer, dev, rank=16):
     labels[:, :T // 2] = 0
     one = _train_step_fn(eng, opt, red, params, tokens, labels, image)
     sec = timer(one, steps, max(1, warmup))
+    if dump is not None:
+        dump["lora"] = train_step_outputs(one, params)
     lora_leg.exposed = _exposed_allreduce(one, red, sec, steps, timer)
     mem = torch.cuda.max_memory_allocated() / 2 ** 30
     loss = float(one.loss)
@@ -1490,7 +1542,8 @@ def _main_legs(a, rank, world, local, json_out):
         dist.all_gather_object(rank_devices, mine)
         check_rank_devices(rank_devices, allow_shared=os.environ.get("A3V_BENCH_ONE_DEVICE") == "1")
     timer = Timer(dist, dev)
-    legs = set((a.legs.split(",") if a.legs else (ALL_LEGS if world == 1 else CORE_LEGS)))
+    headline_only = ("forward",) if a.no_train else ("lora",)
+    legs = set((a.legs.split(",") if a.legs else (ALL_LEGS if world == 1 else CORE_LEGS) if a.full else headline_only))
     if a.model != "7b":
         legs -= {"m13b", "geometry_r", "config5"} if a.model == "13b" else {"m13b"}
     if a.no_train:
@@ -1519,8 +1572,12 @@ def _main_legs(a, rank, world, local, json_out):
             return {"error": f"{name}: {e!r}"[:400]}
 
     fwd = lambda: m.forward_inference(tokens, 0, image)  # noqa: E731
+    dumps = {} if a.dump_outputs else None       # leg -> {name: array} of its last timed step (--dump-outputs)
     if "forward" in legs:
-        sec = timer(fwd, a.steps, a.warmup)
+        last = {}
+        sec = timer((lambda: last.__setitem__("logits", fwd())) if dumps is not None else fwd, a.steps, a.warmup)
+        if dumps is not None:
+            dumps["forward"] = {"logits": last.pop("logits").float().cpu().numpy()}
         res["forward"] = {"samples_s": round(B * world / sec, 3), "ms_per_step": round(sec * 1e3, 3), "tflops": round(fl["total"] * world / sec / 1e12, 1),
                           "mfma_frac": round(fl["total"] / sec / MFMA_PEAK_BF16, 4),
                           "config": f"configs[1]: ViT-L/14@336 (577+2 image words) + Llama-2-{a.model.upper()} bf16 inference forward, bs={B}/GPU, {T}-token prompt, S={S}"}
@@ -1568,7 +1625,7 @@ def _main_legs(a, rank, world, local, json_out):
         res["recipe"] = guarded("recipe", lambda: recipe_leg(m, args, B, timer, dev))
     if "lora" in legs:
         def _lora():
-            sec, tl, mem, ntr = lora_leg(m, args, B, T, image, tokens, a.steps, a.warmup, timer, dev)
+            sec, tl, mem, ntr = lora_leg(m, args, B, T, image, tokens, a.steps, a.warmup, timer, dev, dump=dumps)
             return {"samples_s": round(B * world / sec, 3), "ms_per_step": round(sec * 1e3, 2), "seconds_per_step": sec, "loss": round(tl, 4),
                     "hbm_gib": round(mem, 1), "allreduce": lora_leg.exposed,
                     "trainable_params": ntr, "tflops": round(2 * fl["total"] * world / sec / 1e12, 1), "mfma_frac": round(2 * fl["total"] / sec / MFMA_PEAK_BF16, 4),
@@ -1586,7 +1643,7 @@ def _main_legs(a, rank, world, local, json_out):
     train = None
     if "train" in legs:
         def _train():
-            sec, tl, mem, ntr, rec = train_leg(m, B, T, image, tokens, a.steps, a.warmup, timer)
+            sec, tl, mem, ntr, rec = train_leg(m, B, T, image, tokens, a.steps, a.warmup, timer, dump=dumps)
             return {"samples_s": round(B * world / sec, 3), "ms_per_step": round(sec * 1e3, 2), "seconds_per_step": sec, "loss": round(tl, 4),
                     "hbm_gib": round(mem, 1), "allreduce": train_leg.exposed, "trainable_params": ntr,
                     "tflops": round(3 * fl["total"] * world / sec / 1e12, 1),
@@ -1601,7 +1658,7 @@ def _main_legs(a, rank, world, local, json_out):
     # ---- roofline of the headline step's dominant kernel family (rank 0)
     roof = None
     headline = "lora" if (res.get("train_lora") or {}).get("seconds_per_step") else ("train" if train and train.get("seconds_per_step") else "forward")
-    if rank == 0 and not a.no_roofline:
+    if rank == 0 and a.full and not a.no_roofline:
         def _roof():
             fam, table = time_gemm_shapes(args, B, T, W, dev, train=bool({"train", "lora"} & legs))
             # families of the headline step: LoRA = forward (NT) + input gradients, which the LoRA engine runs on the NT ring kernel over
@@ -1682,13 +1739,14 @@ def _main_legs(a, rank, world, local, json_out):
             "roofline": roof,
         }
         out.update(res)
-        try:
-            z13 = (res.get("m13b") or {}).get("train_zero1") or {}
-            lo = res.get("train_lora") or {}
-            out["wire_prediction_dp8"] = wire_prediction((lo["trainable_params"], lo["ms_per_step"]) if lo.get("trainable_params") else None,
-                                                         (z13["sharded_params"], z13["ms_per_step"]) if z13.get("sharded_params") else None)
-        except Exception as e:
-            out["wire_prediction_dp8"] = {"error": repr(e)[:200]}
+        if a.full:
+            try:
+                z13 = (res.get("m13b") or {}).get("train_zero1") or {}
+                lo = res.get("train_lora") or {}
+                out["wire_prediction_dp8"] = wire_prediction((lo["trainable_params"], lo["ms_per_step"]) if lo.get("trainable_params") else None,
+                                                             (z13["sharded_params"], z13["ms_per_step"]) if z13.get("sharded_params") else None)
+            except Exception as e:
+                out["wire_prediction_dp8"] = {"error": repr(e)[:200]}
         if "cpu" in legs:
             try:
                 out["cpu_baseline"] = cpu_baseline(args, T, W, a.cpu_seconds, dev)
@@ -1701,6 +1759,10 @@ def _main_legs(a, rank, world, local, json_out):
             write_notes(notes, npath)
         except OSError:
             pass
+        if dumps is not None:
+            if headline not in dumps:
+                raise RuntimeError(f"bench.py --dump-outputs: the headline leg `{headline}` did not run")
+            write_outputs(dumps[headline], a.dump_outputs)
         print(json.dumps(out), file=json_out, flush=True)
     if dist is not None:
         dist.barrier()

@@ -18,6 +18,24 @@ def test_defaults_finish_quickly_and_name_the_workload():
     finally:
         sys.argv = sys_argv
     assert a.gpus == 1 and a.steps <= 10 and a.warmup <= 5 and a.batch == 8 and a.prompt == 512 and a.model == "7b"
+    assert a.full is False and a.dump_outputs is None
+
+
+def test_dump_sample_is_fixed_and_takes_every_entry_of_small_outputs(tmp_path):
+    import numpy as np
+    import torch
+    ts = [torch.arange(10, dtype=torch.float32), torch.arange(100, 130, dtype=torch.bfloat16).reshape(5, 6), torch.full((7,), -1.0)]
+    flat = np.concatenate([t.float().reshape(-1).numpy() for t in ts])
+    assert np.array_equal(bench.sample_flat(ts, 1000), flat)
+    s1, s2 = bench.sample_flat(ts, 20), bench.sample_flat(ts, 20)
+    assert s1.dtype == np.float32 and s1.shape == (20,) and np.array_equal(s1, s2)
+    idx = torch.randint(0, flat.size, (20,), generator=torch.Generator().manual_seed(0)).sort().values.numpy()
+    assert np.array_equal(s1, flat[idx])
+    bench.write_outputs({"loss": np.array([1.5]), "sample": s1}, str(tmp_path / "d"))
+    assert np.array_equal(np.load(tmp_path / "d" / "sample.npy"), s1) and np.load(tmp_path / "d" / "loss.npy").dtype == np.float64
+    import pytest
+    with pytest.raises(RuntimeError):
+        bench.write_outputs({"big": np.zeros(bench.DUMP_MAX_BYTES // 4 + 1, np.float32)}, str(tmp_path / "e"))
 
 
 def test_flop_and_byte_accounting_7b():

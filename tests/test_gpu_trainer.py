@@ -109,7 +109,7 @@ def _bench_two_rank_checks(r):
 
 
 _BENCH_ARGS = ["--gpus", "2", "--model", "tiny", "--steps", "2", "--warmup", "1", "--batch", "2", "--prompt", "32", "--decode-steps", "4",
-               "--no-cpu-baseline"]
+               "--no-cpu-baseline", "--full"]
 
 
 def test_bench_gpus_2_without_a_launcher(tmp_path):
@@ -138,6 +138,42 @@ def test_bench_two_ranks_under_torchrun(tmp_path):
                         "--master-port", str(port), os.path.join(ROOT, "bench.py")] + _BENCH_ARGS,
                        cwd=ROOT, env=e, capture_output=True, text=True, timeout=900)
     _bench_two_rank_checks(r)
+
+
+def test_bench_plain_run_times_the_headline_only_and_dumps_its_outputs(tmp_path):
+    """A plain `bench.py` run (no --full) times the headline LoRA step alone: exactly --steps timed steps, the contract fields of the
+    line, no side legs.  --dump-outputs writes the last step's loss and trainable-parameter sample; identical arguments give identical
+    inputs, and the outputs agree up to the order of the fp32 atomic column sums (norm-weight gradients), which AdamW can turn into at
+    most ~lr per step on a parameter whose gradient is near zero."""
+    import numpy as np
+    e = dict(os.environ)
+    e["PYTHONPATH"] = ROOT + os.pathsep + e.get("PYTHONPATH", "")
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
+        e.pop(k, None)
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"dump{i}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--model", "tiny", "--steps", "3", "--warmup", "1",
+                            "--batch", "2", "--prompt", "32", "--dump-outputs", str(d)], cwd=ROOT, env=e, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        line = json.loads(lines[0])
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["unit"] == "samples/s" and line["higher_is_better"] is True
+        assert line["dtype"] == "bf16" and line["config"]["workload"].startswith("configs[2]")
+        assert abs(line["value"] - 2 * 1000.0 / line["ms_per_step"]) / line["value"] < 0.01
+        assert line["train_lora"]["ms_per_step"] > 0 and line["roofline"] is None
+        for leg in ("forward", "decode", "generate", "train", "cpu_baseline", "wire_prediction_dp8"):
+            assert leg not in line, leg
+        files = sorted(os.listdir(d))
+        assert files == ["loss.npy", "trainable_params_sample.npy"], files
+        arrs = {f[:-4]: np.load(d / f) for f in files}
+        assert arrs["loss"].dtype == np.float64 and arrs["loss"].shape == (1,) and np.isfinite(arrs["loss"]).all()
+        assert arrs["trainable_params_sample"].dtype == np.float32 and np.isfinite(arrs["trainable_params_sample"]).all()
+        assert abs(float(arrs["loss"][0]) - line["train_lora"]["loss"]) < 1e-3
+        dumps.append(arrs)
+    np.testing.assert_allclose(dumps[1]["loss"], dumps[0]["loss"], rtol=1e-4, atol=0)
+    np.testing.assert_allclose(dumps[1]["trainable_params_sample"], dumps[0]["trainable_params_sample"], rtol=0, atol=2 * 4 * 2e-5)
 
 
 def _torchrun(module_args, tmp_env=None, nproc=2):

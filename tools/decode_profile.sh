@@ -3,7 +3,7 @@
 root=${GRAFT_REPO_ROOT:-/root/repo}
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/prof_dec
-timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/prof_dec -o dec -- python $root/bench.py --no-cpu-baseline --no-train --steps 2 --warmup 1 > /dev/null 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/prof_dec -o dec -- python $root/bench.py --full --no-cpu-baseline --no-train --steps 2 --warmup 1 > /dev/null 2>&1
 cd $root
 python tools/rocprof_summary.py /tmp/prof_dec/dec_results.db | grep -i "gemv\|skinny\|attn_decode\|rmsnorm\|rope_kv_small\|combine\|argmax"
 python - <<PY

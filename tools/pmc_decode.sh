@@ -6,7 +6,7 @@ mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
 for c in FETCH_SIZE WRITE_SIZE; do
   rm -rf $out/$c
-  timeout 600 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $out/$c -o p -- python $root/bench.py --no-cpu-baseline --no-train --steps 1 --warmup 1 --decode-steps 8 > $out/$c.log 2>&1
+  timeout 600 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $out/$c -o p -- python $root/bench.py --full --no-cpu-baseline --no-train --steps 1 --warmup 1 --decode-steps 8 > $out/$c.log 2>&1
 done
 python - <<PY
 import csv, glob, collections

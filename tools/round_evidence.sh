@@ -9,7 +9,7 @@ out=$root/gpurun_out/$tag
 mkdir -p $out
 cd $root
 timeout 2400 python -m pytest tests -q -m gpu > $out/pytest_gpu.txt 2>&1; echo "pytest rc=$?"; grep -n "passed\|failed" $out/pytest_gpu.txt | tail -2
-timeout 1500 python bench.py > $out/bench_7b.json 2> $out/bench.err; echo "bench rc=$?"
+timeout 1500 python bench.py --full > $out/bench_7b.json 2> $out/bench.err; echo "bench rc=$?"
 cd /tmp && export TMPDIR=/tmp
 prof() {   # name, marker, skip, bench args...
   name=$1; marker=$2; skip=$3; shift 3
