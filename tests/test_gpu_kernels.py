@@ -303,8 +303,8 @@ def run_attn(q, k, v, causal, dtype, Smax=None):
     Sk, Hkv = k.shape[1], k.shape[2]
     Smax = Smax or (Sk + 63) // 64 * 64
     qd = q.to(dtype).to(DEV).contiguous()
-    kc = torch.zeros(B, Hkv, Smax, hd, dtype=dtype, device=DEV)
-    vc = torch.full((B, Hkv, hd, Smax), float("nan"), dtype=dtype, device=DEV)   # poison beyond Sk
+    kc = torch.full((B, Hkv, Smax, hd), float("nan"), dtype=dtype, device=DEV)   # poison beyond Sk (K and V^T caches are torch.empty in
+    vc = torch.full((B, Hkv, hd, Smax), float("nan"), dtype=dtype, device=DEV)   # TrainEngine: their pad rows hold arbitrary bits)
     kc[:, :, :Sk] = k.to(dtype).permute(0, 2, 1, 3).to(DEV)
     vc[:, :, :, :Sk] = v.to(dtype).permute(0, 2, 3, 1).to(DEV)
     out = torch.empty(B, Sq, H, hd, dtype=dtype, device=DEV)

@@ -174,7 +174,11 @@ def test_attention_lse_and_bwd(dtype, B, S, H, Hkv, hd, causal, mfma):
     sc = torch.matmul(q.detach().transpose(1, 2), kk.detach().transpose(-1, -2)) / math.sqrt(hd)
     if causal:
         sc = sc.masked_fill(~mask, float("-inf"))
-    assert relerr(lse, torch.logsumexp(sc, dim=-1)) < (1e-5 if dtype == torch.float32 else 2e-2)
+    want_lse = torch.logsumexp(sc, dim=-1).detach()
+    if dtype == torch.float32:
+        assert relerr(lse, want_lse) < 1e-5
+    else:       # fp32 LSE of bf16 inputs: absolute 2^-8 (one bf16 ulp of exp(lse)), not a norm over the tensor
+        assert float((lse.cpu() - want_lse).abs().max()) <= 2 ** -8
     vrows = v.detach().to(dtype).to(DEV).contiguous()      # [B,S,Hkv,hd]
     dq = torch.empty(B, S, H, hd, dtype=dtype, device=DEV)
     dk = torch.empty(B, Hkv, S, hd, dtype=dtype, device=DEV)
