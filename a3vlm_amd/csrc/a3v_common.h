@@ -225,7 +225,7 @@ __device__ __forceinline__ float ld_agent(const float* p) {          // issue + 
 constexpr int A3V_WS_ATTN_COUNTERS = 16384;
 constexpr int A3V_WS_SSQ = 32768;
 constexpr int A3V_WS_PARTIALS = 65536;
-int a3v_gemv_fused(const void* A, int64_t lda, const void* W, int64_t ldw, const float* wscale, void* C, int64_t ldc, int M, int N,
+int a3v_gemv_fused(const void* A, int64_t lda, const void* W, int64_t ldw, const float* wscale, int n4, void* C, int64_t ldc, int M, int N,
                    int K, const void* residual, int64_t ldr, int epilogue, const void* norm_w, const float* ssq_in, float eps,
                    float* ssq_out, int rope, const float* cos_sin, void* k_cache, void* vt_cache, int H, int Hkv, int hd,
                    int Smax, int pos, void* ws, void* stream);

@@ -54,18 +54,21 @@ extern "C" int a3v_llama_decode_step(const a3v_llama_layer* layers, int n_layers
                                (int64_t)Hkv * hd * Smax, (int64_t)hd * Smax, Smax,
                                (int64_t)H * hd, (int64_t)H * hd, hd};
   int rc;
-  const int w8 = layers[0].wqkv_q != nullptr;
+  // weight format: 0 = bf16, 1 = fp8 images, 2 = NF4 images (every layer the same; fp8 and NF4 fields together are an error)
+  const int w8 = layers[0].wqkv_q != nullptr ? 1 : layers[0].wqkv_n4 != nullptr ? 2 : 0;
   for (int i = 0; i < n_layers; ++i) {
     const a3v_llama_layer& L = layers[i];
     const int q8 = (L.wqkv_q != nullptr) + (L.wo_q != nullptr) + (L.w13_q != nullptr) + (L.w2_q != nullptr);
-    if (q8 != (w8 ? 4 : 0) || (w8 && (!L.wqkv_s || !L.wo_s || !L.w13_s || !L.w2_s))) return A3V_ERR_ARG;   // all four or none
+    const int n4 = (L.wqkv_n4 != nullptr) + (L.wo_n4 != nullptr) + (L.w13_n4 != nullptr) + (L.w2_n4 != nullptr);
+    if (q8 != (w8 == 1 ? 4 : 0) || (w8 == 1 && (!L.wqkv_s || !L.wo_s || !L.w13_s || !L.w2_s))) return A3V_ERR_ARG;   // all four or none
+    if (n4 != (w8 == 2 ? 4 : 0) || (w8 == 2 && (!L.wqkv_n4s || !L.wo_n4s || !L.w13_n4s || !L.w2_n4s))) return A3V_ERR_ARG;
   }
   // The GEMV kernels take up to 16 activation rows.  Batch rows are independent through the whole stack (each has its own KV
   // cache rows), so a batch of 17..32 runs as two row chunks through the same fused launches: the weights are streamed once per
   // chunk (a 32-row batch costs two 16-row steps, i.e. the 16-row tok/s), every buffer is addressed at its row offset.
   const int Bc = B > 16 ? (B + 1) / 2 : B;
   const int form = decode_step_form(B, dim, H, Hkv, hd, ffn, w8);
-  if (!form) return A3V_ERR_SHAPE;                 // fp8 images / 17..32 rows exist only in the fused form (the host takes its general path)
+  if (!form) return A3V_ERR_SHAPE;                 // fp8 / NF4 images and 17..32 rows exist only in the fused form (the host takes its general path)
   const bool fused = form == 2;
   if (fused) {
     float* ssq = (float*)((char*)skinny_ws + A3V_WS_SSQ);
@@ -81,16 +84,27 @@ extern "C" int a3v_llama_decode_step(const a3v_llama_layer* layers, int n_layers
       A3V_LAUNCH_CHECK();
       for (int i = 0; i < n_layers; ++i) {
         const a3v_llama_layer& L = layers[i];
+        const bool q4 = w8 == 2;
+        // per matrix: weight image, its row stride (elements of bf16, bytes of fp8 / NF4) and scales
+        const void* wqkv = q4 ? L.wqkv_n4 : w8 ? L.wqkv_q : L.wqkv;
+        const void* wo = q4 ? L.wo_n4 : w8 ? L.wo_q : L.wo;
+        const void* w13 = q4 ? L.w13_n4 : w8 ? L.w13_q : L.w13;
+        const void* w2 = q4 ? L.w2_n4 : w8 ? L.w2_q : L.w2;
+        const float* sqkv = q4 ? L.wqkv_n4s : L.wqkv_s;
+        const float* so = q4 ? L.wo_n4s : L.wo_s;
+        const float* s13 = q4 ? L.w13_n4s : L.w13_s;
+        const float* s2 = q4 ? L.w2_n4s : L.w2_s;
+        const int dv = q4 ? 2 : 1;
         bf16_t* kc = (bf16_t*)L.k_cache + b0 * kv_b;
         bf16_t* vc = (bf16_t*)L.vt_cache + b0 * kv_b;
-        if ((rc = a3v_gemv_fused(hc, dim, w8 ? L.wqkv_q : L.wqkv, dim, L.wqkv_s, qc, ldq, nb, (int)ldq, dim, nullptr, 0, 0, L.attn_norm_w, ssq, eps,
+        if ((rc = a3v_gemv_fused(hc, dim, wqkv, dim / dv, sqkv, q4, qc, ldq, nb, (int)ldq, dim, nullptr, 0, 0, L.attn_norm_w, ssq, eps,
                                  nullptr, 1, cos_sin, kc, vc, H, Hkv, hd, Smax, pos, skinny_ws, stream))) return rc;
         if ((rc = a3v_attention_decode_fused(qc, kc, vc, ac, nb, pos + 1, H, Hkv, hd, strides, attn_scratch, actr, stream))) return rc;
-        if ((rc = a3v_gemv_fused(ac, (int64_t)H * hd, w8 ? L.wo_q : L.wo, (int64_t)H * hd, L.wo_s, hc, dim, nb, dim, H * hd, hc, dim, A3V_EPI_RESIDUAL,
+        if ((rc = a3v_gemv_fused(ac, (int64_t)H * hd, wo, (int64_t)H * hd / dv, so, q4, hc, dim, nb, dim, H * hd, hc, dim, A3V_EPI_RESIDUAL,
                                  nullptr, nullptr, eps, ssq, 0, nullptr, nullptr, nullptr, H, Hkv, hd, Smax, pos, skinny_ws, stream))) return rc;
-        if ((rc = a3v_gemv_fused(hc, dim, w8 ? L.w13_q : L.w13, dim, L.w13_s, fc, ffn, nb, 2 * ffn, dim, nullptr, 0, A3V_EPI_SWIGLU, L.ffn_norm_w, ssq,
+        if ((rc = a3v_gemv_fused(hc, dim, w13, dim / dv, s13, q4, fc, ffn, nb, 2 * ffn, dim, nullptr, 0, A3V_EPI_SWIGLU, L.ffn_norm_w, ssq,
                                  eps, nullptr, 0, nullptr, nullptr, nullptr, H, Hkv, hd, Smax, pos, skinny_ws, stream))) return rc;
-        if ((rc = a3v_gemv_fused(fc, ffn, w8 ? L.w2_q : L.w2, ffn, L.w2_s, hc, dim, nb, dim, ffn, hc, dim, A3V_EPI_RESIDUAL, nullptr, nullptr, eps, ssq,
+        if ((rc = a3v_gemv_fused(fc, ffn, w2, ffn / dv, s2, q4, hc, dim, nb, dim, ffn, hc, dim, A3V_EPI_RESIDUAL, nullptr, nullptr, eps, ssq,
                                  0, nullptr, nullptr, nullptr, H, Hkv, hd, Smax, pos, skinny_ws, stream))) return rc;
       }
     }

@@ -2658,9 +2658,10 @@ struct GemvArgs {
   const float* cos_sin;     // GEMV_EPI_ROPEKV: fp32 [pos][hd/2][2]
   bf16_t* k_cache;          //   [M, Hkv, Smax, hd]
   bf16_t* vt_cache;         //   [M, Hkv, hd, Smax]
-  const float* wscale;      // W8: per-row dequantisation scales (W rows are fp8 e4m3fn bytes, ldw in BYTES)
+  const float* wscale;      // W8: per-row dequantisation scales (W rows are fp8 e4m3fn bytes, ldw in BYTES); N4: [N, K/64] block scales
   float eps;
   int ssq_tiles, H, Hkv, hd, Smax, pos;
+  int n4;                   // N4: W rows are NF4 nibbles (a3v_quantize_nf4 image, ldw in BYTES)
 };
 
 constexpr int GEMV_EPI_ROPEKV = 1 << 24;
@@ -2736,10 +2737,47 @@ __device__ __forceinline__ void gemv_finish(const GemvArgs& p, f32x4 v, f32x4 u,
   }
 }
 
+// Eight NF4 codes (one dword: byte j holds elements 2j (high nibble) and 2j+1 (low nibble)) -> their code-book values as bf16x8.
+// v_perm_b32 picks bytes out of 8-byte tables: the high and the low bytes of the bf16 code book, entries 0..7 and 8..15 apart
+// (bf16 bits: bf80 bf32 bf06 beca be92 be3d bdba 0000 3da3 3e25 3e7c 3ead 3ee2 3f10 3f39 3f80); bit 3 of a code selects the
+// half by a byte mask.  29 VALU operations per 8 weights.
+__device__ __forceinline__ bf16x8 nf4_bf16x8(uint32_t x) {
+#ifdef A3V_NF4_LOOKUP_AB
+  // timing build only (wrong results): the code dword itself as the MFMA operand, no lookup -- separates the lookup's cost from
+  // the weight stream's (A3V_LIB_PATH + tools/nf4_decode_bench.py --skip-model)
+  return __builtin_bit_cast(bf16x8, u32x4{x, x ^ 0x01010101u, x ^ 0x02020202u, x ^ 0x03030303u} & 0x3f7f3f7fu);
+#endif
+  const uint32_t io = x & 0x07070707u, ie = (x >> 4) & 0x07070707u;           // odd / even elements, low 3 bits
+  const uint32_t mo = ((x >> 3) & 0x01010101u) * 0xFFu, me = ((x >> 7) & 0x01010101u) * 0xFFu;   // bit 3 -> byte masks
+  auto look = [](uint32_t i, uint32_t m, uint32_t t0a, uint32_t t0b, uint32_t t1a, uint32_t t1b) {
+    return (__builtin_amdgcn_perm(t1b, t1a, i) & m) | (__builtin_amdgcn_perm(t0b, t0a, i) & ~m);
+  };
+  const uint32_t he = look(ie, me, 0xbebfbfbfu, 0x00bdbebeu, 0x3e3e3e3du, 0x3f3f3f3eu);
+  const uint32_t le = look(ie, me, 0xca063280u, 0x00ba3d92u, 0xad7c25a3u, 0x803910e2u);
+  const uint32_t ho = look(io, mo, 0xbebfbfbfu, 0x00bdbebeu, 0x3e3e3e3du, 0x3f3f3f3eu);
+  const uint32_t lo = look(io, mo, 0xca063280u, 0x00ba3d92u, 0xad7c25a3u, 0x803910e2u);
+  const uint32_t e01 = __builtin_amdgcn_perm(he, le, 0x05010400u), e23 = __builtin_amdgcn_perm(he, le, 0x07030602u);   // elements 0,2 | 4,6
+  const uint32_t o01 = __builtin_amdgcn_perm(ho, lo, 0x05010400u), o23 = __builtin_amdgcn_perm(ho, lo, 0x07030602u);   // elements 1,3 | 5,7
+  u32x4 r;
+  r[0] = __builtin_amdgcn_perm(o01, e01, 0x05040100u);
+  r[1] = __builtin_amdgcn_perm(o01, e01, 0x07060302u);
+  r[2] = __builtin_amdgcn_perm(o23, e23, 0x05040100u);
+  r[3] = __builtin_amdgcn_perm(o23, e23, 0x07060302u);
+  return __builtin_bit_cast(bf16x8, r);
+}
+
 // W8: the weight rows are OCP fp8 e4m3fn (weight-only quantisation, one fp32 scale per row applied to the summed
 // accumulator).  A ring stage is still 16 rows x 256 B, i.e. 256 k instead of 128; fragments are read 8 B per lane and
 // widened fp8 -> f32 -> bf16 in registers (exact), so the arithmetic is the bf16 MFMA on dequantised weights.
-template <int AROWS, bool PRO, bool W8, int WAUX = 0>   // WAUX: cache-policy bits of the weight-stream LDS-DMA (2 = nt: streamed once)
+//
+// N4: the weight rows are NF4 nibbles (a3v_quantize_nf4: two codes per byte, earlier element high, one fp32 scale per 64-k block).
+// A ring stage is 16 rows x 128 B of nibbles (256 k, so K % 256 == 0 as for W8) plus the 16 rows x 16 B of the stage's four block
+// scales (2 x 16-B + 1 x 4-B LDS-DMA instructions, 2304 B); a stage holds half the bytes of a bf16 / fp8 stage, so the wave's ring
+// has THREE slots of 2304 B in the same 8 KiB (two stages in flight behind the one being consumed instead of one).  The codes are looked up as bf16 by v_perm_b32 from byte tables held in
+// registers (nf4_bf16x8), each 64-k block is accumulated by its own two MFMAs and its scale is applied once per accumulator element:
+// acc += s_b * (codes . a).  Rounding differs from the bf16 GEMV on Wd = bf16(NF4[q] * s_b): the codes are rounded to bf16 and the
+// scale is applied in fp32 to the block sums.
+template <int AROWS, bool PRO, bool W8, int WAUX = 0, bool N4 = false>   // WAUX: cache-policy bits of the weight-stream LDS-DMA (2 = nt: streamed once)
 __global__ __launch_bounds__(256) void gemv_dma_bf16_kernel(GemvArgs p) {
   extern __shared__ __attribute__((aligned(1024))) char gemv_lds[];
   __shared__ float rinv_s[16];
@@ -2749,7 +2787,10 @@ __global__ __launch_bounds__(256) void gemv_dma_bf16_kernel(GemvArgs p) {
   const int sl = xq % p.S;
   const int tg = (xq / p.S) * 8 + (blockIdx.x & 7);
   if (tg >= p.tgs) return;
-  constexpr int APB = W8 ? 2 : 1;                      // 128-k blocks of A per ring stage of W
+  constexpr int APB = (W8 || N4) ? 2 : 1;              // 128-k blocks of A per ring stage of W
+  constexpr int DPS = N4 ? 3 : 4;                      // LDS-DMA instructions per ring stage
+  constexpr int NSL = N4 ? 3 : 2;                      // ring slots per wave
+  constexpr int SSTR = N4 ? 2304 : 4096;               // bytes per ring slot
   const int nst_all = p.nkb / APB;
   const int st0 = (int)(((int64_t)sl * nst_all) / p.S), st1 = (int)(((int64_t)(sl + 1) * nst_all) / p.S);
   const int nst = st1 - st0;                           // ring stages of this slice
@@ -2770,19 +2811,43 @@ __global__ __launch_bounds__(256) void gemv_dma_bf16_kernel(GemvArgs p) {
                                        (__attribute__((address_space(3))) void*)(Alds + kb * ABLK + i * 1024), 16, 0, 0);
     }
   }
-  const char* wrow[4];                                 // a stage row is 256 B in both weight formats
+  const char* wrow[4];                                 // a stage row is 256 B in the bf16 and fp8 formats
+  if constexpr (N4) {
+    // nibbles: instruction i covers rows 8 i + (lane >> 3), 16-B slot lane & 7 of a 128-B stage row (chunk slot ^ row);
+    // scales: one 4-B piece per lane, scale (lane & 3) of the stage's four of row lane >> 2 (16 rows x 16 B = 256 B)
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int row = 4 * i + dr;
-    int wr = n0 + row;
-    wr = wr < p.N ? wr : p.N - 1;
-    wrow[i] = reinterpret_cast<const char*>(p.W) + (int64_t)wr * p.ldw * (W8 ? 1 : 2) + (int64_t)st0 * 256 + ((dslot ^ row) & 15) * 16;
+    for (int i = 0; i < 2; ++i) {
+      const int row = 8 * i + (lane >> 3);
+      int wr = n0 + row;
+      wr = wr < p.N ? wr : p.N - 1;
+      wrow[i] = reinterpret_cast<const char*>(p.W) + (int64_t)wr * p.ldw + (int64_t)st0 * 128 + (((lane & 7) ^ row) & 7) * 16;
+    }
+    int sr = n0 + (lane >> 2);
+    sr = sr < p.N ? sr : p.N - 1;
+    wrow[2] = reinterpret_cast<const char*>(p.wscale + (int64_t)sr * (p.K / 64) + (int64_t)st0 * 4 + (lane & 3));
+  } else {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int row = 4 * i + dr;
+      int wr = n0 + row;
+      wr = wr < p.N ? wr : p.N - 1;
+      wrow[i] = reinterpret_cast<const char*>(p.W) + (int64_t)wr * p.ldw * (W8 ? 1 : 2) + (int64_t)st0 * 256 + ((dslot ^ row) & 15) * 16;
+    }
   }
   auto dma_stage = [&](int st, int slot) {
+    if constexpr (N4) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(wrow[i] + st * 256),
-                                       (__attribute__((address_space(3))) void*)(Wring + slot * 4096 + i * 1024), 16, 0, WAUX);
+      for (int i = 0; i < 2; ++i)
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(wrow[i] + st * 128),
+                                         (__attribute__((address_space(3))) void*)(Wring + slot * SSTR + i * 1024), 16, 0, WAUX);
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(wrow[2] + st * 16),
+                                       (__attribute__((address_space(3))) void*)(Wring + slot * SSTR + 2048), 4, 0, WAUX);
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(wrow[i] + st * 256),
+                                         (__attribute__((address_space(3))) void*)(Wring + slot * 4096 + i * 1024), 16, 0, WAUX);
+    }
   };
   if (PRO) {
     // RMSNorm of the block's K slice of A (model/components.py:39,52-53 rounding: fp32 x*rinv -> bf16 -> * weight -> bf16),
@@ -2833,6 +2898,9 @@ __global__ __launch_bounds__(256) void gemv_dma_bf16_kernel(GemvArgs p) {
     issue(0);
     dma_stage(0, 0);
     if (nst > 1) dma_stage(1, 1);
+    if constexpr (NSL > 2) {
+      if (nst > 2) dma_stage(2, 2);
+    }
 #pragma unroll
     for (int q = 0; q < NQ; ++q)
 #pragma unroll
@@ -2849,13 +2917,25 @@ __global__ __launch_bounds__(256) void gemv_dma_bf16_kernel(GemvArgs p) {
       issue(base);
       finish(base);
     }
+  } else if constexpr (NSL > 2) {
+    dma_stage(0, 0);
+    if (nst > 2) {
+      dma_stage(1, 1);
+      dma_stage(2, 2);
+      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * DPS) : "memory");   // in-order completion: the A pieces issued before the ring prologue
+    } else if (nst > 1) {
+      dma_stage(1, 1);
+      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * DPS) : "memory");
+    } else {
+      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(DPS) : "memory");
+    }
   } else {
     dma_stage(0, 0);
     if (nst > 1) {
       dma_stage(1, 1);
-      asm volatile("s_waitcnt vmcnt(8)" ::: "memory");   // in-order completion: the A pieces issued before the ring prologue
+      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * DPS) : "memory");   // in-order completion: the A pieces issued before the ring prologue
     } else {
-      asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(DPS) : "memory");
     }
   }
   __syncthreads();
@@ -2873,11 +2953,46 @@ __global__ __launch_bounds__(256) void gemv_dma_bf16_kernel(GemvArgs p) {
   // data will do) and the 16 lanes of a group cover 16 distinct slots.
   for (int s4 = 0; s4 < 4; ++s4) aoff[s4] = (((4 * s4 + fg) ^ fr) & 15) * 16;
   for (int st = 0; st < nst; ++st) {
-    const int slot = st & 1;
-    if (st + 2 <= nst) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const int slot = NSL > 2 ? st % NSL : st & 1;
+    if constexpr (NSL > 2) {                            // stage st landed; up to two later stages may still be in flight
+      if (st + 3 <= nst) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * DPS) : "memory");
+      else if (st + 2 <= nst) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(DPS) : "memory");
+      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    } else {
+      if (st + 2 <= nst) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(DPS) : "memory");
+      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
     const char* Ws = Wring + slot * 4096 + fr * 256;
-    if (!W8) {
+    if constexpr (N4) {
+      // 8 MFMA steps per stage, two per 64-k block: step s covers k = 32 s .. 32 s + 31; the lane's 8 codes are dword fg of
+      // 16-B chunk s of its row.  Block scales of rows 4 (lane >> 4) + r: 16 B per row at +2048 of the slot.
+      const char* Wn = Wring + slot * SSTR + fr * 128;
+      const char* Sc = Wring + slot * SSTR + 2048 + (lane >> 4) * 64;
+      uint32_t wq[8];
+      bf16x8 af[8];
+      f32x4 sc[4];
+#pragma unroll
+      for (int s8 = 0; s8 < 8; ++s8) {
+        wq[s8] = *reinterpret_cast<const uint32_t*>(Wn + ((s8 ^ fr) & 7) * 16 + fg * 4);
+        af[s8] = *reinterpret_cast<const bf16x8*>(Alds + (st * 2 + (s8 >> 2)) * ABLK + arow * 256 + aoff[s8 & 3]);
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) sc[r] = *reinterpret_cast<const f32x4*>(Sc + r * 16);
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      if (st + NSL < nst) dma_stage(st + NSL, slot);
+#pragma unroll
+      for (int b = 0; b < 4; ++b) {
+        f32x4 t = __builtin_amdgcn_mfma_f32_16x16x32_bf16(nf4_bf16x8(wq[2 * b]), af[2 * b], f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+        t = __builtin_amdgcn_mfma_f32_16x16x32_bf16(nf4_bf16x8(wq[2 * b + 1]), af[2 * b + 1], t, 0, 0, 0);
+        if (b & 1) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) acc1[r] = fmaf(t[r], sc[r][b], acc1[r]);
+        } else {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) acc0[r] = fmaf(t[r], sc[r][b], acc0[r]);
+        }
+      }
+    } else if (!W8) {
       const char* As = Alds + st * ABLK + arow * 256;
       bf16x8 wf[4], af[4];
 #pragma unroll
@@ -3736,10 +3851,15 @@ static bool gemv_launch(GemvArgs& g, void* ws, hipStream_t st) {
                     : (pro ? gemv_dma_bf16_kernel<16, true, true, AUX> : gemv_dma_bf16_kernel<16, false, true, AUX>))       \
       : (arows == 8 ? (pro ? gemv_dma_bf16_kernel<8, true, false, AUX> : gemv_dma_bf16_kernel<8, false, false, AUX>)        \
                     : (pro ? gemv_dma_bf16_kernel<16, true, false, AUX> : gemv_dma_bf16_kernel<16, false, false, AUX>)))
-  kern = nt ? GEMV_PICK(2) : GEMV_PICK(0);
+#define GEMV_PICK_N4(AUX)                                                                                                   \
+  (arows == 8 ? (pro ? gemv_dma_bf16_kernel<8, true, false, AUX, true> : gemv_dma_bf16_kernel<8, false, false, AUX, true>)    \
+              : (pro ? gemv_dma_bf16_kernel<16, true, false, AUX, true> : gemv_dma_bf16_kernel<16, false, false, AUX, true>))
+  if (g.n4) kern = nt ? GEMV_PICK_N4(2) : GEMV_PICK_N4(0);
+  else kern = nt ? GEMV_PICK(2) : GEMV_PICK(0);
 #undef GEMV_PICK
-  static bool attr_done[A3V_MAX_DEV][16] = {};
-  const int ki = (nt ? 8 : 0) + (w8 ? 4 : 0) + (arows == 16 ? 2 : 0) + (pro ? 1 : 0);
+#undef GEMV_PICK_N4
+  static bool attr_done[A3V_MAX_DEV][32] = {};
+  const int ki = (g.n4 ? 16 : 0) + (nt ? 8 : 0) + (w8 ? 4 : 0) + (arows == 16 ? 2 : 0) + (pro ? 1 : 0);
   if (a3v_dyn_lds_once(attr_done, ki, (const void*)kern, 150 * 1024) != 0) return false;
   hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), ldsb, st, g);
   return true;
@@ -3789,17 +3909,18 @@ extern "C" int a3v_gemm_skinny(const void* A, int64_t lda, const void* W, int64_
 //   norm_w != NULL : A is the un-normalised residual rows h; RMSNorm(h) is applied while the A slice is staged (ssq_in)
 //   rope != 0      : [q|k|v] rows get RoPE and go to C (q) / the KV cache at `pos` (no separate rope kernel)
 //   ssq_out != NULL: with a residual epilogue, also emit the per-tile sums of squares of the new rows
-int a3v_gemv_fused(const void* A, int64_t lda, const void* W, int64_t ldw, const float* wscale, void* C, int64_t ldc, int M, int N,
+int a3v_gemv_fused(const void* A, int64_t lda, const void* W, int64_t ldw, const float* wscale, int n4, void* C, int64_t ldc, int M, int N,
                    int K, const void* residual, int64_t ldr, int epilogue, const void* norm_w, const float* ssq_in, float eps,
                    float* ssq_out, int rope, const float* cos_sin, void* k_cache, void* vt_cache, int H, int Hkv, int hd,
                    int Smax, int pos, void* ws, void* stream) {
   if (M <= 0 || M > 16 || K % 128 || N % 16 || N > 65536 || !ws) return A3V_ERR_SHAPE;
+  if (n4 && (!wscale || K % 256)) return A3V_ERR_ARG;
   GemvArgs g{};
   g.A = (const bf16_t*)A; g.W = (const bf16_t*)W; g.C = C; g.res = residual;
   g.lda = lda; g.ldw = ldw; g.ldc = ldc; g.ldr = ldr;
   g.M = M; g.N = N; g.K = K;
   g.epi = epilogue | (rope ? GEMV_EPI_ROPEKV : 0) | (ssq_out ? GEMV_EPI_SSQ : 0);
-  g.wscale = wscale;
+  g.wscale = wscale; g.n4 = n4 != 0;
   g.norm_w = (const bf16_t*)norm_w; g.ssq_in = ssq_in; g.eps = eps; g.ssq_tiles = K / 16; g.ssq_out = ssq_out;
   g.cos_sin = cos_sin; g.k_cache = (bf16_t*)k_cache; g.vt_cache = (bf16_t*)vt_cache;
   g.H = H; g.Hkv = Hkv; g.hd = hd; g.Smax = Smax; g.pos = pos;
@@ -3822,6 +3943,26 @@ extern "C" int a3v_gemm_skinny_fp8(const void* A, int64_t lda, const void* Wq, i
   if ((epilogue & A3V_EPI_RESIDUAL) && (!residual || (ldr % 4))) return A3V_ERR_ARG;
   GemvArgs g{};
   g.A = (const bf16_t*)A; g.W = (const bf16_t*)Wq; g.C = C; g.res = residual; g.wscale = wscale;
+  g.lda = lda; g.ldw = ldw; g.ldc = ldc; g.ldr = ldr;
+  g.M = M; g.N = N; g.K = K; g.epi = epilogue;
+  if (!gemv_launch(g, workspace, (hipStream_t)stream)) return A3V_ERR_SHAPE;
+  A3V_LAUNCH_CHECK();
+  return A3V_OK;
+}
+
+// Weight-only NF4 form of a3v_gemm_skinny (the decode GEMV of the reference's 4-bit mode, util/quant.py:95-163): Wq [N, K/2] nibbles
+// (row stride ldw BYTES), scales [N, K/64] fp32 (contiguous rows) as a3v_quantize_nf4 writes them; C = epilogue(sum over 64-k blocks of
+// s_b * (A . NF4[q])^T).  K % 256 == 0.
+extern "C" int a3v_gemm_skinny_nf4(const void* A, int64_t lda, const void* Wq, int64_t ldw, const float* scales, void* C, int64_t ldc,
+                                   int M, int N, int K, const void* residual, int64_t ldr, int epilogue, void* workspace, void* stream) {
+  if (M <= 0 || M > 16 || N <= 0 || K <= 0 || !A || !Wq || !scales || !C || !workspace) return A3V_ERR_ARG;
+  if (K % 256 || lda % 8 || ldw % 16 || ldw < K / 2 || N % 4 || ldc % 4) return A3V_ERR_SHAPE;
+  if (((reinterpret_cast<uintptr_t>(Wq) | reinterpret_cast<uintptr_t>(scales) | reinterpret_cast<uintptr_t>(A)) & 15)) return A3V_ERR_SHAPE;
+  if ((epilogue & A3V_EPI_SWIGLU) && (N % 32)) return A3V_ERR_SHAPE;
+  if (epilogue & ~(A3V_EPI_RESIDUAL | A3V_EPI_SWIGLU | A3V_EPI_OUT_F32)) return A3V_ERR_ARG;
+  if ((epilogue & A3V_EPI_RESIDUAL) && (!residual || (ldr % 4))) return A3V_ERR_ARG;
+  GemvArgs g{};
+  g.A = (const bf16_t*)A; g.W = (const bf16_t*)Wq; g.C = C; g.res = residual; g.wscale = scales; g.n4 = 1;
   g.lda = lda; g.ldw = ldw; g.ldc = ldc; g.ldr = ldr;
   g.M = M; g.N = N; g.K = K; g.epi = epilogue;
   if (!gemv_launch(g, workspace, (hipStream_t)stream)) return A3V_ERR_SHAPE;

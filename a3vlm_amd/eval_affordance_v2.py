@@ -153,6 +153,8 @@ def main(args):
     torch.set_default_dtype(old)
     if args.pretrained_path:
         print(f"load pretrained from {args.pretrained_path}:", load_tensor_parallel_model_list(model, args.pretrained_path))
+    if getattr(args, "quant", False):     # eval_affordance_with_quant.py --quant: NF4 decoder linears + LM head (bf16 weights freed)
+        model.llma.quantize_decode_weights("nf4")
     model.eval()
 
     name = os.path.basename(args.dataset).split(".")[0]

@@ -283,6 +283,8 @@ class Transformer(nn.Module):
         pk: Dict[str, torch.Tensor] = {}
         with torch.no_grad():
             for i, lyr in enumerate(self.layers):
+                if getattr(self, "_n4", None) is not None:
+                    break                  # NF4 model: the decoder weights live only as NF4 images (self._n4)
                 a, f = lyr.attention, lyr.feed_forward
                 pk[f"wqkv.{i}"] = torch.cat([a.wq.weight, a.wk.weight, a.wv.weight], dim=0).to(dtp).contiguous()
                 w1, w3 = f.w1.weight, f.w3.weight
@@ -359,6 +361,10 @@ class Transformer(nn.Module):
         return ws
 
     def _linear(self, x, w, out, **kw):
+        if isinstance(w, tuple):           # NF4 image (nibbles, block scales): weight-only NF4 GEMV, <= 16 rows
+            q, sc = w
+            return ops.gemm_skinny_nf4(x, q, sc, out, self._skinny_ws(x.shape[0], q.shape[0], x.shape[1]), residual=kw.get("residual"),
+                                       epilogue=kw.get("epilogue", 0))
         if x.shape[0] <= 16 and x.dtype == torch.bfloat16 and "bias" not in kw and w.shape[1] % 32 == 0:
             ep = kw.get("epilogue", 0)
             return ops.gemm_skinny(x, w, out, self._skinny_ws(x.shape[0], w.shape[0], w.shape[1]), residual=kw.get("residual"), epilogue=ep)
@@ -385,6 +391,7 @@ class Transformer(nn.Module):
         q8 = getattr(self, "_q8", None)
         w8a8 = (q8 is not None and getattr(self, "_fp8_prefill", False) and rows > 16 and h.dtype == torch.bfloat16
                 and hd in (64, 128))
+        n4 = getattr(self, "_n4", None)
         if w8a8:
             if q8[0] != self._packed_version:
                 raise RuntimeError("parameters changed after quantize_decode_weights(): call it again (or with mode=None)")
@@ -412,24 +419,45 @@ class Transformer(nn.Module):
                 ops.quantize_rows_fp8(act, aq, sx)
                 ops.gemm_nt_fp8(aq, sx, w2_q, w2_s, h, residual=h)
                 continue
+            if n4 is None:
+                wqkv, wo, w13, w2 = pk[f"wqkv.{i}"], lyr.attention.wo.weight, pk[f"w13.{i}"], lyr.feed_forward.w2.weight
+            elif rows <= 16 and a.dim >= 512:   # NF4 decode GEMV on the images (its SwiGLU form needs K = dim >= 512: two K slices)
+                wqkv, wo, w13, w2 = (n4[f"{k}.{i}"] for k in ("wqkv", "wo", "w13", "w2"))
+            else:                          # multi-token: the layer's Wd in a reused bf16 scratch, then the bf16 GEMMs unchanged
+                wqkv, wo, w13, w2 = self._nf4_dequant_layer(i)
             ops.rmsnorm(h, lyr.attention_norm.weight, xn, a.norm_eps)
             if rows > 16 and h.dtype == torch.bfloat16 and hd in (64, 128) and self._fuse_qkv_rope:
                 # rotary embedding + cache write in the GEMM epilogue: qkv never makes a second trip through HBM
-                ops.gemm_qkv_rope(xn, pk[f"wqkv.{i}"], qkv, kc, vc, cs, B, S, H, Hkv, hd, start_pos, rope_pos0)
+                ops.gemm_qkv_rope(xn, wqkv, qkv, kc, vc, cs, B, S, H, Hkv, hd, start_pos, rope_pos0)
             else:
-                self._linear(xn, pk[f"wqkv.{i}"], qkv)
+                self._linear(xn, wqkv, qkv)
                 ops.rope_kvcache(qkv, qkv, kc, vc, cs, B, S, H, Hkv, hd, start_pos, rope_pos0)
             ops.attention(qkv, kc, vc, att, B, S, Sk, H, Hkv, hd, strides, causal and S > 1, scratch)
-            self._linear(att, lyr.attention.wo.weight, h, residual=h)
+            self._linear(att, wo, h, residual=h)
             ops.rmsnorm(h, lyr.ffn_norm.weight, xn, a.norm_eps)
-            self._linear(xn, pk[f"w13.{i}"], act, epilogue=ops.EPI_SWIGLU)
-            self._linear(act, lyr.feed_forward.w2.weight, h, residual=h)
+            self._linear(xn, w13, act, epilogue=ops.EPI_SWIGLU)
+            self._linear(act, w2, h, residual=h)
 
     def quantize_decode_weights(self, mode: str = "fp8", prefill: bool = False) -> None:
         """Opt-in fp8 images of the four decoder matrices of every layer (BASELINE config 5; quantiser = a3v_quantize_rows_fp8).
         The single-call decode step streams them weight-only (half the bytes, bf16 activations).  ``prefill=True`` also runs
         the multi-token forward W8A8 (a3v_gemm_nt_fp8: activations quantised per token on the fly); otherwise prefill keeps
-        the bf16 weights.  ``mode=None`` drops the images.  Re-run after the weights change."""
+        the bf16 weights.  ``mode=None`` drops the images.  Re-run after the weights change.
+
+        ``mode="nf4"``: the reference's 4-bit mode (bitsandbytes Linear4bit nf4, util/quant.py:95-163).  Every decoder linear
+        (wq wk wv wo w1 w2 w3) and the LM head ``output`` is quantised module by module by a3v_quantize_nf4 and its bf16
+        weight is FREED (as the reference's ``del module.weight``): irreversible, and gone from ``state_dict()``.  Decode
+        streams the NF4 images (a3v_gemm_skinny_nf4 / the fused step); the multi-token forward dequantises one layer at a time
+        into a reused bf16 scratch (a3v_dequantize_nf4) and runs the bf16 GEMMs on it.  Quantise after ``.to(device)``:
+        the images are not module buffers and do not move with the model.  Decode batches above 32 rows have no GEMV form (as
+        for bf16 / fp8) and take the multi-token path: every generated token then dequantises every layer again (~400 MB
+        written per layer at 7B), far slower than decoding the same batch in bf16."""
+        if getattr(self, "_n4", None) is not None:
+            raise RuntimeError("this model holds NF4 weights: quantize_decode_weights('nf4') freed its bf16 decoder weights and "
+                               "cannot be undone or combined with another mode; reload the checkpoint instead")
+        if mode == "nf4":
+            self._quantize_nf4()
+            return
         self._q8 = None
         self._fp8_prefill = bool(prefill) and mode is not None
         self._layer_tab_key = None
@@ -454,6 +482,83 @@ class Transformer(nn.Module):
                                                    lyr.feed_forward.w2.weight)))
         self._q8 = (self._packed_version, q8)
 
+    def _quantize_nf4(self) -> None:
+        a = self.args
+        H, Hkv, hd = self.n_heads, self.n_kv_heads, self.head_dim
+        if self._dtype != torch.bfloat16 or self._device.type != "cuda":
+            raise ValueError("NF4 weights need a bf16 model on the GPU (quantise after .to(device))")
+        if a.dim % 256 or self.ffn % 256 or (H * hd) % 256 or a.vocab_size % 4 or a.vocab_size > 65536 or 2 * self.ffn > 65536:
+            # the NF4 GEMV (LDS-DMA form only) takes N <= 65536 rows: the LM head and the packed w1|w3 image
+            raise ValueError("NF4 weights need dim, ffn, n_heads*head_dim multiples of 256, vocab_size % 4 == 0 and vocab_size, 2*ffn <= 65536")
+        self._q8, self._fp8_prefill, self._layer_tab_key = None, False, None
+        n4: Dict[str, tuple] = {}
+        ws = torch.empty((int(_lib.load().a3v_quantize_nf4_ws_bytes(max(a.vocab_size, self.ffn * 2), max(a.dim, self.ffn))) + 3) // 4,
+                         dtype=torch.float32, device=self._device)
+
+        def quant(mod):                    # one original module -> (nibbles, scales); its bf16 weight is dropped
+            q, sc, _ = ops.quantize_nf4(mod.weight.data.contiguous(), ws=ws)
+            del mod.weight
+            return q, sc
+
+        def rows16(x, y):                  # w1 / w3 interleaved in 16-row blocks (the SwiGLU GEMV row order, as _pack)
+            nb = x.shape[0] // 16
+            return torch.stack([x.view(nb, 16, -1), y.view(nb, 16, -1)], dim=1).reshape(2 * x.shape[0], -1).contiguous()
+        with torch.no_grad():
+            for i, lyr in enumerate(self.layers):
+                at, f = lyr.attention, lyr.feed_forward
+                (qq, sq), (qk, sk), (qv, sv) = quant(at.wq), quant(at.wk), quant(at.wv)
+                n4[f"wqkv.{i}"] = (torch.cat([qq, qk, qv]), torch.cat([sq, sk, sv]))
+                n4[f"wo.{i}"] = quant(at.wo)
+                (q1, s1), (q3, s3) = quant(f.w1), quant(f.w3)
+                n4[f"w13.{i}"] = (rows16(q1, q3), rows16(s1, s3))
+                n4[f"w2.{i}"] = quant(f.w2)
+                del qq, qk, qv, sq, sk, sv, q1, q3, s1, s3
+                self._packed.pop(f"wqkv.{i}", None)
+                self._packed.pop(f"w13.{i}", None)
+            n4["output"] = quant(self.output)
+        self._n4 = n4
+        self._packed_version = None
+        self._ws.pop("nf4_scratch", None)
+
+    def _nf4_scratch(self, n: int) -> torch.Tensor:
+        buf = self._ws.get("nf4_scratch")
+        if buf is None or buf.numel() < n:
+            self._ws.pop("nf4_scratch", None)
+            a = self.args
+            need = max(((self.n_heads + 2 * self.n_kv_heads) * self.head_dim + 2 * self.ffn) * a.dim + a.dim * (self.n_heads * self.head_dim + self.ffn),
+                       a.vocab_size * a.dim, n)
+            buf = torch.empty(need, dtype=torch.bfloat16, device=self._device)
+            self._ws["nf4_scratch"] = buf
+        return buf
+
+    def _nf4_dequant_layer(self, i: int):
+        """Wd of layer i's four (packed) matrices in the reused scratch: views (wqkv, wo, w13, w2)."""
+        a = self.args
+        shapes = (((self.n_heads + 2 * self.n_kv_heads) * self.head_dim, a.dim), (a.dim, self.n_heads * self.head_dim),
+                  (2 * self.ffn, a.dim), (a.dim, self.ffn))
+        buf = self._nf4_scratch(sum(n * k for n, k in shapes))
+        out, o = [], 0
+        for key, (n, k) in zip(("wqkv", "wo", "w13", "w2"), shapes):
+            w = buf[o:o + n * k].view(n, k)
+            ops.dequantize_nf4(*self._n4[f"{key}.{i}"], w)
+            out.append(w)
+            o += n * k
+        return out
+
+    def _nf4_output_weight(self) -> torch.Tensor:
+        a = self.args
+        w = self._nf4_scratch(a.vocab_size * a.dim)[:a.vocab_size * a.dim].view(a.vocab_size, a.dim)
+        return ops.dequantize_nf4(*self._n4["output"], w)
+
+    def _lm_head_f32(self, xn: torch.Tensor, logits: torch.Tensor) -> None:
+        """fp32 logits of bf16 rows xn: the NF4 GEMV in chunks of 16 rows on an NF4 model, the bf16 path otherwise."""
+        n4 = getattr(self, "_n4", None)
+        if n4 is None:
+            self._linear(xn, self.output.weight, logits, epilogue=ops.EPI_OUT_F32)
+            return
+        for r0 in range(0, xn.shape[0], 16):
+            self._linear(xn[r0:r0 + 16], n4["output"], logits[r0:r0 + 16], epilogue=ops.EPI_OUT_F32)
+
     def _decode_step(self, h: torch.Tensor, B: int, pos: int) -> None:
         """seqlen == 1, bf16: the whole layer stack from one C call (a3v_llama_decode_step)."""
         import ctypes
@@ -463,10 +568,19 @@ class Transformer(nn.Module):
         q8 = getattr(self, "_q8", None)
         if q8 is not None and q8[0] != self._packed_version:
             raise RuntimeError("parameters changed after quantize_decode_weights(): call it again (or with mode=None)")
-        key = (self._packed_version, self._cache_shape, q8 is not None)
+        n4 = getattr(self, "_n4", None)
+        key = (self._packed_version, self._cache_shape, q8 is not None, n4 is not None)
         if getattr(self, "_layer_tab_key", None) != key:
             tab = (_l.LlamaLayer * self.n_layers)()
             for i, lyr in enumerate(self.layers):
+                if n4 is not None:         # NF4 images only: the bf16 fields stay NULL
+                    (tab[i].wqkv_n4, tab[i].wqkv_n4s), (tab[i].wo_n4, tab[i].wo_n4s), (tab[i].w13_n4, tab[i].w13_n4s), (tab[i].w2_n4, tab[i].w2_n4s) = \
+                        [(q.data_ptr(), sc.data_ptr()) for q, sc in (n4[f"{k}.{i}"] for k in ("wqkv", "wo", "w13", "w2"))]
+                    tab[i].attn_norm_w = lyr.attention_norm.weight.data_ptr()
+                    tab[i].ffn_norm_w = lyr.ffn_norm.weight.data_ptr()
+                    tab[i].k_cache = self._k_cache[i].data_ptr()
+                    tab[i].vt_cache = self._vt_cache[i].data_ptr()
+                    continue
                 if q8 is not None:
                     (tab[i].wqkv_q, tab[i].wqkv_s), (tab[i].wo_q, tab[i].wo_s), (tab[i].w13_q, tab[i].w13_s), (tab[i].w2_q, tab[i].w2_s) = \
                         [(q.data_ptr(), sc.data_ptr()) for q, sc in q8[1][i]]
@@ -682,8 +796,9 @@ class Transformer(nn.Module):
         o0 = W if out_from is None else out_from       # h[:, image_words:] (llama_ens5.py:486)
         out = torch.empty(B, S - o0, a.vocab_size, dtype=self._dtype, device=self._device)
         xv = xn.view(B, S, a.dim)
+        wout = self.output.weight if getattr(self, "_n4", None) is None else self._nf4_output_weight()
         for b in range(B):
-            ops.gemm_nt(xv[b, o0:], self.output.weight, out[b])
+            ops.gemm_nt(xv[b, o0:], wout, out[b])
         return out
 
     # ------------------------------------------------------------------ forward_inference (KV cached)
@@ -726,8 +841,8 @@ class Transformer(nn.Module):
             # the C entry says up front which form it takes (a3v_llama_decode_step_form): 17..32 rows need the fused GEMV forms (two row
             # chunks); a geometry they do not take goes through the general kernels -- decided BEFORE h or the KV cache are touched, an
             # error from inside the step is never papered over
-            w8 = 1 if getattr(self, "_q8", None) is not None else 0
-            if _lib.load().a3v_llama_decode_step_form(B, a.dim, a.n_heads, self.n_kv_heads, self.head_dim, self.ffn, w8) or B <= 16:
+            w8 = 2 if getattr(self, "_n4", None) is not None else 1 if getattr(self, "_q8", None) is not None else 0
+            if _lib.load().a3v_llama_decode_step_form(B, a.dim, a.n_heads, self.n_kv_heads, self.head_dim, self.ffn, w8) or (B <= 16 and w8 != 2):
                 self._decode_step(h, B, start_pos)
             else:
                 self._decoder_layers(h, B, S, start_pos, rope0, self._k_cache, self._vt_cache, True)
@@ -740,7 +855,7 @@ class Transformer(nn.Module):
         if self._dtype == torch.float32:
             ops.gemm_nt(xn, self.output.weight, logits)
         else:
-            self._linear(xn, self.output.weight, logits, epilogue=ops.EPI_OUT_F32)
+            self._lm_head_f32(xn, logits)
         # the reference returns a fresh tensor (output(h[:, -1, :]).float(), llama_ens5.py:530-531); `logits` is a cached workspace
         # that the next call overwrites, so hand out a copy (B x V fp32 = 1 MB at bs 8: microseconds next to a 4 ms step)
         return logits.clone()

@@ -59,6 +59,12 @@ class Transformer(base.Transformer):
         self._lora_img: Dict[str, torch.Tensor] = {}
         self._lora_ver = None
 
+    def quantize_decode_weights(self, mode: str = "fp8", prefill: bool = False) -> None:
+        if mode == "nf4":
+            # the reference keeps the LoRA adapters unquantised beside the NF4 base (llama_ens5.py:541-550, QLoRA): a follow-up
+            raise NotImplementedError("NF4 weights with LoRA adapters (QLoRA) are not implemented")
+        super().quantize_decode_weights(mode, prefill)
+
     def get_trainable_params(self, pretrain_stage: bool = False):
         frozen_pre = ("qformer.", "openclip_convnext_xxl.", "clip.", "dinov2_vitg14.", "tok_embeddings.", "output.")
         out = {}

@@ -80,7 +80,10 @@ class MetaModel(nn.Module):
         Folders are loaded in order (``consolidated`` / ``meta_ori`` override, ``consolidated_diff`` adds).  Differences to the
         reference, all forced by the DP-replica design: no process group is created (``mp_group`` must be None or of size 1;
         TP-sharded folders are merged on load), ``hf://`` ids need a network and are refused, and ``quant=True`` selects this
-        package's weight-only fp8 decoder images (``Transformer.quantize_decode_weights("fp8")``) instead of bitsandbytes NF4."""
+        package's weight-only fp8 decoder images (``Transformer.quantize_decode_weights("fp8")``) instead of bitsandbytes NF4.
+        ``quant="nf4"`` is the reference's 4-bit mode (meta.py:197-219, util/quant.py:95-163): the bf16 checkpoint is loaded,
+        then every decoder linear and the LM head is quantised to NF4 layer by layer and its bf16 weight freed
+        (``Transformer.quantize_decode_weights("nf4")``; inference only, irreversible)."""
         import os
         import warnings
         from ..checkpoint import load_tensor_parallel_model_list
@@ -121,7 +124,9 @@ class MetaModel(nn.Module):
             warnings.warn(f"checkpoint and model mismatch: \n{load_result}")
         else:
             print("all params match perfectly!")
-        if quant:
+        if quant == "nf4":
+            model.llma.quantize_decode_weights("nf4")
+        elif quant:
             model.llma.quantize_decode_weights("fp8")
         model.eval()
         return model
@@ -171,6 +176,8 @@ class MetaModel(nn.Module):
         """The HIP forward/backward engine of the plugin (a3vlm_amd/train.py).  compute dtype: bf16
         ("autocast") unless the model is all-fp32 (parity path)."""
         from ..train import TrainEngine
+        if getattr(self.llma, "_n4", None) is not None:
+            raise RuntimeError("this model holds NF4 weights (inference only): training needs the bf16 checkpoint")
         if getattr(self, "_engine", None) is None:
             if compute_dtype is None:
                 frozen = [p for p in self.llma.parameters() if not p.requires_grad]

@@ -247,6 +247,48 @@ def gemm_skinny_fp8(a, wq, wscale, out, workspace, *, residual=None, epilogue: i
     return out
 
 
+def quantize_nf4(w, q=None, scales=None, ws=None):
+    """NF4 image of one bf16 module weight w [N, K] (a3v_quantize_nf4, the format of include/a3vlm_hip.h): returns
+    (nibbles [N, K/2] uint8, block scales [N, K/64] fp32, module offset as a 0-d fp32 device tensor)."""
+    N, K = w.shape
+    if w.dtype != torch.bfloat16 or not w.is_contiguous():
+        raise ValueError("quantize_nf4 needs a contiguous bf16 weight")
+    q = torch.empty(N, K // 2, dtype=torch.uint8, device=w.device) if q is None else q
+    scales = torch.empty(N, K // 64, dtype=torch.float32, device=w.device) if scales is None else scales
+    need = int(_l.load().a3v_quantize_nf4_ws_bytes(N, K))
+    ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=w.device) if ws is None else ws
+    _dev(w, q, scales, ws)
+    assert q.is_contiguous() and scales.is_contiguous() and ws.numel() * 4 >= need
+    rc = _l.load().a3v_quantize_nf4(_p(w), N, K, _p(q), _p(scales), _p(ws), _stream())
+    _l.check(rc, f"a3v_quantize_nf4(N={N},K={K})")
+    return q, scales, ws[0]
+
+
+def dequantize_nf4(q, scales, out):
+    """out [N, K] bf16 = bf16(NF4[q] * s_b) (a3v_dequantize_nf4)."""
+    _dev(q, scales, out)
+    N, K = out.shape
+    assert q.dtype == torch.uint8 and q.is_contiguous() and q.shape == (N, K // 2) and scales.is_contiguous() and scales.numel() == N * K // 64
+    rc = _l.load().a3v_dequantize_nf4(_p(q), _p(scales), _p(out), out.stride(0), N, K, _stream())
+    _l.check(rc, f"a3v_dequantize_nf4(N={N},K={K})")
+    return out
+
+
+def gemm_skinny_nf4(a, q, scales, out, workspace, *, residual=None, epilogue: int = 0):
+    """out = epilogue(sum_b s_b * (a . NF4[q])^T): weight-only NF4 decode GEMV (M <= 16, K % 256 == 0)."""
+    _dev(a, q, scales, out, workspace, residual)
+    M, K = a.shape
+    N = q.shape[0]
+    assert q.dtype == torch.uint8 and q.shape[1] * 2 == K and scales.dtype == torch.float32 and scales.is_contiguous() and scales.numel() == N * K // 64
+    if workspace.numel() * workspace.element_size() < gemm_skinny_ws_bytes(M, N, K):
+        raise ValueError("gemm_skinny workspace too small (a3v_gemm_skinny_ws_bytes)")
+    ep = epilogue | (EPI_RESIDUAL if residual is not None else 0)
+    rc = _l.load().a3v_gemm_skinny_nf4(_p(a), a.stride(0), _p(q), q.stride(0), _p(scales), _p(out), out.stride(0), M, N, K,
+                                       _p(residual), residual.stride(0) if residual is not None else 0, ep, _p(workspace), _stream())
+    _l.check(rc, f"a3v_gemm_skinny_nf4(M={M},N={N},K={K},epi={ep})")
+    return out
+
+
 def rmsnorm(x, w, out, eps: float):
     _dev(x, w, out)
     rows, dim = x.shape

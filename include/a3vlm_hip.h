@@ -175,6 +175,28 @@ int64_t a3v_gemm_skinny_ws_bytes(int M, int N, int K);
 int a3v_gemm_skinny_fp8(const void* A, int64_t lda, const void* Wq, int64_t ldw, const float* wscale, void* C,
                         int64_t ldc, int M, int N, int K, const void* residual, int64_t ldr, int epilogue,
                         void* workspace, void* stream);
+/* NF4 weight-only inference (the reference's quantised mode: bitsandbytes Linear4bit nf4, blocksize 64, compress_statistics=True,
+ * util/quant.py:95-163, applied by MetaModel.from_pretrained(quant=True), meta.py:197-219).  Format, per original module W [N, K]
+ * bf16 (contiguous rows, K % 64 == 0):
+ *   blocks of 64 consecutive elements of the flattened matrix; absmax_b = max|w| (fp32); code q = argmin_i |w * (1/absmax_b) - NF4[i]|
+ *   (correctly rounded fp32 reciprocal, then a product; first minimum on ties) over bitsandbytes' 16-entry NF4 table; two codes per
+ *   byte, the earlier element in the HIGH nibble; an all-zero block gets code 7 and scale 0;
+ *   double quantisation: offset = mean(absmax) over the module, absmax - offset quantised in groups of 256 consecutive blocks to
+ *   the nearest entry of bitsandbytes' signed 8-bit dynamic map with absmax2_g = max|absmax - offset|;
+ *   effective scale s_b = map[qa_b] * absmax2_g + offset in fp32 (two roundings, as dequantize_4bit rebuilds absmax), stored per block;
+ *   dequantised weight Wd = bf16(NF4[q] * s_b).
+ * a3v_quantize_nf4: W -> q [N, K/2] uint8 + scales [N, K/64] fp32; ws = a3v_quantize_nf4_ws_bytes(N, K) bytes of caller workspace
+ * (16-B aligned; after the call ws[0] holds the module offset as a float).  Allocates nothing. */
+int64_t a3v_quantize_nf4_ws_bytes(int N, int K);
+int a3v_quantize_nf4(const void* W, int N, int K, void* q, float* scales, float* ws, void* stream);
+/* Wd [N, K] bf16 (row stride ldd elements, ldd % 8 == 0) = bf16(NF4[q] * s_b): the multi-token forward of an NF4 model runs the bf16
+ * GEMMs on it (bit-identical to the bf16 model holding Wd). */
+int a3v_dequantize_nf4(const void* q, const float* scales, void* Wd, int64_t ldd, int N, int K, void* stream);
+/* Weight-only NF4 decode GEMV, M <= 16, K % 256 == 0: q [N, K/2] (row stride ldw BYTES), scales [N, K/64]; workspace and epilogues
+ * (NONE, RESIDUAL, SWIGLU, OUT_F32) as a3v_gemm_skinny; SWIGLU needs K >= 512 (A3V_ERR_SHAPE otherwise, as the fp8 form).  The codes enter the MFMA as bf16 and each 64-k block sum is scaled by s_b in
+ * fp32, so results differ from the bf16 GEMV on Wd by rounding only. */
+int a3v_gemm_skinny_nf4(const void* A, int64_t lda, const void* Wq, int64_t ldw, const float* scales, void* C, int64_t ldc,
+                        int M, int N, int K, const void* residual, int64_t ldr, int epilogue, void* workspace, void* stream);
 int a3v_gemm_skinny(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc,
                     int M, int N, int K, const void* residual, int64_t ldr, int epilogue,
                     void* partial, void* stream);
@@ -327,6 +349,13 @@ typedef struct a3v_llama_layer {
   const void* wo_q;   const float* wo_s;
   const void* w13_q;  const float* w13_s;
   const void* w2_q;   const float* w2_s;
+  /* optional NF4 images of the four matrices (a3v_quantize_nf4 per original module, rows permuted as the bf16 images: nibbles
+   * [N, K/2], block scales [N, K/64]); all NULL = not NF4.  Setting fp8 and NF4 fields together returns A3V_ERR_ARG.  Fused step
+   * form only (a3v_llama_decode_step_form with w8 = 2). */
+  const void* wqkv_n4; const float* wqkv_n4s;
+  const void* wo_n4;   const float* wo_n4s;
+  const void* w13_n4;  const float* w13_n4s;
+  const void* w2_n4;   const float* w2_n4s;
 } a3v_llama_layer;
 int a3v_llama_decode_step(const a3v_llama_layer* layers, int n_layers, void* h, void* xn, void* qkv,
                           void* att, void* act, float* attn_scratch, void* skinny_ws, const float* cos_sin, int B,
@@ -335,7 +364,7 @@ int a3v_llama_decode_step(const a3v_llama_layer* layers, int n_layers, void* h, 
 /* Which form a3v_llama_decode_step takes for a geometry, decided before anything is launched: 2 = the fused five-launch form,
  * 1 = the per-kernel form (<= 16 rows, bf16 weights), 0 = not taken (the call returns A3V_ERR_SHAPE with every buffer untouched and
  * the host runs the general kernels: llama_ens5.py:490-531 has no batch limit below max_batch_size). */
-int a3v_llama_decode_step_form(int B, int dim, int H, int Hkv, int hd, int ffn, int w8);
+int a3v_llama_decode_step_form(int B, int dim, int H, int Hkv, int hd, int ffn, int w8);   /* w8: 0 bf16, 1 fp8, 2 NF4 images */
 
 /* ---------------------------------------------------------------------------------------
  * Training (backward) entry points.  Reference: autograd through the same modules under
