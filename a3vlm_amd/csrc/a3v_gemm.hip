@@ -51,8 +51,6 @@ struct GemmArgs {
   int64_t lda, ldw, ldc, ldr;
   int M, N, K, epi;
   int tiles_m, tiles_n;
-  int dbg;   // ablation switches for tuning runs (0 in production): 1 = no DMA in the k-loop, 2 = no ds_read in the k-loop
-  int skew;  // ring kernel: XCD x starts x * skew cycles late, so the eight XCDs' store bursts do not hit HBM together
   int slow_epi;   // 1: interior tiles also take the general epilogue (A3V_GEMM_FAST_EPI=0; equality tests and A/B runs)
   int nt_store;   // fast epilogue forms: non-temporal stores of the output tile (A3V_GEMM_NT_STORE, read per launch)
   float* sumsq;   // fp32 outputs (weight gradients): slot (tile * 8 + wave) <- sum of squares of the values this wave stored (NULL: off)
@@ -61,7 +59,6 @@ struct GemmArgs {
   const float* sa;   // GEMM_EPI_SCALE: per-row dequantisation scales of A [M] and W [N]
   const float* sw;
   int xmap;          // ring kernel: 1 = every round of gridDim.x tiles is cut into eight runs, one per XCD (see tile_of)
-  unsigned* xsync;   // ring kernel, A3V_GEMM_LOCKSTEP=1: eight zeroed counters; the blocks of an XCD start each tile round together
 };
 
 __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752440f)); }
@@ -959,95 +956,13 @@ __global__ __launch_bounds__(256) void gemm_nt_skinny_kernel(GemmArgs p) {
   gemm_epilogue<TM, TN, false, EPI_SET_COMMON | EPI_SET_PRE>(acc, p, m0 + wave * WTM, 0, lane, nk > 0 ? lds + wave * 4096 : nullptr);
 }
 
-// Epilogue for v_mfma_f32_32x32x16 accumulators (D = W_frag x A_frag): for tile (i, j) the lane holds
-// C[m = mbase + 32 i + (lane&31)][n = nbase + 32 j + 8 g + 4 (lane>>5) + 0..3], g = reg/4.
-template <int TM, int TN>
-__device__ __forceinline__ void gemm_epilogue32(f32x16 (&acc)[TM][TN], const GemmArgs& p, int mbase, int nbase, int lane) {
-  const int epi = p.epi;
-  const int mrow = lane & 31;
-  const int hh4 = (lane >> 5) * 4;
-#pragma unroll
-  for (int i = 0; i < TM; ++i) {
-    const int m = mbase + i * 32 + mrow;
-    if (m >= p.M) continue;
-    if (epi & A3V_EPI_SWIGLU) {
-      // 16-row interleave: tile rows 0..15 = gate, 16..31 = up  ->  reg groups g (gate) / g+2 (up)
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        const int n = nbase + j * 32;
-        if (n >= p.N) continue;
-#pragma unroll
-        for (int g = 0; g < 2; ++g) {
-          const int oc = (n >> 1) + 8 * g + hh4;
-          bf16x4 o;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float gt = rbf(acc[i][j][4 * g + r]);
-            const float up = rbf(acc[i][j][4 * (g + 2) + r]);
-            o[r] = f2bf(rbf(silu(gt)) * up);
-          }
-          *reinterpret_cast<bf16x4*>(reinterpret_cast<bf16_t*>(p.C) + (int64_t)m * p.ldc + oc) = o;
-        }
-      }
-      continue;
-    }
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int n = nbase + j * 32 + 8 * g + hh4;
-        if (n >= p.N) continue;
-        float v[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = acc[i][j][4 * g + r];
-        if (epi & A3V_EPI_BIAS) {
-          const bf16x4 b = *reinterpret_cast<const bf16x4*>(reinterpret_cast<const bf16_t*>(p.bias) + n);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] += bf2f(b[r]);
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = rbf(v[r]);
-        if (epi & A3V_EPI_GELU) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] = rbf(gelu_erf(v[r]));
-        } else if (epi & A3V_EPI_QUICKGELU) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] = rbf(quick_gelu(v[r]));
-        }
-        if (epi & A3V_EPI_RES_F32) {
-          const f32x4 rr = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(p.res) + (int64_t)m * p.ldr + n);
-          f32x4 o;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) o[r] = rr[r] + v[r];
-          *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(p.C) + (int64_t)m * p.ldc + n) = o;
-          continue;
-        }
-        if (epi & A3V_EPI_RESIDUAL) {
-          const bf16x4 rr = *reinterpret_cast<const bf16x4*>(reinterpret_cast<const bf16_t*>(p.res) + (int64_t)m * p.ldr + n);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] = bf2f(rr[r]) + v[r];
-        }
-        if (epi & A3V_EPI_OUT_F32) {
-          f32x4 o;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) o[r] = v[r];
-          *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(p.C) + (int64_t)m * p.ldc + n) = o;
-        } else {
-          bf16x4 o;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) o[r] = f2bf(v[r]);
-          *reinterpret_cast<bf16x4*>(reinterpret_cast<bf16_t*>(p.C) + (int64_t)m * p.ldc + n) = o;
-        }
-      }
-  }
-}
-
 // ------------------------------------------------------------------------------------
-// 256x256x64 "ping-pong" kernel: 8 waves = 2 groups of 4 (wr = wave/4 owns 128 rows of A; the
-// waves w and w+4 share a SIMD).  Each group alternates a LOAD interval (24 ds_read_b128 for a
-// whole K-tile of its 128x64 wave tile, + its share of the LDS-DMA for a later K-tile) and an
-// MFMA interval (64 v_mfma_f32_16x16x32_bf16 from registers); the groups run ONE barrier apart,
-// so on every SIMD one wave feeds the matrix pipe while its partner reads LDS / issues DMA.
+// 256x256x64 "ping-pong" schedule (the ring kernel below and the two-stage TN / NN kernels): 8 waves =
+// 2 groups of 4 (wr = wave/4 owns 128 rows of A; the waves w and w+4 share a SIMD).  Each group
+// alternates a LOAD interval (24 ds_read_b128 for a whole K-tile of its 128x64 wave tile, + its share
+// of the LDS-DMA for a later K-tile) and an MFMA interval (64 v_mfma_f32_16x16x32_bf16 from registers);
+// the groups run ONE barrier apart, so on every SIMD one wave feeds the matrix pipe while its partner
+// reads LDS / issues DMA.  With two whole-tile stages:
 //
 //   interval:   1      2      3      4      5      6
 //   group 0:   L(0)   M(0)   L(1)   M(1)   L(2)   M(2) ...      L(t): reads buf[t&1]
@@ -1056,15 +971,9 @@ __device__ __forceinline__ void gemm_epilogue32(f32x16 (&acc)[TM][TN], const Gem
 //   DMA wait :                      t=2           t=3    ...    L(t+1), by group 1 in M(t) (same interval:
 //                                                                 the first one after BOTH groups read tile t)
 // Ordering rules used (guide: "read a staged buffer one phase AFTER the wait that retires it"):
-// every wave waits vmcnt(0) for its own DMA pieces in the interval after it issued them, then the
-// interval barrier publishes them; readers start one barrier later.  A wave retires its own
-// ds_reads (lgkmcnt(0)) BEFORE the barrier that ends its LOAD interval, so a buffer is only
-// re-staged after every read of it has returned.
-#ifdef PP_PIN
-#define PP_SB() __builtin_amdgcn_sched_barrier(0)
-#else
-#define PP_SB() do {} while (0)
-#endif
+// every wave waits for its own DMA pieces, then the interval barrier publishes them; readers start
+// one barrier later.  A wave retires its own ds_reads (lgkmcnt(0)) BEFORE the barrier that ends its
+// LOAD interval, so a buffer is only re-staged after every read of it has returned.
 #define A3V_WAIT_LGKM0() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
 #define A3V_WAIT_VM0() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
 #define A3V_BARRIER()                      \
@@ -1074,241 +983,12 @@ __device__ __forceinline__ void gemm_epilogue32(f32x16 (&acc)[TM][TN], const Gem
     asm volatile("" ::: "memory");         \
   } while (0)
 
-#ifdef A3V_EXPERIMENTS   // measured and not dispatched: built only with `make EXPERIMENTS=1`
-template <int DBG, int SCHED>
-__global__ __launch_bounds__(512) void gemm_nt_bf16_pp_kernel(GemmArgs p) {
-  constexpr int TBM = 256, TBN = 256, NW = 8, WTM = 128, WTN = 64, TM = 8, TN = 4;
-  constexpr int STAGE = (TBM + TBN) * BK * 2;   // 64 KiB
-  __shared__ __attribute__((aligned(1024))) char lds[2 * STAGE];
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wr = wave >> 2, wc = wave & 3;
-
-  // Persistent over tiles: block b takes tiles b, b + gridDim.x, ... of the XCD-aware order below (gridDim.x is a multiple of 8,
-  // so a block's tiles all map to its own XCD).  The next tile's first two k-stages are issued BEFORE this tile's epilogue:
-  // the store burst of a tile round (every CU writes its 128 KiB at once) drains while the next operands are already in flight,
-  // and there is no workgroup launch between tiles.
-  const int ntiles = p.tiles_m * p.tiles_n;
-  auto tile_of = [&](int vb, int& tm0, int& tn0) {
-    const int xcd = vb & 7, q = ntiles >> 3, r = ntiles & 7;
-    const int bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (vb >> 3);
-    const int per_group = GROUP_M * p.tiles_n;
-    const int group = bid / per_group;
-    const int first_m = group * GROUP_M;
-    const int gsz = min(p.tiles_m - first_m, GROUP_M);
-    const int in_g = bid - group * per_group;
-    tm0 = (first_m + in_g % gsz) * TBM;
-    tn0 = (in_g / gsz) * TBN;
-  };
-  int m0, n0, sm0, sn0;     // tile being computed / tile being staged
-  tile_of(blockIdx.x, m0, n0);
-  sm0 = m0; sn0 = n0;
-  f32x4 acc[TM][TN];
-
-  const int nk = p.K / BK;
-  // LDS-DMA through buffer descriptors: rows past M / N are out of range and read as zero (no
-  // clamping VALU), addresses are {SGPR descriptor, 32-bit VGPR offset, SGPR k-offset}.
-  const auto rsA = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, (int)(((int64_t)(p.M - 1) * p.lda + p.K) * 2), 0x00020000);
-  const auto rsW = __builtin_amdgcn_make_buffer_rsrc((void*)p.W, 0, (int)(((int64_t)(p.N - 1) * p.ldw + p.K) * 2), 0x00020000);
-  // per-lane byte offset inside an 8-row chunk: row = lane/8, 16-B slot = (lane%8) ^ ((chunk*4 + lane/16) & 7)
-  const unsigned lr = lane >> 3;
-  unsigned voA[2], voW[2];
-#pragma unroll
-  for (int par = 0; par < 2; ++par) {
-    const unsigned sl = (lane & 7) ^ ((par * 4 + (lane >> 4)) & 7);
-    voA[par] = (unsigned)((lr * p.lda + sl * 8) * 2);
-    voW[par] = (unsigned)((lr * p.ldw + sl * 8) * 2);
-  }
-  // one 1-KiB DMA piece: c in [0,8): 0..3 -> A chunks, 4..7 -> W chunks of this wave
-  auto stage_piece = [&](int t, int c) {
-    const int ch = wave * 4 + (c & 3);
-    char* dst = lds + (t & 1) * STAGE + (c >= 4 ? TBM * BK * 2 : 0) + ch * 1024;
-    if (c < 4) {
-      // (row-chunk + k) offset is wave-uniform and changes with t: an SGPR sum added per piece, so
-      // nothing per-piece stays live in VGPRs across the loop
-      const unsigned so = (unsigned)(((int64_t)(sm0 + ch * 8) * p.lda + t * BK) * 2);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (__attribute__((address_space(3))) void*)dst, 16, voA[c & 1] + so, 0, 0, 0);
-    } else {
-      const unsigned so = (unsigned)(((int64_t)(sn0 + ch * 8) * p.ldw + t * BK) * 2);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW, (__attribute__((address_space(3))) void*)dst, 16, voW[c & 1] + so, 0, 0, 0);
-    }
-  };
-  auto stage = [&](int t) {
-#pragma unroll
-    for (int c = 0; c < 8; ++c) stage_piece(t, c);
-  };
-  stage(0);
-  if (nk > 1) stage(1);
-
-  const int frow = lane & 15, fsw = (lane >> 1) & 7, fks = lane >> 4;
-  const int off0 = ((0 * 4 + fks) ^ fsw) << 4, off1 = ((1 * 4 + fks) ^ fsw) << 4;
-  const int a_base = (wr * WTM + frow) * 128;
-  const int w_base = TBM * BK * 2 + (wc * WTN + frow) * 128;
-  bf16x8 af0[TM], af1[TM], wf0[TN], wf1[TN];
-
-#define PP_READ_FRAGS(cur)                                                                           \
-  do {                                                                                               \
-    const char* At_ = (cur) + a_base;                                                                \
-    const char* Wt_ = (cur) + w_base;                                                                \
-    _Pragma("unroll") for (int j = 0; j < TN; ++j) {                                                 \
-      wf0[j] = *reinterpret_cast<const bf16x8*>(Wt_ + j * 2048 + off0);                              \
-      wf1[j] = *reinterpret_cast<const bf16x8*>(Wt_ + j * 2048 + off1);                              \
-    }                                                                                                \
-    _Pragma("unroll") for (int i = 0; i < TM; ++i) {                                                 \
-      af0[i] = *reinterpret_cast<const bf16x8*>(At_ + i * 2048 + off0);                              \
-      af1[i] = *reinterpret_cast<const bf16x8*>(At_ + i * 2048 + off1);                              \
-    }                                                                                                \
-  } while (0)
-
-#define PP_MFMA_ALL()                                                                                \
-  do {                                                                                               \
-    __builtin_amdgcn_s_setprio(1);                                                                   \
-    _Pragma("unroll") for (int i = 0; i < TM; ++i)                                                   \
-      _Pragma("unroll") for (int j = 0; j < TN; ++j)                                                 \
-        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf0[j], af0[i], acc[i][j], 0, 0, 0);     \
-    _Pragma("unroll") for (int i = 0; i < TM; ++i)                                                   \
-      _Pragma("unroll") for (int j = 0; j < TN; ++j)                                                 \
-        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf1[j], af1[i], acc[i][j], 0, 0, 0);     \
-    __builtin_amdgcn_s_setprio(0);                                                                   \
-  } while (0)
-
-  constexpr bool do_dma = !(DBG & 1), do_rd = !(DBG & 2);
-  // DBG == 4: cycle stamps (s_memtime) of block 0, waves 0 and 4, into the buffer passed as `bias`
-  unsigned long long* stamps = (DBG == 4 && blockIdx.x == 0 && (wave == 0 || wave == 4) && lane == 0)
-                                   ? (unsigned long long*)p.bias + (wave ? 1 : 0) * 64 * 8 : nullptr;
-#define PP_STAMP(t, k) do { if (DBG == 4 && stamps && (t) < 64) stamps[(t) * 8 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
-  for (int vb = blockIdx.x;;) {
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  A3V_WAIT_VM0();
-  A3V_BARRIER();
-  if constexpr (SCHED == 1) {
-    // Schedule 1: both groups issue the DMA of tile t+1 in their own LOAD interval (the MFMA intervals
-    // carry no VMEM issue) and wait for it at the end of that interval.  That only works if the DMA
-    // hits in L2, so every wave also TOUCHES one 128-B line of tile t+3 per K-tile (one dword per lane:
-    // waves 0-3 cover the 256 A rows, waves 4-7 the 256 W rows) -- a software L2 prefetch that takes
-    // the fabric (MALL/HBM) latency out of the DMA's completion time.  The touch is the youngest VMEM
-    // op at the interval's wait, hence vmcnt(1).
-    const unsigned pf_vo = (unsigned)((int64_t)((wave & 3) * 64 + lane) * (wr ? p.ldw : p.lda) * 2
-                                      + (int64_t)(wr ? n0 : m0) * (wr ? p.ldw : p.lda) * 2);
-    const auto pf_rs = wr ? rsW : rsA;
-    int pf = 0;
-    if (wr == 1) A3V_BARRIER();
-    for (int t = 0; t < nk; ++t) {
-      PP_STAMP(t, 0);
-      asm volatile("" ::"v"(pf));            // retire the previous touch (compiler-inserted vmcnt)
-      PP_READ_FRAGS(lds + (t & 1) * STAGE);
-      if (do_dma && t >= 1 && t + 1 < nk) stage(t + 1);
-      {
-        const int tp = min(t + 3, nk - 1);
-        pf = __builtin_amdgcn_raw_buffer_load_b32(pf_rs, pf_vo, tp * BK * 2, 0);
-      }
-      A3V_WAIT_LGKM0();
-      PP_STAMP(t, 1);
-      asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-      PP_STAMP(t, 2);
-      A3V_BARRIER();
-      PP_STAMP(t, 3);
-      PP_MFMA_ALL();
-      PP_STAMP(t, 4);
-      A3V_BARRIER();
-      PP_STAMP(t, 5);
-    }
-    asm volatile("" ::"v"(pf));
-    if (wr == 0) A3V_BARRIER();
-  } else if (wr == 0) {
-    for (int t = 0; t < nk; ++t) {
-      PP_STAMP(t, 0);
-      if (do_rd || t == 0) PP_READ_FRAGS(lds + (t & 1) * STAGE);
-      if (do_dma && t >= 1 && t + 1 < nk) stage(t + 1);
-      A3V_WAIT_LGKM0();
-      PP_STAMP(t, 1);
-      A3V_BARRIER();
-      PP_STAMP(t, 2);
-      PP_MFMA_ALL();
-      PP_STAMP(t, 3);
-      A3V_WAIT_VM0();
-      PP_STAMP(t, 4);
-      A3V_BARRIER();
-      PP_STAMP(t, 5);
-    }
-    A3V_BARRIER();
-  } else {
-    A3V_BARRIER();
-    for (int t = 0; t < nk; ++t) {
-      PP_STAMP(t, 0);
-      if (do_rd || t == 0) PP_READ_FRAGS(lds + (t & 1) * STAGE);
-      A3V_WAIT_LGKM0();
-      PP_STAMP(t, 1);
-      A3V_WAIT_VM0();
-      PP_STAMP(t, 2);
-      A3V_BARRIER();
-      PP_STAMP(t, 3);
-#ifndef PP_INTERLEAVE
-      if (do_dma && t + 2 < nk) stage(t + 2);
-      PP_MFMA_ALL();
-#else
-      {
-        // DMA pieces spread through the MFMA stream: one piece per 8 MFMAs
-        const bool has = do_dma && (t + 2 < nk);
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-          if (has) stage_piece(t + 2, c);
-          PP_SB();
-          if (c < 4) {
-#pragma unroll
-            for (int i = 2 * c; i < 2 * c + 2; ++i)
-#pragma unroll
-              for (int j = 0; j < TN; ++j)
-                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf0[j], af0[i], acc[i][j], 0, 0, 0);
-          } else {
-#pragma unroll
-            for (int i = 2 * (c - 4); i < 2 * (c - 4) + 2; ++i)
-#pragma unroll
-              for (int j = 0; j < TN; ++j)
-                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf1[j], af1[i], acc[i][j], 0, 0, 0);
-          }
-          PP_SB();
-        }
-        __builtin_amdgcn_s_setprio(0);
-      }
-#endif
-      PP_STAMP(t, 4);
-      A3V_BARRIER();
-      PP_STAMP(t, 5);
-    }
-  }
-  // every read of both stage buffers is behind the last barrier: stage the next tile now, store this one after
-  const int nb = vb + (int)gridDim.x;
-  if (nb < ntiles) {
-    tile_of(nb, sm0, sn0);
-    stage(0);
-    if (nk > 1) stage(1);
-  }
-  {
-    int lane_e = lane;                       // opaque copy: keeps the epilogue's per-lane address arithmetic from being hoisted
-    asm volatile("" : "+v"(lane_e));         // out of the tile loop (and held in VGPRs across the k-loop)
-    gemm_epilogue<TM, TN>(acc, p, m0 + wr * WTM, n0 + wc * WTN, lane_e);
-  }
-  if (nb >= ntiles) break;
-  vb = nb; m0 = sm0; n0 = sn0;
-  }
-#undef PP_STAMP
-#undef PP_READ_FRAGS
-#undef PP_MFMA_ALL
-}
-#endif  // A3V_EXPERIMENTS
-
 typedef __attribute__((ext_vector_type(4))) int i32x4r;
 // ------------------------------------------------------------------------------------
-// "Ring" form of the ping-pong kernel: the same tile, fragments, MFMA stream and epilogue, but the LDS is cut into three
-// rings that together use all 160 KiB of the CU, so every LDS-DMA piece has THREE OR FOUR intervals (1.5 - 2 K-tile periods)
-// to land instead of two.  The two-stage kernel above waits ~2600 cycles for a stage that it issued one K-tile period
-// (2176 cycles of MFMA) earlier: the k-loop runs at the DMA's completion latency, not at the matrix pipe's rate.
+// "Ring" form of the ping-pong schedule: the LDS is cut into three rings that together use all 160 KiB of the CU, so every
+// LDS-DMA piece has THREE OR FOUR intervals (1.5 - 2 K-tile periods) to land instead of two.  (With two whole-tile stages a
+// wave waits ~2600 cycles for a stage that it issued one K-tile period -- 2176 cycles of MFMA -- earlier: the k-loop runs at
+// the DMA's completion latency, not at the matrix pipe's rate.)
 //
 //   A_top ring : rows   0..127 of the A tile (only group 0 reads them), 2 slots x 16 KiB   slot(t) = t & 1
 //   A_bot ring : rows 128..255 of the A tile (only group 1 reads them), 2 slots x 16 KiB   slot(t) = t & 1
@@ -1323,21 +1003,33 @@ typedef __attribute__((ext_vector_type(4))) int i32x4r;
 //     group 0 in L(t)  : A_bot(t+1) -> needed I = 2t+3 (3 intervals),   W rows 0..127 of tile t+2   -> needed I = 2t+4 (4)
 //     group 1 in L(t)  : W rows 128..255 of tile t+2 and A_top(t+2)     -> needed I = 2t+4 (3 intervals)
 //   counted waits (loads retire in order; a wave only ever waits for its OWN pieces, the barrier publishes them):
-//     group 0, end of L(t): vmcnt(12) = A_bot(t), the first 4 pieces of its previous burst, has landed (group 1 reads it next)
-//              end of M(t): vmcnt(8)  = the rest of that burst (W half of tile t+1) has landed
+//     group 0, top of L(t): vmcnt(16) = its W half of tile t (issued in L(t-2)) has landed.  The late W wait (r03 A/B +1 % on
+//                           every shape, bit-equal): here and not between the group's last MFMA of M(t-1) and the barrier that
+//                           hands the matrix pipe over
+//              end of L(t): vmcnt(12) = A_bot(t), the first 4 pieces of its previous burst, has landed (group 1 reads it next)
 //     group 1, end of L(t): vmcnt(8)  = its previous burst (W half and A_top of tile t+1) has landed
-//   The last two K-tiles issue shorter bursts, so their counts shrink accordingly (the switch below).
+//   The last two K-tiles of a block's last tile issue shorter bursts, so their counts shrink accordingly.
+//
+// The DMA stream runs on ACROSS the block's tiles (r03): the last two LOAD intervals of a tile fetch K-tiles 0 / 1 of the
+// block's next tile into the ring slots they would have used anyway, so there is no prologue burst, no pipeline drain / refill
+// and no block-wide barrier between tiles (see the boundary notes in the body).
+//
+// Template parameters:
+//   SET  : which fast epilogue forms are compiled in (gemm_epilogue_fast).
+//   TBM_ : 256, or 192 (round 5) = a 192 x 256 tile (six 16-row MFMA tiles per wave, 12-KiB A halves, 7 instead of 8 DMA pieces
+//          per wave and LOAD interval): M = 8728 x N = 4096 is 2.875 rounds of these instead of 2.19 rounds of 256 x 256 -- the
+//          rows beyond whole rounds cost no split-K planes.
+//   F8   : (round 5) OCP e4m3fn operands (the W8A8 prefill).  A K-tile is still 128 BYTES per row -- 128 elements -- so rings,
+//          DMA pieces, swizzle and fragment reads are the bf16 kernel's; the two 16-byte fragments of a lane feed ONE
+//          v_mfma_scale_f32_16x16x128_f8f6f4 (unit block scales) instead of two 16x16x32 bf16 MFMAs, and the per-row scales
+//          sa[m] sw[n] are applied to the accumulators in front of the SAME staged epilogues.
 // ------------------------------------------------------------------------------------
-// EARLY: the barrier that ends an MFMA interval is executed EARLY tile-rows before the interval's last MFMA.  Nothing after it
-// needs the barrier (the tail MFMAs read registers only), and the partner wave on the SIMD -- released by the same barrier --
-// starts its own MFMA stream while this wave is still feeding the pipe: no matrix-pipe bubble at the hand-over.
-template <int DBG, bool M32, int EARLY, bool STAGED = true, int SET = EPI_SET_COMMON, bool LW = false, bool LATEW = true, bool CONT = true, int TBM_ = 256, bool F8 = false>   // F8 (round 5): OCP e4m3fn operands (the W8A8 prefill): a K-tile is still 128 BYTES per row -- 128 elements -- so rings, DMA pieces, swizzle and fragment reads are the bf16 kernel's; the two 16-byte fragments of a lane feed ONE v_mfma_scale_f32_16x16x128_f8f6f4 (unit block scales) instead of two 16x16x32 bf16 MFMAs, and the per-row scales sa[m] sw[n] are applied to the accumulators in front of the SAME staged epilogues (the two-stage fp8 kernel it replaces was one tile per block with the general epilogue: 21-25 k cycles of an 83 k-cycle tile); TBM_ (round 5): 192 = a 192 x 256 tile (six 16-row MFMA tiles per wave, 12-KiB A halves, 7 instead of 8 DMA pieces per wave and LOAD interval): M = 8728 x N = 4096 is 2.875 rounds of these instead of 2.19 rounds of 256 x 256 -- the rows beyond whole rounds cost no split-K planes; CONT (product; r03): the DMA stream runs on ACROSS the block's tiles -- the last two LOAD intervals of a tile fetch K-tiles 0 / 1 of the block's next tile into the ring slots they would have used anyway, so there is no prologue burst, no pipeline drain / refill and no block-wide barrier between tiles (see the boundary notes in the body); LATEW (product; r03 A/B +1 % on every shape, bit-equal): group 0 waits for its W pieces of tile t+1 at the TOP of L(t+1) instead of between its last MFMA of M(t) and the barrier that hands the matrix pipe over; SET: which fast epilogue forms (gemm_epilogue_fast); M32: v_mfma_f32_32x32x16_bf16 (4x2 tiles per wave) instead of 16x16x32 (8x4)
+template <int SET = EPI_SET_COMMON, int TBM_ = 256, bool F8 = false>
 __global__ __launch_bounds__(512) void gemm_nt_bf16_ring_kernel(GemmArgs p) {
-  static_assert(TBM_ == 256 || (TBM_ == 192 && !M32 && LATEW && !LW), "the 192-row form exists for the product schedule only");
-  static_assert(!F8 || (!M32 && EARLY == 0 && DBG == 0), "fp8 operands: 16x16x128 MFMA, product schedule");
+  static_assert(TBM_ == 256 || TBM_ == 192, "256- or 192-row tiles");
   constexpr int EB = F8 ? 1 : 2;                        // bytes per operand element
   constexpr int BKE = 128 / EB;                         // elements per K-tile (128 bytes per row either way)
-  constexpr int TBM = TBM_, TBN = 256, WTM = TBM / 2, WTN = 64, TM = M32 ? 4 : WTM / 16, TN = M32 ? 2 : 4;
+  constexpr int TBM = TBM_, TBN = 256, WTM = TBM / 2, WTN = 64, TM = WTM / 16, TN = 4;
   constexpr int AH = WTM * BK * 2;                      // 16 KiB (12 KiB): one group's half of an A K-tile
   constexpr int APW = WTM / 32;                         // 1-KiB pieces (8 rows) of an A half per wave of a group: 4 (3)
   constexpr int BURST = APW + 4;                        // pieces per wave and LOAD interval: A half + W half
@@ -1385,8 +1077,7 @@ __global__ __launch_bounds__(512) void gemm_nt_bf16_ring_kernel(GemmArgs p) {
   int m0, n0, sm0, sn0;     // tile being computed / tile being staged
   tile_of(blockIdx.x, m0, n0);
   sm0 = m0; sn0 = n0;
-  typedef typename std::conditional<M32, f32x16, f32x4>::type acc_t;
-  acc_t acc[TM][TN];
+  f32x4 acc[TM][TN];
 
   // split-K (gridDim.y slices; the tail rows of the hybrid dispatch): slice z takes the k-tiles [z nk/S, (z+1) nk/S) and writes
   // its own raw fp32 plane (summed, rounded and finished by splitk_epilogue_kernel)
@@ -1411,13 +1102,13 @@ __global__ __launch_bounds__(512) void gemm_nt_bf16_ring_kernel(GemmArgs p) {
     voW[par] = (unsigned)(lr * p.ldw * EB + sl * 16);
   }
   // one 1-KiB piece = 8 rows x 128 B; `row` = first row inside the A (W) tile, `par` = its chunk index & 1 (swizzle key)
-  // (`tm0` / `tn0`: first row of the tile the K-tile belongs to -- the tile being computed, or with CONT the block's next one)
+  // (`tm0` / `tn0`: first row of the tile the K-tile belongs to -- the tile being computed, or, at the end of a k-loop, the block's next one)
   auto piece_a = [&](int tm0, int row, int t, int par, char* dst) {
-    const unsigned so = (unsigned)((int64_t)(tm0 + row) * p.lda * EB + (DBG == 7 ? (t & 3) : t) * 128);   // DBG 7 (timing experiment): the same four K-tiles over and over = cache-resident operands
+    const unsigned so = (unsigned)((int64_t)(tm0 + row) * p.lda * EB + t * 128);
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (__attribute__((address_space(3))) void*)dst, 16, voA[par] + so, 0, 0, 0);
   };
   auto piece_w = [&](int tn0, int row, int t, int par, char* dst) {
-    const unsigned so = (unsigned)((int64_t)(tn0 + row) * p.ldw * EB + (DBG == 7 ? (t & 3) : t) * 128);
+    const unsigned so = (unsigned)((int64_t)(tn0 + row) * p.ldw * EB + t * 128);
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW, (__attribute__((address_space(3))) void*)dst, 16, voW[par] + so, 0, 0, 0);
   };
   // tile prologue (all 8 waves, 14 pieces each): K-tile 0 whole, A_top and W of K-tile 1
@@ -1445,21 +1136,16 @@ __global__ __launch_bounds__(512) void gemm_nt_bf16_ring_kernel(GemmArgs p) {
     }
   };
   prologue();
-  if (p.skew > 0 && (blockIdx.x & 7)) {                 // persistent blocks: blockIdx & 7 = XCD; the delay persists over the tile walk
-    const unsigned long long t0 = __builtin_amdgcn_s_memtime(), d = (unsigned long long)(blockIdx.x & 7) * (unsigned)p.skew;
-    while (__builtin_amdgcn_s_memtime() - t0 < d) __builtin_amdgcn_s_sleep(16);
-  }
 
-  // fragments.  16x16x32: lane -> row (lane&15), 16-B slots (lane>>4) and 4 + (lane>>4) of the 64-k row (two MFMAs per tile);
-  // 32x32x16: lane -> row (lane&31), slots 2 kk + (lane>>5), kk = 0..3 (four MFMAs per tile).  24 ds_read_b128 either way.
-  const int frow = M32 ? (lane & 31) : (lane & 15), fsw = (lane >> 1) & 7;
-  constexpr int NKK = M32 ? 4 : 2;
+  // fragments: lane -> row (lane&15), 16-B slots (lane>>4) and 4 + (lane>>4) of the 64-k row (two MFMAs per tile): 24 ds_read_b128
+  const int frow = lane & 15, fsw = (lane >> 1) & 7;
+  constexpr int NKK = 2;
   int offk[NKK];
 #pragma unroll
-  for (int kk = 0; kk < NKK; ++kk) offk[kk] = (M32 ? ((kk * 2 + (lane >> 5)) ^ fsw) : ((kk * 4 + (lane >> 4)) ^ fsw)) << 4;
+  for (int kk = 0; kk < NKK; ++kk) offk[kk] = ((kk * 4 + (lane >> 4)) ^ fsw) << 4;
   const int a_base = frow * 128;                        // inside the group's own A ring slot
   const int w_base = (wc * WTN + frow) * 128;
-  constexpr int TSTRIDE = (M32 ? 32 : 16) * 128;        // bytes between the row tiles of a fragment set
+  constexpr int TSTRIDE = 16 * 128;       // bytes between the row tiles of a fragment set
   bf16x8 af[NKK][TM], wf[NKK][TN];
 
 #define RG_READ_FRAGS(aslot, wslot)                                                                  \
@@ -1474,41 +1160,25 @@ __global__ __launch_bounds__(512) void gemm_nt_bf16_ring_kernel(GemmArgs p) {
         af[kk][i] = *reinterpret_cast<const bf16x8*>(At_ + i * TSTRIDE + offk[kk]);                  \
   } while (0)
 
-#define RG_MFMA_PART(tail)                                                                           \
+#define RG_MFMA()                                                                          \
   do {                                                                                               \
     if constexpr (F8) {                                                                              \
-      if (!(tail)) {                                                                                 \
-        _Pragma("unroll") for (int i = 0; i < TM; ++i)                                               \
-          _Pragma("unroll") for (int j = 0; j < TN; ++j)                                             \
-            acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(                            \
-                __builtin_shufflevector(__builtin_bit_cast(i32x4r, wf[0][j]), __builtin_bit_cast(i32x4r, wf[1][j]), 0, 1, 2, 3, 4, 5, 6, 7), \
-                __builtin_shufflevector(__builtin_bit_cast(i32x4r, af[0][i]), __builtin_bit_cast(i32x4r, af[1][i]), 0, 1, 2, 3, 4, 5, 6, 7), \
-                acc[i][j], 0, 0, 0, 0x7f7f7f7f, 0, 0x7f7f7f7f);                                      \
-      }                                                                                              \
+      _Pragma("unroll") for (int i = 0; i < TM; ++i)                                                 \
+        _Pragma("unroll") for (int j = 0; j < TN; ++j)                                               \
+          acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(                              \
+              __builtin_shufflevector(__builtin_bit_cast(i32x4r, wf[0][j]), __builtin_bit_cast(i32x4r, wf[1][j]), 0, 1, 2, 3, 4, 5, 6, 7), \
+              __builtin_shufflevector(__builtin_bit_cast(i32x4r, af[0][i]), __builtin_bit_cast(i32x4r, af[1][i]), 0, 1, 2, 3, 4, 5, 6, 7), \
+              acc[i][j], 0, 0, 0, 0x7f7f7f7f, 0, 0x7f7f7f7f);                                        \
     } else                                                                                           \
     _Pragma("unroll") for (int kk = 0; kk < NKK; ++kk)                                               \
-      _Pragma("unroll") for (int i = 0; i < TM; ++i) {                                               \
-        const bool in_tail = (kk == NKK - 1) && (i >= TM - EARLY);                                   \
-        if (in_tail == (tail)) {                                                                     \
-          _Pragma("unroll") for (int j = 0; j < TN; ++j) {                                           \
-            if constexpr (M32) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[kk][j], af[kk][i], acc[i][j], 0, 0, 0); \
-            else acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[kk][j], af[kk][i], acc[i][j], 0, 0, 0);               \
-          }                                                                                          \
-        }                                                                                            \
-      }                                                                                              \
+      _Pragma("unroll") for (int i = 0; i < TM; ++i)                                                 \
+        _Pragma("unroll") for (int j = 0; j < TN; ++j)                                               \
+          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[kk][j], af[kk][i], acc[i][j], 0, 0, 0); \
   } while (0)
 #define RG_VMCNT(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
 
-  // DBG == 4: cycle stamps (s_memtime) of block 0, waves 0 and 4, into the buffer passed as `bias`
-  unsigned long long* stamps = (DBG == 4 && blockIdx.x == 0 && (wave == 0 || wave == 4) && lane == 0)
-                                   ? (unsigned long long*)p.bias + (wave ? 1 : 0) * 64 * 8 : nullptr;
-#define RG_STAMP(t, k) do { if (DBG == 4 && stamps && (t) < 64) stamps[(t) * 8 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
   const int g4 = wave & 3;
-  int tile_no = 0;
-  // tile-level stamps (DBG == 4), column 7 of rows 5 n .. 5 n + 4 for the block's n-th tile: k-loop entry, k-loop exit,
-  // next tile's prologue issued, epilogue issued, (next row group) next k-loop entry
-#define RG_TSTAMP(k) do { if (DBG == 4 && stamps && tile_no < 12) stamps[(tile_no * 5 + (k)) * 8 + 7] = __builtin_amdgcn_s_memtime(); } while (0)
-  // Tile boundaries with CONT (cont: the block has a next tile and nk >= 2).  The ping-pong keeps its two barriers per K-tile,
+  // Tile boundaries (cont: the block has a next tile and nk >= 2).  The ping-pong keeps its two barriers per K-tile,
   //   X(t) = [group 0: end of L(t) | group 1: end of M(t-1)]      Y(t) = [group 0: end of M(t) | group 1: end of L(t)]
   // and the boundary only stretches the interval between Y(nk-1) and X(0') of the next tile:
   //   group 0:  ... M(nk-1) Y(nk-1) [store tile]          L(0') X(0') M(0') ...
@@ -1520,44 +1190,29 @@ __global__ __launch_bounds__(512) void gemm_nt_bf16_ring_kernel(GemmArgs p) {
   //   after the wave's own epilogue, so no block-wide barrier is needed before the slot is reused;
   // * the stores of the epilogue count in vmcnt like the DMA pieces: one vmcnt(0) behind them (they were issued thousands of cycles
   //   after the last pieces) and the next k-loop's counted waits see DMA pieces only.
-  // Without CONT (and for nk == 1): prologue burst for the next tile before the epilogue, vmcnt(0) + block barrier at the k-loop entry.
+  // Without cont (nk == 1): prologue burst for the next tile before the epilogue, vmcnt(0) + block barrier at the k-loop entry.
   int wcur = 0, pa = 0;                                  // W ring slot / A parity of K-tile 0 of the current tile
-  bool fresh = true;                                     // the tile's K-tiles 0 / 1 come from a prologue burst (first tile, or no CONT)
+  bool fresh = true;                                     // the tile's K-tiles 0 / 1 come from a prologue burst (first tile, or nk == 1)
   for (int vb = blockIdx.x;;) {
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
-      for (int j = 0; j < TN; ++j) acc[i][j] = acc_t{};
-    if (p.xsync && gridDim.y == 1 && tid == 0) {
-      // the XCD's blocks (blockIdx & 7) start their n-th tile together: tiles that share operand panels then stream them through
-      // the XCD's L2 in step instead of drifting apart over the rounds.  Bounded spin: a block that cannot see its peers goes on alone.
-      const int x = blockIdx.x & 7, G = (int)gridDim.x, nbx = (G - x + 7) >> 3;
-      unsigned target = 0;
-      for (int r = 0; r <= tile_no; ++r) {
-        const int rem = ntiles - G * r - x;
-        target += (unsigned)min(max((rem + 7) >> 3, 0), nbx);
-      }
-      __hip_atomic_fetch_add(p.xsync + x, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      for (int it = 0; it < 400 && __hip_atomic_load(p.xsync + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target; ++it)
-        __builtin_amdgcn_s_sleep(4);
-    }
+      for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{};
     const int nb = vb + (int)gridDim.x;
     const bool more = nb < ntiles;
-    const bool cont = CONT && more && nk >= 2;           // K-tiles nk, nk+1 of this k-loop are K-tiles 0, 1 of the block's next tile
+    const bool cont = more && nk >= 2;                   // K-tiles nk, nk+1 of this k-loop are K-tiles 0, 1 of the block's next tile
     if (cont) tile_of(nb, sm0, sn0);                     // (sm0, sn0): the tile being staged = the next one from here on
     if (fresh) {
       A3V_WAIT_VM0();
       A3V_BARRIER();
       wcur = 0; pa = 0;
     }
-    RG_TSTAMP(0);
     // The k-loop is split into its steady part (t + 2 < nk: every piece belongs to this tile, no condition, addresses advance by a
     // constant) and the last two iterations, which may stage the next tile (TAIL): with the selects in every iteration the LOAD
     // interval grew from ~900 to ~1140 cycles and the whole K-tile period with it (the two intervals are co-critical).
     if (wr == 0) {
       auto iter = [&](int t, auto tailc) {
         constexpr bool TAIL = decltype(tailc)::value;
-        RG_STAMP(t, 0);
         const int wn2 = wcur == 0 ? 2 : wcur - 1;        // slot of K-tile t + 2
         if (!TAIL || t + 1 < nk || cont) {
           const bool nx = TAIL && t + 1 >= nk;
@@ -1571,47 +1226,21 @@ __global__ __launch_bounds__(512) void gemm_nt_bf16_ring_kernel(GemmArgs p) {
 #pragma unroll
           for (int c = 0; c < 4; ++c) piece_w(tn, (g4 * 4 + c) * 8, tk, c & 1, lds + WB + wn2 * WT + (g4 * 4 + c) * 1024);
         }
-        if constexpr (LATEW) {
-          // everything older than the bursts of L(t-1) and L(t) has landed: in particular this group's W half of tile t (the reads
-          // below); in steady state 8 + 8 pieces may stay in flight, the last two tiles of the block's last k-loop issue shorter bursts
-          if (!TAIL || t + 2 < nk || cont) vm_wait_imm<2 * BURST>();          // (16 with 256-row tiles)
-          else if (t + 2 == nk) vm_wait_imm<BURST + APW>();                      // L(t-1): A + W, L(t): A only (12)
-          else vm_wait_imm<APW>();                                                // only A_bot(nk-1) of L(nk-2) may be in flight (4)
-        }
+        // everything older than the bursts of L(t-1) and L(t) has landed: in particular this group's W half of tile t (the reads
+        // below); in steady state 8 + 8 pieces may stay in flight, the last two tiles of the block's last k-loop issue shorter bursts
+        if (!TAIL || t + 2 < nk || cont) vm_wait_imm<2 * BURST>();            // (16 with 256-row tiles)
+        else if (t + 2 == nk) vm_wait_imm<BURST + APW>();                        // L(t-1): A + W, L(t): A only (12)
+        else vm_wait_imm<APW>();                                                  // only A_bot(nk-1) of L(nk-2) may be in flight (4)
         RG_READ_FRAGS(lds + ATOP + ((pa ^ t) & 1) * AH, lds + WB + wcur * WT);
         A3V_WAIT_LGKM0();
-        RG_STAMP(t, 1);
-        if constexpr (LW) {                              // variant: W(t+1) is waited for HERE (one interval earlier), so nothing stands
-          if (!TAIL || t + 2 < nk || cont) RG_VMCNT(8);  // between this group's last MFMA and the barrier that releases the other group
-          else if (t + 2 == nk) RG_VMCNT(4);
-          else RG_VMCNT(0);                               // (LW: 256-row tiles only)
-        } else {
-          if (!TAIL || t + 2 < nk || cont) vm_wait_imm<BURST + 4>();              // this burst + the W half of the previous one (12)
-          else if (t + 2 == nk) vm_wait_imm<APW + 4>();                          // this burst (A only) + the W half of L(t-1) (8)
-          else RG_VMCNT(0);
-        }
-        RG_STAMP(t, 2);
+        if (!TAIL || t + 2 < nk || cont) vm_wait_imm<BURST + 4>();                // this burst + the W half of the previous one (12)
+        else if (t + 2 == nk) vm_wait_imm<APW + 4>();                            // this burst (A only) + the W half of L(t-1) (8)
+        else RG_VMCNT(0);
         A3V_BARRIER();
-        RG_STAMP(t, 3);
         __builtin_amdgcn_s_setprio(1);
-        RG_MFMA_PART(false);
+        RG_MFMA();
         __builtin_amdgcn_s_setprio(0);                 // never wait (vmcnt / barrier) at raised priority: measured -20 %
-        RG_STAMP(t, 4);
-        if constexpr (!LW && !LATEW) {
-          if (!TAIL || t + 2 < nk || cont) RG_VMCNT(8);
-          else if (t + 2 == nk) RG_VMCNT(4);
-          else RG_VMCNT(0);
-        }
-        RG_STAMP(t, 5);
-        if constexpr (EARLY > 0) __builtin_amdgcn_sched_barrier(0);   // keep the tail MFMAs behind the barrier, the others before it
         A3V_BARRIER();
-        if constexpr (EARLY > 0) __builtin_amdgcn_sched_barrier(0);
-        RG_STAMP(t, 6);
-        if constexpr (EARLY > 0) {
-          __builtin_amdgcn_s_setprio(1);
-          RG_MFMA_PART(true);
-          __builtin_amdgcn_s_setprio(0);
-        }
         wcur = wcur == 2 ? 0 : wcur + 1;
       };
       int t = 0;
@@ -1622,7 +1251,6 @@ __global__ __launch_bounds__(512) void gemm_nt_bf16_ring_kernel(GemmArgs p) {
       if (fresh) A3V_BARRIER();
       auto iter = [&](int t, auto tailc) {
         constexpr bool TAIL = decltype(tailc)::value;
-        RG_STAMP(t, 0);
         const int wn2 = wcur == 0 ? 2 : wcur - 1;
         if (!TAIL || t + 2 < nk || cont) {
           const bool nx = TAIL && t + 2 >= nk;
@@ -1634,41 +1262,24 @@ __global__ __launch_bounds__(512) void gemm_nt_bf16_ring_kernel(GemmArgs p) {
         }
         RG_READ_FRAGS(lds + ABOT + ((pa ^ t) & 1) * AH, lds + WB + wcur * WT);
         A3V_WAIT_LGKM0();
-        RG_STAMP(t, 1);
         if (!TAIL || t + 2 < nk || cont) vm_wait_imm<BURST>();                   // its previous burst (W half + A_top of tile t+1) has landed (8)
         else RG_VMCNT(0);
-        RG_STAMP(t, 2);
         A3V_BARRIER();
-        RG_STAMP(t, 3);
         __builtin_amdgcn_s_setprio(1);
-        RG_MFMA_PART(false);
+        RG_MFMA();
         __builtin_amdgcn_s_setprio(0);                 // never wait (vmcnt / barrier) at raised priority: measured -20 %
-        RG_STAMP(t, 4);
-        RG_STAMP(t, 5);
-        if (!TAIL || t + 1 < nk || !cont) {                       // X(t+1) (or the block barrier that ends a k-loop without cont); with cont X(0') follows the epilogue
-          if constexpr (EARLY > 0) __builtin_amdgcn_sched_barrier(0);   // keep the tail MFMAs behind the barrier, the others before it
-          A3V_BARRIER();
-          if constexpr (EARLY > 0) __builtin_amdgcn_sched_barrier(0);
-        }
-        RG_STAMP(t, 6);
-        if constexpr (EARLY > 0) {
-          __builtin_amdgcn_s_setprio(1);
-          RG_MFMA_PART(true);
-          __builtin_amdgcn_s_setprio(0);
-        }
+        if (!TAIL || t + 1 < nk || !cont) A3V_BARRIER();          // X(t+1) (or the block barrier that ends a k-loop without cont); with cont X(0') follows the epilogue
         wcur = wcur == 2 ? 0 : wcur + 1;
       };
       int t = 0;
       for (; t + 2 < nk; ++t) iter(t, std::false_type{});
       for (; t < nk; ++t) iter(t, std::true_type{});
     }
-    RG_TSTAMP(1);
     // every read of the rings is behind the last barrier.  No cont: stage the next tile now (prologue burst), store this one after.
     if (more && !cont) {
       tile_of(nb, sm0, sn0);
       prologue();
     }
-    RG_TSTAMP(2);
     {
       int lane_e = lane;
       asm volatile("" : "+v"(lane_e));
@@ -1691,11 +1302,8 @@ __global__ __launch_bounds__(512) void gemm_nt_bf16_ring_kernel(GemmArgs p) {
             for (int r = 0; r < 4; ++r) acc[i][j][r] *= sam * swv[j][r];
         }
       }
-      if constexpr (M32) gemm_epilogue32<TM, TN>(acc, p, m0 + wr * WTM, n0 + wc * WTN, lane_e);
-      else gemm_epilogue<TM, TN, false, SET>(acc, p, m0 + wr * WTM, n0 + wc * WTN, lane_e, STAGED ? lds + WB + wst * WT + wave * 4096 : nullptr);
+      gemm_epilogue<TM, TN, false, SET>(acc, p, m0 + wr * WTM, n0 + wc * WTN, lane_e, lds + WB + wst * WT + wave * 4096);
     }
-    RG_TSTAMP(3);
-    ++tile_no;
     if (!more) break;
     if (cont) {
       A3V_WAIT_LGKM0();                                  // the wave's own patch reads are done: its next pieces may land in the patch
@@ -1708,370 +1316,10 @@ __global__ __launch_bounds__(512) void gemm_nt_bf16_ring_kernel(GemmArgs p) {
     }
     vb = nb; m0 = sm0; n0 = sn0;
   }
-#undef RG_TSTAMP
-#undef RG_STAMP
 #undef RG_VMCNT
 #undef RG_READ_FRAGS
-#undef RG_MFMA_PART
+#undef RG_MFMA
 }
-
-// ------------------------------------------------------------------------------------
-// One-wave-per-SIMD form: 256 threads = 4 waves (2 x 2), each wave owns a 128 x 128 quarter of the 256 x 256 tile (256 fp32
-// accumulators in the accumulation registers + two fragment buffers of 64 VGPRs: the 512-register budget of a wave that has its
-// SIMD to itself).  No second wave to hand the matrix pipe to: the fragment reads of sub-stage s+1 are issued between the MFMAs
-// of sub-stage s by the same wave, and the only synchronisation is one workgroup barrier per 32-k sub-stage.
-//   LDS: ring of 5 sub-stages x 32 KiB; a sub-stage = 32 k of the A tile (256 rows x 64 B) + 32 k of the W tile (256 x 64 B);
-//        the 16-byte slot q of row r sits at q ^ ((r >> 2) & 3): conflict-free ds_read_b128 of 16 rows x one slot.
-//   DMA: each wave issues 8 one-KiB pieces (16 rows x 64 B) per sub-stage, four sub-stages (two K-tile periods) ahead.
-//   iteration s:  vmcnt(own pieces of s+1 landed) ; barrier  (=> stage s+1 visible, stage s read by everyone)
-//                 per MFMA row (8 MFMAs): two ds_read_b128 of stage s+1 into the other buffer and one DMA piece of stage s+4
-//                 -> slot (s+4) % 5 (stage s-1's slot).  All eight pieces in one burst from four waves at once cost 520
-//                 cycles per sub-stage: the CU's address unit takes ~16 cycles per piece and the issuing wave stalls
-//   LDS read traffic per K-tile and CU: 128 KiB (8-wave kernels: 192 KiB).
-// ------------------------------------------------------------------------------------
-#ifdef A3V_EXPERIMENTS   // measured and not dispatched: built only with `make EXPERIMENTS=1`
-template <int DBG, int SET = EPI_SET_COMMON>   // DBG 4: cycle stamps; 8: no DMA in the k-loop, 9: no DMA and no fragment reads, 10: every k-loop piece out of bounds = issued but fetching nothing (timing experiments, wrong results)
-__global__ __launch_bounds__(256) void gemm_nt_bf16_w4_kernel(GemmArgs p) {
-  constexpr int TBM = 256, TBN = 256, KS = 32, NST = 5;
-  constexpr int HALF = 256 * KS * 2;                    // 16 KiB: the A (or W) part of a sub-stage
-  constexpr int STG = 2 * HALF;                         // 32 KiB
-  __shared__ __attribute__((aligned(1024))) char lds[NST * STG];   // 163840 B
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wr = wave >> 1, wc = wave & 1;
-
-  const int ntiles = p.tiles_m * p.tiles_n;
-  auto tile_of = [&](int vb, int& tm0, int& tn0) {
-    const int xcd = vb & 7, q = ntiles >> 3, r = ntiles & 7;
-    const int bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (vb >> 3);
-    const int per_group = GROUP_M * p.tiles_n;
-    const int group = bid / per_group;
-    const int first_m = group * GROUP_M;
-    const int gsz = min(p.tiles_m - first_m, GROUP_M);
-    const int in_g = bid - group * per_group;
-    tm0 = (first_m + in_g % gsz) * TBM;
-    tn0 = (in_g / gsz) * TBN;
-  };
-  int m0, n0, sm0, sn0;
-  tile_of(blockIdx.x, m0, n0);
-  sm0 = m0; sn0 = n0;
-  if (gridDim.y > 1) {                                  // split-K slices as in the ring kernel
-    const int nk_all = p.K / BK, z = blockIdx.y, S = gridDim.y;
-    const int t0 = (int)(((int64_t)z * nk_all) / S), t1 = (int)(((int64_t)(z + 1) * nk_all) / S);
-    p.A += (int64_t)t0 * BK;
-    p.W += (int64_t)t0 * BK;
-    p.K = (t1 - t0) * BK;
-    p.C = reinterpret_cast<char*>(p.C) + (int64_t)z * p.c_split;
-  }
-  const int ns = p.K / KS;                              // even (K % 64 == 0)
-  const auto rsA = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, (int)(((int64_t)(p.M - 1) * p.lda + p.K) * 2), 0x00020000);
-  const auto rsW = __builtin_amdgcn_make_buffer_rsrc((void*)p.W, 0, (int)(((int64_t)(p.N - 1) * p.ldw + p.K) * 2), 0x00020000);
-  // DMA lane -> (row lane/4 of the 16-row piece, physical slot lane%4) <- logical slot (lane%4) ^ ((row >> 2) & 3)
-  const unsigned lsl = (lane & 3) ^ ((lane >> 4) & 3);
-  const unsigned voA = (unsigned)(((lane >> 2) * p.lda + lsl * 8) * 2);
-  const unsigned voW = (unsigned)(((lane >> 2) * p.ldw + lsl * 8) * 2);
-  // piece c (0..3: A rows, 4..7: W rows) of this wave's 8 one-KiB pieces of sub-stage s of tile (sm0, sn0)
-  // `kill` = 0x80000000 pushes the offset past the buffer's bound: the piece fetches nothing (zeros land in a free slot) but still
-  // counts in vmcnt, so the k-loop needs no branches and one constant wait count
-  auto piece = [&](int s, int c, unsigned kill) {
-    char* const dst = lds + (s % NST) * STG;
-    const int ch = wave * 4 + (c & 3);
-    if (c < 4) {
-      const unsigned so = (unsigned)(((int64_t)(sm0 + ch * 16) * p.lda + s * KS) * 2) | kill;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (__attribute__((address_space(3))) void*)(dst + ch * 1024), 16, voA + so, 0, 0, 0);
-    } else {
-      const unsigned so = (unsigned)(((int64_t)(sn0 + ch * 16) * p.ldw + s * KS) * 2) | kill;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW, (__attribute__((address_space(3))) void*)(dst + HALF + ch * 1024), 16, voW + so, 0, 0, 0);
-    }
-  };
-  auto stage = [&](int s) {
-#pragma unroll
-    for (int c = 0; c < 8; ++c) piece(s, c, 0u);
-  };
-  auto prologue = [&]() {                               // stages 0..3, the two halves of a line back to back (ns is even)
-#pragma unroll
-    for (int s = 0; s < 4; s += 2)
-      if (s < ns) {
-#pragma unroll
-        for (int c = 0; c < 8; ++c) { piece(s, c, 0u); piece(s + 1, c, 0u); }
-      }
-  };
-  prologue();
-
-  // fragments of one sub-stage: A row tile i -> row wr*128 + 16 i + (lane & 15), logical slot lane >> 4; W likewise with wc
-  const int fl = lane & 15;
-  const int fq = ((lane >> 4) ^ ((fl >> 2) & 3)) << 4;
-  const int a_off = (wr * 128 + fl) * 64 + fq;
-  const int w_off = HALF + (wc * 128 + fl) * 64 + fq;
-  bf16x8 af[2][8], wf[2][8];
-  f32x4 accl[8][4], accr[8][4];                         // columns 0..63 / 64..127 of the wave's quarter (two epilogue calls)
-
-  unsigned long long* stamps = (DBG == 4 && blockIdx.x == 0 && lane == 0) ? (unsigned long long*)p.bias + wave * 64 * 8 : nullptr;
-#define W4_STAMP(s, k) do { if (DBG == 4 && stamps && (s) < 64) stamps[(s) * 8 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
-#define W4_TSTAMP(k) do { if (DBG == 4 && stamps && tile_no < 12) stamps[tile_no * 8 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
-  int tile_no = 0;
-#define W4_VMCNT(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
-  // The k-loop is written instruction by instruction (volatile asm keeps the order): accumulators pinned to the accumulation
-  // registers ("+a", in place), fragment reads as explicit ds_read_b128 placed between the MFMA rows.  The compiler's own
-  // scheduling of the builtin form moved half of the accumulators into VGPRs and shuffled them through v_accvgpr moves.
-#define W4_READ(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
-#define W4_MFMA(c, w, a) asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(c) : "v"(w), "v"(a))
-  // MFMA j of row g; after it, this wave's slot j of the row: wave PH reads its two fragments behind MFMAs 2 PH and 2 PH + 1
-  // (row 7: both behind MFMA PH, so the last reads have >= 4 MFMAs to return in) and issues its DMA piece behind MFMA
-  // (2 PH + 4) % 8.  The four waves run in lock step (one barrier per sub-stage): without the stagger they hit the LDS and the
-  // address unit in the same cycle and each piece stalls its wave ~50 cycles (40 % of the kernel).
-#define W4_SLOT(cur, nxt, s, PH, g, j, EVEN)                                                                  \
-  do {                                                                                                        \
-    if ((j) < 4) W4_MFMA(accl[g][(j) & 3], wf[cur][j], af[cur][g]);                                           \
-    else W4_MFMA(accr[g][(j) & 3], wf[cur][j], af[cur][g]);                                                   \
-    if (DBG != 9 && (j) == ((g) < 7 ? 2 * (PH) : (PH))) W4_READ(af[nxt][g], ra_, (g) * 1024);                 \
-    if (DBG != 9 && (j) == ((g) < 7 ? 2 * (PH) + 1 : (PH))) W4_READ(wf[nxt][g], rw_, (g) * 1024);             \
-    if (DBG < 8 && (EVEN) && (j) == ((2 * (PH) + 4) & 7)) piece((s) + 4, g, kill_);                           \
-    if (DBG < 8 && (EVEN) && (j) == ((2 * (PH) + 5) & 7)) piece((s) + 5, g, kill2_);                          \
-  } while (0)
-  // one sub-stage: MFMAs of stage s from buffer `cur`, the fragments of stage s+1 into buffer `nxt`; EVEN sub-stages issue the
-  // pieces of stages s+4 and s+5 pairwise -- the two 64-byte halves of the same 128-byte lines back to back, so the second
-  // request finds the line in (or on its way into) the vector L1 instead of fetching it from L2 a second time one sub-stage later
-#define W4_ITER(cur, nxt, s, PH, EVEN)                                                                        \
-  do {                                                                                                        \
-    W4_STAMP(s, 0);                                                                                           \
-    if (DBG < 8) W4_VMCNT(16);                          /* everything but the newest pair of stages has landed */ \
-    W4_STAMP(s, 1);                                                                                           \
-    A3V_BARRIER();                                                                                            \
-    W4_STAMP(s, 2);                                                                                           \
-    const unsigned nb_ = (unsigned)((((s) + 1) % NST) * STG);                                                 \
-    const unsigned ra_ = nb_ + (unsigned)a_off, rw_ = nb_ + (unsigned)w_off;                                  \
-    const unsigned kill_ = ((s) + 4 < ns && DBG != 10) ? 0u : 0x80000000u, kill2_ = ((s) + 5 < ns && DBG != 10) ? 0u : 0x80000000u; \
-    _Pragma("unroll") for (int g = 0; g < 8; ++g) {                                                           \
-      _Pragma("unroll") for (int j = 0; j < 8; ++j) W4_SLOT(cur, nxt, s, PH, g, j, EVEN);                     \
-    }                                                                                                         \
-    W4_STAMP(s, 3);                                                                                           \
-    A3V_WAIT_LGKM0();                                                                                         \
-    W4_STAMP(s, 4);                                                                                           \
-  } while (0)
-#define W4_KLOOP(PH)                                                                                          \
-  for (int s = 0; s < ns; s += 2) {                     /* (the last sub-stage reads one stage past the end: in-ring, never used) */ \
-    W4_ITER(0, 1, s, PH, true);                                                                               \
-    W4_ITER(1, 0, s + 1, PH, false);                                                                          \
-  }
-
-  // clock probe (DBG >= 4 with a buffer in `bias`): shader-clock and 100-MHz real-time counters at kernel entry / exit of block 0
-  unsigned long long* const probe = (DBG >= 4 && p.bias && blockIdx.x == 0 && tid == 0) ? (unsigned long long*)p.bias + 4 * 64 * 8 : nullptr;
-  if (probe) { probe[0] = __builtin_amdgcn_s_memtime(); probe[1] = __builtin_amdgcn_s_memrealtime(); }
-  for (int vb = blockIdx.x;;) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) { accl[i][j] = f32x4{}; accr[i][j] = f32x4{}; }
-    W4_TSTAMP(5);
-    A3V_WAIT_VM0();
-    A3V_BARRIER();
-    W4_TSTAMP(6);
-#pragma unroll
-    for (int g = 0; g < 8; ++g) { W4_READ(af[0][g], (unsigned)a_off, g * 1024); W4_READ(wf[0][g], (unsigned)w_off, g * 1024); }
-    A3V_WAIT_LGKM0();
-    if (wave == 0) { W4_KLOOP(0) }
-    else if (wave == 1) { W4_KLOOP(1) }
-    else if (wave == 2) { W4_KLOOP(2) }
-    else { W4_KLOOP(3) }
-    asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");    // the last MFMAs retire before the epilogue's v_accvgpr_read (no interlock)
-    W4_TSTAMP(7);
-    A3V_BARRIER();                                       // the last reads of the ring are done: the next tile may land
-    const int nb = vb + (int)gridDim.x;
-    if (nb < ntiles) {
-      tile_of(nb, sm0, sn0);
-      prologue();
-    }
-    {
-      int lane_e = lane;
-      asm volatile("" : "+v"(lane_e));
-      char* const patch = lds + 4 * STG + wave * 4096;   // slot 4: the prologue fills slots 0..3
-      gemm_epilogue<8, 4, false, SET>(accl, p, m0 + wr * 128, n0 + wc * 128, lane_e, patch);
-      gemm_epilogue<8, 4, false, SET>(accr, p, m0 + wr * 128, n0 + wc * 128 + 64, lane_e, patch);
-    }
-    ++tile_no;
-    if (nb >= ntiles) break;
-    vb = nb; m0 = sm0; n0 = sn0;
-  }
-  if (probe) { probe[2] = __builtin_amdgcn_s_memtime(); probe[3] = __builtin_amdgcn_s_memrealtime(); }
-#undef W4_TSTAMP
-#undef W4_KLOOP
-#undef W4_ITER
-#undef W4_SLOT
-#undef W4_READ
-#undef W4_MFMA
-#undef W4_VMCNT
-#undef W4_STAMP
-}
-#endif  // A3V_EXPERIMENTS
-
-// ------------------------------------------------------------------------------------
-// "Overlapped" form: the 8 waves and 128 x 64 wave tiles of the ring kernel on the 32-k sub-stage ring of the kernel above, but
-// no L / M phases: every wave runs ONE stream in which its own fragment reads (12 per sub-stage) and DMA pieces sit in the
-// shadows of its MFMAs (32 per sub-stage), hand-ordered (volatile asm), accumulators pinned to AGPRs.  The two waves of a SIMD
-// issue into the matrix pipe whenever they can; when one stalls on a load issue the other one's MFMAs go out -- nobody hands
-// the pipe over.  One barrier per sub-stage; the two groups meet it half a sub-stage apart (group 0 at the top of its
-// iteration, group 1 after its 16th MFMA), so while one wave of a SIMD waits, its partner still has MFMAs to issue.
-//   group 0, iteration s:  vmcnt ; barrier(s) ; rows 0..7: 4 MFMAs + reads of stage s+1 (+ pieces on even s) ; lgkmcnt(0)
-//   group 1, iteration s:  rows 0..3: 4 MFMAs (+ pieces on even s) ; vmcnt ; barrier(s) ; rows 4..7: 4 MFMAs + reads ; lgkmcnt(0)
-//   pieces: 16 rows x 64 B; even sub-stages issue stages s+4 and s+5 pairwise (both halves of a 128-B line back to back).
-// ------------------------------------------------------------------------------------
-#ifdef A3V_EXPERIMENTS   // measured and not dispatched: built only with `make EXPERIMENTS=1`
-template <int DBG, int SET = EPI_SET_COMMON>
-__global__ __launch_bounds__(512) void gemm_nt_bf16_ov_kernel(GemmArgs p) {
-  constexpr int TBM = 256, TBN = 256, KS = 32, NST = 5;
-  constexpr int HALF = 256 * KS * 2;                    // 16 KiB: the A (or W) part of a sub-stage
-  constexpr int STG = 2 * HALF;                         // 32 KiB
-  __shared__ __attribute__((aligned(1024))) char lds[NST * STG];   // 163840 B
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wr = wave >> 2, wc = wave & 3;             // wr = group: waves 0..3 and 4..7 share the four SIMDs pairwise
-
-  const int ntiles = p.tiles_m * p.tiles_n;
-  auto tile_of = [&](int vb, int& tm0, int& tn0) {
-    const int xcd = vb & 7, q = ntiles >> 3, r = ntiles & 7;
-    const int bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (vb >> 3);
-    const int per_group = GROUP_M * p.tiles_n;
-    const int group = bid / per_group;
-    const int first_m = group * GROUP_M;
-    const int gsz = min(p.tiles_m - first_m, GROUP_M);
-    const int in_g = bid - group * per_group;
-    tm0 = (first_m + in_g % gsz) * TBM;
-    tn0 = (in_g / gsz) * TBN;
-  };
-  int m0, n0, sm0, sn0;
-  tile_of(blockIdx.x, m0, n0);
-  sm0 = m0; sn0 = n0;
-  if (gridDim.y > 1) {                                  // split-K slices as in the ring kernel
-    const int nk_all = p.K / BK, z = blockIdx.y, S = gridDim.y;
-    const int t0 = (int)(((int64_t)z * nk_all) / S), t1 = (int)(((int64_t)(z + 1) * nk_all) / S);
-    p.A += (int64_t)t0 * BK;
-    p.W += (int64_t)t0 * BK;
-    p.K = (t1 - t0) * BK;
-    p.C = reinterpret_cast<char*>(p.C) + (int64_t)z * p.c_split;
-  }
-  const int ns = p.K / KS;                              // even (K % 64 == 0)
-  const auto rsA = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, (int)(((int64_t)(p.M - 1) * p.lda + p.K) * 2), 0x00020000);
-  const auto rsW = __builtin_amdgcn_make_buffer_rsrc((void*)p.W, 0, (int)(((int64_t)(p.N - 1) * p.ldw + p.K) * 2), 0x00020000);
-  const unsigned lsl = (lane & 3) ^ ((lane >> 4) & 3);
-  const unsigned voA = (unsigned)(((lane >> 2) * p.lda + lsl * 8) * 2);
-  const unsigned voW = (unsigned)(((lane >> 2) * p.ldw + lsl * 8) * 2);
-  // piece c (0, 1: A rows, 2, 3: W rows) of this wave's 4 one-KiB pieces of sub-stage s; `kill`: see the kernel above
-  auto piece = [&](int s, int c, unsigned kill) {
-    char* const dst = lds + (s % NST) * STG;
-    const int ch = wave * 2 + (c & 1);
-    if (c < 2) {
-      const unsigned so = (unsigned)(((int64_t)(sm0 + ch * 16) * p.lda + (DBG == 11 ? (s & 3) : DBG == 12 ? (s & 7) : DBG == 13 ? (s & 31) : s) * KS) * 2) | kill;   // DBG 11 / 12 / 13: the same 4 / 8 / 32 sub-stages over and over (L1 / L2 hits)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (__attribute__((address_space(3))) void*)(dst + ch * 1024), 16, voA + so, 0, 0, 0);
-    } else {
-      const unsigned so = (unsigned)(((int64_t)(sn0 + ch * 16) * p.ldw + (DBG == 11 ? (s & 3) : DBG == 12 ? (s & 7) : DBG == 13 ? (s & 31) : s) * KS) * 2) | kill;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW, (__attribute__((address_space(3))) void*)(dst + HALF + ch * 1024), 16, voW + so, 0, 0, 0);
-    }
-  };
-  auto prologue = [&]() {                               // stages 0..3, the two halves of a line back to back (ns is even)
-#pragma unroll
-    for (int s = 0; s < 4; s += 2)
-      if (s < ns) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) { piece(s, c, 0u); piece(s + 1, c, 0u); }
-      }
-  };
-  prologue();
-
-  const int fl = lane & 15;
-  const int fq = ((lane >> 4) ^ ((fl >> 2) & 3)) << 4;
-  const int a_off = (wr * 128 + fl) * 64 + fq;
-  const int w_off = HALF + (wc * 64 + fl) * 64 + fq;
-  bf16x8 af[2][8], wf[2][4];
-  f32x4 acc[8][4];
-
-#define OV_VMCNT(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
-#define OV_READ(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
-#define OV_MFMA(c, w, a) asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(c) : "v"(w), "v"(a))
-  // the 12 reads of stage s+1 in read slots 0..15 (slot = 4 * row-in-window + MFMA index): A_0..A_7 in slots 0..7, W_0..W_3 in 8..11
-#define OV_RSLOT(nxt, q)                                                                                      \
-  do {                                                                                                        \
-    if (DBG != 9 && (q) < 8) OV_READ(af[nxt][(q) & 7], ra_, ((q) & 7) * 1024);                                \
-    if (DBG != 9 && (q) >= 8 && (q) < 12) OV_READ(wf[nxt][(q) & 3], rw_, ((q) & 3) * 1024);                   \
-  } while (0)
-  // row g of the MFMA stream.  RB = first row of the read window (group 0: rows 0..7 two MFMAs apart, group 1: rows 4..7 every MFMA)
-#define OV_ROW(cur, nxt, s, g, GRP, EVEN)                                                                     \
-  do {                                                                                                        \
-    _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                           \
-      OV_MFMA(acc[g][j], wf[cur][j], af[cur][g]);                                                             \
-      if ((GRP) == 0) { if (((j) & 1) == 0) OV_RSLOT(nxt, (g) * 2 + ((j) >> 1)); }                            \
-      else { if ((g) >= 4) OV_RSLOT(nxt, ((g) - 4) * 4 + (j)); }                                              \
-      if (DBG < 8 && (EVEN) && (j) == 1 && ((GRP) == 0 || (g) < 4)) {                                         \
-        if ((GRP) == 0) piece((s) + 4 + ((g) & 1), (g) >> 1, ((g) & 1) ? kill2_ : kill_);                     \
-        else { piece((s) + 4, g, kill_); }                                                                    \
-      }                                                                                                       \
-      if (DBG < 8 && (EVEN) && (j) == 3 && (GRP) == 1 && (g) < 4) piece((s) + 5, g, kill2_);                  \
-    }                                                                                                         \
-  } while (0)
-#define OV_ITER(cur, nxt, s, GRP, EVEN)                                                                       \
-  do {                                                                                                        \
-    const unsigned nb_ = (unsigned)((((s) + 1) % NST) * STG);                                                 \
-    const unsigned ra_ = nb_ + (unsigned)a_off, rw_ = nb_ + (unsigned)w_off;                                  \
-    const unsigned kill_ = ((s) + 4 < ns && DBG != 10) ? 0u : 0x80000000u, kill2_ = ((s) + 5 < ns && DBG != 10) ? 0u : 0x80000000u; \
-    if ((GRP) == 0) {                                                                                         \
-      if (DBG < 8) OV_VMCNT(8);                         /* all but the newest pair of stages (4 pieces each) */ \
-      A3V_BARRIER();                                                                                          \
-      _Pragma("unroll") for (int g = 0; g < 8; ++g) OV_ROW(cur, nxt, s, g, GRP, EVEN);                        \
-    } else {                                                                                                  \
-      _Pragma("unroll") for (int g = 0; g < 4; ++g) OV_ROW(cur, nxt, s, g, GRP, EVEN);                        \
-      if (DBG < 8) { if (EVEN) OV_VMCNT(16); else OV_VMCNT(8); }   /* EVEN: this iteration's pair is already out */ \
-      A3V_BARRIER();                                                                                          \
-      _Pragma("unroll") for (int g = 4; g < 8; ++g) OV_ROW(cur, nxt, s, g, GRP, EVEN);                        \
-    }                                                                                                         \
-    A3V_WAIT_LGKM0();                                                                                         \
-  } while (0)
-#define OV_KLOOP(GRP)                                                                                         \
-  for (int s = 0; s < ns; s += 2) {                     /* (the last sub-stage reads one stage past the end: in-ring, never used) */ \
-    OV_ITER(0, 1, s, GRP, true);                                                                              \
-    OV_ITER(1, 0, s + 1, GRP, false);                                                                         \
-  }
-
-  for (int vb = blockIdx.x;;) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{};
-    A3V_WAIT_VM0();
-    A3V_BARRIER();
-#pragma unroll
-    for (int g = 0; g < 8; ++g) OV_READ(af[0][g], (unsigned)a_off, g * 1024);
-#pragma unroll
-    for (int g = 0; g < 4; ++g) OV_READ(wf[0][g], (unsigned)w_off, g * 1024);
-    A3V_WAIT_LGKM0();
-    if (wr == 0) { OV_KLOOP(0) }
-    else { OV_KLOOP(1) }
-    asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");    // the last MFMAs retire before the epilogue's v_accvgpr_read (no interlock)
-    A3V_BARRIER();                                       // the last reads of the ring are done: the next tile may land
-    const int nb = vb + (int)gridDim.x;
-    if (nb < ntiles) {
-      tile_of(nb, sm0, sn0);
-      prologue();
-    }
-    {
-      int lane_e = lane;
-      asm volatile("" : "+v"(lane_e));
-      char* const patch = lds + 4 * STG + wave * 4096;   // slot 4: the prologue fills slots 0..3
-      gemm_epilogue<8, 4, false, SET>(acc, p, m0 + wr * 128, n0 + wc * 64, lane_e, patch);
-    }
-    if (nb >= ntiles) break;
-    vb = nb; m0 = sm0; n0 = sn0;
-  }
-#undef OV_KLOOP
-#undef OV_ITER
-#undef OV_ROW
-#undef OV_RSLOT
-#undef OV_MFMA
-#undef OV_READ
-#undef OV_VMCNT
-}
-#endif  // A3V_EXPERIMENTS
 
 // ------------------------------------------------------------------------------------
 // fp8 (OCP e4m3fn) form of the 256x256 ping-pong kernel: A [M][K] and W [N][K] are fp8 bytes, one k-tile is 128 elements =
@@ -2387,137 +1635,6 @@ __global__ __launch_bounds__(512) void gemm_tn_bf16_pp_kernel(GemmArgs p) {
 // transpose reads has to be issued from inline asm (s_mov_b32 m0 / buffer_load_dwordx4 ... offen lds).
 // Same schedule with v_mfma_f32_32x32x16_bf16 (8-pass, higher sustained rate than 16x16x32):
 // wave tile 128x64 = 4x2 tiles of 32x32, 4 k-steps of 16 per K-tile, 32 MFMAs per interval.
-#ifdef A3V_EXPERIMENTS   // measured and not dispatched: built only with `make EXPERIMENTS=1`
-template <int DBG>
-__global__ __launch_bounds__(512) void gemm_nt_bf16_pp32_kernel(GemmArgs p) {
-  constexpr int TBM = 256, TBN = 256, NW = 8, WTM = 128, WTN = 64, TM = 4, TN = 2;
-  constexpr int STAGE = (TBM + TBN) * BK * 2;   // 64 KiB
-  __shared__ __attribute__((aligned(1024))) char lds[2 * STAGE];
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wr = wave >> 2, wc = wave & 3;
-
-  const int nwg = gridDim.x;
-  int bid = blockIdx.x;
-  {
-    const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
-  const int per_group = GROUP_M * p.tiles_n;
-  const int group = bid / per_group;
-  const int first_m = group * GROUP_M;
-  const int gsz = min(p.tiles_m - first_m, GROUP_M);
-  const int in_g = bid - group * per_group;
-  const int tm = first_m + in_g % gsz;
-  const int tn = in_g / gsz;
-  const int m0 = tm * TBM, n0 = tn * TBN;
-
-  f32x16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-  const int nk = p.K / BK;
-  // LDS-DMA through buffer descriptors: rows past M / N are out of range and read as zero (no
-  // clamping VALU), addresses are {SGPR descriptor, 32-bit VGPR offset, SGPR k-offset}.
-  const auto rsA = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, (int)(((int64_t)(p.M - 1) * p.lda + p.K) * 2), 0x00020000);
-  const auto rsW = __builtin_amdgcn_make_buffer_rsrc((void*)p.W, 0, (int)(((int64_t)(p.N - 1) * p.ldw + p.K) * 2), 0x00020000);
-  // per-lane byte offset inside an 8-row chunk: row = lane/8, 16-B slot = (lane%8) ^ ((chunk*4 + lane/16) & 7)
-  const unsigned lr = lane >> 3;
-  unsigned voA[2], voW[2];
-#pragma unroll
-  for (int par = 0; par < 2; ++par) {
-    const unsigned sl = (lane & 7) ^ ((par * 4 + (lane >> 4)) & 7);
-    voA[par] = (unsigned)((lr * p.lda + sl * 8) * 2);
-    voW[par] = (unsigned)((lr * p.ldw + sl * 8) * 2);
-  }
-  // one 1-KiB DMA piece: c in [0,8): 0..3 -> A chunks, 4..7 -> W chunks of this wave
-  auto stage_piece = [&](int t, int c) {
-    const int ch = wave * 4 + (c & 3);
-    char* dst = lds + (t & 1) * STAGE + (c >= 4 ? TBM * BK * 2 : 0) + ch * 1024;
-    if (c < 4) {
-      // (row-chunk + k) offset is wave-uniform and changes with t: an SGPR sum added per piece, so
-      // nothing per-piece stays live in VGPRs across the loop
-      const unsigned so = (unsigned)(((int64_t)(m0 + ch * 8) * p.lda + t * BK) * 2);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (__attribute__((address_space(3))) void*)dst, 16, voA[c & 1] + so, 0, 0, 0);
-    } else {
-      const unsigned so = (unsigned)(((int64_t)(n0 + ch * 8) * p.ldw + t * BK) * 2);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW, (__attribute__((address_space(3))) void*)dst, 16, voW[c & 1] + so, 0, 0, 0);
-    }
-  };
-  auto stage = [&](int t) {
-#pragma unroll
-    for (int c = 0; c < 8; ++c) stage_piece(t, c);
-  };
-  stage(0);
-  if (nk > 1) stage(1);
-  A3V_WAIT_VM0();
-  A3V_BARRIER();
-
-  // fragments: lane -> row (lane&31) of a 32-row tile, 16-B slot kk*2 + (lane>>5) of the 64-k row
-  const int frow = lane & 31, fsw = (lane >> 1) & 7, fhh = lane >> 5;
-  int offk[4];
-#pragma unroll
-  for (int kk = 0; kk < 4; ++kk) offk[kk] = ((kk * 2 + fhh) ^ fsw) << 4;
-  const int a_base = (wr * WTM + frow) * 128;
-  const int w_base = TBM * BK * 2 + (wc * WTN + frow) * 128;
-  bf16x8 af[4][TM], wf[4][TN];
-
-#define PP_READ_FRAGS(cur)                                                                           \
-  do {                                                                                               \
-    const char* At_ = (cur) + a_base;                                                                \
-    const char* Wt_ = (cur) + w_base;                                                                \
-    _Pragma("unroll") for (int kk = 0; kk < 4; ++kk) {                                               \
-      _Pragma("unroll") for (int j = 0; j < TN; ++j)                                                 \
-        wf[kk][j] = *reinterpret_cast<const bf16x8*>(Wt_ + j * 4096 + offk[kk]);                     \
-      _Pragma("unroll") for (int i = 0; i < TM; ++i)                                                 \
-        af[kk][i] = *reinterpret_cast<const bf16x8*>(At_ + i * 4096 + offk[kk]);                     \
-    }                                                                                                \
-  } while (0)
-
-#define PP_MFMA_ALL()                                                                                \
-  do {                                                                                               \
-    __builtin_amdgcn_s_setprio(1);                                                                   \
-    _Pragma("unroll") for (int kk = 0; kk < 4; ++kk)                                                 \
-      _Pragma("unroll") for (int i = 0; i < TM; ++i)                                                 \
-        _Pragma("unroll") for (int j = 0; j < TN; ++j)                                               \
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[kk][j], af[kk][i], acc[i][j], 0, 0, 0); \
-    __builtin_amdgcn_s_setprio(0);                                                                   \
-  } while (0)
-
-  constexpr bool do_dma = !(DBG & 1), do_rd = !(DBG & 2);
-  if (wr == 0) {
-    for (int t = 0; t < nk; ++t) {
-      if (do_rd || t == 0) PP_READ_FRAGS(lds + (t & 1) * STAGE);
-      if (do_dma && t >= 1 && t + 1 < nk) stage(t + 1);
-      A3V_WAIT_LGKM0();
-      A3V_BARRIER();
-      PP_MFMA_ALL();
-      A3V_WAIT_VM0();
-      A3V_BARRIER();
-    }
-    A3V_BARRIER();
-  } else {
-    A3V_BARRIER();
-    for (int t = 0; t < nk; ++t) {
-      if (do_rd || t == 0) PP_READ_FRAGS(lds + (t & 1) * STAGE);
-      A3V_WAIT_LGKM0();
-      A3V_WAIT_VM0();
-      A3V_BARRIER();
-      if (do_dma && t + 2 < nk) stage(t + 2);
-      PP_MFMA_ALL();
-      A3V_BARRIER();
-    }
-  }
-#undef PP_READ_FRAGS
-#undef PP_MFMA_ALL
-  gemm_epilogue32<TM, TN>(acc, p, m0 + wr * WTM, n0 + wc * WTN, lane);
-}
-#endif  // A3V_EXPERIMENTS
 
 // ------------------------------------------------------------------------------------
 // Skinny GEMM, single launch: one 8-wave block per 16 (or 32 with SwiGLU: gate block + up block)
@@ -2627,7 +1744,6 @@ __global__ __launch_bounds__(512) void gemm_skinny1_bf16_kernel(Skinny1Args p) {
     *reinterpret_cast<bf16x4*>(reinterpret_cast<bf16_t*>(p.C) + (int64_t)m * p.ldc + n) = o;
   }
 }
-
 
 // ------------------------------------------------------------------------------------
 // Decode GEMV, M <= 16, K % 128 == 0: W streamed ONCE from HBM by LDS-DMA.
@@ -3349,14 +2465,6 @@ extern "C" int a3v_version(void) { return 100; }
 static int g_env_generation = 0;
 int a3v_env_generation() { return g_env_generation; }
 extern "C" int a3v_reload_env(void) { return ++g_env_generation; }
-// bit 0: built with -DA3V_EXPERIMENTS (the measured-and-not-dispatched GEMM kernels and their switches are present)
-extern "C" int a3v_build_flags(void) {
-#ifdef A3V_EXPERIMENTS
-  return 1;
-#else
-  return 0;
-#endif
-}
 
 // Optional scratch for the split-K forms of the hybrid dispatch (tail rows, few-tile problems): the library never allocates, so without
 // it those rows run as plain launches.  Registrations are keyed by (device, stream): two streams that run GEMMs concurrently must not
@@ -3477,20 +2585,6 @@ static bool pp_persistent() { return A3V_ENV_INT("A3V_GEMM_PERSISTENT", 1) != 0;
 static int nt_store_env() { return A3V_ENV_INT("A3V_GEMM_NT_STORE", 0); }
 static int slow_epi_env() { return A3V_ENV_INT("A3V_GEMM_FAST_EPI", 1) == 0 ? 1 : 0; }   // 0: every tile through the general epilogue
 
-#ifdef A3V_EXPERIMENTS
-static bool pp_ring() { return A3V_ENV_INT("A3V_GEMM_RING", 1) != 0; }       // 0: the two-stage ping-pong kernel
-static unsigned* xsync_buffer(hipStream_t st) {   // A3V_GEMM_LOCKSTEP=1: eight counters, zeroed on the launch stream before every launch
-  if (!A3V_ENV_INT("A3V_GEMM_LOCKSTEP", 0)) return nullptr;
-  static unsigned* buf = nullptr;
-  if (!buf && hipMalloc(&buf, 64) != hipSuccess) { buf = nullptr; return nullptr; }
-  if (hipMemsetAsync(buf, 0, 64, st) != hipSuccess) return nullptr;
-  return buf;
-}
-static int w4_env() { return A3V_ENV_INT("A3V_GEMM_W4", 0); }   // 1: one-wave-per-SIMD kernel, 20: overlapped form, ... (tools/gemm_w4_ab.py)
-#else
-static bool pp_ring() { return true; }
-#endif
-
 template <bool A_ROWS>
 static void launch_tn(dim3 grid, hipStream_t st, const GemmArgs& q0) {
   GemmArgs q = q0;
@@ -3504,6 +2598,7 @@ static int gemm_nt_impl(const void* A, int64_t lda, const void* W, int64_t ldw, 
                         int M, int N, int K, const void* bias, const void* residual, int64_t ldr,
                         int epilogue, int dtype, void* stream, const RopeKvArgs* rk) {
   if (M <= 0 || N <= 0 || K <= 0 || !A || !W || !C) return A3V_ERR_ARG;
+  if (epilogue & (1 << 19)) return A3V_ERR_ARG;   // the retired 32x32x16-MFMA tile switch: an error, not some other tile
   if ((epilogue & A3V_EPI_BIAS) && !bias) return A3V_ERR_ARG;
   if ((epilogue & (A3V_EPI_RESIDUAL | A3V_EPI_RES_F32)) && !residual) return A3V_ERR_ARG;
   if (epilogue & A3V_EPI_SWIGLU_BWD) {     // alone (no bias / activation / residual kinds), bf16, gate / up rows in `residual`
@@ -3532,7 +2627,6 @@ static int gemm_nt_impl(const void* A, int64_t lda, const void* W, int64_t ldw, 
   p.A = (const bf16_t*)A; p.W = (const bf16_t*)W; p.C = C; p.bias = bias; p.res = residual;
   p.lda = lda; p.ldw = ldw; p.ldc = ldc; p.ldr = ldr;
   p.M = M; p.N = N; p.K = K; p.epi = epilogue & 0xffff;
-  p.dbg = (epilogue >> 24) & 0xf;
   p.c_split = 0;
   p.rk = RopeKvArgs{};
   if (rk) { p.rk = *rk; p.epi |= GEMM_EPI_ROPEKV; }
@@ -3555,73 +2649,40 @@ static int gemm_nt_impl(const void* A, int64_t lda, const void* W, int64_t ldw, 
     if (cfg == 256) { hipLaunchKernelGGL((gemm_nt_bf16_kernel<256, 256, 2, 4>), g, b, 0, st, q); return; }
     q.xmap = (g.x & 63) ? 0 : A3V_ENV_INT("A3V_GEMM_XMAP", 1);   // =0: one contiguous run of tiles per XCD (A/B)
     if (!((q.xmap & 4) && g.x == 256 && (q.tiles_m & 15) == 0 && (q.tiles_n & 15) == 0)) q.xmap &= ~4;
-    q.skew = 0; q.xsync = nullptr;
-#ifdef A3V_EXPERIMENTS
-    if (cfg == 258) { hipLaunchKernelGGL(gemm_nt_bf16_pp32_kernel<0>, g, b, 0, st, q); return; }
-    {
-      int dbg = q.dbg;
-      if (dbg == 0 && pp_ring()) dbg = 5;
-      q.skew = A3V_ENV_INT("A3V_GEMM_SKEW", 0);
-      q.xsync = (dbg == 5 && g.y == 1) ? xsync_buffer(st) : nullptr;
-      if (dbg != 5 || w4_env() != 0) {
-        switch (dbg) {
-          case 0: hipLaunchKernelGGL((gemm_nt_bf16_pp_kernel<0, 0>), g, b, 0, st, q); break;
-          case 5:
-            if (q.epi & GEMM_EPI_ROPEKV) hipLaunchKernelGGL((gemm_nt_bf16_ring_kernel<0, false, 0, true, EPI_SET_ROPE>), g, b, 0, st, q);
-            else if (q.epi & (A3V_EPI_BIAS | A3V_EPI_GELU | A3V_EPI_QUICKGELU))
-              hipLaunchKernelGGL((gemm_nt_bf16_ring_kernel<0, false, 0, true, EPI_SET_COMMON | EPI_SET_PRE>), g, b, 0, st, q);
-            else if (w4_env() == 1) hipLaunchKernelGGL((gemm_nt_bf16_w4_kernel<0>), g, dim3(256), 0, st, q);
-            else if (w4_env() == 2) hipLaunchKernelGGL((gemm_nt_bf16_w4_kernel<4>), g, dim3(256), 0, st, q);   // cycle stamps into `bias`
-            else if (w4_env() == 8) hipLaunchKernelGGL((gemm_nt_bf16_w4_kernel<8>), g, dim3(256), 0, st, q);
-            else if (w4_env() == 9) hipLaunchKernelGGL((gemm_nt_bf16_w4_kernel<9>), g, dim3(256), 0, st, q);
-            else if (w4_env() == 10) hipLaunchKernelGGL((gemm_nt_bf16_w4_kernel<10>), g, dim3(256), 0, st, q);   // every k-loop piece out of bounds
-            else if (w4_env() == 7) hipLaunchKernelGGL((gemm_nt_bf16_ring_kernel<7, false, 0>), g, b, 0, st, q);   // ring kernel, cache-resident operands (timing experiment, wrong results)
-            else if (w4_env() == 20) hipLaunchKernelGGL((gemm_nt_bf16_ov_kernel<0>), g, b, 0, st, q);            // overlapped 8-wave form
-            else if (w4_env() == 28) hipLaunchKernelGGL((gemm_nt_bf16_ov_kernel<8>), g, b, 0, st, q);
-            else if (w4_env() == 29) hipLaunchKernelGGL((gemm_nt_bf16_ov_kernel<9>), g, b, 0, st, q);
-            else if (w4_env() == 30) hipLaunchKernelGGL((gemm_nt_bf16_ov_kernel<10>), g, b, 0, st, q);
-            else if (w4_env() == 31) hipLaunchKernelGGL((gemm_nt_bf16_ov_kernel<11>), g, b, 0, st, q);
-            else if (w4_env() == 32) hipLaunchKernelGGL((gemm_nt_bf16_ov_kernel<12>), g, b, 0, st, q);
-            else if (w4_env() == 33) hipLaunchKernelGGL((gemm_nt_bf16_ov_kernel<13>), g, b, 0, st, q);
-            else hipLaunchKernelGGL((gemm_nt_bf16_ring_kernel<0, false, 0>), g, b, 0, st, q);
-            break;
-          case 11: hipLaunchKernelGGL((gemm_nt_bf16_ring_kernel<0, false, 0, false>), g, b, 0, st, q); break;   // ring, direct (unstaged) epilogue stores
-          case 12: hipLaunchKernelGGL((gemm_nt_bf16_ring_kernel<0, false, 0, true, EPI_SET_COMMON, true>), g, b, 0, st, q); break;   // ring, group 0 waits for its W half at the end of L
-          case 13: hipLaunchKernelGGL((gemm_nt_bf16_ring_kernel<4, false, 0, true, EPI_SET_COMMON, true>), g, b, 0, st, q); break;   // ... with cycle stamps
-          case 14: hipLaunchKernelGGL((gemm_nt_bf16_ring_kernel<0, false, 1, true, EPI_SET_COMMON, true>), g, b, 0, st, q); break;   // ... + barrier 1 tile row before the last MFMA
-          case 15: hipLaunchKernelGGL((gemm_nt_bf16_ring_kernel<0, false, 2, true, EPI_SET_COMMON, true>), g, b, 0, st, q); break;   // ... 2 tile rows
-          case 8: hipLaunchKernelGGL((gemm_nt_bf16_ring_kernel<0, false, 4, true, EPI_SET_COMMON, true>), g, b, 0, st, q); break;    // ... 4 tile rows
-          case 7: hipLaunchKernelGGL((gemm_nt_bf16_pp_kernel<0, 0>), g, b, 0, st, q); break;   // two-stage kernel, for A/B runs
-          case 9: hipLaunchKernelGGL((gemm_nt_bf16_ring_kernel<0, true, 0>), g, b, 0, st, q); break;   // ring, 32x32x16 MFMA
-          case 10: hipLaunchKernelGGL((gemm_nt_bf16_ring_kernel<4, true, 0>), g, b, 0, st, q); break;   // 32x32x16, stamps
-          case 6: hipLaunchKernelGGL((gemm_nt_bf16_ring_kernel<4, false, 0>), g, b, 0, st, q); break;   // cycle stamps (tools/ring_stamps.py)
-          case 1: hipLaunchKernelGGL((gemm_nt_bf16_ring_kernel<0, false, 0, true, EPI_SET_COMMON, false, false>), g, b, 0, st, q); break;   // ablation: the wait after the MFMAs (round-2 form)
-          case 2: hipLaunchKernelGGL((gemm_nt_bf16_ring_kernel<4, false, 0, true, EPI_SET_COMMON, false, false>), g, b, 0, st, q); break;   // same, stamps
-          case 3: hipLaunchKernelGGL((gemm_nt_bf16_ring_kernel<0, false, 0, true, EPI_SET_COMMON, false, true, false>), g, b, 0, st, q); break;   // ablation: prologue burst + block barrier per tile (no cross-tile DMA stream)
-          default: break;
-        }
-        return;
-      }
-    }
-#endif
     // the product path: the ring kernel, instantiated per set of fast epilogue forms
     if (cfg == 259) {                                    // 192 x 256 tiles (the fused-qkv form has no instantiation: general epilogue there)
       if (q.epi & (A3V_EPI_BIAS | A3V_EPI_GELU | A3V_EPI_QUICKGELU))
-        hipLaunchKernelGGL((gemm_nt_bf16_ring_kernel<0, false, 0, true, EPI_SET_COMMON | EPI_SET_PRE, false, true, true, 192>), g, b, 0, st, q);
-      else hipLaunchKernelGGL((gemm_nt_bf16_ring_kernel<0, false, 0, true, EPI_SET_COMMON, false, true, true, 192>), g, b, 0, st, q);
+        hipLaunchKernelGGL((gemm_nt_bf16_ring_kernel<EPI_SET_COMMON | EPI_SET_PRE, 192>), g, b, 0, st, q);
+      else hipLaunchKernelGGL((gemm_nt_bf16_ring_kernel<EPI_SET_COMMON, 192>), g, b, 0, st, q);
       return;
     }
-    if (q.epi & GEMM_EPI_ROPEKV) hipLaunchKernelGGL((gemm_nt_bf16_ring_kernel<0, false, 0, true, EPI_SET_ROPE>), g, b, 0, st, q);
+    if (q.epi & GEMM_EPI_ROPEKV) hipLaunchKernelGGL((gemm_nt_bf16_ring_kernel<EPI_SET_ROPE>), g, b, 0, st, q);
     else if (q.epi & (A3V_EPI_BIAS | A3V_EPI_GELU | A3V_EPI_QUICKGELU))
-      hipLaunchKernelGGL((gemm_nt_bf16_ring_kernel<0, false, 0, true, EPI_SET_COMMON | EPI_SET_PRE>), g, b, 0, st, q);
-    else hipLaunchKernelGGL((gemm_nt_bf16_ring_kernel<0, false, 0>), g, b, 0, st, q);
+      hipLaunchKernelGGL((gemm_nt_bf16_ring_kernel<EPI_SET_COMMON | EPI_SET_PRE>), g, b, 0, st, q);
+    else hipLaunchKernelGGL((gemm_nt_bf16_ring_kernel<EPI_SET_COMMON>), g, b, 0, st, q);
+  };
+  // split-K: S slices of the K loop of `src` write raw fp32 planes into the workspace (ring kernel on 256 x 256 tiles, or the
+  // 128 x 128 kernel); one reduce pass sums them and applies the epilogue (the bias, if any, there) on the way to src's output
+  auto launch_splitk = [&](int tile, int S, const GemmArgs& src) {
+    GemmArgs t = src;
+    t.C = gws.p; t.ldc = N; t.res = nullptr; t.bias = nullptr;
+    t.epi = A3V_EPI_OUT_F32 | GEMM_EPI_RAW;
+    t.tiles_m = (t.M + tile - 1) / tile; t.tiles_n = (N + tile - 1) / tile;
+    t.c_split = (int64_t)t.M * N * 4;
+    t.slow_epi = slow_epi_env(); t.nt_store = nt_store_env();
+    const dim3 g(t.tiles_m * t.tiles_n, S);
+    if (tile == 256) hipLaunchKernelGGL((gemm_nt_bf16_ring_kernel<EPI_SET_COMMON>), g, dim3(512), 0, st, t);
+    else hipLaunchKernelGGL((gemm_nt_bf16_kernel<128, 128, 2, 2>), g, dim3(256), 0, st, t);
+    const int64_t n4 = (int64_t)t.M * (N / 4);
+    const int rb = (int)((n4 + 255) / 256 > 2048 ? 2048 : (n4 + 255) / 256);
+    hipLaunchKernelGGL(splitk_epilogue_kernel, dim3(rb), dim3(256), 0, st, gws.p, S, (int64_t)t.M * N, t.M, N, src.C, src.ldc, src.res, src.ldr,
+                       src.epi & ~A3V_EPI_BIAS, (src.epi & A3V_EPI_BIAS) ? (const bf16_t*)src.bias : nullptr);
   };
   const int64_t bytesA = ((int64_t)(M - 1) * lda + K) * 2, bytesW = ((int64_t)(N - 1) * ldw + K) * 2;
   const bool desc_ok = bytesA < (1LL << 31) && bytesW < (1LL << 31);   // buffer descriptors: 32-bit offsets
-  if (epilogue & (A3V_EPI_TILE_256PP32 | A3V_EPI_TILE_256PP | A3V_EPI_TILE_256 | A3V_EPI_TILE_128 | A3V_EPI_TILE_192PP)) {
+  if (epilogue & (A3V_EPI_TILE_256PP | A3V_EPI_TILE_256 | A3V_EPI_TILE_128 | A3V_EPI_TILE_192PP)) {
     int cfg = 128;
     if (epilogue & A3V_EPI_TILE_192PP) cfg = 259;
-    else if (epilogue & A3V_EPI_TILE_256PP32) cfg = 258;
     else if (epilogue & A3V_EPI_TILE_256PP) cfg = 257;
     else if (epilogue & A3V_EPI_TILE_256) cfg = 256;
     if (cfg > 256 && !desc_ok) return A3V_ERR_SHAPE;
@@ -3651,13 +2712,13 @@ static int gemm_nt_impl(const void* A, int64_t lda, const void* W, int64_t ldw, 
       const bool simple_epi = !(p.epi & ~(A3V_EPI_RESIDUAL | A3V_EPI_RES_F32 | A3V_EPI_OUT_F32)) && gws.p && N % 4 == 0;
       // (round 5 recalibration, tools/ring192_ab.py) the split-K tail costs its 1 / S of a tile time plus ~32 us that do not depend on K
       // (plane traffic + two launches): 0.30 of a round at K = 4096, 0.07 at K = 22016, where a round of 256 tiles takes ~12 + 0.0206 K us
-      const double tail = (S2 >= 3 && simple_epi && pp_ring() && pp_persistent()) ? 1.0 / S2 + 32.0 / round_us : small_cost(tail_rows) + 0.25;
+      const double tail = (S2 >= 3 && simple_epi && pp_persistent()) ? 1.0 / S2 + 32.0 / round_us : small_cost(tail_rows) + 0.25;
       c_hyb = (double)((mt_h * tn256 + 255) / 256) + tail;
     }
     // (round 5) the whole problem on 192 x 256 ring tiles: a round of them takes 0.79 of a 256 x 256 round (48 instead of 64 MFMAs per
     // wave and K-tile on 7 / 8 of the LDS-DMA pieces); 8728 x 4096 is 2.875 rounds of these against 2 rounds + a split-K tail
     double c_192 = 1e30;
-    if (eligible && !rk && pp_ring() && pp_persistent() && A3V_ENV_INT("A3V_GEMM_RING_192", 1) != 0 && !(p.epi & A3V_EPI_SWIGLU))
+    if (eligible && !rk && pp_persistent() && A3V_ENV_INT("A3V_GEMM_RING_192", 1) != 0 && !(p.epi & A3V_EPI_SWIGLU))
       c_192 = 0.79 * (double)((((long)(M + 191) / 192) * tn256 + 255) / 256) + 0.02;
     // few big tiles (small N or M: the ViT's output projections, 76 tiles): the whole problem on the ring kernel split over K
     double c_spl = 1e30;
@@ -3669,24 +2730,14 @@ static int gemm_nt_impl(const void* A, int64_t lda, const void* W, int64_t ldw, 
       while (S3 > 1 && K / 64 < 8 * S3) --S3;
       const int okbits = A3V_EPI_BIAS | A3V_EPI_RESIDUAL | A3V_EPI_RES_F32 | A3V_EPI_OUT_F32;
       const bool on = A3V_ENV_INT("A3V_GEMM_RING_SPLIT", 1) != 0;
-      if (on && eligible && S3 >= 3 && !(p.epi & ~okbits) && pp_ring() && pp_persistent() && gws.p && N % 4 == 0 &&
+      if (on && eligible && S3 >= 3 && !(p.epi & ~okbits) && pp_persistent() && gws.p && N % 4 == 0 &&
           (int64_t)S3 * M * N * 4 <= gws.bytes && (!(p.epi & A3V_EPI_BIAS) || !(reinterpret_cast<uintptr_t>(bias) & 7)))
         c_spl = 1.0 / S3 + 0.2;
     }
     if (c_192 < c_spl && c_192 < c_small && c_192 < c_big && c_192 < c_hyb) {
       launch(259, p);
     } else if (c_spl < c_small && c_spl < c_big && c_spl < c_hyb) {
-      GemmArgs t = p;
-      t.C = gws.p; t.ldc = N; t.res = nullptr; t.bias = nullptr;
-      t.epi = A3V_EPI_OUT_F32 | GEMM_EPI_RAW;
-      t.tiles_m = (M + 255) / 256; t.tiles_n = (int)tn256;
-      t.c_split = (int64_t)M * N * 4;
-      t.slow_epi = slow_epi_env(); t.nt_store = nt_store_env();
-      hipLaunchKernelGGL((gemm_nt_bf16_ring_kernel<0, false, 0>), dim3(t.tiles_m * t.tiles_n, S3), dim3(512), 0, st, t);
-      const int64_t n4 = (int64_t)M * (N / 4);
-      const int rb = (int)((n4 + 255) / 256 > 2048 ? 2048 : (n4 + 255) / 256);
-      hipLaunchKernelGGL(splitk_epilogue_kernel, dim3(rb), dim3(256), 0, st, gws.p, S3, (int64_t)M * N, M, N, p.C, p.ldc, p.res, p.ldr,
-                         p.epi & ~A3V_EPI_BIAS, (p.epi & A3V_EPI_BIAS) ? (const bf16_t*)p.bias : nullptr);
+      launch_splitk(256, S3, p);
     } else if (c_big <= c_small && c_big <= c_hyb) {
       launch(257, p);
     } else if (c_hyb < c_small) {
@@ -3716,29 +2767,10 @@ static int gemm_nt_impl(const void* A, int64_t lda, const void* W, int64_t ldw, 
       while (S2 > 1 && K / 64 < 8 * S2) --S2;
       { const int e = A3V_ENV_INT("A3V_GEMM_TAIL_SLICES", 0); if (e >= 3 && e <= 16 && K / 64 >= 2 * e) S2 = e; }      // sweeps (tools/tail_cost.py)
       const bool ring_tail = A3V_ENV_INT("A3V_GEMM_RING_TAIL", 1) != 0;
-      if (ring_tail && pp_ring() && pp_persistent() && S2 >= 3 && !(p.epi & ~simple) && gws.p && (int64_t)S2 * r.M * N * 4 <= gws.bytes && N % 4 == 0) {
-        GemmArgs t = r;
-        t.C = gws.p; t.ldc = N; t.res = nullptr; t.bias = nullptr;
-        t.epi = A3V_EPI_OUT_F32 | GEMM_EPI_RAW;
-        t.tiles_m = (t.M + 255) / 256; t.tiles_n = (int)tn256;
-        t.c_split = (int64_t)t.M * N * 4;
-        t.slow_epi = slow_epi_env(); t.nt_store = nt_store_env();
-        t.skew = 0;
-        hipLaunchKernelGGL((gemm_nt_bf16_ring_kernel<0, false, 0>), dim3(big_tiles, S2), dim3(512), 0, st, t);
-        const int64_t n4 = (int64_t)r.M * (N / 4);
-        const int rb = (int)((n4 + 255) / 256 > 2048 ? 2048 : (n4 + 255) / 256);
-        hipLaunchKernelGGL(splitk_epilogue_kernel, dim3(rb), dim3(256), 0, st, gws.p, S2, (int64_t)r.M * N, r.M, N, r.C, r.ldc, r.res, r.ldr, p.epi);
+      if (ring_tail && pp_persistent() && S2 >= 3 && !(p.epi & ~simple) && gws.p && (int64_t)S2 * r.M * N * 4 <= gws.bytes && N % 4 == 0) {
+        launch_splitk(256, S2, r);
       } else if (S > 1 && !(p.epi & ~simple) && gws.p && (int64_t)S * r.M * N * 4 <= gws.bytes && N % 4 == 0) {
-        GemmArgs t = r;
-        t.C = gws.p; t.ldc = N; t.res = nullptr; t.bias = nullptr;
-        t.epi = A3V_EPI_OUT_F32 | GEMM_EPI_RAW;
-        t.tiles_m = (t.M + 127) / 128; t.tiles_n = (N + 127) / 128;
-        t.c_split = (int64_t)t.M * N * 4;
-        t.slow_epi = slow_epi_env(); t.nt_store = nt_store_env();
-        hipLaunchKernelGGL((gemm_nt_bf16_kernel<128, 128, 2, 2>), dim3(t.tiles_m * t.tiles_n, S), dim3(256), 0, st, t);
-        const int64_t n4 = (int64_t)r.M * (N / 4);
-        const int rb = (int)((n4 + 255) / 256 > 2048 ? 2048 : (n4 + 255) / 256);
-        hipLaunchKernelGGL(splitk_epilogue_kernel, dim3(rb), dim3(256), 0, st, gws.p, S, (int64_t)r.M * N, r.M, N, r.C, r.ldc, r.res, r.ldr, p.epi);
+        launch_splitk(128, S, r);
       } else {
         launch(128, r);
       }
@@ -4005,7 +3037,7 @@ extern "C" int a3v_gemm_nt_splitk(const void* A, int64_t lda, const void* W, int
   GemmArgs p{};
   p.A = (const bf16_t*)A; p.W = (const bf16_t*)W; p.C = partial; p.bias = nullptr; p.res = nullptr;
   p.lda = lda; p.ldw = ldw; p.ldc = N; p.ldr = 0;
-  p.M = M; p.N = N; p.K = K; p.epi = A3V_EPI_OUT_F32 | GEMM_EPI_RAW; p.dbg = 0;
+  p.M = M; p.N = N; p.K = K; p.epi = A3V_EPI_OUT_F32 | GEMM_EPI_RAW;
   p.c_split = (int64_t)M * N * 4;
   // Rows of the streamed operand per block and LDS stages (tools/skinny_stages_bench.py, operands rotating through 700 MB, us incl.
   // the reduce pass at 8728 x 64 x K = 4096 / 11008 / 12288 / 22016):
@@ -4092,7 +3124,7 @@ static int gemm_tn_impl(const void* At, int64_t lda, const void* Wt, int64_t ldw
   GemmArgs p{};
   p.A = (const bf16_t*)At; p.W = (const bf16_t*)Wt; p.C = C; p.bias = nullptr; p.res = residual;
   p.lda = lda; p.ldw = ldw; p.ldc = ldc; p.ldr = ldr;
-  p.M = M; p.N = N; p.K = K; p.epi = epilogue; p.dbg = 0;
+  p.M = M; p.N = N; p.K = K; p.epi = epilogue;
   p.tiles_n = (N + 255) / 256;
   p.sumsq = sumsq;
   hipStream_t st = (hipStream_t)stream;
@@ -4164,7 +3196,7 @@ extern "C" int a3v_gemm_tn_splitk(const void* At, int64_t lda, const void* Wt, i
   GemmArgs p{};
   p.A = (const bf16_t*)At; p.W = (const bf16_t*)Wt; p.C = partial; p.bias = nullptr; p.res = nullptr;
   p.lda = lda; p.ldw = ldw; p.ldc = N; p.ldr = 0;
-  p.M = M; p.N = N; p.K = K; p.epi = A3V_EPI_OUT_F32 | GEMM_EPI_RAW; p.dbg = 0;
+  p.M = M; p.N = N; p.K = K; p.epi = A3V_EPI_OUT_F32 | GEMM_EPI_RAW;
   p.tiles_m = (M + 255) / 256; p.tiles_n = (N + 255) / 256;
   p.c_split = (int64_t)M * N * 4;
   launch_tn<false>(dim3(p.tiles_m * p.tiles_n, S), (hipStream_t)stream, p);
@@ -4180,14 +3212,13 @@ static bool launch_ring_fp8(GemmArgs q, int grid_y, hipStream_t st, int tbm = 25
   if (q.epi & (A3V_EPI_BIAS | A3V_EPI_GELU | A3V_EPI_QUICKGELU)) return false;
   q.epi &= ~GEMM_EPI_SCALE;                              // the kernel scales its accumulators itself, in front of the staged epilogues
   q.slow_epi = slow_epi_env(); q.nt_store = nt_store_env();
-  q.skew = 0; q.xsync = nullptr;
   const int nt = q.tiles_m * q.tiles_n;
   const dim3 g(grid_y > 1 ? nt : std::min(nt, cu_count()), grid_y), b(512);
   q.xmap = (g.x & 63) || grid_y > 1 ? 0 : A3V_ENV_INT("A3V_GEMM_XMAP", 1);
   if (!((q.xmap & 4) && g.x == 256 && (q.tiles_m & 15) == 0 && (q.tiles_n & 15) == 0)) q.xmap &= ~4;
-  if (tbm == 192) hipLaunchKernelGGL((gemm_nt_bf16_ring_kernel<0, false, 0, true, EPI_SET_COMMON, false, true, true, 192, true>), g, b, 0, st, q);
-  else if (q.epi & GEMM_EPI_ROPEKV) hipLaunchKernelGGL((gemm_nt_bf16_ring_kernel<0, false, 0, true, EPI_SET_ROPE, false, true, true, 256, true>), g, b, 0, st, q);
-  else hipLaunchKernelGGL((gemm_nt_bf16_ring_kernel<0, false, 0, true, EPI_SET_COMMON, false, true, true, 256, true>), g, b, 0, st, q);
+  if (tbm == 192) hipLaunchKernelGGL((gemm_nt_bf16_ring_kernel<EPI_SET_COMMON, 192, true>), g, b, 0, st, q);
+  else if (q.epi & GEMM_EPI_ROPEKV) hipLaunchKernelGGL((gemm_nt_bf16_ring_kernel<EPI_SET_ROPE, 256, true>), g, b, 0, st, q);
+  else hipLaunchKernelGGL((gemm_nt_bf16_ring_kernel<EPI_SET_COMMON, 256, true>), g, b, 0, st, q);
   return true;
 }
 
@@ -4206,7 +3237,7 @@ static int gemm_nt_fp8_impl(const void* Aq, int64_t lda, const float* sa, const 
   GemmArgs p{};
   p.A = (const bf16_t*)Aq; p.W = (const bf16_t*)Wq; p.C = C; p.bias = bias; p.res = residual;
   p.lda = lda; p.ldw = ldw; p.ldc = ldc; p.ldr = ldr;
-  p.M = M; p.N = N; p.K = K; p.epi = epilogue | GEMM_EPI_SCALE; p.dbg = 0;
+  p.M = M; p.N = N; p.K = K; p.epi = epilogue | GEMM_EPI_SCALE;
   p.sa = sa; p.sw = sw;
   if (rk) { p.rk = *rk; p.epi |= GEMM_EPI_ROPEKV; }
   p.tiles_n = (N + 255) / 256;
@@ -4309,7 +3340,7 @@ extern "C" int a3v_gemm_nn(const void* A, int64_t lda, const void* Wt, int64_t l
   GemmArgs p{};
   p.A = (const bf16_t*)A; p.W = (const bf16_t*)Wt; p.C = C; p.bias = nullptr; p.res = residual;
   p.lda = lda; p.ldw = ldw; p.ldc = ldc; p.ldr = ldr;
-  p.M = M; p.N = N; p.K = K; p.epi = epilogue; p.dbg = 0;
+  p.M = M; p.N = N; p.K = K; p.epi = epilogue;
   p.tiles_n = (N + 255) / 256;
   const int ncu = cu_count();
   const int tm_all = (M + 255) / 256;

@@ -17,7 +17,7 @@ BF16, F32 = 0, 1
 EPI_NONE, EPI_BIAS, EPI_GELU, EPI_QUICKGELU, EPI_RESIDUAL, EPI_SWIGLU, EPI_OUT_F32, EPI_RES_F32 = 0, 1, 2, 4, 8, 16, 32, 64
 EPI_SWIGLU_BWD = 128
 
-EPI_TILE_128, EPI_TILE_256, EPI_TILE_256PP, EPI_TILE_256PP32 = 1 << 16, 1 << 17, 1 << 18, 1 << 19
+EPI_TILE_128, EPI_TILE_256, EPI_TILE_256PP = 1 << 16, 1 << 17, 1 << 18
 EPI_TILE_192PP = 1 << 23
 
 P, I, L, F = c_void_p, c_int, c_int64, c_float
@@ -26,7 +26,6 @@ P, I, L, F = c_void_p, c_int, c_int64, c_float
 SIGNATURES = {
     "a3v_version": (I, []),
     "a3v_reload_env": (I, []),
-    "a3v_build_flags": (I, []),
     "a3v_gemm_nt": (I, [P, L, P, L, P, L, I, I, I, P, P, L, I, I, P]),
     "a3v_gemm_qkv_rope": (I, [P, L, P, L, I, P, L, P, P, P, L, P, L, P, I, I, I, I, I, I, I, I, P]),
     "a3v_gemm_nt_fp8": (I, [P, L, P, P, L, P, P, L, I, I, I, P, P, L, I, P]),
@@ -143,11 +142,6 @@ def load() -> ctypes.CDLL:
         fn.argtypes = args
     _lib = lib
     return lib
-
-
-def has_experiments() -> bool:
-    """True when the library was built with `make EXPERIMENTS=1` (the measured-and-not-dispatched GEMM kernels exist)."""
-    return bool(load().a3v_build_flags() & 1)
 
 
 class env:

@@ -62,7 +62,7 @@ enum {
   A3V_EPI_TILE_128 = 1 << 16,  /* force the 128x128 tile kernel (tuning / tests)       */
   A3V_EPI_TILE_256 = 1 << 17,  /* force the 256x256 tile kernel (tuning / tests)       */
   A3V_EPI_TILE_256PP = 1 << 18,/* force the 256x256 ping-pong kernel (tuning / tests)  */
-  A3V_EPI_TILE_256PP32 = 1 << 19, /* ... its 32x32x16-MFMA form                        */
+  /* 1 << 19: retired (was a tuning switch): A3V_ERR_ARG                              */
   A3V_EPI_TILE_192PP = 1 << 23  /* force the ring kernel's 192 x 256 tile form (round 5; tuning / tests) */
 };
 
@@ -72,9 +72,6 @@ int a3v_version(void);
  * cached: a process that changes one after its first launch calls this to have them re-read.  Returns the new generation.
  * (No reference counterpart: the reference has no native code.) */
 int a3v_reload_env(void);
-/* bit 0: the library was built with -DA3V_EXPERIMENTS (`make EXPERIMENTS=1`): the measured-and-not-dispatched GEMM kernels
- * (two-stage ping-pong, one wave per SIMD, overlapped, 32x32x16 forms, stamped builds) and their switches exist. */
-int a3v_build_flags(void);
 /* C[M,N] = epilogue(A[M,K] @ W[N,K]^T).  Replaces every F.linear on the path:
  * wq/wk/wv/wo (LLM/llama_ens5.py:63-90,112,169), w1/w2/w3 (:202-217), output (:267-269,
  * 486,530), visual_proj[0] (:330-333), the open_clip in_proj/out_proj/c_fc/c_proj, and

@@ -68,10 +68,6 @@ def test_gemm_bf16_tile_configs_agree(M, N, K):
         o3.zero_()
         ops.gemm_nt(a, w, o3, bias=bias, epilogue=ops.EPI_GELU | lib.EPI_TILE_256PP)
         assert torch.equal(o1, o3)
-        if lib.has_experiments():      # (`make EXPERIMENTS=1` builds only)
-            o3.zero_()   # 32x32x16 MFMA form: different in-instruction summation order -> tolerance, not bits
-            ops.gemm_nt(a, w, o3, bias=bias, epilogue=ops.EPI_GELU | lib.EPI_TILE_256PP32)
-            assert_close(o3, want, rtol=2 ** -6, atol=4e-3, what="gemm pp32")
     want = rt(F.gelu(rt(a.float().cpu() @ w.float().cpu().t() + bias.float().cpu())))
     assert_close(o2, want, rtol=2 ** -6, atol=4e-3, what="gemm 256 tile")
 
@@ -786,10 +782,9 @@ def test_gemm_ring_ragged_rows_over_several_tiles_per_block():
     for (M, N, K) in [(8728, 4096, 1024), (8728, 3072, 256)]:
         a, w = gen(M, K, seed=80).to(BF).to(DEV), gen(N, K, seed=81, scale=0.05).to(BF).to(DEV)
         want = a.float() @ w.float().t()
-        for dbg in ((0, 7) if lib.has_experiments() else (0,)):     # ring (default) and, in experiment builds, the two-stage kernel
-            o = torch.full((M, N), 3.0, dtype=BF, device=DEV)
-            ops.gemm_nt(a, w, o, epilogue=lib.EPI_TILE_256PP | (dbg << 24))
-            assert_close(o, want, rtol=2 ** -7, atol=1e-3 * math.sqrt(K) * 0.05, what=f"ring ragged {M}x{N}x{K} dbg {dbg}")
+        o = torch.full((M, N), 3.0, dtype=BF, device=DEV)
+        ops.gemm_nt(a, w, o, epilogue=lib.EPI_TILE_256PP)
+        assert_close(o, want, rtol=2 ** -7, atol=1e-3 * math.sqrt(K) * 0.05, what=f"ring ragged {M}x{N}x{K}")
         r = gen(M, N, seed=82).to(DEV)
         o = r.clone()
         ops.gemm_nt(a, w, o, residual=o, epilogue=lib.EPI_TILE_256PP | ops.EPI_RES_F32)
@@ -901,38 +896,6 @@ def test_gemm_swiglu_backward_epilogue_equals_gemm_then_swiglu_bwd(M, F, K, tile
         got2 = torch.full((M, 2 * F + 64), 5.0, dtype=BF, device=DEV)
         ops.gemm_nn(dy, wt, got2[:, :2 * F], residual=gu, epilogue=ops.EPI_SWIGLU_BWD)
         assert torch.equal(got2, want2), int((got2 != want2).sum())
-
-
-def test_gemm_one_wave_per_simd_kernel_equals_ring_kernel():
-    """(Also the overlapped 8-wave form, A3V_GEMM_W4=20.)  The opt-in 4-wave (one wave per SIMD, 128 x 128 per wave, 5 x 32-KiB sub-stage ring) form of the NT kernel
-    (A3V_GEMM_W4=1; DESIGN.md section 4: measured, slower than the ring kernel, kept for the record) accumulates in the same
-    order through the same epilogues: bit-equal results on interior + ragged tiles, several tiles per block and the fp32 /
-    residual / SwiGLU output kinds."""
-    from a3vlm_amd import lib
-    if not lib.has_experiments():
-        pytest.skip("the experiment kernels are only in `make EXPERIMENTS=1` builds (not in the product library)")
-    for (M, N, K) in [(8728, 3072, 256), (2048, 1024, 512), (520, 264, 128)]:
-        a, w = gen(M, K, seed=83).to(BF).to(DEV), gen(N, K, seed=84, scale=0.05).to(BF).to(DEV)
-        resf = gen(M, N, seed=85).to(DEV)
-
-        def run(kind):
-            if kind == "swiglu":
-                o = torch.full((M, N // 2), 3.0, dtype=BF, device=DEV)
-                return ops.gemm_nt(a, w, o, epilogue=lib.EPI_TILE_256PP | ops.EPI_SWIGLU)
-            if kind == "res_f32":
-                o = resf.clone()
-                return ops.gemm_nt(a, w, o, residual=o, epilogue=lib.EPI_TILE_256PP | ops.EPI_RES_F32)
-            o = torch.full((M, N), 3.0, dtype=torch.float32 if kind == "out_f32" else BF, device=DEV)
-            return ops.gemm_nt(a, w, o, epilogue=lib.EPI_TILE_256PP | (ops.EPI_OUT_F32 if kind == "out_f32" else 0))
-        for kind in ["plain", "res_f32", "out_f32"] + (["swiglu"] if N % 32 == 0 else []):
-            outs = []
-            for flag in ("0", "1", "20"):                                # ring, one wave per SIMD, overlapped 8-wave form
-                with lib.env(A3V_GEMM_W4=flag):
-                    outs.append(run(kind).clone())
-            assert torch.equal(outs[0], outs[1]) and torch.equal(outs[0], outs[2]), (M, N, K, kind)
-        with lib.env(A3V_GEMM_W4="1"):
-            o = run("plain")
-        assert_close(o, a.float() @ w.float().t(), rtol=2 ** -7, atol=1e-3 * math.sqrt(K) * 0.05, what=f"w4 {M}x{N}x{K} vs fp32")
 
 
 @pytest.mark.parametrize("M,N,K", [(1024, 768, 1000), (4352, 2048, 1024), (520, 264, 512)])
