@@ -32,7 +32,7 @@ struct AttnArgs {
   float scale;
   float* lse;                   // optional [B,H,Sq] log-sum-exp of the scaled scores (training backward)
   int head_group;               // causal prefill: heads per tile-rank-major group of the block order (1 = head-major)
-  int staged_o;                 // prefill: O leaves through an LDS patch as whole rows (A3V_ATTN_STAGED_O=0: per-lane row stores)
+  int staged_o;                 // prefill: O leaves through an LDS patch as whole rows (0, the decode entry: per-lane row stores)
   int lazy_rescale;             // prefill: the softmax reference only moves when a row's exponent would exceed 2^8 (A3V_ATTN_LAZY=0: every tile)
 };
 
@@ -48,12 +48,12 @@ __device__ __forceinline__ void xchg32(float x, float& a, float& b) {
   asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
 }
 
-// PSWAP: the P^T operand is regrouped so that a lane half holds 8 CONSECUTIVE keys (two v_permlane32_swap per 16 keys exchange the
+// The P^T operand is regrouped so that a lane half holds 8 CONSECUTIVE keys (two v_permlane32_swap per 16 keys exchange the
 // {4 hh .. 4 hh + 3} quarters between lanes l and l + 32), and the V^T fragment becomes ONE 16-B chunk per lane (ds_read_b128,
 // lanes 0-31 chunk c, lanes 32-63 chunk c + 1: the 16 lanes of a read group cover 16 distinct bank slots) instead of two 8-B
 // halves of two chunks (ds_read_b64 pairs where rows r and r + 16 of a lane half share their banks: 2-way on every read,
 // 1.18e7 conflict cycles per launch against 3.2e6 active LDS cycles in profiles/r01u_pmc_decode_lds.txt).
-template <int HD, bool CAUSAL, bool PSWAP = true>
+template <int HD, bool CAUSAL>
 __global__ __launch_bounds__(256, 2) void attn_prefill_bf16_kernel(AttnArgs p) {
   constexpr int KVB = 64;
   constexpr int KROW = HD * 2;            // bytes per K row in LDS
@@ -222,18 +222,14 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_bf16_kernel(AttnArgs p) {
     if (full_tile(t)) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       AP_ST(t, 6);
-#ifndef AP_NO_BAR
       __syncthreads();
-#endif
     } else {                          // this tile's buffer was last read in iteration t-2, which the barrier of t-1 closed
       load_tile(kv0);
       write_tile(Ks, Vs);
       __syncthreads();
     }
     AP_ST(t, 5);
-#ifndef AP_NO_DMA
     if (t + 1 < n_tiles && full_tile(t + 1)) dma_tile(kv0 + KVB, lds + (1 - BUF) * TILEB, lds + (1 - BUF) * TILEB + KVB * KROW);
-#endif
     AP_ST(t, 1);
     // causal: a tile whose first key lies past this wave's LAST query row contributes nothing to the wave (the block walks the
     // tiles its last wave needs); the wave only keeps the block's barrier / DMA cadence and leaves the SIMD to its partner
@@ -245,11 +241,7 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_bf16_kernel(AttnArgs p) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) s[tb][r] = 0.f;
     // the two key blocks' accumulation chains alternate (back-to-back MFMAs on ONE accumulator issue at ~72 cycles, not 32)
-#ifdef AP_FRAG_NEAR      // fragments read right in front of their MFMA (the round-1..3 form; A/B builds)
-    constexpr bool FRAG_AHEAD = false;
-#else
     constexpr bool FRAG_AHEAD = HD == 128;      // hd 64 (the ViT) measured 15 % slower with the reads ahead: 34.5-36.0 against 29.8-30.6 us
-#endif
     if constexpr (!FRAG_AHEAD) {
 #pragma unroll
       for (int ks = 0; ks < HD / 16; ++ks)
@@ -275,24 +267,11 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_bf16_kernel(AttnArgs p) {
           asm volatile("" : "+v"(qf[ks]) :: "memory");      // the k-step's MFMAs (they read qf[ks]) stay BEHIND the reads issued above
         }
 #pragma unroll
-        for (int tb = 0; tb < 2; ++tb) {
-#ifdef AP_NO_QK
-          if (ks == 0)
-#endif
-          s[tb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kr[ks % 3][tb], qf[ks], s[tb], 0, 0, 0);
-        }
+        for (int tb = 0; tb < 2; ++tb) s[tb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kr[ks % 3][tb], qf[ks], s[tb], 0, 0, 0);
       }
     }
     AP_ST(t, 2);
     // ---- mask + online softmax (lane owns query column ql; kv = 32tb + (r&3)+8(r>>2)+4hh) ----
-#ifdef AP_NO_SM
-    bf16x8 pf[2][2];
-#pragma unroll
-    for (int tb = 0; tb < 2; ++tb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) pf[tb][r >> 3][r & 7] = f2bf(s[tb][r]);
-    const bool resc = false;
-#else
     const int qlim = CAUSAL ? (qrow + off) : 0x7fffffff;
     // interior tiles (every key of the tile visible to every query row of this wave) skip the 32 compare/selects
     const bool need_mask = (kv0 + KVB > p.Sk) || (CAUSAL && kv0 + KVB - 1 > q0 + off);
@@ -337,41 +316,34 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_bf16_kernel(AttnArgs p) {
     for (int tb = 0; tb < 2; ++tb)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-#ifdef AP_NO_EXP
-        const float pv = fmaf(s[tb][r], p.scale_log2, -mb);
-#else
         const float pv = __builtin_amdgcn_exp2f(fmaf(s[tb][r], p.scale_log2, -mb));
-#endif
         lsum += pv;
         pf[tb][r >> 3][r & 7] = f2bf(pv);
       }
     l_run = resc ? l_run * alpha + lsum : l_run + lsum;
-    if constexpr (PSWAP) {
 #pragma unroll
-      for (int tb = 0; tb < 2; ++tb)
+    for (int tb = 0; tb < 2; ++tb)
 #pragma unroll
-        for (int c = 0; c < 2; ++c) {
-          u32x4 w;
-          __builtin_memcpy(&w, &pf[tb][c], 16);           // dwords: keys 16c + 4hh + {0,1 | 2,3} and 16c + 8 + 4hh + {0,1 | 2,3}
+      for (int c = 0; c < 2; ++c) {
+        u32x4 w;
+        __builtin_memcpy(&w, &pf[tb][c], 16);           // dwords: keys 16c + 4hh + {0,1 | 2,3} and 16c + 8 + 4hh + {0,1 | 2,3}
 #pragma unroll
-          for (int e = 0; e < 2; ++e) {
-            const auto sw = __builtin_amdgcn_permlane32_swap(w[e], w[2 + e], false, false);
-            w[e] = sw[0];                                 // lanes < 32: own first quarter   | lanes >= 32: partner's third quarter
-            w[2 + e] = sw[1];                             // lanes < 32: partner's 2nd quarter | lanes >= 32: own fourth quarter
-          }
-          __builtin_memcpy(&pf[tb][c], &w, 16);           // lanes < 32: keys 16c + 0..7, lanes >= 32: keys 16c + 8..15
+        for (int e = 0; e < 2; ++e) {
+          const auto sw = __builtin_amdgcn_permlane32_swap(w[e], w[2 + e], false, false);
+          w[e] = sw[0];                                 // lanes < 32: own first quarter   | lanes >= 32: partner's third quarter
+          w[2 + e] = sw[1];                             // lanes < 32: partner's 2nd quarter | lanes >= 32: own fourth quarter
         }
-    }
+        __builtin_memcpy(&pf[tb][c], &w, 16);           // lanes < 32: keys 16c + 0..7, lanes >= 32: keys 16c + 8..15
+      }
     if (resc) {
 #pragma unroll
       for (int d = 0; d < HD / 32; ++d)
 #pragma unroll
         for (int r = 0; r < 16; ++r) o[d][r] *= alpha;
     }
-#endif
     AP_ST(t, 3);
     // ---- O^T += V^T . P^T ----
-    if constexpr (PSWAP && FRAG_AHEAD) {
+    if constexpr (FRAG_AHEAD) {
       // the four V^T fragments of the next (key block, 16-key chunk) group are read while the current group's four MFMAs run
       constexpr int ND = HD / 32;
       bf16x8 vr[2][ND];
@@ -388,35 +360,19 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_bf16_kernel(AttnArgs p) {
           asm volatile("" : "+v"(pf[tb][c]) :: "memory");   // the group's MFMAs (they read pf[tb][c]) stay BEHIND the reads issued above
         }
 #pragma unroll
-        for (int d = 0; d < ND; ++d) {
-#ifdef AP_NO_PV
-          if (gI == 0)
-#endif
-          o[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vr[gI & 1][d], pf[tb][c], o[d], 0, 0, 0);
-        }
+        for (int d = 0; d < ND; ++d) o[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vr[gI & 1][d], pf[tb][c], o[d], 0, 0, 0);
       }
     } else {
 #pragma unroll
-    for (int tb = 0; tb < 2; ++tb)
+      for (int tb = 0; tb < 2; ++tb)
 #pragma unroll
-      for (int c = 0; c < 2; ++c)
+        for (int c = 0; c < 2; ++c)
 #pragma unroll
-        for (int d = 0; d < HD / 32; ++d) {   // (the d blocks' chains interleaved, see the QK product)
-          const int drow = d * 32 + ql;
-          const int g = (drow >> 1) & 7;
-          const char* vp = Vs + drow * 128 + hh * 8;
-          const int c16 = 4 * tb + 2 * c;      // 16-B chunk of kv columns {0..7}; lane half hh takes its 8-B half (k = 4hh..4hh+3)
-          bf16x8 vf;
-          if constexpr (PSWAP) {               // lane half hh takes the WHOLE chunk c16 + hh (8 consecutive keys)
-            vf = *reinterpret_cast<const bf16x8*>(Vs + d * 32 * 128 + (vfb ^ (c16 << 4)));
-          } else {
-            const u32x2 a0 = *reinterpret_cast<const u32x2*>(vp + ((c16 ^ g) << 4));
-            const u32x2 a1 = *reinterpret_cast<const u32x2*>(vp + (((c16 + 1) ^ g) << 4));
-            const u32x4 av = {a0[0], a0[1], a1[0], a1[1]};
-            __builtin_memcpy(&vf, &av, 16);
+          for (int d = 0; d < HD / 32; ++d) {   // (the d blocks' chains interleaved, see the QK product)
+            const int c16 = 4 * tb + 2 * c;     // lane half hh takes the WHOLE 16-B chunk c16 + hh (8 consecutive keys)
+            const bf16x8 vf = *reinterpret_cast<const bf16x8*>(Vs + d * 32 * 128 + (vfb ^ (c16 << 4)));
+            o[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf[tb][c], o[d], 0, 0, 0);
           }
-          o[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf[tb][c], o[d], 0, 0, 0);
-        }
     }
     AP_ST(t, 4);
   };
@@ -485,7 +441,7 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_bf16_kernel(AttnArgs p) {
   }
 }
 
-// Fused combine of the decode kernels (all threads of the block call it; `po` = this block's partial, already written with plain stores)
+// Fused combine of the wave-streaming decode kernel (all threads of the block call it; `po` = this block's partial, already written with plain stores)
 template <int HD>
 __device__ __forceinline__ void decode_combine_tail(const AttnArgs& p, float* part, float* po, int nsplit, int* counters, int b, int h, int tid) {
   // Fused combine (decode step): the block that arrives last at the (batch, head) counter merges the nsplit partials.
@@ -548,8 +504,8 @@ __device__ __forceinline__ void decode_combine_tail(const AttnArgs& p, float* pa
 // ------------------------------------------------------------------------------------
 // Decode (Sq == 1): grid (nsplit, H, B); block 256.  part[b][h][split] = {o[HD], m, l}
 // ------------------------------------------------------------------------------------
-template <int HD, bool NT = false>   // NT: non-temporal policy on the K / V^T stream (read once per step by one block)
-__global__ __launch_bounds__(256) void attn_decode_bf16_kernel(AttnArgs p, float* part, int nsplit, int chunk, int* counters) {
+template <int HD>
+__global__ __launch_bounds__(256) void attn_decode_bf16_kernel(AttnArgs p, float* part, int nsplit, int chunk) {
   constexpr int LPR = HD / 8;            // lanes per K row (16-B each)
   constexpr int RPW = 64 / LPR;          // K rows per wave-load
   extern __shared__ __attribute__((aligned(16))) char dsm[];
@@ -565,12 +521,11 @@ __global__ __launch_bounds__(256) void attn_decode_bf16_kernel(AttnArgs p, float
   if (n <= 0) {          // cannot happen with decode_plan's splits (every split owns >= 1 key); kept for safety
     if (tid < HD) po[tid] = 0.f;
     if (tid == 0) { po[HD] = -INFINITY; po[HD + 1] = 0.f; }
-    if (!counters) return;
+    return;
   }
   const bf16_t* Q = (const bf16_t*)p.q + b * p.q_sb + h * p.q_sh;
   const bf16_t* K = (const bf16_t*)p.k + b * p.k_sb + hk * p.k_sh;
   const bf16_t* VT = (const bf16_t*)p.vt + b * p.v_sb + hk * p.v_sh;
-  if (n > 0) {
   // phase 1: scores.  lane -> (row-in-group, 8 d's); U independent row groups in flight per wave
   float qv[8];
   load8(Q + (lane % LPR) * 8, qv);
@@ -583,7 +538,7 @@ __global__ __launch_bounds__(256) void attn_decode_bf16_kernel(AttnArgs p, float
       int r = r0 + u * RPW + lr;
       r = r < n ? r : n - 1;
       const bf16x8* kp = reinterpret_cast<const bf16x8*>(K + (int64_t)(kv_lo + r) * p.k_ss + lc);
-      kk[u] = NT ? __builtin_nontemporal_load(kp) : *kp;
+      kk[u] = *kp;
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -634,7 +589,7 @@ __global__ __launch_bounds__(256) void attn_decode_bf16_kernel(AttnArgs p, float
 #pragma unroll
       for (int j = 0; j < DB; ++j) {
         const bf16x8* vp = reinterpret_cast<const bf16x8*>(VT + (int64_t)(d0 + j) * p.v_sd + kv_lo + c);
-        vv[j] = NT ? __builtin_nontemporal_load(vp) : *vp;
+        vv[j] = *vp;
       }
       float pv[8];
       const int nvalid = p.Sk - (kv_lo + c);          // >= 8 except in the last chunk
@@ -652,9 +607,6 @@ __global__ __launch_bounds__(256) void attn_decode_bf16_kernel(AttnArgs p, float
     }
   }
   if (tid == 0) { po[HD] = mx; po[HD + 1] = ls; }
-  }  // n > 0
-  if (!counters) return;
-  decode_combine_tail<HD>(p, part, po, nsplit, counters, b, h, tid);
 }
 
 // Sums over the 16 (8) lanes of a DPP row (half row) with four (three) v_add_f32_dpp: quad_perm [1,0,3,2], [2,3,0,1], row_half_mirror,
@@ -680,7 +632,7 @@ __device__ __forceinline__ float row8_max(float v) { return dpp_max<0x141>(dpp_m
 // without leaving the wave; the eight waves merge (m, l, o) once through LDS.  No block-wide phase change, and with one block
 // per (batch, head) no cross-block hand-off either.
 // ------------------------------------------------------------------------------------
-template <int HD, bool NT>
+template <int HD>
 __global__ __launch_bounds__(512) void attn_decode_wave_kernel(AttnArgs p, float* part, int nsplit, int chunk, int* counters) {
   constexpr int LPR = HD / 8;        // lanes per K row (16 B each)
   constexpr int RPW = 64 / LPR;      // K rows per wave-wide load
@@ -715,7 +667,7 @@ __global__ __launch_bounds__(512) void attn_decode_wave_kernel(AttnArgs p, float
       for (int u = 0; u < NKL; ++u) {
         const int r = min(t0 + u * RPW + lr, hi - 1);
         const bf16x8* kp = reinterpret_cast<const bf16x8*>(K + (int64_t)r * p.k_ss + lc);
-        kk[u] = NT ? __builtin_nontemporal_load(kp) : *kp;
+        kk[u] = __builtin_nontemporal_load(kp);            // non-temporal: the K / V^T stream is read once per step by one block
       }
     };
     load_k(lo);
@@ -728,7 +680,7 @@ __global__ __launch_bounds__(512) void attn_decode_wave_kernel(AttnArgs p, float
 #pragma unroll
       for (int j = 0; j < NVL; ++j) {
         const bf16x8* vp = reinterpret_cast<const bf16x8*>(VT + (int64_t)(j * 8 + dr) * p.v_sd + kvc);
-        vv[j] = NT ? __builtin_nontemporal_load(vp) : *vp;
+        vv[j] = __builtin_nontemporal_load(vp);
       }
 #pragma unroll
       for (int u = 0; u < NKL; ++u) {
@@ -881,14 +833,9 @@ __global__ __launch_bounds__(64) void attn_generic_kernel(AttnArgs p, int hd, in
 
 inline void decode_plan(int B, int H, int Sk, int* nsplit, int* chunk) {
   // ~768 blocks: at B*H = 256 three splits of the context beat four by 5-8 % for 600..1500 keys (larger chunks fill the 64 lanes of
-  // the V^T scan and the K scan's 128-row passes; sweep with tools/attn_decode_bench.py under -DA3V_ABLATION, A3V_DECODE_WANT)
-#ifndef A3V_DECODE_BLOCKS
-#define A3V_DECODE_BLOCKS 768
-#endif
+  // the V^T scan and the K scan's 128-row passes)
+  constexpr int A3V_DECODE_BLOCKS = 768;
   int want = (A3V_DECODE_BLOCKS + B * H - 1) / (B * H);
-#ifdef A3V_ABLATION
-  { const int e = A3V_ENV_INT("A3V_DECODE_WANT", 0); if (e) want = e; }
-#endif
   int maxs = (Sk + 127) / 128;
   int ns = want < maxs ? want : maxs;
   if (ns < 1) ns = 1;
@@ -925,7 +872,7 @@ static int attention_impl(const void* q, const void* k, const void* vt, void* ou
   p.scale_log2 = p.scale * 1.4426950408889634f;
   p.lse = lse;
   p.head_group = 1;
-  p.staged_o = A3V_ENV_INT("A3V_ATTN_STAGED_O", 1) != 0;
+  p.staged_o = 1;
   p.lazy_rescale = A3V_ENV_INT("A3V_ATTN_LAZY", 1);     // bit 0: lazy rescale; bit 1: ds_bpermute form of the row-maximum exchange (A/B)
   if (lse && Sq == 1 && dtype == A3V_BF16 && (hd == 64 || hd == 128)) return A3V_ERR_ARG;  // decode kernel has no LSE output
   if (dtype == A3V_F32) {
@@ -956,21 +903,21 @@ static int attention_impl(const void* q, const void* k, const void* vt, void* ou
       int ch2 = (((Sk + ns2 - 1) / ns2) + 63) & ~63;
       ns2 = (Sk + ch2 - 1) / ch2;
       if (hd == 128) {
-        hipLaunchKernelGGL((attn_decode_wave_kernel<128, true>), dim3(ns2, H, B), dim3(512), 0, st, p, scratch, ns2, ch2, (int*)nullptr);
+        hipLaunchKernelGGL((attn_decode_wave_kernel<128>), dim3(ns2, H, B), dim3(512), 0, st, p, scratch, ns2, ch2, (int*)nullptr);
         hipLaunchKernelGGL(attn_decode_combine_kernel<128>, dim3(H, B), dim3(128), 0, st, scratch, out, p.o_sb, p.o_sh, H, ns2, dtype);
       } else {
-        hipLaunchKernelGGL((attn_decode_wave_kernel<64, true>), dim3(ns2, H, B), dim3(512), 0, st, p, scratch, ns2, ch2, (int*)nullptr);
+        hipLaunchKernelGGL((attn_decode_wave_kernel<64>), dim3(ns2, H, B), dim3(512), 0, st, p, scratch, ns2, ch2, (int*)nullptr);
         hipLaunchKernelGGL(attn_decode_combine_kernel<64>, dim3(H, B), dim3(64), 0, st, scratch, out, p.o_sb, p.o_sh, H, ns2, dtype);
       }
       A3V_LAUNCH_CHECK();
       return A3V_OK;
     }
     if (hd == 128) {
-      hipLaunchKernelGGL(attn_decode_bf16_kernel<128>, dim3(ns, H, B), dim3(256), shm, st, p, scratch, ns, ch, (int*)nullptr);
+      hipLaunchKernelGGL(attn_decode_bf16_kernel<128>, dim3(ns, H, B), dim3(256), shm, st, p, scratch, ns, ch);
       A3V_LAUNCH_CHECK();
       hipLaunchKernelGGL(attn_decode_combine_kernel<128>, dim3(H, B), dim3(128), 0, st, scratch, out, p.o_sb, p.o_sh, H, ns, dtype);
     } else {
-      hipLaunchKernelGGL(attn_decode_bf16_kernel<64>, dim3(ns, H, B), dim3(256), shm, st, p, scratch, ns, ch, (int*)nullptr);
+      hipLaunchKernelGGL(attn_decode_bf16_kernel<64>, dim3(ns, H, B), dim3(256), shm, st, p, scratch, ns, ch);
       A3V_LAUNCH_CHECK();
       hipLaunchKernelGGL(attn_decode_combine_kernel<64>, dim3(H, B), dim3(64), 0, st, scratch, out, p.o_sb, p.o_sh, H, ns, dtype);
     }
@@ -990,14 +937,8 @@ static int attention_impl(const void* q, const void* k, const void* vt, void* ou
     p.head_group = G;
   }
   if (hd == 128) {
-    const bool ps = A3V_ENV_INT("A3V_ATTN_PSWAP", 1) != 0;          // A3V_ATTN_PSWAP=0: the 8-B-half V^T reads (A/B runs)
-    if (causal) {
-      if (ps) hipLaunchKernelGGL((attn_prefill_bf16_kernel<128, true, true>), grid, dim3(256), 0, st, p);
-      else hipLaunchKernelGGL((attn_prefill_bf16_kernel<128, true, false>), grid, dim3(256), 0, st, p);
-    } else {
-      if (ps) hipLaunchKernelGGL((attn_prefill_bf16_kernel<128, false, true>), grid, dim3(256), 0, st, p);
-      else hipLaunchKernelGGL((attn_prefill_bf16_kernel<128, false, false>), grid, dim3(256), 0, st, p);
-    }
+    if (causal) hipLaunchKernelGGL((attn_prefill_bf16_kernel<128, true>), grid, dim3(256), 0, st, p);
+    else hipLaunchKernelGGL((attn_prefill_bf16_kernel<128, false>), grid, dim3(256), 0, st, p);
   } else {
     if (causal) hipLaunchKernelGGL((attn_prefill_bf16_kernel<64, true>), grid, dim3(256), 0, st, p);
     else hipLaunchKernelGGL((attn_prefill_bf16_kernel<64, false>), grid, dim3(256), 0, st, p);
@@ -1019,7 +960,7 @@ extern "C" int a3v_attention_lse(const void* q, const void* k, const void* vt, v
   return attention_impl(q, k, vt, out, B, Sq, Sk, H, Hkv, hd, strides, causal, nullptr, lse, dtype, stream);
 }
 
-// Decode attention with the split combine folded into the same launch (see attn_decode_bf16_kernel); `counters` are
+// Decode attention with the split combine folded into the same launch (see attn_decode_wave_kernel); `counters` are
 // B*H zero-initialised ints that the kernel leaves zero.  bf16, hd in {64, 128}.
 int a3v_attention_decode_fused(const void* q, const void* k, const void* vt, void* out, int B, int Sk, int H, int Hkv, int hd,
                                const int64_t* strides, float* scratch, int* counters, void* stream) {
@@ -1039,39 +980,17 @@ int a3v_attention_decode_fused(const void* q, const void* k, const void* vt, voi
   p.staged_o = 0;
   int ns, ch;
   decode_plan(B, H, Sk, &ns, &ch);
-  const size_t shm = (size_t)(ch + 8) * sizeof(float);
   hipStream_t st = (hipStream_t)stream;
-  const bool nt = A3V_ENV_INT("A3V_ATTN_DECODE_NT", 1) != 0;       // default: non-temporal KV stream (=0 for A/B runs)
-  if (A3V_ENV_INT("A3V_ATTN_DECODE_WAVE", 1) != 0) {     // default: the wave-streaming form (=0: the two-phase form)
-    // one block per (batch, head) when that alone covers the CUs, else the fewest splits that do (never more than the
-    // two-phase plan: the scratch buffer is sized for that one)
-    int ns2 = (256 + B * H - 1) / (B * H);
-#ifdef A3V_ABLATION
-    { const int e = A3V_ENV_INT("A3V_DECODE_WAVE_SPLITS", 0); if (e > 0) ns2 = e; }      // sweeps: splits of the wave-streaming form
-#endif
-    if (ns2 > ns) ns2 = ns;
-    int ch2 = (Sk + ns2 - 1) / ns2;
-    ch2 = (ch2 + 63) & ~63;
-    ns2 = (Sk + ch2 - 1) / ch2;
-    const dim3 grid(ns2, H, B);
-    if (hd == 128) {
-      if (nt) hipLaunchKernelGGL((attn_decode_wave_kernel<128, true>), grid, dim3(512), 0, st, p, scratch, ns2, ch2, counters);
-      else hipLaunchKernelGGL((attn_decode_wave_kernel<128, false>), grid, dim3(512), 0, st, p, scratch, ns2, ch2, counters);
-    } else {
-      if (nt) hipLaunchKernelGGL((attn_decode_wave_kernel<64, true>), grid, dim3(512), 0, st, p, scratch, ns2, ch2, counters);
-      else hipLaunchKernelGGL((attn_decode_wave_kernel<64, false>), grid, dim3(512), 0, st, p, scratch, ns2, ch2, counters);
-    }
-    A3V_LAUNCH_CHECK();
-    return A3V_OK;
-  }
-  if (hd == 128) {
-    if (nt) hipLaunchKernelGGL((attn_decode_bf16_kernel<128, true>), dim3(ns, H, B), dim3(256), shm, st, p, scratch, ns, ch, counters);
-    else hipLaunchKernelGGL((attn_decode_bf16_kernel<128, false>), dim3(ns, H, B), dim3(256), shm, st, p, scratch, ns, ch, counters);
-  } else {
-    if (nt) hipLaunchKernelGGL((attn_decode_bf16_kernel<64, true>), dim3(ns, H, B), dim3(256), shm, st, p, scratch, ns, ch, counters);
-    else hipLaunchKernelGGL((attn_decode_bf16_kernel<64, false>), dim3(ns, H, B), dim3(256), shm, st, p, scratch, ns, ch, counters);
-  }
+  // one block per (batch, head) when that alone covers the CUs, else the fewest splits that do (never more than the
+  // two-phase plan: the scratch buffer is sized for that one)
+  int ns2 = (256 + B * H - 1) / (B * H);
+  if (ns2 > ns) ns2 = ns;
+  int ch2 = (Sk + ns2 - 1) / ns2;
+  ch2 = (ch2 + 63) & ~63;
+  ns2 = (Sk + ch2 - 1) / ch2;
+  const dim3 grid(ns2, H, B);
+  if (hd == 128) hipLaunchKernelGGL(attn_decode_wave_kernel<128>, grid, dim3(512), 0, st, p, scratch, ns2, ch2, counters);
+  else hipLaunchKernelGGL(attn_decode_wave_kernel<64>, grid, dim3(512), 0, st, p, scratch, ns2, ch2, counters);
   A3V_LAUNCH_CHECK();
   return A3V_OK;
 }
-

@@ -9,7 +9,7 @@
 //      S^T  = K . Q^T ,  dP^T = V . dO^T            (A = K / V rows from LDS, B = Q / dO in registers)
 //      P^T  = exp(S^T*scale - lse[q]) ;  dS^T = P^T o (dP^T - D[q]) * scale     (lane-local)
 //      dQ^T += K^T . dS^T                            (A = K^T rows from LDS, B = dS^T from the accumulators)
-//  dK/dV kernels (grid over kv tiles; loop over queries and the n_rep query heads; one launch per output):   lane <-> key
+//  dK/dV kernel (grid over kv tiles; loop over queries and the n_rep query heads; both outputs in one launch):   lane <-> key
 //      S    = Q . K^T ,  dP = dO . V^T               (A = Q / dO rows from LDS, B = K / V in registers)
 //      P, dS with lse[q], D[q] per REGISTER row (read from LDS)
 //      dV^T += dO^T . P ,  dK^T += Q^T . dS          (A = dO^T / Q^T fragments by transpose reads of the dO / Q row tiles, B = P / dS)
@@ -61,9 +61,6 @@ __device__ __forceinline__ int tile_swz(int row) {
 // rows past the end read as zeros (their scores are masked).
 __device__ __forceinline__ void buf_dma16(__amdgpu_buffer_rsrc_t rs, char* lds_dst, unsigned voff) {
   __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)lds_dst, 16, voff, 0, 0, 0);
-}
-__device__ __forceinline__ void buf_dma4(__amdgpu_buffer_rsrc_t rs, void* lds_dst, unsigned voff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)lds_dst, 4, voff, 0, 0, 0);
 }
 // Per-lane byte offset of DMA instruction 0 of a tile (thread id -> row id / KCH, physical chunk id % KCH, source chunk = physical ^
 // swizzle(row)).  Instruction i covers the rows 256 / KCH further down (16 at HD 128, 32 at HD 64): tile_swz only looks at row bits
@@ -348,208 +345,12 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(BwdArgs p) {
   }
 }
 
-// ------------------------------------------------------------------ dK, dV
-// Two specialisations of one kernel, launched back to back: WHICH == 0 accumulates dV (needs S only), WHICH == 1
-// accumulates dK (needs S and dP).  Each keeps ONE [HD x 32-key] accumulator set (64 VGPRs) instead of two, which brings
-// the kernel under 256 VGPRs = two waves per SIMD and cuts the LDS tiles staged per query tile from four to two / three;
-// the price is one extra S^T recompute (5 instead of 4 tile products), paid back ~1.5x by the doubled occupancy.
-template <int HD, int WHICH, bool PACKED>
-__global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(BwdArgs p) {
-  constexpr int TILE = 64 * HD * 2;
-  // two (Q, dO) tile pairs + their lse / D rows: pair i+1 streams in by LDS-DMA while pair i is consumed (see the dQ kernel)
-  __shared__ __attribute__((aligned(1024))) char lds[4 * TILE + 1024];
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  int head_slot, kt_;
-  xcd_head_tile((p.S + 127) / 128, head_slot, kt_, p.group_kv);
-  const int b = head_slot / p.Hkv, hk = head_slot - b * p.Hkv;
-  const int nrep = p.H / p.Hkv;
-  const int kl = lane & 31, hh = lane >> 5;
-  const int kvrow = kt_ * 128 + wave * 32 + kl;
-  const int kc = kvrow < p.S ? kvrow : p.S - 1;
-  const bf16_t* Kr = p.k + b * p.k_sb + hk * p.k_sh + (int64_t)kc * HD;
-  const bf16_t* Vr = p.v + b * p.v_sb + hk * p.v_sh + (int64_t)kc * p.v_ss;
-  bf16x8 kf[HD / 16], vf[WHICH == 1 ? HD / 16 : 1];
-#pragma unroll
-  for (int ks = 0; ks < HD / 16; ++ks) {
-    kf[ks] = *reinterpret_cast<const bf16x8*>(Kr + ks * 16 + hh * 8);
-    if (WHICH == 1) vf[ks] = *reinterpret_cast<const bf16x8*>(Vr + ks * 16 + hh * 8);
-  }
-  f32x16 acc[HD / 32];
-#pragma unroll
-  for (int d = 0; d < HD / 32; ++d)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[d][r] = 0.f;
-  const float sl2 = p.scale * 1.4426950408889634f;
-  const int q_begin = p.causal ? (kt_ * 128) / 64 : 0;      // first q tile that can see this block's keys
-  const int n_qt = (p.S + 63) / 64;
-  const int n_it = n_qt - q_begin, total = nrep * n_it;
-  // pair `it` = (head repetition it / n_it, query tile q_begin + it % n_it) -> buffer it & 1:
-  //   [Q rows | dO rows] (S^T recompute from row fragments; Q^T for dK / dO^T for dV by transpose reads) + lse[64] | D[64]
-  // (the pair indices are carried as counters: two integer divisions per iteration were ~50 instructions)
-  const unsigned qoff = dma_lane_offset0<HD>((int64_t)p.H * HD, tid);          // Q and dO rows share the row stride H*HD
-  const int fbase = frag_rows_base<HD>(kl, hh);
-  const TrBase trb = tr_bases<HD>(lane);
-  int rep_n = 0, qi_n = 0;                       // (head repetition, query tile index) of the next pair to issue
-  auto issue = [&](int it) {
-    const int h = hk * nrep + rep_n, q0 = (q_begin + qi_n) * 64;
-    if (++qi_n == n_it) { qi_n = 0; ++rep_n; }
-    char* buf = lds + (it & 1) * 2 * TILE;
-    stage_rows_dma<HD>(p.q + ((int64_t)b * p.S * p.H + h) * HD, (int64_t)p.H * HD, q0, p.S, buf, qoff, wave);
-    stage_rows_dma<HD>(p.dout + ((int64_t)b * p.S * p.H + h) * HD, (int64_t)p.H * HD, q0, p.S, buf + TILE, qoff, wave);
-    float* sm = reinterpret_cast<float*>(lds + 4 * TILE) + (it & 1) * 128;
-    if (wave == 0) {
-      const auto rs = __builtin_amdgcn_make_buffer_rsrc((void*)(p.lse + ((int64_t)b * p.H + h) * p.S + q0), 0, (p.S - q0) * 4, 0x00020000);
-      buf_dma4(rs, sm, lane * 4);
-    }
-    if (WHICH == 1 && wave == 1) {
-      const auto rs = __builtin_amdgcn_make_buffer_rsrc((void*)(p.D + ((int64_t)b * p.S + q0) * p.H + h), 0, ((p.S - 1 - q0) * p.H + 1) * 4, 0x00020000);
-      buf_dma4(rs, sm + 64, lane * p.H * 4);
-    }
-  };
-  if (total > 0) issue(0);
-#ifdef AB_STAMP
-  unsigned long long* stamps = (p.stamps && blockIdx.x == AB_STAMP && tid == 0) ? p.stamps : nullptr;
-#endif
-  int qi_c = 0;                                  // query tile index of the pair being consumed
-  // The loop is unrolled by two with the buffer index a compile-time constant: every LDS read address is then (per-lane base ^ constant)
-  // + an instruction offset.  With a run-time buffer base each of the 40 - 64 fragment reads of an iteration paid its own v_or / v_add.
-  auto body = [&](int it, auto bufc) {
-    constexpr int BUF = decltype(bufc)::value;
-    AB_ST(1 + WHICH, it, 0);
-    {
-      const int q0 = (q_begin + qi_c) * 64;
-      if (++qi_c == n_it) qi_c = 0;
-      const char* Qs = lds + BUF * 2 * TILE;
-      const char* T1 = Qs + TILE;
-      const float* lse_s = reinterpret_cast<const float*>(lds + 4 * TILE) + BUF * 128;
-      const float* D_s = lse_s + 64;
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      AB_ST(1 + WHICH, it, 1);
-      __syncthreads();                       // pair `it` has landed; every wave is done with the other buffer (pair it - 1)
-      AB_ST(1 + WHICH, it, 2);
-      if (it + 1 < total) issue(it + 1);
-      AB_ST(1 + WHICH, it, 3);
-      if (p.causal && q0 + 63 < kt_ * 128 + wave * 32) return;            // every query row of the tile is before this wave's first key
-      bf16x8 bf[2][2];                       // P (dV) or dS (dK) as the B operand of the accumulation products
-      const int kv_hi = kt_ * 128 + wave * 32 + 31;                        // last key of this wave (wave-uniform)
-      const bool interior = (q0 + 64 <= p.S) && (kv_hi < p.S) && (!p.causal || q0 >= kv_hi);
-#pragma unroll
-      for (int tb = 0; tb < 2; ++tb) {
-        f32x16 s, dp;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
-#pragma unroll
-        for (int ks = 0; ks < HD / 16; ++ks) {
-          s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows<HD>(Qs, fbase, tb, ks), kf[ks], s, 0, 0, 0);
-          if (WHICH == 1) dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows<HD>(T1, fbase, tb, ks), vf[ks], dp, 0, 0, 0);
-        }
-#pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) {
-          const int qb = tb * 32 + 8 * g4 + 4 * hh;                       // 4 consecutive query rows of the tile
-          f32x4 l4 = *reinterpret_cast<const f32x4*>(lse_s + qb);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) l4[e] *= 1.4426950408889634f;       // lse * log2(e)
-          f32x4 d4 = {0.f, 0.f, 0.f, 0.f};
-          if (WHICH == 1) d4 = *reinterpret_cast<const f32x4*>(D_s + qb);
-          // interior pairs (all 64 query rows exist and see all 32 keys of this wave): no compare / select per element; on
-          // the others the exponential is evaluated unconditionally and selected (an `ok ? exp : 0` form compiles to one
-          // exec-mask branch per element: 32 per tile)
-          if (interior) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              const int r = g4 * 4 + e;
-              const float pr = __builtin_amdgcn_exp2f(fmaf(s[r], sl2, -l4[e]));
-              bf[tb][r >> 3][r & 7] = WHICH == 0 ? f2bf(pr) : f2bf(pr * (dp[r] - d4[e]));
-            }
-          } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              const int r = g4 * 4 + e;
-              const int qg = q0 + qb + e;
-              const bool ok = (qg < p.S) && (kvrow < p.S) && (!p.causal || kvrow <= qg);
-              const float ev = __builtin_amdgcn_exp2f(fmaf(s[r], sl2, -l4[e]));
-              const float val = WHICH == 0 ? ev : ev * (dp[r] - d4[e]);
-              bf[tb][r >> 3][r & 7] = f2bf(ok ? val : 0.f);
-            }
-          }
-        }
-      }
-      AB_ST(1 + WHICH, it, 4);
-      const char* At = WHICH == 0 ? T1 : Qs;      // dV^T += dO^T . P^T ; dK^T += Q^T . dS^T : transposed operands read out of the row tiles
-#pragma unroll
-      for (int tb = 0; tb < 2; ++tb)
-#pragma unroll
-        for (int c = 0; c < 2; ++c)
-#pragma unroll
-          for (int d = 0; d < HD / 32; ++d)    // (chains interleaved, see the dQ kernel)
-            acc[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows_tr<HD>(At, trb, d, tb, c), bf[tb][c], acc[d], 0, 0, 0);
-      AB_ST(1 + WHICH, it, 5);
-    }
-  };
-  {
-    int it = 0;
-    for (; it + 1 < total; it += 2) {
-      body(it, std::integral_constant<int, 0>{});
-      body(it + 1, std::integral_constant<int, 1>{});
-    }
-    if (it < total) body(it, std::integral_constant<int, 0>{});
-  }
-  if (WHICH == 1) {        // dS was formed without the 1 / sqrt(hd) factor (see the dQ kernel)
-#pragma unroll
-    for (int d = 0; d < HD / 32; ++d)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[d][r] *= p.scale;
-  }
-  // (the stores are written out here rather than through store_grad_rows: routed through the helper, this kernel went from
-  //  240 VGPRs to 256 + 18 spills inside the query loop -- two waves per SIMD leave the allocator no slack)
-  if (kvrow < p.S) {
-    if constexpr (!PACKED) {
-      bf16_t* O = (WHICH == 0 ? p.dv : p.dk) + (((int64_t)b * p.Hkv + hk) * p.S + kvrow) * HD;
-#pragma unroll
-      for (int d = 0; d < HD / 32; ++d)
-#pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) {
-          bf16x4 a;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) a[e] = f2bf(acc[d][g4 * 4 + e]);
-          *reinterpret_cast<bf16x4*>(O + d * 32 + g4 * 8 + hh * 4) = a;
-        }
-    }
-  }
-  if constexpr (PACKED) {
-    // packed mode: the wave's 32 x HD tile goes through a private LDS patch (the row tiles are free after one more barrier) and
-    // leaves as whole rows of the fused-qkv gradient
-    __syncthreads();
-    char* patch = lds + wave * (32 * HD * 2);
-    char* wrow = patch + kl * (HD * 2);
-    const int wx = (kl & (HD / 8 - 1)) << 1;
-    const float* CS = p.cos_sin + (int64_t)(p.rope_pos0 + kc) * HD;          // [pos][HD / 2][cos, sin] (kc: the clamped row)
-#pragma unroll
-    for (int d = 0; d < HD / 32; ++d)
-#pragma unroll
-      for (int g4 = 0; g4 < 4; ++g4) {
-        const int dc = d * 32 + g4 * 8 + hh * 4;
-        float v0 = acc[d][g4 * 4 + 0], v1 = acc[d][g4 * 4 + 1], v2 = acc[d][g4 * 4 + 2], v3 = acc[d][g4 * 4 + 3];
-        if (WHICH == 1) {      // dK: rotate back, dx = R(-theta) dy on the (even, odd) pairs (LLM/llama_ens5.py:123-135 backward)
-          const f32x4 cs = *reinterpret_cast<const f32x4*>(CS + dc);
-          const float a0 = v0 * cs[0] + v1 * cs[1], a1 = -v0 * cs[1] + v1 * cs[0];
-          const float a2 = v2 * cs[2] + v3 * cs[3], a3 = -v2 * cs[3] + v3 * cs[2];
-          v0 = a0; v1 = a1; v2 = a2; v3 = a3;
-        }
-        bf16x4 ov;
-        ov[0] = f2bf(v0); ov[1] = f2bf(v1); ov[2] = f2bf(v2); ov[3] = f2bf(v3);
-        *reinterpret_cast<bf16x4*>(wrow + (((d * 8 + g4 * 2 + hh) ^ wx) << 3)) = ov;
-      }
-    store_patch_rows<HD>(patch, p.dqkv + (int64_t)b * p.S * p.ld_qkv + (int64_t)(WHICH == 0 ? p.H + p.Hkv + hk : p.H + hk) * HD, p.ld_qkv,
-                         kt_ * 128 + wave * 32, p.S, lane);
-  }
-}
-
 // ------------------------------------------------------------------ dK + dV in ONE pass (round 4)
-// The two kernels above run two waves per SIMD at 254 VGPRs: no room to hold a fragment ahead of its MFMA, so hipcc emits
-// `ds_read -> s_waitcnt lgkmcnt(0) -> v_mfma` 48 times per query tile and the matrix pipe waits out an LDS round trip per MFMA
-// (the partner wave of an unrelated block is the only cover): 0.14 of the MFMA peak, and S^T is recomputed in each of them.
-// Here a block is still 4 waves x 32 keys, but ONE wave per SIMD with the whole 512-register file, both accumulator sets
+// The round-1 form (one launch per output, one [HD x 32-key] accumulator set each) ran two waves per SIMD at
+// 254 VGPRs: no room to hold a fragment ahead of its MFMA, so hipcc emitted `ds_read -> s_waitcnt lgkmcnt(0) -> v_mfma` 48 times per
+// query tile and the matrix pipe waited out an LDS round trip per MFMA (the partner wave of an unrelated block was the only cover):
+// 0.14 of the MFMA peak, and S^T was recomputed in each launch.
+// Here a block is 4 waves x 32 keys, ONE wave per SIMD with the whole 512-register file, both accumulator sets
 // (dV^T, dK^T: 128 registers), K and V of the wave's keys (64) and a software pipeline over 32-query UNITS u = (pair, half):
 //     step u:   A(u+1)  S = Q K^T, dP = dO V^T of the NEXT unit      16 MFMAs, fragments fetched one step ahead
 //             ∥ B(u)    P = exp2(S sl2 - lse), dS = P o (dP - D)      ~100 VALU in the shadow of A's MFMAs
@@ -558,7 +359,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(BwdArgs p) {
 // so every MFMA finds its operands in registers and the only synchronisation is one block barrier per pair (64 queries).
 // (Q, dO) pairs stream through a ring of FOUR LDS buffers by LDS-DMA, issued two iterations ahead of their first read.  4 tile products per
 // (query, key) tile pair instead of the 5 of the two-launch form; same fragment helpers, same arithmetic per element, same
-// per-accumulator MFMA order: the results are bit-identical to attn_bwd_dkv_kernel<.., 0 / 1, ..>.
+// per-accumulator MFMA order: the results were bit-identical to that form's.
 //
 // Register plan.  hipcc places the A / B operands of an MFMA builtin in arch VGPRs only and has no pressure-aware scheduling: with the
 // loop-invariant K / V fragments there the loop wants ~300 arch VGPRs, the invariants are spilled (a scratch reload + vmcnt(0) in front of
@@ -1115,17 +916,10 @@ static int attention_bwd_mfma_impl(const void* q, const void* k, int64_t k_sb, i
   };
   p.group_q = group_of(B * H, gq.x);
   p.group_kv = group_of(B * Hkv, gk.x);
-  // A3V_ATTN_BWD_V2 (default 1): dK and dV by the one-pass, one-wave-per-SIMD kernel (0: the two round-1 launches; A/B and equality tests)
-  const int v2 = A3V_ENV_INT("A3V_ATTN_BWD_V2", 1);
 #define A3V_BWD_LAUNCH(HDV, PK)                                                                  \
   do {                                                                                           \
     hipLaunchKernelGGL((attn_bwd_dq_kernel<HDV, PK>), gq, dim3(256), 0, st, p);                  \
-    if (v2 & 1) {                                                                                \
-      hipLaunchKernelGGL((attn_bwd_dkv2_kernel<HDV, PK>), gk, dim3(256), 0, st, p);              \
-    } else {                                                                                     \
-      hipLaunchKernelGGL((attn_bwd_dkv_kernel<HDV, 0, PK>), gk, dim3(256), 0, st, p);            \
-      hipLaunchKernelGGL((attn_bwd_dkv_kernel<HDV, 1, PK>), gk, dim3(256), 0, st, p);            \
-    }                                                                                            \
+    hipLaunchKernelGGL((attn_bwd_dkv2_kernel<HDV, PK>), gk, dim3(256), 0, st, p);                \
   } while (0)
   if (hd == 128) {
     if (dqkv) A3V_BWD_LAUNCH(128, true); else A3V_BWD_LAUNCH(128, false);

@@ -23,10 +23,7 @@
 namespace {
 
 constexpr int BK = 64;
-#ifndef A3V_GROUP_M
-#define A3V_GROUP_M 8
-#endif
-constexpr int GROUP_M = A3V_GROUP_M;
+constexpr int GROUP_M = 8;
 constexpr int GEMM_EPI_RAW = 1 << 20;     // internal: fp32 output without the bf16 rounding of the accumulator
 constexpr int GEMM_EPI_SCALE = 1 << 22;   // internal: fp8 operands -- accumulator *= sa[m] * sw[n] (per-row scales of A and W) first
 constexpr int GEMM_EPI_ROPEKV = 1 << 21;  // internal: fused-qkv epilogue (a3v_gemm_qkv_rope): RoPE on q / k, k -> K cache, v -> V^T cache
@@ -445,12 +442,7 @@ __device__ __forceinline__ bool gemm_epilogue_fast(f32x4 (&acc)[TM][TN], const G
             asm volatile("" : "+v"(sqr));
             const float* csr = csb + (((int64_t)(k.rope_pos0 + sqr)) << k.hd_shift);      // (pos << (hd_shift - 1)) * 2 floats
 #pragma unroll
-#ifdef ROPE_NO_CS      // timing build (wrong results): no cos / sin loads -- they are 21 of the epilogue's 28 us per launch (r04g_decode_fixup_and_rope_epilogue.txt)
-            for (int j = 0; j < 4; ++j) cs[ii][j] = f32x4{1.f, 0.f, 1.f, 0.f};
-            (void)csr;
-#else
             for (int j = 0; j < 4; ++j) cs[ii][j] = *reinterpret_cast<const f32x4*>(csr + j * 16);
-#endif
             sqr += 16;
             if (sqr >= S_) sqr -= S_;
           }
@@ -1858,11 +1850,6 @@ __device__ __forceinline__ void gemv_finish(const GemvArgs& p, f32x4 v, f32x4 u,
 // (bf16 bits: bf80 bf32 bf06 beca be92 be3d bdba 0000 3da3 3e25 3e7c 3ead 3ee2 3f10 3f39 3f80); bit 3 of a code selects the
 // half by a byte mask.  29 VALU operations per 8 weights.
 __device__ __forceinline__ bf16x8 nf4_bf16x8(uint32_t x) {
-#ifdef A3V_NF4_LOOKUP_AB
-  // timing build only (wrong results): the code dword itself as the MFMA operand, no lookup -- separates the lookup's cost from
-  // the weight stream's (A3V_LIB_PATH + tools/nf4_decode_bench.py --skip-model)
-  return __builtin_bit_cast(bf16x8, u32x4{x, x ^ 0x01010101u, x ^ 0x02020202u, x ^ 0x03030303u} & 0x3f7f3f7fu);
-#endif
   const uint32_t io = x & 0x07070707u, ie = (x >> 4) & 0x07070707u;           // odd / even elements, low 3 bits
   const uint32_t mo = ((x >> 3) & 0x01010101u) * 0xFFu, me = ((x >> 7) & 0x01010101u) * 0xFFu;   // bit 3 -> byte masks
   auto look = [](uint32_t i, uint32_t m, uint32_t t0a, uint32_t t0b, uint32_t t1a, uint32_t t1b) {
@@ -1893,8 +1880,9 @@ __device__ __forceinline__ bf16x8 nf4_bf16x8(uint32_t x) {
 // registers (nf4_bf16x8), each 64-k block is accumulated by its own two MFMAs and its scale is applied once per accumulator element:
 // acc += s_b * (codes . a).  Rounding differs from the bf16 GEMV on Wd = bf16(NF4[q] * s_b): the codes are rounded to bf16 and the
 // scale is applied in fp32 to the block sums.
-template <int AROWS, bool PRO, bool W8, int WAUX = 0, bool N4 = false>   // WAUX: cache-policy bits of the weight-stream LDS-DMA (2 = nt: streamed once)
+template <int AROWS, bool PRO, bool W8, bool N4 = false>
 __global__ __launch_bounds__(256) void gemv_dma_bf16_kernel(GemvArgs p) {
+  constexpr int WAUX = 2;   // cache-policy bits of the weight-stream LDS-DMA: nt (the weights are streamed once per step by ONE CU each)
   extern __shared__ __attribute__((aligned(1024))) char gemv_lds[];
   __shared__ float rinv_s[16];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -2140,16 +2128,10 @@ __global__ __launch_bounds__(256) void gemv_dma_bf16_kernel(GemvArgs p) {
 #pragma unroll
         for (int h2 = 0; h2 < 2; ++h2) {
           // (round 5) v_cvt_scalef32_pk_bf16_fp8 (gfx950): two e4m3 bytes -> two bf16 in ONE VALU op (scale 1: exact, as the fp8 -> f32
-          // -> bf16 pair of ops it replaces; A3V_W8_CVT_F32 builds keep those for the A/B)
-#ifdef A3V_W8_CVT_F32
-          const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)wq[s8][h2], false);
-          const f32x2 hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)wq[s8][h2], true);
-          wf[4 * h2 + 0] = f2bf(lo[0]); wf[4 * h2 + 1] = f2bf(lo[1]); wf[4 * h2 + 2] = f2bf(hi[0]); wf[4 * h2 + 3] = f2bf(hi[1]);
-#else
+          // -> bf16 pair of ops it replaces)
           const bf16x2 lo = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(wq[s8][h2], 1.0f, false);
           const bf16x2 hi = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(wq[s8][h2], 1.0f, true);
           wf[4 * h2 + 0] = lo[0]; wf[4 * h2 + 1] = lo[1]; wf[4 * h2 + 2] = hi[0]; wf[4 * h2 + 3] = hi[1];
-#endif
         }
         if (s8 & 1) acc1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, af[s8], acc1, 0, 0, 0);
         else acc0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, af[s8], acc0, 0, 0, 0);
@@ -2167,9 +2149,6 @@ __global__ __launch_bounds__(256) void gemv_dma_bf16_kernel(GemvArgs p) {
     // access, no cache-wide write-back / invalidate), waits for the acknowledge, then bumps the arrival counter of its
     // tile (of its gate/up tile PAIR with SwiGLU).  The wave that arrives last reloads all partials in one round trip,
     // sums them in slice order (bit-identical whichever wave is last), resets the counter and runs the epilogue.
-#ifdef GEMV_NO_FIXUP   // timing build (wrong results): slice 0 finishes on its own partial, nobody stores or waits: 3.85 -> 3.43 ms per decode step
-    if (sl != 0) return;
-#else
     float* mine = p.part + (((int64_t)(tg * p.S + sl) * 4 + wave) * 64 + lane) * 4;
     asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" ::"v"(mine), "v"(v) : "memory");   // (s_nop: the store's data registers, see the V^T store of the fused-qkv epilogue)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -2209,7 +2188,6 @@ __global__ __launch_bounds__(256) void gemv_dma_bf16_kernel(GemvArgs p) {
           for (int r = 0; r < 4; ++r) u[r] += y[s8][r];
         }
       }
-#endif
   }
   if (W8) {                 // per-row dequantisation scale on the summed accumulator (rows clamp: the stores are masked)
     const int nr = nt0 + (lane >> 4) * 4;
@@ -2809,14 +2787,10 @@ extern "C" int a3v_gemm_qkv_rope(const void* A, int64_t lda, const void* W, int6
 // split-K factor of the DMA GEMV: enough blocks (row groups x S >= A3V_GEMV_BLOCKS) for 256 CUs, S <= 8, S <= number of ring stages
 static int gemv_split(int N, int K, bool w8) {
   const int tgs = (N + 63) / 64, nst = K / (w8 ? 256 : 128);
-// block target of the split: 768 measured best in the decode bench of the 7B geometry (qkv: 4 slices instead of 8, LM head 2 instead
-// of 4; +2-3 % decode tok/s, +6 % with fp8 weights; 640 / 896 / 1024 / 1536 all slower) -- sweep with -DA3V_GEMV_BLOCKS=n
-#ifndef A3V_GEMV_BLOCKS
-#define A3V_GEMV_BLOCKS 768
-#endif
-#ifndef A3V_GEMV_MAXS
-#define A3V_GEMV_MAXS 8
-#endif
+  // block target of the split: 768 measured best in the decode bench of the 7B geometry (qkv: 4 slices instead of 8, LM head 2 instead
+  // of 4; +2-3 % decode tok/s, +6 % with fp8 weights; 640 / 896 / 1024 / 1536 all slower)
+  constexpr int A3V_GEMV_BLOCKS = 768;
+  constexpr int A3V_GEMV_MAXS = 8;      // the fix-up reloads at most eight partials in one round trip
   int S = 1;
   while (S < A3V_GEMV_MAXS && tgs * S < A3V_GEMV_BLOCKS && S * 2 <= nst) S *= 2;
   return S;
@@ -2859,9 +2833,6 @@ static bool gemv_launch(GemvArgs& g, void* ws, hipStream_t st) {
     const bool sw = (g.epi & A3V_EPI_SWIGLU) != 0;
     int slices = g.S;
     if (sw && slices > 6) slices = 6;
-#ifdef A3V_ABLATION
-    { const int e = A3V_ENV_INT("A3V_GEMV_KQ_SLICES", 0); if (e > 0) slices = sw && e > 6 ? 6 : (e > 12 ? 12 : e); }     // sweeps (tools/ab_gemv_kq.py)
-#endif
     while (slices > 1 && g.nkb < 2 * slices) --slices;
     const int nw = slices * (sw ? 2 : 1);
     const int tiles = g.N / 16;
@@ -2876,22 +2847,18 @@ static bool gemv_launch(GemvArgs& g, void* ws, hipStream_t st) {
     }
   }
   void (*kern)(GemvArgs);
-  // weights are streamed once per step by ONE CU each: non-temporal policy on their LDS-DMA (A3V_GEMV_NT=0: default policy, A/B)
-  const bool nt = A3V_ENV_INT("A3V_GEMV_NT", 1) != 0;
-#define GEMV_PICK(AUX)                                                                                                      \
-  (w8 ? (arows == 8 ? (pro ? gemv_dma_bf16_kernel<8, true, true, AUX> : gemv_dma_bf16_kernel<8, false, true, AUX>)          \
-                    : (pro ? gemv_dma_bf16_kernel<16, true, true, AUX> : gemv_dma_bf16_kernel<16, false, true, AUX>))       \
-      : (arows == 8 ? (pro ? gemv_dma_bf16_kernel<8, true, false, AUX> : gemv_dma_bf16_kernel<8, false, false, AUX>)        \
-                    : (pro ? gemv_dma_bf16_kernel<16, true, false, AUX> : gemv_dma_bf16_kernel<16, false, false, AUX>)))
-#define GEMV_PICK_N4(AUX)                                                                                                   \
-  (arows == 8 ? (pro ? gemv_dma_bf16_kernel<8, true, false, AUX, true> : gemv_dma_bf16_kernel<8, false, false, AUX, true>)    \
-              : (pro ? gemv_dma_bf16_kernel<16, true, false, AUX, true> : gemv_dma_bf16_kernel<16, false, false, AUX, true>))
-  if (g.n4) kern = nt ? GEMV_PICK_N4(2) : GEMV_PICK_N4(0);
-  else kern = nt ? GEMV_PICK(2) : GEMV_PICK(0);
+#define GEMV_PICK(W8V)                                                                                            \
+  (arows == 8 ? (pro ? gemv_dma_bf16_kernel<8, true, W8V> : gemv_dma_bf16_kernel<8, false, W8V>)                   \
+              : (pro ? gemv_dma_bf16_kernel<16, true, W8V> : gemv_dma_bf16_kernel<16, false, W8V>))
+#define GEMV_PICK_N4                                                                                              \
+  (arows == 8 ? (pro ? gemv_dma_bf16_kernel<8, true, false, true> : gemv_dma_bf16_kernel<8, false, false, true>)   \
+              : (pro ? gemv_dma_bf16_kernel<16, true, false, true> : gemv_dma_bf16_kernel<16, false, false, true>))
+  if (g.n4) kern = GEMV_PICK_N4;
+  else kern = w8 ? GEMV_PICK(true) : GEMV_PICK(false);
 #undef GEMV_PICK
 #undef GEMV_PICK_N4
-  static bool attr_done[A3V_MAX_DEV][32] = {};
-  const int ki = (g.n4 ? 16 : 0) + (nt ? 8 : 0) + (w8 ? 4 : 0) + (arows == 16 ? 2 : 0) + (pro ? 1 : 0);
+  static bool attr_done[A3V_MAX_DEV][16] = {};
+  const int ki = (g.n4 ? 8 : 0) + (w8 ? 4 : 0) + (arows == 16 ? 2 : 0) + (pro ? 1 : 0);
   if (a3v_dyn_lds_once(attr_done, ki, (const void*)kern, 150 * 1024) != 0) return false;
   hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), ldsb, st, g);
   return true;
@@ -3063,19 +3030,11 @@ extern "C" int a3v_gemm_nt_splitk(const void* A, int64_t lda, const void* W, int
       attr_rc = a3v_dyn_lds_once(attr, ai, (const void*)kern, bytes);
       if (attr_rc == 0) hipLaunchKernelGGL(kern, dim3(p.tiles_m, S), dim3(256), (size_t)bytes, (hipStream_t)stream, p);
     };
-    // the product library carries the two forms the rule above picks; the other rows / stages of the sweep only in A3V_ABLATION builds
+    // the library carries the two forms the rule above picks (and the two-stage kernels below)
     const int bytes = (rows + 64) * 128 * nst;
     if (rows == 64 && nst == 4) go(gemm_nt_skinny_kernel<64, 4>, bytes, 1);
     else if (rows == 256 && nst == 3) go(gemm_nt_skinny_kernel<256, 3>, bytes, 6);
-#ifdef A3V_ABLATION
-    else if (rows == 64 && nst == 3) go(gemm_nt_skinny_kernel<64, 3>, bytes, 0);
-    else if (rows == 64 && nst == 5) go(gemm_nt_skinny_kernel<64, 5>, bytes, 2);
-    else if (rows == 128 && nst == 3) go(gemm_nt_skinny_kernel<128, 3>, bytes, 3);
-    else if (rows == 128 && nst == 4) go(gemm_nt_skinny_kernel<128, 4>, bytes, 4);
-    else if (rows == 128 && nst == 5) go(gemm_nt_skinny_kernel<128, 5>, bytes, 5);
-    else if (rows == 256 && nst == 4) go(gemm_nt_skinny_kernel<256, 4>, bytes, 7);
-#endif
-    else if (nst != 2) return A3V_ERR_ARG;               // a rows / stages pair this build does not carry (sweeps only)
+    else if (nst != 2) return A3V_ERR_ARG;               // a rows / stages pair the library does not carry
     else if (narrow == 3) {
       hipLaunchKernelGGL((gemm_nt_bf16_kernel<64, 64, 4, 1>), dim3(p.tiles_m, S), dim3(256), 0, (hipStream_t)stream, p);
     } else if (narrow == 2) {

@@ -150,8 +150,7 @@ extern "C" int a3v_gemm_tn_strip(const void* T, int64_t ldt, const void* X, int6
   if (((int64_t)(Kt - 1) * ldt + 64) * 2 >= (1LL << 31) || ((int64_t)(Kt - 1) * ldx + N) * 2 >= (1LL << 31)) return A3V_ERR_SHAPE;
   if ((reinterpret_cast<uintptr_t>(T) | reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(partial)) & 15) return A3V_ERR_SHAPE;
   StripArgs p{(const bf16_t*)T, (const bf16_t*)X, partial, ldt, ldx, R, N, Kt};
-  if (A3V_ENV_INT("A3V_STRIP_STAGES", 2) == 3) hipLaunchKernelGGL(gemm_tn_strip_kernel<3>, dim3((N + SBN - 1) / SBN, S), dim3(256), 0, (hipStream_t)stream, p);
-  else hipLaunchKernelGGL(gemm_tn_strip_kernel<2>, dim3((N + SBN - 1) / SBN, S), dim3(256), 0, (hipStream_t)stream, p);
+  hipLaunchKernelGGL(gemm_tn_strip_kernel<2>, dim3((N + SBN - 1) / SBN, S), dim3(256), 0, (hipStream_t)stream, p);
   A3V_LAUNCH_CHECK();
   return A3V_OK;
 }

@@ -147,12 +147,8 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_vec_kernel(const TS* __restri
   }
   const int row0 = blockIdx.x * RPB;
   // bf16 stream: the NEXT row's x, dy and dh vectors (2 registers each) are requested before the current row's reductions and barrier,
-  // so the row loop no longer pays a memory round trip per row behind its barrier (round 4, rows wider than 4096; A/B macro RMSB_NO_PREFETCH)
-#ifdef RMSB_NO_PREFETCH
-  constexpr bool PF = false;
-#else
+  // so the row loop no longer pays a memory round trip per row behind its barrier (round 4, rows wider than 4096)
   constexpr bool PF = sizeof(TS) == 2 && sizeof(TA) == 2 && MAXV > 4;     // dim 5120 (13B): 115 -> 82 us; dim 4096: 53 -> 55 us, kept off (tools/rmsnorm_bwd_bf16_bench.py)
-#endif
   bf16x4 nx[MAXV], ng[MAXV], nh[MAXV];
   auto fetch = [&](int row) {
     if constexpr (PF) {
@@ -842,10 +838,8 @@ extern "C" int a3v_layernorm_bwd_bf16(const void* x, int64_t ldx, const float* w
   return layernorm_bwd_impl(x, ldx, w, dy, A3V_BF16, lddy, row_map, dx, lddx, dw, db, rows, dim, eps, A3V_BF16, stream);
 }
 
-// cache policy of the streaming training kernels (A3V_STREAM_NT: bit 0 non-temporal loads, bit 1 stores; read per launch)
-static int stream_nt() {
-  return A3V_ENV_INT("A3V_STREAM_NT", 3) & 3;      // default: both (SwiGLU forward 102 -> 91 us, backward 174 -> 154 us at 7B size, tools/stream_nt_bench.py)
-}
+// cache policy of the streaming bf16 training kernels: non-temporal loads and stores (SwiGLU forward 102 -> 91 us, backward 174 -> 154 us at 7B size)
+constexpr int STREAM_NT = 3;
 
 extern "C" int a3v_swiglu_fwd(const void* gu, int64_t ldg, void* act, int64_t lda, int rows, int F, int interleaved, int dtype, void* stream) {
   const int inter = interleaved;
@@ -853,10 +847,7 @@ extern "C" int a3v_swiglu_fwd(const void* gu, int64_t ldg, void* act, int64_t ld
   if ((ldg % 8) || (lda % 8)) return A3V_ERR_SHAPE;
   int64_t n = (int64_t)rows * (F / 8);
   int blocks = (int)((n + 255) / 256 > 16384 ? 16384 : (n + 255) / 256);
-  const int nt = stream_nt();
-  if (dtype == A3V_BF16 && nt == 3) hipLaunchKernelGGL((swiglu_fwd_kernel<bf16_t, 3>), dim3(blocks), dim3(256), 0, ST, (const bf16_t*)gu, ldg, (bf16_t*)act, lda, rows, F, inter);
-  else if (dtype == A3V_BF16 && nt == 1) hipLaunchKernelGGL((swiglu_fwd_kernel<bf16_t, 1>), dim3(blocks), dim3(256), 0, ST, (const bf16_t*)gu, ldg, (bf16_t*)act, lda, rows, F, inter);
-  else if (dtype == A3V_BF16) hipLaunchKernelGGL(swiglu_fwd_kernel<bf16_t>, dim3(blocks), dim3(256), 0, ST, (const bf16_t*)gu, ldg, (bf16_t*)act, lda, rows, F, inter);
+  if (dtype == A3V_BF16) hipLaunchKernelGGL((swiglu_fwd_kernel<bf16_t, STREAM_NT>), dim3(blocks), dim3(256), 0, ST, (const bf16_t*)gu, ldg, (bf16_t*)act, lda, rows, F, inter);
   else if (dtype == A3V_F32) hipLaunchKernelGGL(swiglu_fwd_kernel<float>, dim3(blocks), dim3(256), 0, ST, (const float*)gu, ldg, (float*)act, lda, rows, F, inter);
   else return A3V_ERR_DTYPE;
   A3V_LAUNCH_CHECK();
@@ -870,10 +861,7 @@ extern "C" int a3v_swiglu_bwd(const void* gu, int64_t ldg, const void* dact, int
   if ((ldg % 8) || (lda % 8) || (lddg % 8)) return A3V_ERR_SHAPE;
   int64_t n = (int64_t)rows * (F / 8);
   int blocks = (int)((n + 255) / 256 > 16384 ? 16384 : (n + 255) / 256);
-  const int nt = stream_nt();
-  if (dtype == A3V_BF16 && nt == 3) hipLaunchKernelGGL((swiglu_bwd_kernel<bf16_t, 3>), dim3(blocks), dim3(256), 0, ST, (const bf16_t*)gu, ldg, (const bf16_t*)dact, lda, (bf16_t*)dgu, lddg, rows, F, inter);
-  else if (dtype == A3V_BF16 && nt == 1) hipLaunchKernelGGL((swiglu_bwd_kernel<bf16_t, 1>), dim3(blocks), dim3(256), 0, ST, (const bf16_t*)gu, ldg, (const bf16_t*)dact, lda, (bf16_t*)dgu, lddg, rows, F, inter);
-  else if (dtype == A3V_BF16) hipLaunchKernelGGL(swiglu_bwd_kernel<bf16_t>, dim3(blocks), dim3(256), 0, ST, (const bf16_t*)gu, ldg, (const bf16_t*)dact, lda, (bf16_t*)dgu, lddg, rows, F, inter);
+  if (dtype == A3V_BF16) hipLaunchKernelGGL((swiglu_bwd_kernel<bf16_t, STREAM_NT>), dim3(blocks), dim3(256), 0, ST, (const bf16_t*)gu, ldg, (const bf16_t*)dact, lda, (bf16_t*)dgu, lddg, rows, F, inter);
   else if (dtype == A3V_F32) hipLaunchKernelGGL(swiglu_bwd_kernel<float>, dim3(blocks), dim3(256), 0, ST, (const float*)gu, ldg, (const float*)dact, lda, (float*)dgu, lddg, rows, F, inter);
   else return A3V_ERR_DTYPE;
   A3V_LAUNCH_CHECK();
@@ -1068,18 +1056,10 @@ extern "C" int a3v_adamw_scaled(float* param, const float* grad, float* exp_avg,
   int64_t blocks = (n4 + 255) / 256;
   if (blocks > 256 * 16) blocks = 256 * 16;
   if (blocks < 1) blocks = 1;
-  // every byte of p / g / m / v / image is touched once per step: non-temporal loads AND stores (default 3) are 6.8 % faster than
-  // the default cache policy (271.6 -> 253.2 us on a 45-M-element tensor, tools/adamw_bench.py; either alone: nothing)
-  const int nt = A3V_ENV_INT("A3V_ADAMW_NT", 3);               // 0..3 (bit 0 loads, bit 1 stores; A/B runs)
-#define A3V_ADAMW_LAUNCH(V) hipLaunchKernelGGL(adamw_kernel<V>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n4, n, decay, \
-                     beta1, beta2, step_size, inv_bc2_sqrt, eps, (bf16_t*)bf16_image, grad_scale)
-  switch (nt & 3) {
-    case 1: A3V_ADAMW_LAUNCH(1); break;
-    case 2: A3V_ADAMW_LAUNCH(2); break;
-    case 3: A3V_ADAMW_LAUNCH(3); break;
-    default: A3V_ADAMW_LAUNCH(0); break;
-  }
-#undef A3V_ADAMW_LAUNCH
+  // every byte of p / g / m / v / image is touched once per step: non-temporal loads AND stores are 6.8 % faster than
+  // the default cache policy (271.6 -> 253.2 us on a 45-M-element tensor; either alone: nothing)
+  hipLaunchKernelGGL(adamw_kernel<3>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n4, n, decay,
+                     beta1, beta2, step_size, inv_bc2_sqrt, eps, (bf16_t*)bf16_image, grad_scale);
   A3V_LAUNCH_CHECK();
   return A3V_OK;
 }
@@ -1159,7 +1139,7 @@ extern "C" int a3v_adamw_scaled_t(float* param, const float* grad, float* exp_av
   const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
   const float step_size = (float)((double)lr / bc1), inv_bc2_sqrt = (float)(1.0 / sqrt(bc2));
   const float decay = (float)(1.0 - (double)lr * (double)weight_decay);
-  const int tr = (rows & 127) || A3V_ENV_INT("A3V_ADAMW_T_ROWS", 128) == 64 ? 64 : 128;
+  const int tr = (rows & 127) ? 64 : 128;
   int64_t blocks = (int64_t)(rows / tr) * (cols >> 6);
   if (blocks > 256 * 8) blocks = 256 * 8;
   if (tr == 128) hipLaunchKernelGGL(adamw_tile_t_kernel<128>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, rows, cols,

@@ -55,7 +55,7 @@ def test_gemm_kernels_stay_inside_their_register_budget(tmp_path):
         if "ELi192ELb" in n:
             assert scratch[n] == 0, (n, scratch[n])          # six row tiles per wave leave 40 registers: nothing spills
     skinny = [n for n in scratch if "gemm_nt_skinny_kernel" in n]
-    assert len(skinny) == 2, skinny      # the two forms a3v_gemm_nt_splitk picks; the sweep's other rows / stages only with -DA3V_ABLATION
+    assert len(skinny) == 2, skinny      # the two forms a3v_gemm_nt_splitk picks; the sweep's other rows / stages are not built
     for key, limit in BUDGET:
         hits = {n: v for n, v in scratch.items() if key in n}
         assert hits, f"kernel {key} not found (renamed? update the budget table)"

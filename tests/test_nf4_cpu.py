@@ -161,5 +161,5 @@ def test_nf4_gemv_instantiations_use_no_scratch(tmp_path):
         if m and name:
             scratch[name] = int(m.group(1))
     n4 = {n: v for n, v in scratch.items() if "gemv_dma_bf16_kernel" in n and n.endswith("ELb1EEEvNS_8GemvArgsE")}
-    assert len(n4) == 8, sorted(scratch)            # {8, 16} rows x {RMSNorm prologue, none} x {nt, default} weight-stream policy
+    assert len(n4) == 4, sorted(scratch)            # {8, 16} rows x {RMSNorm prologue, none}; the weight stream is always non-temporal
     assert all(v == 0 for v in n4.values()), n4

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """A/B on one box: greedy decode model step (bs 8, 7B, context ~1100) with an environment switch of the library toggled per
 round inside ONE process (the library caches its switches: every toggle goes through lib.env, which calls a3v_reload_env -- a bare
-os.environ write is NOT seen and both legs silently run the same kernels).  usage: ab_decode.py ENV_NAME [rounds]   e.g. ab_decode.py A3V_GEMV_NT"""
+os.environ write is NOT seen and both legs silently run the same kernels).  usage: ab_decode.py ENV_NAME [rounds]   e.g. ab_decode.py A3V_GEMV_KQ"""
 import os
 import sys
 

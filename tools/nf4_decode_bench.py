@@ -2,8 +2,7 @@
 """NF4 decode measurement: per-shape NF4 GEMV time (vs the bf16 and fp8 GEMVs on the same shape) and the 7B decode step with bf16,
 fp8 and NF4 weights at bench.py's decode geometry (B 8, 512-token prompt + 579 image words, 16 timed steps).  One JSON object on
 stdout.  Reuses bench.py's model builder, decode_leg and byte model.   usage: tools/nf4_decode_bench.py [--skip-model]
-With A3V_LIB_PATH pointing at a build with -DA3V_NF4_LOOKUP_AB (no code-book lookup, wrong results) and --skip-model, the per-shape
-times separate the lookup's cost from the weight stream's."""
+(--skip-model: the per-shape GEMV times only)."""
 import json
 import os
 import sys
