@@ -18,6 +18,7 @@
 //  * gemm_nt_f32_kernel : fp32 parity path (plain FMA, 64x64x16 tile).
 #include "a3v_common.h"
 #include <algorithm>
+#include <cstring>
 #include <type_traits>
 
 namespace {
@@ -2563,13 +2564,387 @@ static bool pp_persistent() { return A3V_ENV_INT("A3V_GEMM_PERSISTENT", 1) != 0;
 static int nt_store_env() { return A3V_ENV_INT("A3V_GEMM_NT_STORE", 0); }
 static int slow_epi_env() { return A3V_ENV_INT("A3V_GEMM_FAST_EPI", 1) == 0 ? 1 : 0; }   // 0: every tile through the general epilogue
 
-template <bool A_ROWS>
-static void launch_tn(dim3 grid, hipStream_t st, const GemmArgs& q0) {
-  GemmArgs q = q0;
-  q.slow_epi = slow_epi_env(); q.nt_store = nt_store_env();
-  q.xmap = A3V_ENV_INT("A3V_GEMM_XMAP_TN", 1);   // =0: one contiguous run of tiles per XCD (A/B); 1: round-major; +2: serpentine; +4: 16 x 16 super-tiles where they fit
-  if (!((q.xmap & 4) && (q.tiles_m & 15) == 0 && (q.tiles_n & 15) == 0)) q.xmap &= ~4;
-  hipLaunchKernelGGL(gemm_tn_bf16_pp_kernel<A_ROWS>, grid, dim3(512), 0, st, q);
+// ------------------------------------------------------------------------------------
+// GEMM dispatch: a pure function per family decides (the plan), one executor launches it.
+//
+// A plan is at most three steps: the tiles that run as one launch, the rows beyond whole rounds of the CUs ("tail") and, when the
+// tail is split over K into raw fp32 planes, the reduce pass that sums the planes and applies the epilogue.  The plan functions take
+// values only (no pointer, no HIP call; the A3V_* switches through A3V_ENV_INT, each at one call site); a3v_gemm_plan returns the
+// same plan to a caller without a GPU, and profiles/gemm_dispatch_*.tsv + tests/test_gemm_plan_cpu.py pin it for the product shapes.
+//
+// Known, kept (each is today's behaviour; changing one is a behaviour change with its own measurement):
+//  - NT cost model against NT launch: the hybrid tail is priced as a ring split when S >= 3, the epilogue is plain / residual / fp32
+//    and a workspace is registered -- without the workspace-size check and without A3V_GEMM_TAIL_SLICES / A3V_GEMM_RING_TAIL.  The
+//    launch applies all three, so it may run the 128 x 128 split-K tail or the plain 128 x 128 tail under a price it did not get.
+//  - NT counts floor(M / 256) tile rows against rounds of 256 tiles; fp8 / TN / NN count ceil(M / 256) against rounds of the CU count.
+//  - slice rules: slices_nt_ring (min(8, cus / tiles), K/64 >= 8 S, used only when S >= 3), slices_tn_nn (the same with >= 16 S, TN
+//    on ceil(K/64), NN on K/64), slices_fp8 (powers of two, 2 S rem <= cus, K/128 >= 8 S), and the NT small-tile tail's own
+//    slices_nt_small (powers of two up to 512 blocks, K/64 >= 16 S).  Their values differ for the same tail; they are not merged.
+//  - xmap (ring kernels): 0 when grid_x & 63 and for every split launch (grid_y > 1); bit 2 cleared unless grid_x == 256 and both
+//    tile counts are 16-aligned.  TN / NN read A3V_GEMM_XMAP_TN, also for the split tail, bit 2 on the tile counts alone.
+//  - fp8: bias / GELU epilogues have no ring instantiation and take the two-stage kernel; the 192-row form is tried before the tail
+//    form and without looking at the workspace, and when the ring kernel is off it falls through to the other forms.
+//  - the reduce pass adds the bias only for the NT whole-problem ring split (no tail form accepts a bias epilogue); the TN reduce
+//    pass writes its sumsq partials behind the tile slots, from slot ceil(M/256) * ceil(N/256) * 8.
+// ------------------------------------------------------------------------------------
+struct GemmStep { int32_t kernel, grid_x, grid_y, block, xmap, row0, rows, slices; };   // the A3V_GEMM_STEP_INTS fields of a3v_gemm_plan
+static_assert(sizeof(GemmStep) == A3V_GEMM_STEP_INTS * sizeof(int32_t), "a3v_gemm_plan copies steps as int32 fields");
+struct GemmPlan { int n; GemmStep step[A3V_GEMM_MAX_STEPS]; };
+struct GemmShape {      // the value inputs of a plan
+  int M, N, K;
+  int64_t lda, ldw;
+  int epilogue, dtype;  // the caller's epilogue word (A3V_EPI_TILE_* included)
+  bool rope, bias_al8, sumsq, ws;   // fused rope / cache write; bias 8-byte aligned; sumsq requested (no decision reads it); a workspace is registered
+  int64_t ws_bytes;
+  int cus;
+};
+struct KernelShape { int tbm, tbn, block; };
+static KernelShape kernel_shape(int kernel) {
+  switch (kernel) {
+    case A3V_GEMM_K_NT_128: return {128, 128, 256};
+    case A3V_GEMM_K_RING_192: case A3V_GEMM_K_RING_PRE_192: case A3V_GEMM_K_RING_192_F8: return {192, 256, 512};
+    case A3V_GEMM_K_F32: return {64, 64, 256};
+    default: return {256, 256, 512};
+  }
+}
+static void add_step(GemmPlan& pl, int kernel, int gx, int gy, int xmap, int row0, int rows, int slices) {
+  pl.step[pl.n++] = GemmStep{kernel, gx, gy, kernel_shape(kernel).block, xmap, row0, rows, slices};
+}
+static int tiles_of(int kernel, int rows, int N) {
+  const KernelShape k = kernel_shape(kernel);
+  return ((rows + k.tbm - 1) / k.tbm) * ((N + k.tbn - 1) / k.tbn);
+}
+// rows [row0, row0 + rows) split S ways over K into fp32 planes on `kernel`, and the reduce pass over them
+static void add_split(GemmPlan& pl, int kernel, int xmap, int S, int row0, int rows, int N) {
+  add_step(pl, kernel, tiles_of(kernel, rows, N), S, xmap, row0, rows, S);
+  const int64_t n4 = (int64_t)rows * (N / 4);
+  pl.step[pl.n++] = GemmStep{A3V_GEMM_K_REDUCE, (int)std::min<int64_t>(2048, (n4 + 255) / 256), 1, 256, 0, row0, rows, S};
+}
+
+// tile rows (of `tiles_m`, each `tiles_n` tiles wide) that make whole rounds of `round` concurrent tiles, and what lies beyond them
+struct Rounds { long mt_h, rem_tiles; int m_big; };
+static Rounds whole_rounds(long tiles_m, long tiles_n, int round) {
+  const long total = tiles_m * tiles_n;
+  const long mt_h = (total / round) * round / tiles_n;
+  return {mt_h, total - mt_h * tiles_n, (int)(mt_h * 256)};
+}
+// as many K-slices as fill the CUs once, at most 8, each at least 8 k-tiles long (the caller takes the split only for S >= 3)
+static int slices_nt_ring(long tiles, int K, int cus) {
+  int S = tiles > 0 ? (int)(cus / tiles) : 0;
+  if (S > 8) S = 8;
+  while (S > 1 && K / 64 < 8 * S) --S;
+  return S;
+}
+// the NT tail on 128 x 128 tiles: powers of two while the blocks stay under one round of 512
+static int slices_nt_small(int tblocks, int K) {
+  int S = 1;
+  while (tblocks * S < 512 && S < 8 && K / 64 >= 16 * S) S *= 2;
+  return S;
+}
+// TN / NN: as slices_nt_ring with at least 16 k-tiles per slice (round 2: was the largest power of two with 2 S rem_tiles <= CUs, i.e.
+// 96 blocks for the 48 tail tiles of a [8728, 4096] output; 5 slices = 240 blocks finish the tail in 1/5 of a tile time instead of 1/2)
+static int slices_tn_nn(long rem_tiles, int ktiles, int cus) {
+  int S = rem_tiles > 0 ? (int)std::min<long>(8, cus / rem_tiles) : 1;
+  while (S > 1 && ktiles < 16 * S) --S;
+  return S < 1 ? 1 : S;
+}
+// fp8: measured on wo / w2 of 7B: S = 2 (96 blocks) beat S = 8 (384 blocks)
+static int slices_fp8(long rem_tiles, int K, int cus) {
+  int S = 1;
+  while (rem_tiles * S * 2 <= cus && S < 8 && (K / 128) >= 8 * S) S *= 2;
+  return S;
+}
+
+// ring kernels: 1 = every round of gridDim.x tiles is cut into eight runs, one per XCD; =0: one contiguous run of tiles per XCD (A/B)
+static int ring_xmap(int gx, int tiles_m, int tiles_n) {
+  int xmap = (gx & 63) ? 0 : A3V_ENV_INT("A3V_GEMM_XMAP", 1);
+  if (!((xmap & 4) && gx == 256 && (tiles_m & 15) == 0 && (tiles_n & 15) == 0)) xmap &= ~4;
+  return xmap;
+}
+// TN / NN: =0: one contiguous run of tiles per XCD (A/B); 1: round-major; +2: serpentine; +4: 16 x 16 super-tiles where they fit
+static int tn_xmap(int tiles_m, int tiles_n) {
+  int xmap = A3V_ENV_INT("A3V_GEMM_XMAP_TN", 1);
+  if (!((xmap & 4) && (tiles_m & 15) == 0 && (tiles_n & 15) == 0)) xmap &= ~4;
+  return xmap;
+}
+
+// One NT launch of rows [row0, row0 + rows) on one tile form: 256x256 ping-pong ring (8 waves, 1 block/CU, persistent: one block per
+// CU walks its tiles; A3V_GEMM_PERSISTENT=0: one block per tile), its 192 x 256 form (the fused-qkv form has no instantiation
+// there), the plain 256 x 256 kernel or the 128x128 kernel (4 waves, 2 blocks/CU).  The ring kernel is instantiated per set of fast
+// epilogue forms.
+// `tile`: A3V_GEMM_K_NT_128, _NT_256, _RING or _RING_192; the ring forms are refined by the epilogue here.
+static void add_nt(GemmPlan& pl, int tile, int epi, bool rope, int row0, int rows, int N, int cus) {
+  if (tile == A3V_GEMM_K_NT_128 || tile == A3V_GEMM_K_NT_256) {
+    add_step(pl, tile, tiles_of(tile, rows, N), 1, 0, row0, rows, 1);
+    return;
+  }
+  const bool pre = (epi & (A3V_EPI_BIAS | A3V_EPI_GELU | A3V_EPI_QUICKGELU)) != 0;
+  const int k = tile == A3V_GEMM_K_RING_192 ? (pre ? A3V_GEMM_K_RING_PRE_192 : A3V_GEMM_K_RING_192)
+                : rope              ? A3V_GEMM_K_RING_ROPE
+                                    : (pre ? A3V_GEMM_K_RING_PRE : A3V_GEMM_K_RING);
+  const KernelShape ks = kernel_shape(k);
+  const int tiles_m = (rows + ks.tbm - 1) / ks.tbm, tiles_n = (N + 255) / 256, nt = tiles_m * tiles_n;
+  const int gx = pp_persistent() ? std::min(nt, cus) : nt;
+  add_step(pl, k, gx, 1, ring_xmap(gx, tiles_m, tiles_n), row0, rows, 1);
+}
+
+// a3v_gemm_nt / a3v_gemm_qkv_rope
+static int plan_nt(const GemmShape& s, GemmPlan& pl) {
+  const int M = s.M, N = s.N, K = s.K, cus = s.cus, epi = s.epilogue & 0xffff;
+  if (s.dtype == A3V_F32) {
+    const int ncols = (epi & A3V_EPI_SWIGLU) ? N / 2 : N;
+    const int tile_c = (epi & A3V_EPI_SWIGLU) ? 32 : 64;
+    add_step(pl, A3V_GEMM_K_F32, (ncols + tile_c - 1) / tile_c, (M + 63) / 64, 0, 0, M, 1);
+    return A3V_OK;
+  }
+  if (s.dtype != A3V_BF16) return A3V_ERR_DTYPE;
+  const int64_t bytesA = ((int64_t)(M - 1) * s.lda + K) * 2, bytesW = ((int64_t)(N - 1) * s.ldw + K) * 2;
+  const bool desc_ok = bytesA < (1LL << 31) && bytesW < (1LL << 31);   // buffer descriptors: 32-bit offsets
+  // A3V_EPI_TILE_* force one configuration for the whole problem (tuning / tests)
+  if (s.epilogue & (A3V_EPI_TILE_256PP | A3V_EPI_TILE_256 | A3V_EPI_TILE_128 | A3V_EPI_TILE_192PP)) {
+    const int tile = (s.epilogue & A3V_EPI_TILE_192PP) ? A3V_GEMM_K_RING_192 : (s.epilogue & A3V_EPI_TILE_256PP) ? A3V_GEMM_K_RING
+                     : (s.epilogue & A3V_EPI_TILE_256) ? A3V_GEMM_K_NT_256 : A3V_GEMM_K_NT_128;
+    if (tile >= A3V_GEMM_K_RING && !desc_ok) return A3V_ERR_SHAPE;
+    add_nt(pl, tile, epi, s.rope, 0, M, N, cus);
+    return A3V_OK;
+  }
+  // Cost model in units of one 256x256 tile's time on one CU (T256): a "round" is 256 concurrent big tiles or
+  // 512 concurrent 128x128 tiles (2 blocks/CU, each ~0.65 T256 at the small kernel's lower rate); a second launch
+  // costs ~0.1.  Candidates: small kernel for everything, big kernel for everything, or big kernel on the M-tile rows
+  // that fill whole rounds + small kernel on the remaining rows.
+  const long tn256 = (N + 255) / 256, tn128 = (N + 127) / 128;
+  const bool eligible = desc_ok && M >= 512 && N >= 512;
+  const int simple = A3V_EPI_RESIDUAL | A3V_EPI_RES_F32 | A3V_EPI_OUT_F32;
+  // (round 2 recalibration, tools/hybrid_vs_ring.py: with the ring kernel at 1.35-1.45 PF and the small kernel at ~0.6 PF a round
+  // of 512 small tiles costs ~1.15 T256, and a split-K tail adds its reduce pass: the 7B qkv shape (6.56 rounds) went to the
+  // hybrid under the old 0.65 and lost 11 % to the all-ring launch)
+  auto small_cost = [&](long rows) { return rows <= 0 ? 0.0 : 1.15 * std::max(0.5, (double)((rows + 127) / 128) * tn128 / 512.0); };
+  const double round_us = 12.0 + 0.0206 * K;          // one round of 256 tiles of 256 x 256 on the ring kernel (M = 8192, N = 4096: 98 us at K = 4096, 476 at 22016)
+  const double c_small = small_cost(M);
+  const double c_big = eligible ? (double)((((long)(M + 255) / 256) * tn256 + 255) / 256) : 1e30;
+  const Rounds r = whole_rounds(M / 256, tn256, 256);
+  double c_hyb = 1e30;
+  if (eligible && r.mt_h >= 1 && r.m_big < M) {
+    // tail rows: on the ring kernel split over K when that fills the CUs (1/S of a tile time + the reduce pass), else small tiles
+    const long tail_rows = M - r.m_big;
+    const int S2 = slices_nt_ring(((tail_rows + 255) / 256) * tn256, K, cus);
+    const bool simple_epi = !(epi & ~simple) && !s.rope && s.ws && N % 4 == 0;
+    // (round 5 recalibration, tools/ring192_ab.py) the split-K tail costs its 1 / S of a tile time plus ~32 us that do not depend on K
+    // (plane traffic + two launches): 0.30 of a round at K = 4096, 0.07 at K = 22016, where a round of 256 tiles takes ~12 + 0.0206 K us
+    const double tail = (S2 >= 3 && simple_epi && pp_persistent()) ? 1.0 / S2 + 32.0 / round_us : small_cost(tail_rows) + 0.25;
+    c_hyb = (double)((r.mt_h * tn256 + 255) / 256) + tail;
+  }
+  // (round 5) the whole problem on 192 x 256 ring tiles: a round of them takes 0.79 of a 256 x 256 round (48 instead of 64 MFMAs per
+  // wave and K-tile on 7 / 8 of the LDS-DMA pieces); 8728 x 4096 is 2.875 rounds of these against 2 rounds + a split-K tail
+  double c_192 = 1e30;
+  if (eligible && !s.rope && pp_persistent() && A3V_ENV_INT("A3V_GEMM_RING_192", 1) != 0 && !(epi & A3V_EPI_SWIGLU))
+    c_192 = 0.79 * (double)((((long)(M + 191) / 192) * tn256 + 255) / 256) + 0.02;
+  // few big tiles (small N or M: the ViT's output projections, 76 tiles): the whole problem on the ring kernel split over K
+  double c_spl = 1e30;
+  const int S3 = slices_nt_ring(((long)(M + 255) / 256) * tn256, K, cus);
+  if (A3V_ENV_INT("A3V_GEMM_RING_SPLIT", 1) != 0 && eligible && S3 >= 3 && !(epi & ~(A3V_EPI_BIAS | simple)) && !s.rope && pp_persistent() && s.ws &&
+      N % 4 == 0 && (int64_t)S3 * M * N * 4 <= s.ws_bytes && (!(epi & A3V_EPI_BIAS) || s.bias_al8))
+    c_spl = 1.0 / S3 + 0.2;
+  if (c_192 < c_spl && c_192 < c_small && c_192 < c_big && c_192 < c_hyb) {
+    add_nt(pl, A3V_GEMM_K_RING_192, epi, s.rope, 0, M, N, cus);
+  } else if (c_spl < c_small && c_spl < c_big && c_spl < c_hyb) {
+    add_split(pl, A3V_GEMM_K_RING, 0, S3, 0, M, N);
+  } else if (c_big <= c_small && c_big <= c_hyb) {
+    add_nt(pl, A3V_GEMM_K_RING, epi, s.rope, 0, M, N, cus);
+  } else if (c_hyb < c_small) {
+    add_nt(pl, A3V_GEMM_K_RING, epi, s.rope, 0, r.m_big, N, cus);
+    // tail rows: a few hundred rows x N on 128x128 tiles = ~160 blocks with a serial K loop (50 us at K = 4096, 135 us at
+    // K = 11008).  With a registered workspace the K loop is split into S planes (more blocks, 1/S the latency) and a
+    // reduce pass applies the epilogue; only the plain / residual / fp32 forms are handled there.
+    const int rows = M - r.m_big;
+    const int S = slices_nt_small(tiles_of(A3V_GEMM_K_NT_128, rows, N), K);
+    // (round 2) the same tail on the ring kernel: its ceil(rows / 256) x tn256 big tiles split S ways over K so that they fill the
+    // CUs once -- a fraction 1/S of a tile time instead of ~0.6 on the small kernel (wo: 257 -> ~235 us)
+    int S2 = slices_nt_ring(tiles_of(A3V_GEMM_K_RING, rows, N), K, cus);
+    { const int e = A3V_ENV_INT("A3V_GEMM_TAIL_SLICES", 0); if (e >= 3 && e <= 16 && K / 64 >= 2 * e) S2 = e; }      // sweeps (tools/tail_cost.py)
+    const bool ring_tail = A3V_ENV_INT("A3V_GEMM_RING_TAIL", 1) != 0;
+    const bool can_split = !(epi & ~simple) && !s.rope && s.ws && N % 4 == 0;
+    if (ring_tail && pp_persistent() && S2 >= 3 && can_split && (int64_t)S2 * rows * N * 4 <= s.ws_bytes) {
+      add_split(pl, A3V_GEMM_K_RING, 0, S2, r.m_big, rows, N);
+    } else if (S > 1 && can_split && (int64_t)S * rows * N * 4 <= s.ws_bytes) {
+      add_split(pl, A3V_GEMM_K_NT_128, 0, S, r.m_big, rows, N);
+    } else {
+      add_nt(pl, A3V_GEMM_K_NT_128, epi, s.rope, r.m_big, rows, N, cus);
+    }
+  } else {
+    add_nt(pl, A3V_GEMM_K_NT_128, epi, s.rope, 0, M, N, cus);
+  }
+  return A3V_OK;
+}
+
+// a3v_gemm_tn / a3v_gemm_tn_sumsq (nn = false) and a3v_gemm_nn (nn = true): 256 x 256 tiles.  Rows of C beyond whole tile rounds (e.g.
+// dW of w1|w3: 86 x 16 tiles = 5.4 rounds) are split over the contracted index into fp32 planes + the reduce epilogue (needs the
+// registered workspace; otherwise one plain launch).
+static int plan_tn_nn(const GemmShape& s, bool nn, GemmPlan& pl) {
+  const int M = s.M, N = s.N, cus = s.cus, k = nn ? A3V_GEMM_K_NN : A3V_GEMM_K_TN;
+  const int tiles_n = (N + 255) / 256, tm_all = (M + 255) / 256;
+  const Rounds r = whole_rounds(tm_all, tiles_n, cus);
+  const int S = slices_tn_nn(r.rem_tiles, nn ? s.K / 64 : (s.K + 63) / 64, cus);
+  const bool tail_on = nn ? s.epilogue != A3V_EPI_SWIGLU_BWD : A3V_ENV_INT("A3V_TN_TAIL", 1) != 0;
+  const int rows = M - r.m_big;
+  if (tail_on && r.mt_h >= 1 && r.m_big < M && S > 1 && r.rem_tiles * 4 < 3 * cus && s.ws && (int64_t)S * rows * N * 4 <= s.ws_bytes) {
+    add_step(pl, k, (int)r.mt_h * tiles_n, 1, tn_xmap((int)r.mt_h, tiles_n), 0, r.m_big, 1);
+    add_split(pl, k, tn_xmap((rows + 255) / 256, tiles_n), S, r.m_big, rows, N);
+  } else {
+    add_step(pl, k, tm_all * tiles_n, 1, tn_xmap(tm_all, tiles_n), 0, M, 1);
+  }
+  return A3V_OK;
+}
+
+// a3v_gemm_nt_fp8 / a3v_gemm_qkv_rope_fp8.  (round 5) the fp8 product runs on the ring kernel: persistent tile walk, three LDS rings,
+// staged epilogues; bias / activation kinds keep the two-stage kernel (no fp8 instantiation of that epilogue set).
+// A3V_GEMM_FP8_RING=0: the two-stage kernel for everything (A/B runs, equality tests).
+static int plan_nt_fp8(const GemmShape& s, GemmPlan& pl) {
+  const int M = s.M, N = s.N, K = s.K, cus = s.cus, epi = s.epilogue;
+  const bool ring_on = A3V_ENV_INT("A3V_GEMM_FP8_RING", 1) != 0 && pp_persistent();
+  // one launch of rows [row0, row0 + rows) on the ring kernel (one block per CU), or on the two-stage kernel (one block per tile)
+  auto add_fp8 = [&](int ring_kernel, int row0, int rows) {
+    const bool ring = ring_on && !(epi & (A3V_EPI_BIAS | A3V_EPI_GELU | A3V_EPI_QUICKGELU));
+    const int k = ring ? ring_kernel : A3V_GEMM_K_FP8_PP;
+    const KernelShape ks = kernel_shape(k);
+    const int tiles_m = (rows + ks.tbm - 1) / ks.tbm, tiles_n = (N + 255) / 256, nt = tiles_m * tiles_n;
+    const int gx = ring ? std::min(nt, cus) : nt;
+    add_step(pl, k, gx, 1, ring ? ring_xmap(gx, tiles_m, tiles_n) : 0, row0, rows, 1);
+  };
+  // when the last round would be mostly empty (e.g. 35 x 16 = 560 tiles on 256 CUs: a third round at 19 %), the rows beyond whole rounds
+  // are split over K -- S times the blocks at 1/S the length (needs the registered workspace; otherwise one plain launch)
+  const int tiles_n = (N + 255) / 256;
+  const Rounds r = whole_rounds((M + 255) / 256, tiles_n, cus);
+  const long total = (long)((M + 255) / 256) * tiles_n;
+  const int S = slices_fp8(r.rem_tiles, K, cus);
+  const int simple = A3V_EPI_RESIDUAL | A3V_EPI_RES_F32 | A3V_EPI_OUT_F32;
+  const bool tail_form = !s.rope && !(epi & ~simple) && r.mt_h >= 1 && r.m_big < M && S > 1 && r.rem_tiles * 4 < 3 * cus;
+  // (round 5) 192 x 256 ring tiles where they cost fewer rounds than whole 256-row rounds + a split-K tail (a round of them is 0.79 of a
+  // 256-row round; the tail's ~32 us do not shrink with the fp8 round time ~12 + 0.0103 K us): A3V_GEMM_FP8_192 = 0 never, 2 always
+  const int e192 = A3V_ENV_INT("A3V_GEMM_FP8_192", 1);
+  const double round_us = 12.0 + 0.0103 * K;
+  const double c_now = tail_form ? (double)(r.mt_h * tiles_n / cus) + 1.0 / S + 32.0 / round_us : (double)((total + cus - 1) / cus);
+  const long t192 = (long)((M + 191) / 192) * tiles_n;
+  const double c_192 = 0.79 * (double)((t192 + cus - 1) / cus) + 0.02;
+  if (e192 && !s.rope && !(epi & (A3V_EPI_SWIGLU | A3V_EPI_BIAS | A3V_EPI_GELU | A3V_EPI_QUICKGELU)) && M >= 512 && N >= 512 &&
+      (e192 == 2 || c_192 < c_now) && ring_on) {
+    add_fp8(A3V_GEMM_K_RING_192_F8, 0, M);
+    return A3V_OK;
+  }
+  const int rows = M - r.m_big;
+  if (tail_form && s.ws && (int64_t)S * rows * N * 4 <= s.ws_bytes) {
+    add_fp8(A3V_GEMM_K_RING_F8, 0, r.m_big);
+    add_split(pl, ring_on ? A3V_GEMM_K_RING_F8 : A3V_GEMM_K_FP8_PP, 0, S, r.m_big, rows, N);
+  } else {
+    add_fp8(s.rope ? A3V_GEMM_K_RING_ROPE_F8 : A3V_GEMM_K_RING_F8, 0, M);
+  }
+  return A3V_OK;
+}
+
+static int gemm_plan(int family, const GemmShape& s, GemmPlan& pl) {
+  pl.n = 0;
+  return family == A3V_GEMM_NT ? plan_nt(s, pl) : family == A3V_GEMM_NT_FP8 ? plan_nt_fp8(s, pl)
+         : family == A3V_GEMM_TN || family == A3V_GEMM_NN ? plan_tn_nn(s, family == A3V_GEMM_NN, pl) : A3V_ERR_ARG;
+}
+
+extern "C" int a3v_gemm_plan(int family, int M, int N, int K, int64_t lda, int64_t ldw, int epilogue, int dtype, int rope,
+                             int bias_aligned, int sumsq, int64_t workspace_bytes, int cus, int32_t* steps) {
+  if (M <= 0 || N <= 0 || K <= 0 || cus <= 0 || !steps) return A3V_ERR_ARG;
+  const GemmShape s{M, N, K, lda, ldw, epilogue, dtype, rope != 0, bias_aligned != 0, sumsq != 0, workspace_bytes > 0, workspace_bytes, cus};
+  GemmPlan pl;
+  const int rc = gemm_plan(family, s, pl);
+  if (rc != A3V_OK) return rc;
+  memcpy(steps, pl.step, sizeof(GemmStep) * pl.n);
+  return pl.n;
+}
+
+// ---- the executor: the only code that fills GemmArgs for, and launches, the kernels of a plan ----
+static GemmArgs gemm_args(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc, const void* res, int64_t ldr,
+                          int M, int N, int K, int epi) {
+  GemmArgs p{};
+  p.A = (const bf16_t*)A; p.W = (const bf16_t*)W; p.C = C; p.res = res;
+  p.lda = lda; p.ldw = ldw; p.ldc = ldc; p.ldr = ldr;
+  p.M = M; p.N = N; p.K = K; p.epi = epi;
+  return p;
+}
+
+// rows [row0, row0 + rows) of the problem `p` as a problem of its own
+static GemmArgs gemm_rows(const GemmArgs& p, int family, int row0, int rows) {
+  GemmArgs q = p;
+  q.M = rows;
+  // A: rows of lda bf16 (NT, NN) or of lda bytes (fp8); TN's At is [K][lda] with the C-row index contiguous: columns row0.. of At
+  const int64_t a_bytes = family == A3V_GEMM_TN ? (int64_t)row0 * 2 : (int64_t)row0 * p.lda * (family == A3V_GEMM_NT_FP8 ? 1 : 2);
+  q.A = (const bf16_t*)((const char*)p.A + a_bytes);
+  if (p.sa) q.sa = p.sa + row0;
+  q.rk.m_off = p.rk.m_off + row0;
+  const int esz = (p.epi & (A3V_EPI_OUT_F32 | A3V_EPI_RES_F32)) ? 4 : 2;
+  q.C = (char*)p.C + (int64_t)row0 * p.ldc * esz;
+  if (p.res) q.res = (const char*)p.res + (int64_t)row0 * p.ldr * ((p.epi & A3V_EPI_RES_F32) ? 4 : 2);
+  return q;
+}
+
+static void launch_step(const GemmStep& s, GemmArgs q, hipStream_t st) {
+  const KernelShape ks = kernel_shape(s.kernel);
+  const dim3 g(s.grid_x, s.grid_y), b(s.block);
+  q.tiles_m = (q.M + ks.tbm - 1) / ks.tbm; q.tiles_n = (q.N + ks.tbn - 1) / ks.tbn;
+  q.xmap = s.xmap;
+  if (s.kernel != A3V_GEMM_K_FP8_PP) { q.slow_epi = slow_epi_env(); q.nt_store = nt_store_env(); }
+  switch (s.kernel) {
+    case A3V_GEMM_K_NT_128: hipLaunchKernelGGL((gemm_nt_bf16_kernel<128, 128, 2, 2>), g, b, 0, st, q); break;
+    case A3V_GEMM_K_NT_256: hipLaunchKernelGGL((gemm_nt_bf16_kernel<256, 256, 2, 4>), g, b, 0, st, q); break;
+    case A3V_GEMM_K_RING: hipLaunchKernelGGL((gemm_nt_bf16_ring_kernel<EPI_SET_COMMON>), g, b, 0, st, q); break;
+    case A3V_GEMM_K_RING_PRE: hipLaunchKernelGGL((gemm_nt_bf16_ring_kernel<EPI_SET_COMMON | EPI_SET_PRE>), g, b, 0, st, q); break;
+    case A3V_GEMM_K_RING_ROPE: hipLaunchKernelGGL((gemm_nt_bf16_ring_kernel<EPI_SET_ROPE>), g, b, 0, st, q); break;
+    case A3V_GEMM_K_RING_192: hipLaunchKernelGGL((gemm_nt_bf16_ring_kernel<EPI_SET_COMMON, 192>), g, b, 0, st, q); break;
+    case A3V_GEMM_K_RING_PRE_192: hipLaunchKernelGGL((gemm_nt_bf16_ring_kernel<EPI_SET_COMMON | EPI_SET_PRE, 192>), g, b, 0, st, q); break;
+    case A3V_GEMM_K_TN: hipLaunchKernelGGL(gemm_tn_bf16_pp_kernel<false>, g, b, 0, st, q); break;
+    case A3V_GEMM_K_NN: hipLaunchKernelGGL(gemm_tn_bf16_pp_kernel<true>, g, b, 0, st, q); break;
+    case A3V_GEMM_K_FP8_PP: hipLaunchKernelGGL(gemm_nt_fp8_pp_kernel, g, b, 0, st, q); break;
+    case A3V_GEMM_K_F32: {
+      GemmF32Args f{(const float*)q.A, (const float*)q.W, (float*)q.C, (const float*)q.bias, (const float*)q.res,
+                    q.lda, q.ldw, q.ldc, q.ldr, q.M, q.N, q.K, q.epi};
+      hipLaunchKernelGGL(gemm_nt_f32_kernel, g, b, 0, st, f);
+      break;
+    }
+    default:      // the fp8 ring kernel scales its accumulators itself, in front of the staged epilogues
+      q.epi &= ~GEMM_EPI_SCALE;
+      if (s.kernel == A3V_GEMM_K_RING_192_F8) hipLaunchKernelGGL((gemm_nt_bf16_ring_kernel<EPI_SET_COMMON, 192, true>), g, b, 0, st, q);
+      else if (s.kernel == A3V_GEMM_K_RING_ROPE_F8) hipLaunchKernelGGL((gemm_nt_bf16_ring_kernel<EPI_SET_ROPE, 256, true>), g, b, 0, st, q);
+      else hipLaunchKernelGGL((gemm_nt_bf16_ring_kernel<EPI_SET_COMMON, 256, true>), g, b, 0, st, q);
+  }
+}
+
+// The split-K tail of every family: `tail.slices` slices of the K loop of the rows `q` (of the whole problem `p`) write raw fp32
+// planes into the workspace; one reduce pass sums them in order and applies the epilogue (the bias, if any, there) on the way to
+// q's output.
+static void launch_split(const GemmStep& tail, const GemmStep& reduce, const GemmArgs& p, const GemmArgs& q, float* ws, hipStream_t st) {
+  GemmArgs t = q;
+  t.C = ws; t.ldc = q.N; t.res = nullptr; t.bias = nullptr; t.sumsq = nullptr;
+  t.epi = A3V_EPI_OUT_F32 | GEMM_EPI_RAW | (q.epi & GEMM_EPI_SCALE);
+  t.c_split = (int64_t)q.M * q.N * 4;
+  launch_step(tail, t, st);
+  const int64_t tile_slots = (int64_t)((p.M + 255) / 256) * ((p.N + 255) / 256) * 8;   // a3v_gemm_tn_sumsq_slots: the reduce blocks' slots follow
+  hipLaunchKernelGGL(splitk_epilogue_kernel, dim3(reduce.grid_x), dim3(reduce.block), 0, st, ws, reduce.slices, (int64_t)q.M * q.N, q.M, q.N,
+                     q.C, q.ldc, q.res, q.ldr, q.epi & (A3V_EPI_RESIDUAL | A3V_EPI_RES_F32 | A3V_EPI_OUT_F32),
+                     (q.epi & A3V_EPI_BIAS) ? (const bf16_t*)q.bias : nullptr, q.sumsq ? q.sumsq + tile_slots : nullptr);
+}
+
+// plan the problem `p` (epilogue / dtype: the caller's words) with the stream's workspace and this device's CUs, and launch the plan
+static int gemm_run(int family, const GemmArgs& p, int epilogue, int dtype, bool rope, hipStream_t st) {
+  const GemmWs gws = gemm_ws_for(st);
+  const GemmShape s{p.M, p.N, p.K, p.lda, p.ldw, epilogue, dtype, rope, !(reinterpret_cast<uintptr_t>(p.bias) & 7), p.sumsq != nullptr,
+                    gws.p != nullptr, gws.bytes, cu_count()};
+  GemmPlan pl;
+  const int rc = gemm_plan(family, s, pl);
+  if (rc != A3V_OK) return rc;
+  for (int i = 0; i < pl.n; ++i) {
+    const GemmStep& step = pl.step[i];
+    const GemmArgs q = gemm_rows(p, family, step.row0, step.rows);
+    if (i + 1 < pl.n && pl.step[i + 1].kernel == A3V_GEMM_K_REDUCE) launch_split(step, pl.step[++i], p, q, gws.p, st);
+    else launch_step(step, q, st);
+  }
+  A3V_LAUNCH_CHECK();
+  return A3V_OK;
 }
 
 static int gemm_nt_impl(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc,
@@ -2583,181 +2958,19 @@ static int gemm_nt_impl(const void* A, int64_t lda, const void* W, int64_t ldw, 
     if (!residual || dtype != A3V_BF16 || (epilogue & 0xffff & ~A3V_EPI_SWIGLU_BWD)) return A3V_ERR_ARG;
     if ((N % 8) || (ldr % 4) || ldr < 2 * (int64_t)N || ldc < 2 * (int64_t)N) return A3V_ERR_SHAPE;
   }
-  hipStream_t st = (hipStream_t)stream;
-  const GemmWs gws = gemm_ws_for(st);
   if (dtype == A3V_F32) {
     if (K % 16 || lda % 4 || ldw % 4) return A3V_ERR_SHAPE;
     if ((epilogue & A3V_EPI_SWIGLU) && (N % 32)) return A3V_ERR_SHAPE;
-    GemmF32Args p{(const float*)A, (const float*)W, (float*)C, (const float*)bias, (const float*)residual,
-                  lda, ldw, ldc, ldr, M, N, K, epilogue};
-    const int ncols = (epilogue & A3V_EPI_SWIGLU) ? N / 2 : N;
-    const int tile_c = (epilogue & A3V_EPI_SWIGLU) ? 32 : 64;
-    dim3 grid((ncols + tile_c - 1) / tile_c, (M + 63) / 64);
-    hipLaunchKernelGGL(gemm_nt_f32_kernel, grid, dim3(256), 0, st, p);
-    A3V_LAUNCH_CHECK();
-    return A3V_OK;
-  }
-  if (dtype != A3V_BF16) return A3V_ERR_DTYPE;
-  if (K % BK || lda % 8 || ldw % 8 || N % 4 || ldc % 4) return A3V_ERR_SHAPE;
-  if ((epilogue & A3V_EPI_SWIGLU) && (N % 32)) return A3V_ERR_SHAPE;
-  if ((epilogue & (A3V_EPI_RESIDUAL | A3V_EPI_RES_F32)) && (ldr % 4)) return A3V_ERR_SHAPE;
-  GemmArgs p{};
-  p.A = (const bf16_t*)A; p.W = (const bf16_t*)W; p.C = C; p.bias = bias; p.res = residual;
-  p.lda = lda; p.ldw = ldw; p.ldc = ldc; p.ldr = ldr;
-  p.M = M; p.N = N; p.K = K; p.epi = epilogue & 0xffff;
-  p.c_split = 0;
-  p.rk = RopeKvArgs{};
-  if (rk) { p.rk = *rk; p.epi |= GEMM_EPI_ROPEKV; }
-  // Tile choice.  256x256 ping-pong (8 waves, 1 block/CU) for the rows that fill whole 256-row
-  // tiles when its grid keeps the 256 CUs busy (>= 75 % of its last round); the remaining (< 256)
-  // rows, and every problem the big tile would quantise badly, go to the 128x128 kernel (4 waves,
-  // 2 blocks/CU).  A3V_EPI_TILE_* force one configuration for the whole problem (tuning / tests).
-  auto launch = [&](int cfg, GemmArgs q) {
-    q.slow_epi = slow_epi_env(); q.nt_store = nt_store_env();
-    if (cfg == 128) {
-      q.tiles_m = (q.M + 127) / 128; q.tiles_n = (q.N + 127) / 128;
-      hipLaunchKernelGGL((gemm_nt_bf16_kernel<128, 128, 2, 2>), dim3(q.tiles_m * q.tiles_n), dim3(256), 0, st, q);
-      return;
-    }
-    const int tbm = cfg == 259 ? 192 : 256;
-    q.tiles_m = (q.M + tbm - 1) / tbm; q.tiles_n = (q.N + 255) / 256;
-    const int nt = q.tiles_m * q.tiles_n;
-    // the ping-pong kernel is persistent: one block per CU walks its tiles (A3V_GEMM_PERSISTENT=0: one block per tile, for A/B runs)
-    const dim3 g((cfg == 257 || cfg == 259) && pp_persistent() ? std::min(nt, cu_count()) : nt), b(512);
-    if (cfg == 256) { hipLaunchKernelGGL((gemm_nt_bf16_kernel<256, 256, 2, 4>), g, b, 0, st, q); return; }
-    q.xmap = (g.x & 63) ? 0 : A3V_ENV_INT("A3V_GEMM_XMAP", 1);   // =0: one contiguous run of tiles per XCD (A/B)
-    if (!((q.xmap & 4) && g.x == 256 && (q.tiles_m & 15) == 0 && (q.tiles_n & 15) == 0)) q.xmap &= ~4;
-    // the product path: the ring kernel, instantiated per set of fast epilogue forms
-    if (cfg == 259) {                                    // 192 x 256 tiles (the fused-qkv form has no instantiation: general epilogue there)
-      if (q.epi & (A3V_EPI_BIAS | A3V_EPI_GELU | A3V_EPI_QUICKGELU))
-        hipLaunchKernelGGL((gemm_nt_bf16_ring_kernel<EPI_SET_COMMON | EPI_SET_PRE, 192>), g, b, 0, st, q);
-      else hipLaunchKernelGGL((gemm_nt_bf16_ring_kernel<EPI_SET_COMMON, 192>), g, b, 0, st, q);
-      return;
-    }
-    if (q.epi & GEMM_EPI_ROPEKV) hipLaunchKernelGGL((gemm_nt_bf16_ring_kernel<EPI_SET_ROPE>), g, b, 0, st, q);
-    else if (q.epi & (A3V_EPI_BIAS | A3V_EPI_GELU | A3V_EPI_QUICKGELU))
-      hipLaunchKernelGGL((gemm_nt_bf16_ring_kernel<EPI_SET_COMMON | EPI_SET_PRE>), g, b, 0, st, q);
-    else hipLaunchKernelGGL((gemm_nt_bf16_ring_kernel<EPI_SET_COMMON>), g, b, 0, st, q);
-  };
-  // split-K: S slices of the K loop of `src` write raw fp32 planes into the workspace (ring kernel on 256 x 256 tiles, or the
-  // 128 x 128 kernel); one reduce pass sums them and applies the epilogue (the bias, if any, there) on the way to src's output
-  auto launch_splitk = [&](int tile, int S, const GemmArgs& src) {
-    GemmArgs t = src;
-    t.C = gws.p; t.ldc = N; t.res = nullptr; t.bias = nullptr;
-    t.epi = A3V_EPI_OUT_F32 | GEMM_EPI_RAW;
-    t.tiles_m = (t.M + tile - 1) / tile; t.tiles_n = (N + tile - 1) / tile;
-    t.c_split = (int64_t)t.M * N * 4;
-    t.slow_epi = slow_epi_env(); t.nt_store = nt_store_env();
-    const dim3 g(t.tiles_m * t.tiles_n, S);
-    if (tile == 256) hipLaunchKernelGGL((gemm_nt_bf16_ring_kernel<EPI_SET_COMMON>), g, dim3(512), 0, st, t);
-    else hipLaunchKernelGGL((gemm_nt_bf16_kernel<128, 128, 2, 2>), g, dim3(256), 0, st, t);
-    const int64_t n4 = (int64_t)t.M * (N / 4);
-    const int rb = (int)((n4 + 255) / 256 > 2048 ? 2048 : (n4 + 255) / 256);
-    hipLaunchKernelGGL(splitk_epilogue_kernel, dim3(rb), dim3(256), 0, st, gws.p, S, (int64_t)t.M * N, t.M, N, src.C, src.ldc, src.res, src.ldr,
-                       src.epi & ~A3V_EPI_BIAS, (src.epi & A3V_EPI_BIAS) ? (const bf16_t*)src.bias : nullptr);
-  };
-  const int64_t bytesA = ((int64_t)(M - 1) * lda + K) * 2, bytesW = ((int64_t)(N - 1) * ldw + K) * 2;
-  const bool desc_ok = bytesA < (1LL << 31) && bytesW < (1LL << 31);   // buffer descriptors: 32-bit offsets
-  if (epilogue & (A3V_EPI_TILE_256PP | A3V_EPI_TILE_256 | A3V_EPI_TILE_128 | A3V_EPI_TILE_192PP)) {
-    int cfg = 128;
-    if (epilogue & A3V_EPI_TILE_192PP) cfg = 259;
-    else if (epilogue & A3V_EPI_TILE_256PP) cfg = 257;
-    else if (epilogue & A3V_EPI_TILE_256) cfg = 256;
-    if (cfg > 256 && !desc_ok) return A3V_ERR_SHAPE;
-    launch(cfg, p);
   } else {
-    // Cost model in units of one 256x256 tile's time on one CU (T256): a "round" is 256 concurrent big tiles or
-    // 512 concurrent 128x128 tiles (2 blocks/CU, each ~0.65 T256 at the small kernel's lower rate); a second launch
-    // costs ~0.1.  Candidates: small kernel for everything, big kernel for everything, or big kernel on the M-tile rows
-    // that fill whole rounds + small kernel on the remaining rows.
-    const long tn256 = (N + 255) / 256, tn128 = (N + 127) / 128;
-    const bool eligible = desc_ok && M >= 512 && N >= 512;
-    // (round 2 recalibration, tools/hybrid_vs_ring.py: with the ring kernel at 1.35-1.45 PF and the small kernel at ~0.6 PF a round
-    // of 512 small tiles costs ~1.15 T256, and a split-K tail adds its reduce pass: the 7B qkv shape (6.56 rounds) went to the
-    // hybrid under the old 0.65 and lost 11 % to the all-ring launch)
-    auto small_cost = [&](long rows) { return rows <= 0 ? 0.0 : 1.15 * std::max(0.5, (double)((rows + 127) / 128) * tn128 / 512.0); };
-    const double round_us = 12.0 + 0.0206 * K;          // one round of 256 tiles of 256 x 256 on the ring kernel (M = 8192, N = 4096: 98 us at K = 4096, 476 at 22016)
-    const double c_small = small_cost(M);
-    const double c_big = eligible ? (double)((((long)(M + 255) / 256) * tn256 + 255) / 256) : 1e30;
-    long mt_h = ((long)(M / 256) * tn256 / 256) * 256 / tn256;          // M-tile rows that make whole rounds
-    double c_hyb = 1e30;
-    if (eligible && mt_h >= 1 && mt_h * 256 < M) {
-      // tail rows: on the ring kernel split over K when that fills the CUs (1/S of a tile time + the reduce pass), else small tiles
-      const long tail_rows = M - mt_h * 256, tail_tiles = ((tail_rows + 255) / 256) * tn256;
-      int S2 = tail_tiles > 0 ? (int)(cu_count() / tail_tiles) : 0;
-      if (S2 > 8) S2 = 8;
-      while (S2 > 1 && K / 64 < 8 * S2) --S2;
-      const bool simple_epi = !(p.epi & ~(A3V_EPI_RESIDUAL | A3V_EPI_RES_F32 | A3V_EPI_OUT_F32)) && gws.p && N % 4 == 0;
-      // (round 5 recalibration, tools/ring192_ab.py) the split-K tail costs its 1 / S of a tile time plus ~32 us that do not depend on K
-      // (plane traffic + two launches): 0.30 of a round at K = 4096, 0.07 at K = 22016, where a round of 256 tiles takes ~12 + 0.0206 K us
-      const double tail = (S2 >= 3 && simple_epi && pp_persistent()) ? 1.0 / S2 + 32.0 / round_us : small_cost(tail_rows) + 0.25;
-      c_hyb = (double)((mt_h * tn256 + 255) / 256) + tail;
-    }
-    // (round 5) the whole problem on 192 x 256 ring tiles: a round of them takes 0.79 of a 256 x 256 round (48 instead of 64 MFMAs per
-    // wave and K-tile on 7 / 8 of the LDS-DMA pieces); 8728 x 4096 is 2.875 rounds of these against 2 rounds + a split-K tail
-    double c_192 = 1e30;
-    if (eligible && !rk && pp_persistent() && A3V_ENV_INT("A3V_GEMM_RING_192", 1) != 0 && !(p.epi & A3V_EPI_SWIGLU))
-      c_192 = 0.79 * (double)((((long)(M + 191) / 192) * tn256 + 255) / 256) + 0.02;
-    // few big tiles (small N or M: the ViT's output projections, 76 tiles): the whole problem on the ring kernel split over K
-    double c_spl = 1e30;
-    int S3 = 0;
-    {
-      const long tiles_all = ((long)(M + 255) / 256) * tn256;
-      S3 = tiles_all > 0 ? (int)(cu_count() / tiles_all) : 0;
-      if (S3 > 8) S3 = 8;
-      while (S3 > 1 && K / 64 < 8 * S3) --S3;
-      const int okbits = A3V_EPI_BIAS | A3V_EPI_RESIDUAL | A3V_EPI_RES_F32 | A3V_EPI_OUT_F32;
-      const bool on = A3V_ENV_INT("A3V_GEMM_RING_SPLIT", 1) != 0;
-      if (on && eligible && S3 >= 3 && !(p.epi & ~okbits) && pp_persistent() && gws.p && N % 4 == 0 &&
-          (int64_t)S3 * M * N * 4 <= gws.bytes && (!(p.epi & A3V_EPI_BIAS) || !(reinterpret_cast<uintptr_t>(bias) & 7)))
-        c_spl = 1.0 / S3 + 0.2;
-    }
-    if (c_192 < c_spl && c_192 < c_small && c_192 < c_big && c_192 < c_hyb) {
-      launch(259, p);
-    } else if (c_spl < c_small && c_spl < c_big && c_spl < c_hyb) {
-      launch_splitk(256, S3, p);
-    } else if (c_big <= c_small && c_big <= c_hyb) {
-      launch(257, p);
-    } else if (c_hyb < c_small) {
-      const int m_big = (int)(mt_h * 256);
-      GemmArgs q = p;
-      q.M = m_big;
-      launch(257, q);
-      GemmArgs r = p;
-      r.M = M - m_big;
-      r.A = p.A + (int64_t)m_big * lda;
-      r.rk.m_off = m_big;
-      const int esz = (p.epi & (A3V_EPI_OUT_F32 | A3V_EPI_RES_F32)) ? 4 : 2;
-      r.C = (char*)p.C + (int64_t)m_big * ldc * esz;
-      if (p.res) r.res = (const char*)p.res + (int64_t)m_big * ldr * ((p.epi & A3V_EPI_RES_F32) ? 4 : 2);
-      // tail rows: a few hundred rows x N on 128x128 tiles = ~160 blocks with a serial K loop (50 us at K = 4096, 135 us at
-      // K = 11008).  With a registered workspace the K loop is split into S planes (more blocks, 1/S the latency) and a
-      // reduce pass applies the epilogue; only the plain / residual / fp32 forms are handled there.
-      const int simple = A3V_EPI_RESIDUAL | A3V_EPI_RES_F32 | A3V_EPI_OUT_F32;
-      int S = 1;
-      const int tblocks = ((r.M + 127) / 128) * ((N + 127) / 128);
-      while (tblocks * S < 512 && S < 8 && K / 64 >= 16 * S) S *= 2;
-      // (round 2) the same tail on the ring kernel: its ceil(rows / 256) x tn256 big tiles split S ways over K so that they fill the
-      // CUs once -- a fraction 1/S of a tile time instead of ~0.6 on the small kernel (wo: 257 -> ~235 us)
-      const int big_tiles = (int)(((r.M + 255) / 256) * tn256);
-      int S2 = big_tiles > 0 ? cu_count() / big_tiles : 0;
-      if (S2 > 8) S2 = 8;
-      while (S2 > 1 && K / 64 < 8 * S2) --S2;
-      { const int e = A3V_ENV_INT("A3V_GEMM_TAIL_SLICES", 0); if (e >= 3 && e <= 16 && K / 64 >= 2 * e) S2 = e; }      // sweeps (tools/tail_cost.py)
-      const bool ring_tail = A3V_ENV_INT("A3V_GEMM_RING_TAIL", 1) != 0;
-      if (ring_tail && pp_persistent() && S2 >= 3 && !(p.epi & ~simple) && gws.p && (int64_t)S2 * r.M * N * 4 <= gws.bytes && N % 4 == 0) {
-        launch_splitk(256, S2, r);
-      } else if (S > 1 && !(p.epi & ~simple) && gws.p && (int64_t)S * r.M * N * 4 <= gws.bytes && N % 4 == 0) {
-        launch_splitk(128, S, r);
-      } else {
-        launch(128, r);
-      }
-    } else {
-      launch(128, p);
-    }
+    if (dtype != A3V_BF16) return A3V_ERR_DTYPE;
+    if (K % BK || lda % 8 || ldw % 8 || N % 4 || ldc % 4) return A3V_ERR_SHAPE;
+    if ((epilogue & A3V_EPI_SWIGLU) && (N % 32)) return A3V_ERR_SHAPE;
+    if ((epilogue & (A3V_EPI_RESIDUAL | A3V_EPI_RES_F32)) && (ldr % 4)) return A3V_ERR_SHAPE;
   }
-  A3V_LAUNCH_CHECK();
-  return A3V_OK;
+  GemmArgs p = gemm_args(A, lda, W, ldw, C, ldc, residual, ldr, M, N, K, dtype == A3V_F32 ? epilogue : epilogue & 0xffff);
+  p.bias = bias;
+  if (rk && dtype == A3V_BF16) { p.rk = *rk; p.epi |= GEMM_EPI_ROPEKV; }
+  return gemm_run(A3V_GEMM_NT, p, epilogue, dtype, rk != nullptr, (hipStream_t)stream);
 }
 
 extern "C" int a3v_gemm_nt(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc,
@@ -3001,10 +3214,7 @@ extern "C" int a3v_gemm_nt_splitk(const void* A, int64_t lda, const void* W, int
                                   void* stream) {
   if (!A || !W || !partial || M <= 0 || N <= 0 || K <= 0 || S < 1 || S > 64) return A3V_ERR_ARG;
   if (K % 64 || lda % 8 || ldw % 8 || N % 4 || S > K / 64) return A3V_ERR_SHAPE;
-  GemmArgs p{};
-  p.A = (const bf16_t*)A; p.W = (const bf16_t*)W; p.C = partial; p.bias = nullptr; p.res = nullptr;
-  p.lda = lda; p.ldw = ldw; p.ldc = N; p.ldr = 0;
-  p.M = M; p.N = N; p.K = K; p.epi = A3V_EPI_OUT_F32 | GEMM_EPI_RAW;
+  GemmArgs p = gemm_args(A, lda, W, ldw, partial, N, nullptr, 0, M, N, K, A3V_EPI_OUT_F32 | GEMM_EPI_RAW);
   p.c_split = (int64_t)M * N * 4;
   // Rows of the streamed operand per block and LDS stages (tools/skinny_stages_bench.py, operands rotating through 700 MB, us incl.
   // the reduce pass at 8728 x 64 x K = 4096 / 11008 / 12288 / 22016):
@@ -3080,55 +3290,9 @@ static int gemm_tn_impl(const void* At, int64_t lda, const void* Wt, int64_t ldw
   if (epilogue & ~(A3V_EPI_RESIDUAL | A3V_EPI_RES_F32 | A3V_EPI_OUT_F32)) return A3V_ERR_ARG;
   if ((epilogue & (A3V_EPI_RESIDUAL | A3V_EPI_RES_F32)) && !residual) return A3V_ERR_ARG;
   if (((int64_t)(K - 1) * lda + M) * 2 >= (1LL << 31) || ((int64_t)(K - 1) * ldw + N) * 2 >= (1LL << 31)) return A3V_ERR_SHAPE;
-  GemmArgs p{};
-  p.A = (const bf16_t*)At; p.W = (const bf16_t*)Wt; p.C = C; p.bias = nullptr; p.res = residual;
-  p.lda = lda; p.ldw = ldw; p.ldc = ldc; p.ldr = ldr;
-  p.M = M; p.N = N; p.K = K; p.epi = epilogue;
-  p.tiles_n = (N + 255) / 256;
+  GemmArgs p = gemm_args(At, lda, Wt, ldw, C, ldc, residual, ldr, M, N, K, epilogue);
   p.sumsq = sumsq;
-  hipStream_t st = (hipStream_t)stream;
-  const GemmWs gws = gemm_ws_for(st);
-  // rows of C beyond whole tile rounds (e.g. dW of w1|w3: 86 x 16 tiles = 5.4 rounds): split over the contracted index into fp32
-  // planes + the reduce epilogue, as in a3v_gemm_nn / a3v_gemm_nt (needs the registered workspace; otherwise one plain launch)
-  const int ncu = cu_count();
-  const int tm_all = (M + 255) / 256;
-  const long total = (long)tm_all * p.tiles_n;
-  const long mt_h = (total / ncu) * ncu / p.tiles_n;
-  const long rem_tiles = total - mt_h * p.tiles_n;
-  int S = 1;
-  // as many K-slices as fill the CUs once (round 2: was the largest power of two with 2 S rem_tiles <= CUs, i.e. 96 blocks for the 48
-  // tail tiles of a [8728, 4096] output; 5 slices = 240 blocks finish the tail in 1/5 of a tile time instead of 1/2)
-  S = rem_tiles > 0 ? (int)std::min<long>(8, ncu / rem_tiles) : 1;
-  while (S > 1 && ((K + 63) / 64) < 16 * S) --S;
-  if (S < 1) S = 1;
-  const int m_big = (int)(mt_h * 256);
-  const bool tail_on = A3V_ENV_INT("A3V_TN_TAIL", 1) != 0;
-  if (tail_on && mt_h >= 1 && m_big < M && S > 1 && rem_tiles * 4 < 3 * ncu && gws.p && (int64_t)S * (M - m_big) * N * 4 <= gws.bytes) {
-    GemmArgs q = p;
-    q.M = m_big; q.tiles_m = (int)mt_h;
-    launch_tn<false>(dim3(q.tiles_m * q.tiles_n), st, q);
-    GemmArgs t = p;
-    t.M = M - m_big;
-    t.A = p.A + m_big;                      // At is [K][lda] with the C-row index contiguous: the tail rows of C are columns m_big.. of At
-    t.C = gws.p; t.ldc = N; t.res = nullptr; t.sumsq = nullptr;      // (raw planes: the reduce pass below adds up the final values)
-    t.epi = A3V_EPI_OUT_F32 | GEMM_EPI_RAW;
-    t.tiles_m = (t.M + 255) / 256;
-    t.c_split = (int64_t)t.M * N * 4;
-    launch_tn<false>(dim3(t.tiles_m * t.tiles_n, S), st, t);
-    const int esz = (epilogue & (A3V_EPI_OUT_F32 | A3V_EPI_RES_F32)) ? 4 : 2;
-    void* Ct = (char*)C + (int64_t)m_big * ldc * esz;
-    const void* Rt = residual ? (const char*)residual + (int64_t)m_big * ldr * ((epilogue & A3V_EPI_RES_F32) ? 4 : 2) : nullptr;
-    const int64_t n4 = (int64_t)t.M * (N / 4);
-    const int rb = (int)((n4 + 255) / 256 > 2048 ? 2048 : (n4 + 255) / 256);
-    hipLaunchKernelGGL(splitk_epilogue_kernel, dim3(rb), dim3(256), 0, st, gws.p, S, (int64_t)t.M * N, t.M, N, Ct, ldc, Rt, ldr, epilogue,
-                       (const bf16_t*)nullptr, sumsq ? sumsq + (int64_t)tm_all * p.tiles_n * 8 : nullptr);
-    A3V_LAUNCH_CHECK();
-    return A3V_OK;
-  }
-  p.tiles_m = tm_all;
-  launch_tn<false>(dim3(p.tiles_m * p.tiles_n), st, p);
-  A3V_LAUNCH_CHECK();
-  return A3V_OK;
+  return gemm_run(A3V_GEMM_TN, p, epilogue, A3V_BF16, false, (hipStream_t)stream);
 }
 
 extern "C" int a3v_gemm_tn(const void* At, int64_t lda, const void* Wt, int64_t ldw, void* C, int64_t ldc, int M, int N, int K,
@@ -3152,33 +3316,14 @@ extern "C" int a3v_gemm_tn_splitk(const void* At, int64_t lda, const void* Wt, i
   if (!At || !Wt || !partial || M <= 0 || N <= 0 || K <= 0 || S < 1 || S > 64) return A3V_ERR_ARG;
   if (lda % 8 || ldw % 8 || N % 4 || M % 8 || S > (K + 63) / 64) return A3V_ERR_SHAPE;
   if (((int64_t)(K - 1) * lda + M) * 2 >= (1LL << 31) || ((int64_t)(K - 1) * ldw + N) * 2 >= (1LL << 31)) return A3V_ERR_SHAPE;
-  GemmArgs p{};
-  p.A = (const bf16_t*)At; p.W = (const bf16_t*)Wt; p.C = partial; p.bias = nullptr; p.res = nullptr;
-  p.lda = lda; p.ldw = ldw; p.ldc = N; p.ldr = 0;
-  p.M = M; p.N = N; p.K = K; p.epi = A3V_EPI_OUT_F32 | GEMM_EPI_RAW;
+  GemmArgs p = gemm_args(At, lda, Wt, ldw, partial, N, nullptr, 0, M, N, K, A3V_EPI_OUT_F32 | GEMM_EPI_RAW);
   p.tiles_m = (M + 255) / 256; p.tiles_n = (N + 255) / 256;
   p.c_split = (int64_t)M * N * 4;
-  launch_tn<false>(dim3(p.tiles_m * p.tiles_n, S), (hipStream_t)stream, p);
+  p.slow_epi = slow_epi_env(); p.nt_store = nt_store_env();
+  p.xmap = tn_xmap(p.tiles_m, p.tiles_n);
+  hipLaunchKernelGGL(gemm_tn_bf16_pp_kernel<false>, dim3(p.tiles_m * p.tiles_n, S), dim3(512), 0, (hipStream_t)stream, p);
   A3V_LAUNCH_CHECK();
   return A3V_OK;
-}
-
-// (round 5) the fp8 product on the ring kernel: persistent tile walk, three LDS rings, staged epilogues.  `grid_y` > 1: split-K planes.
-// Bias / activation kinds keep the two-stage kernel (no fp8 instantiation of that epilogue set).  A3V_GEMM_FP8_RING=0: the two-stage
-// kernel for everything (A/B runs, equality tests).
-static bool launch_ring_fp8(GemmArgs q, int grid_y, hipStream_t st, int tbm = 256) {
-  if (A3V_ENV_INT("A3V_GEMM_FP8_RING", 1) == 0 || !pp_persistent()) return false;
-  if (q.epi & (A3V_EPI_BIAS | A3V_EPI_GELU | A3V_EPI_QUICKGELU)) return false;
-  q.epi &= ~GEMM_EPI_SCALE;                              // the kernel scales its accumulators itself, in front of the staged epilogues
-  q.slow_epi = slow_epi_env(); q.nt_store = nt_store_env();
-  const int nt = q.tiles_m * q.tiles_n;
-  const dim3 g(grid_y > 1 ? nt : std::min(nt, cu_count()), grid_y), b(512);
-  q.xmap = (g.x & 63) || grid_y > 1 ? 0 : A3V_ENV_INT("A3V_GEMM_XMAP", 1);
-  if (!((q.xmap & 4) && g.x == 256 && (q.tiles_m & 15) == 0 && (q.tiles_n & 15) == 0)) q.xmap &= ~4;
-  if (tbm == 192) hipLaunchKernelGGL((gemm_nt_bf16_ring_kernel<EPI_SET_COMMON, 192, true>), g, b, 0, st, q);
-  else if (q.epi & GEMM_EPI_ROPEKV) hipLaunchKernelGGL((gemm_nt_bf16_ring_kernel<EPI_SET_ROPE, 256, true>), g, b, 0, st, q);
-  else hipLaunchKernelGGL((gemm_nt_bf16_ring_kernel<EPI_SET_COMMON, 256, true>), g, b, 0, st, q);
-  return true;
 }
 
 // C = epilogue((Aq . Wq^T) * sa[m] * sw[n]): fp8 (OCP e4m3fn) activations and weights with per-row fp32 scales, MX-scaled
@@ -3193,70 +3338,10 @@ static int gemm_nt_fp8_impl(const void* Aq, int64_t lda, const float* sa, const 
   if ((epilogue & (A3V_EPI_RESIDUAL | A3V_EPI_RES_F32)) && (!residual || ldr % 4)) return A3V_ERR_ARG;
   if ((epilogue & A3V_EPI_SWIGLU) && (N % 32)) return A3V_ERR_SHAPE;
   if ((int64_t)(M - 1) * lda + K >= (1LL << 31) || (int64_t)(N - 1) * ldw + K >= (1LL << 31)) return A3V_ERR_SHAPE;
-  GemmArgs p{};
-  p.A = (const bf16_t*)Aq; p.W = (const bf16_t*)Wq; p.C = C; p.bias = bias; p.res = residual;
-  p.lda = lda; p.ldw = ldw; p.ldc = ldc; p.ldr = ldr;
-  p.M = M; p.N = N; p.K = K; p.epi = epilogue | GEMM_EPI_SCALE;
-  p.sa = sa; p.sw = sw;
+  GemmArgs p = gemm_args(Aq, lda, Wq, ldw, C, ldc, residual, ldr, M, N, K, epilogue | GEMM_EPI_SCALE);
+  p.bias = bias; p.sa = sa; p.sw = sw;
   if (rk) { p.rk = *rk; p.epi |= GEMM_EPI_ROPEKV; }
-  p.tiles_n = (N + 255) / 256;
-  hipStream_t st = (hipStream_t)stream;
-  const GemmWs gws = gemm_ws_for(st);
-  // Tile rounds: tiles_m x tiles_n blocks over the CUs.  When the last round would be mostly empty (e.g. 35 x 16 = 560 tiles on 256
-  // CUs: a third round at 19 %), the tile rows that fill whole rounds run as usual and the remaining rows (< one round of tiles)
-  // are split over K into raw fp32 planes -- S times the blocks at 1/S the length -- which a reduce pass rounds and stores with
-  // the residual forms of the epilogue (needs the registered workspace of a3v_gemm_set_workspace; otherwise one plain launch).
-  const int ncu = cu_count();
-  const int tm_all = (M + 255) / 256;
-  const long total = (long)tm_all * p.tiles_n;
-  const int simple = A3V_EPI_RESIDUAL | A3V_EPI_RES_F32 | A3V_EPI_OUT_F32;
-  const long mt_h = (total / ncu) * ncu / p.tiles_n;                 // tile rows that make whole rounds
-  const long rem_tiles = total - mt_h * p.tiles_n;
-  int S = 1;
-  while (rem_tiles * S * 2 <= ncu && S < 8 && (K / 128) >= 8 * S) S *= 2;   // measured on wo / w2 of 7B: S = 2 (96 blocks) beat S = 8 (384 blocks)
-  const int m_big = (int)(mt_h * 256);
-  // (round 5) 192 x 256 ring tiles where they cost fewer rounds than whole 256-row rounds + a split-K tail (a round of them is 0.79 of a
-  // 256-row round; the tail's ~32 us do not shrink with the fp8 round time ~12 + 0.0103 K us): A3V_GEMM_FP8_192 = 0 never, 2 always
-  {
-    const int e192 = A3V_ENV_INT("A3V_GEMM_FP8_192", 1);
-    const bool tail_form = !rk && !(epilogue & ~simple) && mt_h >= 1 && m_big < M && S > 1 && rem_tiles * 4 < 3 * ncu;
-    const double round_us = 12.0 + 0.0103 * K;
-    const double c_now = tail_form ? (double)(mt_h * p.tiles_n / ncu) + 1.0 / S + 32.0 / round_us : (double)((total + ncu - 1) / ncu);
-    const long t192 = (long)((M + 191) / 192) * p.tiles_n;
-    const double c_192 = 0.79 * (double)((t192 + ncu - 1) / ncu) + 0.02;
-    if (e192 && !rk && !(epilogue & (A3V_EPI_SWIGLU | A3V_EPI_BIAS | A3V_EPI_GELU | A3V_EPI_QUICKGELU)) && M >= 512 && N >= 512 && (e192 == 2 || c_192 < c_now)) {
-      GemmArgs q = p;
-      q.tiles_m = (M + 191) / 192;
-      if (launch_ring_fp8(q, 1, st, 192)) { A3V_LAUNCH_CHECK(); return A3V_OK; }
-    }
-  }
-  if (!rk && !(epilogue & ~simple) && mt_h >= 1 && m_big < M && S > 1 && rem_tiles * 4 < 3 * ncu && gws.p &&
-      (int64_t)S * (M - m_big) * N * 4 <= gws.bytes) {
-    GemmArgs q = p;
-    q.M = m_big; q.tiles_m = (int)mt_h;
-    if (!launch_ring_fp8(q, 1, st)) hipLaunchKernelGGL(gemm_nt_fp8_pp_kernel, dim3(q.tiles_m * q.tiles_n), dim3(512), 0, st, q);
-    GemmArgs t = p;
-    t.M = M - m_big;
-    t.A = (const bf16_t*)((const char*)Aq + (int64_t)m_big * lda);
-    t.sa = sa + m_big;
-    t.C = gws.p; t.ldc = N; t.res = nullptr; t.bias = nullptr;
-    t.epi = A3V_EPI_OUT_F32 | GEMM_EPI_RAW | GEMM_EPI_SCALE;
-    t.tiles_m = (t.M + 255) / 256;
-    t.c_split = (int64_t)t.M * N * 4;
-    if (!launch_ring_fp8(t, S, st)) hipLaunchKernelGGL(gemm_nt_fp8_pp_kernel, dim3(t.tiles_m * t.tiles_n, S), dim3(512), 0, st, t);
-    const int esz = (epilogue & (A3V_EPI_OUT_F32 | A3V_EPI_RES_F32)) ? 4 : 2;
-    void* Ct = (char*)C + (int64_t)m_big * ldc * esz;
-    const void* Rt = residual ? (const char*)residual + (int64_t)m_big * ldr * ((epilogue & A3V_EPI_RES_F32) ? 4 : 2) : nullptr;
-    const int64_t n4 = (int64_t)t.M * (N / 4);
-    const int rb = (int)((n4 + 255) / 256 > 2048 ? 2048 : (n4 + 255) / 256);
-    hipLaunchKernelGGL(splitk_epilogue_kernel, dim3(rb), dim3(256), 0, st, gws.p, S, (int64_t)t.M * N, t.M, N, Ct, ldc, Rt, ldr, epilogue);
-    A3V_LAUNCH_CHECK();
-    return A3V_OK;
-  }
-  p.tiles_m = tm_all;
-  if (!launch_ring_fp8(p, 1, st)) hipLaunchKernelGGL(gemm_nt_fp8_pp_kernel, dim3(p.tiles_m * p.tiles_n), dim3(512), 0, st, p);
-  A3V_LAUNCH_CHECK();
-  return A3V_OK;
+  return gemm_run(A3V_GEMM_NT_FP8, p, epilogue, A3V_BF16, rk != nullptr, (hipStream_t)stream);
 }
 
 extern "C" int a3v_gemm_nt_fp8(const void* Aq, int64_t lda, const float* sa, const void* Wq, int64_t ldw, const float* sw, void* C,
@@ -3279,8 +3364,6 @@ extern "C" int a3v_gemm_qkv_rope_fp8(const void* Aq, int64_t lda, const float* s
 
 // "NN" GEMM: C[M,N] = epilogue(A . Wt) with A [M, K] row-major and Wt [K, N] row-major (the contracted index is Wt's ROW index) --
 // the input gradient dX = dY . W on the weight image the forward pass uses, without a transposed copy of W.  K % 64 == 0.
-// Tile rows that fill whole rounds of the CUs run as one launch; the remaining rows are split over K into fp32 planes + the
-// reduce epilogue when a workspace is registered (a3v_gemm_set_workspace), exactly as in a3v_gemm_nt / a3v_gemm_nt_fp8.
 extern "C" int a3v_gemm_nn(const void* A, int64_t lda, const void* Wt, int64_t ldw, void* C, int64_t ldc, int M, int N, int K,
                            const void* residual, int64_t ldr, int epilogue, void* stream) {
   if (!A || !Wt || !C || M <= 0 || N <= 0 || K <= 0) return A3V_ERR_ARG;
@@ -3294,47 +3377,6 @@ extern "C" int a3v_gemm_nn(const void* A, int64_t lda, const void* Wt, int64_t l
   }
   if ((epilogue & (A3V_EPI_RESIDUAL | A3V_EPI_RES_F32)) && (!residual || ldr % 4)) return A3V_ERR_ARG;
   if (((int64_t)(M - 1) * lda + K) * 2 >= (1LL << 31) || ((int64_t)(K - 1) * ldw + N) * 2 >= (1LL << 31)) return A3V_ERR_SHAPE;
-  hipStream_t st = (hipStream_t)stream;
-  const GemmWs gws = gemm_ws_for(st);
-  GemmArgs p{};
-  p.A = (const bf16_t*)A; p.W = (const bf16_t*)Wt; p.C = C; p.bias = nullptr; p.res = residual;
-  p.lda = lda; p.ldw = ldw; p.ldc = ldc; p.ldr = ldr;
-  p.M = M; p.N = N; p.K = K; p.epi = epilogue;
-  p.tiles_n = (N + 255) / 256;
-  const int ncu = cu_count();
-  const int tm_all = (M + 255) / 256;
-  const long total = (long)tm_all * p.tiles_n;
-  const long mt_h = (total / ncu) * ncu / p.tiles_n;
-  const long rem_tiles = total - mt_h * p.tiles_n;
-  int S = 1;
-  S = rem_tiles > 0 ? (int)std::min<long>(8, ncu / rem_tiles) : 1;      // as many K-slices as fill the CUs once (see a3v_gemm_tn)
-  while (S > 1 && (K / 64) < 16 * S) --S;
-  if (S < 1) S = 1;
-  const int m_big = (int)(mt_h * 256);
-  if (!swb && mt_h >= 1 && m_big < M && S > 1 && rem_tiles * 4 < 3 * ncu && gws.p && (int64_t)S * (M - m_big) * N * 4 <= gws.bytes) {
-    GemmArgs q = p;
-    q.M = m_big; q.tiles_m = (int)mt_h;
-    launch_tn<true>(dim3(q.tiles_m * q.tiles_n), st, q);
-    GemmArgs t = p;
-    t.M = M - m_big;
-    t.A = p.A + (int64_t)m_big * lda;
-    t.C = gws.p; t.ldc = N; t.res = nullptr;
-    t.epi = A3V_EPI_OUT_F32 | GEMM_EPI_RAW;
-    t.tiles_m = (t.M + 255) / 256;
-    t.c_split = (int64_t)t.M * N * 4;
-    launch_tn<true>(dim3(t.tiles_m * t.tiles_n, S), st, t);
-    const int esz = (epilogue & (A3V_EPI_OUT_F32 | A3V_EPI_RES_F32)) ? 4 : 2;
-    void* Ct = (char*)C + (int64_t)m_big * ldc * esz;
-    const void* Rt = residual ? (const char*)residual + (int64_t)m_big * ldr * ((epilogue & A3V_EPI_RES_F32) ? 4 : 2) : nullptr;
-    const int64_t n4 = (int64_t)t.M * (N / 4);
-    const int rb = (int)((n4 + 255) / 256 > 2048 ? 2048 : (n4 + 255) / 256);
-    hipLaunchKernelGGL(splitk_epilogue_kernel, dim3(rb), dim3(256), 0, st, gws.p, S, (int64_t)t.M * N, t.M, N, Ct, ldc, Rt, ldr, epilogue);
-    A3V_LAUNCH_CHECK();
-    return A3V_OK;
-  }
-  p.tiles_m = tm_all;
-  launch_tn<true>(dim3(p.tiles_m * p.tiles_n), st, p);
-  A3V_LAUNCH_CHECK();
-  return A3V_OK;
+  return gemm_run(A3V_GEMM_NN, gemm_args(A, lda, Wt, ldw, C, ldc, residual, ldr, M, N, K, epilogue), epilogue, A3V_BF16, false, (hipStream_t)stream);
 }
 

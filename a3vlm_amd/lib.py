@@ -51,6 +51,7 @@ SIGNATURES = {
     "a3v_gemm_tn": (I, [P, L, P, L, P, L, I, I, I, P, L, I, P]),
     "a3v_gemm_tn_sumsq": (I, [P, L, P, L, P, L, I, I, I, P, L, I, P, L, P]),
     "a3v_gemm_tn_sumsq_slots": (L, [I, I]),
+    "a3v_gemm_plan": (I, [I, I, I, I, L, L, I, I, I, I, I, L, I, P]),
     "a3v_gemm_set_workspace": (I, [P, L]),
     "a3v_gemm_set_workspace_for": (I, [P, P, L]),
     "a3v_gemm_nt_splitk": (I, [P, L, P, L, P, I, I, I, I, P]),

@@ -147,6 +147,37 @@ int a3v_gemm_set_workspace_for(void* stream, void* ptr, int64_t bytes);
  * on any other stream without a registration of their own get no scratch (plain launches), never this buffer. */
 int a3v_gemm_set_workspace(void* ptr, int64_t bytes);
 
+/* Which kernels a3v_gemm_nt / _qkv_rope (A3V_GEMM_NT), a3v_gemm_nt_fp8 / _qkv_rope_fp8 (A3V_GEMM_NT_FP8), a3v_gemm_tn / _tn_sumsq
+ * (A3V_GEMM_TN) and a3v_gemm_nn (A3V_GEMM_NN) launch for a problem, on what grid: the plan those entry points execute, computed by the
+ * same host code from values alone (no device, no pointer; the A3V_* switches apply).  `epilogue` / `dtype` as passed to the entry
+ * point (dtype is read by A3V_GEMM_NT only); rope: the fused-qkv form; bias_aligned: the bias pointer is 8-byte aligned; sumsq: the
+ * _tn_sumsq form; workspace_bytes: the registered workspace of the stream (0 = none); cus: the device's compute units (256 on MI355X).
+ * Writes up to A3V_GEMM_MAX_STEPS steps of A3V_GEMM_STEP_INTS values each into `steps` -- kernel (A3V_GEMM_K_*), grid x, grid y,
+ * block size, xmap, first row of C, rows of C, K-slices -- in launch order and returns their number, or A3V_ERR_*.  Shapes that the
+ * entry point itself refuses are not checked here. */
+enum { A3V_GEMM_NT = 0, A3V_GEMM_NT_FP8 = 1, A3V_GEMM_TN = 2, A3V_GEMM_NN = 3 };
+enum { A3V_GEMM_MAX_STEPS = 3, A3V_GEMM_STEP_INTS = 8 };
+enum {                          /* one value per kernel instantiation the dispatch launches */
+  A3V_GEMM_K_NT_128 = 0,        /* gemm_nt_bf16_kernel<128, 128, 2, 2>                      */
+  A3V_GEMM_K_NT_256,            /* gemm_nt_bf16_kernel<256, 256, 2, 4>                      */
+  A3V_GEMM_K_RING,              /* gemm_nt_bf16_ring_kernel<COMMON>                         */
+  A3V_GEMM_K_RING_PRE,          /* ...<COMMON | PRE> (bias / GELU forms)                    */
+  A3V_GEMM_K_RING_ROPE,         /* ...<ROPE> (fused qkv)                                    */
+  A3V_GEMM_K_RING_192,          /* ...<COMMON, 192>                                         */
+  A3V_GEMM_K_RING_PRE_192,      /* ...<COMMON | PRE, 192>                                   */
+  A3V_GEMM_K_RING_F8,           /* ...<COMMON, 256, fp8>                                    */
+  A3V_GEMM_K_RING_ROPE_F8,      /* ...<ROPE, 256, fp8>                                      */
+  A3V_GEMM_K_RING_192_F8,       /* ...<COMMON, 192, fp8>                                    */
+  A3V_GEMM_K_FP8_PP,            /* gemm_nt_fp8_pp_kernel (two-stage)                        */
+  A3V_GEMM_K_TN,                /* gemm_tn_bf16_pp_kernel<false>                            */
+  A3V_GEMM_K_NN,                /* gemm_tn_bf16_pp_kernel<true>                             */
+  A3V_GEMM_K_F32,               /* gemm_nt_f32_kernel                                       */
+  A3V_GEMM_K_REDUCE,            /* splitk_epilogue_kernel                                   */
+  A3V_GEMM_K_COUNT
+};
+int a3v_gemm_plan(int family, int M, int N, int K, int64_t lda, int64_t ldw, int epilogue, int dtype, int rope,
+                  int bias_aligned, int sumsq, int64_t workspace_bytes, int cus, int32_t* steps);
+
 /* Split-K form for skinny products with a long K (the LoRA adapter GEMMs of model/peft.py:84-99 and their gradients:
  * N or M = 64, K = 4096 ... 22016): slice s of S writes the fp32 plane partial[s][M][N]; a3v_splitk_reduce sums the
  * planes in order, optionally accumulates into `out` (fp32 gradients) and rounds once to out_dtype.
