@@ -154,6 +154,89 @@ __global__ __launch_bounds__(256) void nf4_dequant_kernel(const uint8_t* __restr
   }
   *reinterpret_cast<bf16x8*>(Wd + n * ldd + k) = o;
 }
+
+// ---- streaming dequantiser of the QLoRA training step (a3v_dequantize_nf4_images): runs two to three times per layer per step.
+// One workgroup owns a 64-row x 128-k tile: every thread reads 16 B of codes (32 weights of one row, inside one scale block) and one
+// scale, rounds exactly as nf4_dequant_kernel (__fmul_rn of the fp32 code-book value, then f2bf: the bf16 v_perm tables of the decode
+// GEMV hold the code book ROUNDED to bf16 and cannot give these bits, so the 16 fp32 entries sit in LDS: one ds_read_b32 per weight,
+// 16 distinct dwords whatever the codes), and parks the tile in LDS twice: row-major (272-B pitch) for Wd and transposed (144-B
+// pitch) for Wt.  Both are then stored with 16-B pieces that are contiguous along the destination's rows (256 B per Wd row, 128 B
+// per Wt row).  The transposed tile is written with 2-byte LDS stores (32 per thread); lanes of one store differ in the k-segment s
+// (k rows 32 s apart: the same bank at every pitch) and in the row, so the column is XOR-ed with 16 s (whole 16-B pieces move, banks
+// shift by 8 s); two lanes still share each dword.  By the bank rule that layout should not serialise; no counter has been read and
+// the kernel has not been timed (tools/qlora_bench.py).  If it comes in under the copy rate, the 2-byte stores are the first suspect:
+// pack row pairs into ds_write_b32.  The algorithm needs ~2.56 B of HBM traffic per weight for both images.
+constexpr int QI_TN = 64, QI_TK = 128, QI_DP = QI_TK + 8, QI_TP = QI_TN + 8;     // tile and LDS pitches (elements)
+
+template <bool HAS_D, bool HAS_T>
+__global__ __launch_bounds__(256) void nf4_images_kernel(const uint8_t* __restrict__ q, const float* __restrict__ scales,
+                                                         bf16_t* __restrict__ Wd, int64_t ldd, bf16_t* __restrict__ Wt, int64_t ldt,
+                                                         int N, int K) {
+  __shared__ float tab[16];
+  __shared__ __attribute__((aligned(16))) bf16_t sD[HAS_D ? QI_TN * QI_DP : 8];
+  __shared__ __attribute__((aligned(16))) bf16_t sT[HAS_T ? QI_TK * QI_TP : 8];
+  const int t = threadIdx.x;
+  if (t < 16) tab[t] = nf4_value(t);
+  __syncthreads();
+  const int n0 = blockIdx.x * QI_TN, k0 = blockIdx.y * QI_TK;
+  const int r = t >> 2, s = t & 3;                     // tile row, 32-wide k segment
+  const int n = n0 + r, k = k0 + s * 32;
+  bf16x8 v[4];
+  if (n < N && k < K) {
+    const u32x4 w = *reinterpret_cast<const u32x4*>(q + (int64_t)n * (K >> 1) + (k >> 1));
+    const float sc = scales[(int64_t)n * (K >> 6) + (k >> 6)];
+#pragma unroll
+    for (int d = 0; d < 4; ++d)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        v[d][2 * j] = f2bf(__fmul_rn(tab[(w[d] >> (8 * j + 4)) & 15], sc));
+        v[d][2 * j + 1] = f2bf(__fmul_rn(tab[(w[d] >> (8 * j)) & 15], sc));
+      }
+  } else {
+#pragma unroll
+    for (int d = 0; d < 4; ++d)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[d][e] = (bf16_t)0.f;
+  }
+  if (HAS_D) {
+#pragma unroll
+    for (int d = 0; d < 4; ++d) *reinterpret_cast<bf16x8*>(&sD[r * QI_DP + s * 32 + d * 8]) = v[d];
+  }
+  if (HAS_T) {
+    const int col = r ^ (s << 4);
+#pragma unroll
+    for (int d = 0; d < 4; ++d)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) sT[(s * 32 + d * 8 + e) * QI_TP + col] = v[d][e];
+  }
+  __syncthreads();
+  if (HAS_D) {
+#pragma unroll
+    for (int it = 0; it < 4; ++it) {
+      const int row = it * 16 + (t >> 4), c = t & 15;
+      const int nn = n0 + row, kk = k0 + c * 8;
+      if (nn < N && kk < K) *reinterpret_cast<bf16x8*>(Wd + (int64_t)nn * ldd + kk) = *reinterpret_cast<const bf16x8*>(&sD[row * QI_DP + c * 8]);
+    }
+  }
+  if (HAS_T) {
+#pragma unroll
+    for (int it = 0; it < 4; ++it) {
+      const int kr = it * 32 + (t >> 3), c = t & 7;
+      const int kk = k0 + kr, nn = n0 + c * 8;
+      if (kk < K && nn < N) {
+        const bf16x8 o = *reinterpret_cast<const bf16x8*>(&sT[kr * QI_TP + ((c ^ ((kr >> 5) << 1)) << 3)]);
+        bf16_t* dst = Wt + (int64_t)kk * ldt + nn;
+        if (nn + 8 <= N) {
+          *reinterpret_cast<bf16x8*>(dst) = o;
+        } else {                                       // ragged last piece of a row: only the N columns of the window are written
+#pragma unroll
+          for (int e = 0; e < 8; ++e)
+            if (nn + e < N) dst[e] = o[e];
+        }
+      }
+    }
+  }
+}
 }  // namespace
 
 extern "C" int64_t a3v_quantize_nf4_ws_bytes(int N, int K) {
@@ -186,6 +269,25 @@ extern "C" int a3v_dequantize_nf4(const void* q, const float* scales, void* Wd, 
   const int64_t n8 = (int64_t)N * K / 8;
   hipLaunchKernelGGL(nf4_dequant_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const uint8_t*)q, scales,
                      (bf16_t*)Wd, ldd, K, n8);
+  A3V_LAUNCH_CHECK();
+  return A3V_OK;
+}
+
+extern "C" int a3v_dequantize_nf4_images(const void* q, const float* scales, int N, int K, void* Wd, int64_t ldd, void* Wt, int64_t ldt,
+                                         void* stream) {
+  if (!q || !scales || (!Wd && !Wt)) return A3V_ERR_ARG;
+  if (N <= 0 || K <= 0 || K % 64 || (K + QI_TK - 1) / QI_TK > 65535) return A3V_ERR_SHAPE;
+  if (reinterpret_cast<uintptr_t>(q) & 15) return A3V_ERR_SHAPE;
+  if (Wd && (ldd < K || ldd % 8 || (reinterpret_cast<uintptr_t>(Wd) & 15))) return A3V_ERR_SHAPE;
+  if (Wt && (ldt < N || ldt % 8 || (reinterpret_cast<uintptr_t>(Wt) & 15))) return A3V_ERR_SHAPE;
+  const dim3 grid((unsigned)((N + QI_TN - 1) / QI_TN), (unsigned)((K + QI_TK - 1) / QI_TK));
+  hipStream_t st = (hipStream_t)stream;
+  if (Wd && Wt)
+    hipLaunchKernelGGL((nf4_images_kernel<true, true>), grid, dim3(256), 0, st, (const uint8_t*)q, scales, (bf16_t*)Wd, ldd, (bf16_t*)Wt, ldt, N, K);
+  else if (Wd)
+    hipLaunchKernelGGL((nf4_images_kernel<true, false>), grid, dim3(256), 0, st, (const uint8_t*)q, scales, (bf16_t*)Wd, ldd, (bf16_t*)nullptr, (int64_t)0, N, K);
+  else
+    hipLaunchKernelGGL((nf4_images_kernel<false, true>), grid, dim3(256), 0, st, (const uint8_t*)q, scales, (bf16_t*)nullptr, (int64_t)0, (bf16_t*)Wt, ldt, N, K);
   A3V_LAUNCH_CHECK();
   return A3V_OK;
 }

@@ -10,8 +10,13 @@ model/accessory/main_finetune.py:57-136 as used by scripts/a3vlm_train.sh:46-55)
 Call order follows main_finetune.py:141-362: dist init (one process per GPU, backend "nccl" = RCCL) -> MetaModel in
 bf16 on the GPU -> trainables promoted to fp32 -> checkpoint load -> identical weights on all ranks (broadcast) ->
 AdamW(add_weight_decay, betas 0.9/0.95) -> FinetuneDistSampler -> epochs of train_one_epoch -> save_checkpoint.
-FSDP / tensor parallelism / ``--checkpointing`` / ``--quant`` are accepted and ignored or rejected as documented
-in DESIGN.md (DP replicas, activations kept in HBM).  ``--synthetic N`` substitutes a seeded synthetic dataset of N
+FSDP / tensor parallelism / ``--checkpointing`` are accepted and ignored or rejected as documented in DESIGN.md (DP replicas,
+activations kept in HBM).  ``--quant`` is the reference's QLoRA fine-tune (main_finetune.py:172-209): the model is built in bf16, the
+checkpoint loaded, the decoder linears and the LM head quantised to NF4 (``quantize_base_weights``, every DP rank its own copy after the
+broadcast) and what is left trainable -- adapters, norms, projectors -- trained; it needs a peft ``--llama_type``,
+``--only_save_trainable`` and ``--precision bf16``, and does not combine with ``--zero1``.  To resume, give the base
+checkpoint as ``--pretrained_path`` and the adapter checkpoint as ``--resume``: the base is quantised before the adapters are loaded by
+name.  ``--synthetic N`` substitutes a seeded synthetic dataset of N
 items of the dialog dataset's output shape (the real dataset classes are the next host-side row).
 """
 from __future__ import annotations
@@ -131,7 +136,15 @@ def main(args):
     if args.model_parallel_size != 1:
         raise SystemExit("tensor parallelism is not part of this build (DP replicas only, SURVEY 8(e)): use --model_parallel_size 1")
     if args.quant:
-        raise SystemExit("--quant (bitsandbytes NF4) is CUDA-only and out of scope (SURVEY 8(a) row Q)")
+        # QLoRA: LoRA fine-tune on a frozen NF4 base (the reference's main_finetune.py:172-209); refused up front, before the GPU is touched
+        if "peft" not in args.llama_type:
+            raise SystemExit(f"--quant trains adapters on a frozen NF4 base: it needs a peft --llama_type (llama_ens5_peft), not {args.llama_type}")
+        if not args.only_save_trainable:
+            raise SystemExit("--quant needs --only_save_trainable: the NF4 base matrices are not in state_dict() (main_finetune.py:175)")
+        if args.precision != "bf16":
+            raise SystemExit("--quant needs --precision bf16 (NF4 weights dequantise to bf16 GEMM images)")
+        if args.zero1:
+            raise SystemExit("--quant does not combine with --zero1: ZeRO-1 shards compute-dtype base matrices, and an NF4 base has none")
     if os.environ.get("A3V_ONE_DEVICE") == "1":      # tests: several ranks on a single-GPU box (with A3V_DIST_BACKEND=gloo)
         local = 0
     torch.cuda.set_device(local)
@@ -155,6 +168,8 @@ def main(args):
     if distributed:                                                      # :237-239 (every parameter, trainable or frozen)
         for p in model.parameters():
             dist.broadcast(p.data, src=0)
+    if args.quant:                                                       # :200-209, after the checkpoint: each rank quantises its own copy
+        model.llma.quantize_base_weights("nf4")
     model.llma.invalidate_packed_weights()
     if args.precision == "tf32":
         model.train_compute_dtype = torch.float32

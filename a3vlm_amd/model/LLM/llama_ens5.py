@@ -550,6 +550,10 @@ class Transformer(nn.Module):
         w = self._nf4_scratch(a.vocab_size * a.dim)[:a.vocab_size * a.dim].view(a.vocab_size, a.dim)
         return ops.dequantize_nf4(*self._n4["output"], w)
 
+    def _head_weight(self) -> torch.Tensor:
+        """The LM head as a bf16 GEMM operand (an NF4 model: dequantised into the reused scratch)."""
+        return self.output.weight if getattr(self, "_n4", None) is None else self._nf4_output_weight()
+
     def _lm_head_f32(self, xn: torch.Tensor, logits: torch.Tensor) -> None:
         """fp32 logits of bf16 rows xn: the NF4 GEMV in chunks of 16 rows on an NF4 model, the bf16 path otherwise."""
         n4 = getattr(self, "_n4", None)
@@ -796,7 +800,7 @@ class Transformer(nn.Module):
         o0 = W if out_from is None else out_from       # h[:, image_words:] (llama_ens5.py:486)
         out = torch.empty(B, S - o0, a.vocab_size, dtype=self._dtype, device=self._device)
         xv = xn.view(B, S, a.dim)
-        wout = self.output.weight if getattr(self, "_n4", None) is None else self._nf4_output_weight()
+        wout = self._head_weight()
         for b in range(B):
             ops.gemm_nt(xv[b, o0:], wout, out[b])
         return out

@@ -23,6 +23,7 @@ import torch
 import torch.nn as nn
 
 from ... import ops
+from ... import lib as _lib
 from . import llama_ens5 as base
 from .llama_ens5 import _W
 
@@ -35,6 +36,12 @@ class ModelArgs(base.ModelArgs):
 
 def _pad64(n: int) -> int:
     return (n + 63) // 64 * 64
+
+
+def base_shape(mod) -> tuple:
+    """(out, in) of a decoder linear's base matrix, also after ``quantize_base_weights`` freed its bf16 ``weight``."""
+    q4 = getattr(mod, "q4", None)
+    return tuple(mod.weight.shape) if q4 is None else q4[2]
 
 
 class Transformer(base.Transformer):
@@ -58,12 +65,103 @@ class Transformer(base.Transformer):
         self._per_kernel_decode = True       # the single-call decode step has no adapter hooks
         self._lora_img: Dict[str, torch.Tensor] = {}
         self._lora_ver = None
+        self._q4: Optional[Dict[str, tuple]] = None      # quantize_base_weights: module name -> (nibbles, scales, (N, K))
 
     def quantize_decode_weights(self, mode: str = "fp8", prefill: bool = False) -> None:
         if mode == "nf4":
             # the reference keeps the LoRA adapters unquantised beside the NF4 base (llama_ens5.py:541-550, QLoRA): a follow-up
             raise NotImplementedError("NF4 weights with LoRA adapters (QLoRA) are not implemented")
         super().quantize_decode_weights(mode, prefill)
+
+    def quantize_base_weights(self, mode: str = "nf4") -> None:
+        """QLoRA (the reference's ``main_finetune.py --quant``: bf16 model, checkpoint, ``quantize(model, nf4)``, then train what is left
+        trainable; util/quant.py:95-163 skips every ``lora`` module).  The seven decoder linears of every layer and ``output`` are
+        quantised by a3v_quantize_nf4 -- one ORIGINAL module at a time, rows in module order -- and each bf16 ``weight`` is freed
+        (gone from ``state_dict()``; irreversible).  ``(nibbles, scales, (N, K))`` is kept per module (``self._q4[name]`` and
+        ``module.q4``).  Adapters, norms, embeddings, projectors and tags are untouched and train as before.
+
+        Training: ``TrainEngine`` dequantises one layer at a time into a reused scratch (a3v_dequantize_nf4_images) and runs the bf16
+        LoRA step on it.  Inference (``forward``, ``forward_inference``, ``generate``) works for every row count the same way: a
+        layer's Wd in a reused scratch, then the bf16 kernels plus adapters of the unquantised plugin -- bit-identical to the bf16 model
+        holding Wd, but every decode step dequantises every layer again: decode speed on this path is not a goal.
+
+        Needs bf16 base matrices on the GPU and K % 64 == 0 for every module (the format); none of the NF4 decode GEMV's limits."""
+        if mode != "nf4":
+            raise ValueError("only 'nf4' base weights are implemented")
+        if self._q4 is not None:
+            raise RuntimeError("the base weights are already NF4")
+        named = []
+        for i, lyr in enumerate(self.layers):
+            at, f = lyr.attention, lyr.feed_forward
+            named += [(f"layers.{i}.attention.{n}", getattr(at, n)) for n in ("wq", "wk", "wv", "wo")]
+            named += [(f"layers.{i}.feed_forward.{n}", getattr(f, n)) for n in ("w1", "w3", "w2")]
+        named.append(("output", self.output))
+        for name, mod in named:
+            w = mod.weight
+            if w.dtype != torch.bfloat16 or w.device.type != "cuda":
+                raise ValueError(f"NF4 base weights need a bf16 model on the GPU (quantise after .to(device)); {name}.weight is {w.dtype} on {w.device}")
+            if w.shape[1] % 64:
+                raise ValueError(f"NF4 base weights need K % 64 == 0 for every module; {name}.weight is {tuple(w.shape)}")
+        ws = torch.empty((max(int(_lib.load().a3v_quantize_nf4_ws_bytes(*mod.weight.shape)) for _, mod in named) + 3) // 4,
+                         dtype=torch.float32, device=named[0][1].weight.device)
+        q4: Dict[str, tuple] = {}
+        with torch.no_grad():
+            for name, mod in named:
+                q, sc, _ = ops.quantize_nf4(mod.weight.data.contiguous(), ws=ws)
+                mod.q4 = q4[name] = (q, sc, tuple(mod.weight.shape))
+                del mod.weight                          # quant.py:163
+        self._q4 = q4
+        self._packed, self._packed_version = {}, None
+        self._lora_ver = None
+
+    def _pack(self, check: bool = False) -> Dict[str, torch.Tensor]:
+        if self._q4 is None:
+            return super()._pack(check)
+        if self._packed_version is not None and not check:
+            return self._packed
+        ver = self._weights_version()
+        if self._packed_version != ver:              # NF4 base: the decoder matrices live only as NF4 images
+            with torch.no_grad():
+                self._packed = self._pack_vision() if self.with_visual else {}
+            self._packed_version = ver
+        return self._packed
+
+    def _q4_layer_weights(self, i: int):
+        """Wd of layer i in the reused scratch, in the row orders of ``_pack``: (wqkv, wo, w13 in 16-row blocks, w2)."""
+        a = self.args
+        H, Hkv, hd, F, dim = self.n_heads, self.n_kv_heads, self.head_dim, self.ffn, a.dim
+        shapes = (((H + 2 * Hkv) * hd, dim), (dim, H * hd), (2 * F, dim), (dim, F), (2 * F, dim))
+        buf = self._buf("q4_scratch", (sum(n * k for n, k in shapes),), torch.bfloat16)
+        views, o = [], 0
+        for n, k in shapes:
+            views.append(buf[o:o + n * k].view(n, k))
+            o += n * k
+        wqkv, wo, w13, w2, tmp = views
+        p = f"layers.{i}."
+        row = 0
+        for nm in ("wq", "wk", "wv"):
+            q, sc, (n, _) = self._q4[p + "attention." + nm]
+            ops.dequantize_nf4_images(q, sc, wd=wqkv[row:row + n])
+            row += n
+        ops.dequantize_nf4_images(*self._q4[p + "attention.wo"][:2], wd=wo)
+        ops.dequantize_nf4_images(*self._q4[p + "feed_forward.w2"][:2], wd=w2)
+        ops.dequantize_nf4_images(*self._q4[p + "feed_forward.w1"][:2], wd=tmp[:F])
+        ops.dequantize_nf4_images(*self._q4[p + "feed_forward.w3"][:2], wd=tmp[F:])
+        w13.view(F // 16, 2, 16, dim).copy_(tmp.view(2, F // 16, 16, dim).transpose(0, 1))     # data movement only (the SwiGLU row order)
+        return wqkv, wo, w13, w2
+
+    def _head_weight(self) -> torch.Tensor:
+        if self._q4 is None:
+            return super()._head_weight()
+        q, sc, (n, k) = self._q4["output"]
+        w = self._buf("q4_head", (n, k), torch.bfloat16)
+        ops.dequantize_nf4_images(q, sc, wd=w)
+        return w
+
+    def _lm_head_f32(self, xn: torch.Tensor, logits: torch.Tensor) -> None:
+        if self._q4 is None:
+            return super()._lm_head_f32(xn, logits)
+        self._linear(xn, self._head_weight(), logits, epilogue=ops.EPI_OUT_F32)
 
     def get_trainable_params(self, pretrain_stage: bool = False):
         frozen_pre = ("qformer.", "openclip_convnext_xxl.", "clip.", "dinov2_vitg14.", "tok_embeddings.", "output.")
@@ -97,12 +195,12 @@ class Transformer(base.Transformer):
             for i in range(self.n_layers):
                 for key, mods, inter in self.lora_groups(i):
                     Rp = _pad64(len(mods) * r)
-                    in_f = mods[0].weight.shape[1]
+                    in_f = base_shape(mods[0])[1]
                     A = torch.zeros(Rp, in_f, dtype=dtype, device=self._device)
                     blocks = []
                     for j, mod in enumerate(mods):
                         A[j * r:(j + 1) * r] = mod.lora_a.weight.to(dtype)
-                        Bj = torch.zeros(mod.weight.shape[0], Rp, dtype=dtype, device=self._device)
+                        Bj = torch.zeros(base_shape(mod)[0], Rp, dtype=dtype, device=self._device)
                         Bj[:, j * r:(j + 1) * r] = mod.lora_b.weight.to(dtype)
                         blocks.append(Bj)
                     if inter and interleave_w13:
@@ -144,6 +242,10 @@ class Transformer(base.Transformer):
         for i, lyr in enumerate(self.layers):
             kc, vc = k_caches[i], vt_caches[i]
             smax = kc.shape[2]
+            if self._q4 is None:
+                wqkv, wo, w13, w2 = pk[f"wqkv.{i}"], lyr.attention.wo.weight, pk[f"w13.{i}"], lyr.feed_forward.w2.weight
+            else:                              # NF4 base: the layer's Wd in a reused scratch, then the bf16 kernels unchanged
+                wqkv, wo, w13, w2 = self._q4_layer_weights(i)
             ops.rmsnorm(h, lyr.attention_norm.weight, xn, a.norm_eps)
             if rows > 16 and h.dtype == torch.bfloat16 and hd in (64, 128) and self._fuse_qkv_rope:
                 # prefill: the adapter term is written into the qkv buffer and enters the fused qkv / RoPE / cache GEMM as an
@@ -153,21 +255,21 @@ class Transformer(base.Transformer):
                 t = self._buf("lora_t", (rows, A.shape[0]))
                 self._linear(xn, A, t)
                 self._linear(t, Bm, qkv)
-                ops.gemm_qkv_rope(xn, pk[f"wqkv.{i}"], qkv, kc, vc, cs, B, S, H, Hkv, hd, start_pos, rope_pos0, delta=qkv)
+                ops.gemm_qkv_rope(xn, wqkv, qkv, kc, vc, cs, B, S, H, Hkv, hd, start_pos, rope_pos0, delta=qkv)
             else:
-                self._linear(xn, pk[f"wqkv.{i}"], qkv)
+                self._linear(xn, wqkv, qkv)
                 self._lora_add(f"qkv.{i}", xn, qkv)
                 ops.rope_kvcache(qkv, qkv, kc, vc, cs, B, S, H, Hkv, hd, start_pos, rope_pos0)
             strides = (S * ldq, ldq, hd, Hkv * smax * hd, smax * hd, hd, Hkv * hd * smax, hd * smax, smax, S * H * hd, H * hd, hd)
             ops.attention(qkv, kc, vc, att, B, S, Sk, H, Hkv, hd, strides, causal and S > 1, scratch)
             # out = wo(att) + lora (rounded), then the residual add -- the reference's order (peft.py:95, llama_ens5.py:238)
-            self._linear(att, lyr.attention.wo.weight, o)
+            self._linear(att, wo, o)
             self._lora_add(f"wo.{i}", att, o)
             ops.add2d(h, o)
             ops.rmsnorm(h, lyr.ffn_norm.weight, xn, a.norm_eps)
-            self._linear(xn, pk[f"w13.{i}"], gu)                 # un-fused SwiGLU: the adapters add before the activation
+            self._linear(xn, w13, gu)                 # un-fused SwiGLU: the adapters add before the activation
             self._lora_add(f"w13.{i}", xn, gu)
             ops.swiglu_fwd(gu, act, self.ffn, interleaved=True)
-            self._linear(act, lyr.feed_forward.w2.weight, o)
+            self._linear(act, w2, o)
             self._lora_add(f"w2.{i}", act, o)
             ops.add2d(h, o)

@@ -274,6 +274,19 @@ def dequantize_nf4(q, scales, out):
     return out
 
 
+def dequantize_nf4_images(q, scales, wd=None, wt=None):
+    """wd [N, K] and / or wt [K, N] = wd^T (bf16 views, unit column stride, any row stride) from one read of the NF4 image
+    (a3v_dequantize_nf4_images).  Only those windows are written: they may sit inside wider images."""
+    _dev(q, scales, wd, wt)
+    N, K = q.shape[0], q.shape[1] * 2
+    assert q.dtype == torch.uint8 and q.is_contiguous() and scales.dtype == torch.float32 and scales.is_contiguous() and scales.numel() == N * K // 64
+    for w, shape in ((wd, (N, K)), (wt, (K, N))):
+        assert w is None or (w.dtype == torch.bfloat16 and tuple(w.shape) == shape and w.stride(1) == 1)
+    rc = _l.load().a3v_dequantize_nf4_images(_p(q), _p(scales), N, K, _p(wd), wd.stride(0) if wd is not None else 0,
+                                             _p(wt), wt.stride(0) if wt is not None else 0, _stream())
+    _l.check(rc, f"a3v_dequantize_nf4_images(N={N},K={K})")
+
+
 def gemm_skinny_nf4(a, q, scales, out, workspace, *, residual=None, epilogue: int = 0):
     """out = epilogue(sum_b s_b * (a . NF4[q])^T): weight-only NF4 decode GEMV (M <= 16, K % 256 == 0)."""
     _dev(a, q, scales, out, workspace, residual)

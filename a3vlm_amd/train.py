@@ -100,6 +100,8 @@ class TrainEngine:
             # current in the optimizer pass (+2 B of writes per parameter; same-box 336.0 -> 328 ms per 7B step).  ZeRO-1 updates flat
             # slices (no per-matrix pass to write W^T from): the NN kernel on the forward images stays there.
             self.nn_dgrad = bool(self.zero1_world)
+        if self._q4base() and self.zero1_world:
+            raise ValueError("ZeRO-1 shards compute-dtype base matrices; an NF4 base (quantize_base_weights) has none")
         self._flat_params: Optional[torch.Tensor] = None    # zero1: the sharded parameters' storage (compute dtype, flat-gradient layout)
         self._z1: List[tuple] = []                          # zero1: (bucket, start, end, shard_start, shard_end, [(seg_start, seg_end, name)])
         self._z1_fresh = True                               # zero1: the sharded gradients restart (store / zero) at the next backward
@@ -154,6 +156,16 @@ class TrainEngine:
                 torch.cuda.current_stream().wait_event(ev)
             self._weights_ready.clear()
 
+    def _q4base(self) -> bool:
+        """The base matrices are NF4 (``llama_ens5_peft.Transformer.quantize_base_weights``): no bf16 ``weight`` exists; the GEMM images
+        of one layer at a time are dequantised into a reused scratch (``_Nf4Images``)."""
+        return getattr(self.m, "_q4", None) is not None
+
+    def weight_image_bytes(self, head: bool = True) -> int:
+        """Bytes of compute-dtype weight images the engine holds right now (decoder GEMM images and their transposes; ``head``: also
+        the LM head's).  bf16 base: grows with the layers served so far.  NF4 base: one layer's worth whatever the depth."""
+        return self._images().nbytes(head)
+
     def _kext_cols(self, key: str) -> int:
         """Width of the adapter block appended to the image / input of decoder GEMM ``key`` (0: adapters not folded in)."""
         if not self._kext() or not key.startswith(("qkv.", "wo.", "w13.", "w2.")):
@@ -166,7 +178,7 @@ class TrainEngine:
         if not self._kext() or sel in ("", "0"):
             return False
         g = key.split(".")[0]
-        frozen = not any(q.requires_grad for q in self._group_base_params(key))
+        frozen = self._q4base() or not any(q.requires_grad for q in self._group_base_params(key))
         return frozen and (sel == "all" or g in sel.split(","))
 
     def _group_base_params(self, key: str):
@@ -194,13 +206,14 @@ class TrainEngine:
         m = self.m
         items: List[Tuple[str, List[Tuple[str, torch.nn.Parameter]]]] = []
         items.append(("embed", [("tok_embeddings.weight", m.tok_embeddings.weight)]))
+        w = lambda mod: getattr(mod, "weight", None)       # None: an NF4 base matrix (frozen, no bf16 parameter)
         for i, l in enumerate(m.layers):
             p = f"layers.{i}."
             items.append((f"layer{i}", [
-                (p + "attention.wq.weight", l.attention.wq.weight), (p + "attention.wk.weight", l.attention.wk.weight),
-                (p + "attention.wv.weight", l.attention.wv.weight), (p + "attention.wo.weight", l.attention.wo.weight),
-                (p + "feed_forward.w1.weight", l.feed_forward.w1.weight), (p + "feed_forward.w3.weight", l.feed_forward.w3.weight),
-                (p + "feed_forward.w2.weight", l.feed_forward.w2.weight),
+                (p + "attention.wq.weight", w(l.attention.wq)), (p + "attention.wk.weight", w(l.attention.wk)),
+                (p + "attention.wv.weight", w(l.attention.wv)), (p + "attention.wo.weight", w(l.attention.wo)),
+                (p + "feed_forward.w1.weight", w(l.feed_forward.w1)), (p + "feed_forward.w3.weight", w(l.feed_forward.w3)),
+                (p + "feed_forward.w2.weight", w(l.feed_forward.w2)),
                 (p + "attention_norm.weight", l.attention_norm.weight), (p + "ffn_norm.weight", l.ffn_norm.weight)]))
             if self.lora:
                 # group-major: the lora_a of the modules that share an input are adjacent ([n r, in] as one matrix: the group's dA
@@ -213,7 +226,7 @@ class TrainEngine:
                         items[-1][1].append((p + sub + ".lora_a.weight", mod.lora_a.weight))
                     for sub, mod in group:
                         items[-1][1].append((p + sub + ".lora_b.weight", mod.lora_b.weight))
-        items.append(("head", [("norm.weight", m.norm.weight), ("output.weight", m.output.weight)]))
+        items.append(("head", [("norm.weight", m.norm.weight), ("output.weight", w(m.output))]))
         if m.with_visual:
             vp0, vp1 = getattr(m.visual_proj, "0"), getattr(m.visual_proj, "1")
             vis = [("visual_proj.0.weight", vp0.weight), ("visual_proj.0.bias", vp0.bias),
@@ -227,7 +240,7 @@ class TrainEngine:
                         ("qformer_proj.1.weight", q1.weight), ("qformer_proj.1.bias", q1.bias)]
             items.append(("vision_proj", vis))
         # frozen parameters get no gradient storage (LoRA / partial fine-tuning)
-        lay = [(b, [(n, q) for n, q in plist if q.requires_grad]) for b, plist in items]
+        lay = [(b, [(n, q) for n, q in plist if q is not None and q.requires_grad]) for b, plist in items]
         if self.zero1_world:           # sharded (compute-dtype) parameters first in every bucket: one contiguous span per bucket (stable order)
             lay = [(b, [it for it in pl if it[1].dtype != torch.float32] + [it for it in pl if it[1].dtype == torch.float32]) for b, pl in lay]
         return lay
@@ -385,7 +398,7 @@ class TrainEngine:
         is (re)built on first use after its parameters changed.  (Issuing the AdamW update per layer on a side stream under the
         next forward was tried on top of this and measured no gain: the 256x256 GEMM leaves no VGPRs for a co-resident kernel.)"""
         if self._img is None or not isinstance(self._img, _Images):
-            self._img = _Images(self)
+            self._img = _Nf4Images(self) if self._q4base() else _Images(self)
         return self._img
 
     # ------------------------------------------------------------------ GEMM helpers
@@ -534,7 +547,9 @@ class TrainEngine:
                 vp = v
             ops.transpose(vp, vt, _pad64(R), C, _pad64(R))
             li[k + "t"] = vt
-        if self._kext():
+        if self._kext() and not self._q4base():
+            # (NF4 base: every layer's images share one scratch, so the adapter blocks stay these persistent tensors -- the optimizer
+            # sinks and a3v_lora_refresh write them -- and _Nf4Images copies them into the scratch tails of the layer it serves)
             im = self._images()
             for i in range(m.n_layers):
                 for key, _, _ in m.lora_groups(i):
@@ -775,6 +790,8 @@ class TrainEngine:
         rows = B * S
         l = m.layers[i]
         pre = f"layers.{i}."
+        if not self._saved.get("kept"):
+            im.recompute_backward(i)     # (NF4 base: the block's forward and input-gradient images from one read of its codes)
         k = self._saved["kept"][i] if self._saved.get("kept") else self._block_forward(i, h_in, B, S, keep=True)
         # ---- FFN: out = h_mid + w2(silu(g) * u)
         lt = k.get("lt", {})
@@ -973,7 +990,7 @@ class TrainEngine:
             # with the transposed images against 455.5 / 452.4 without, for 24 GiB: not taken there unless A3V_NN_DGRAD=0 asks for it)
             if free - need < 8 * 2 ** 30 or (self.recompute and "A3V_NN_DGRAD" not in os.environ):
                 self.nn_dgrad = True
-        if self.lora and not getattr(self, "_nt_mem_checked", False):
+        if self.lora and not self._q4base() and not getattr(self, "_nt_mem_checked", False):
             # LoRA engines: the input gradients of the frozen matrices run on the NT kernel over transposed images that
             # are built once (2 B per base parameter: 12.3 GiB at 7B) and, with nn_dgrad off, the head's W^T too -- the same headroom
             # rule as the full fine-tune above: without 8 GiB left after them the NN kernel on the forward images is used instead
@@ -1246,6 +1263,18 @@ class _Images:
                     if self.tver.get(key + ".t") == old and all(id(q) in written_t_ids for q, (k, _) in zip(ps, where) if k == key):
                         self.tver[key + ".t"] = self.ver[g]
 
+    def recompute_backward(self, i: int) -> None:
+        """Layer i is about to be recomputed and back-propagated (persistent images: nothing to prepare)."""
+
+    def nbytes(self, head: bool = True) -> int:
+        seen = {}
+        for k, t in self.store.items():
+            g = self._group(k)
+            if g.startswith("L") or (head and g == "out"):
+                st = t.untyped_storage()
+                seen[st.data_ptr()] = st.nbytes()
+        return sum(seen.values())
+
     def __getitem__(self, key: str) -> torch.Tensor:
         eng, m = self.eng, self.eng.m
         g = self._group(key)
@@ -1272,6 +1301,132 @@ class _Images:
         if key.endswith(".t"):
             return self._transposed(key, ver)
         return self.store[key]
+
+
+class _Nf4Images(_Images):
+    """The same keys over an NF4 base (QLoRA): ``qkv.i`` / ``wo.i`` / ``w13.i`` / ``w2.i`` (+ ``.x`` ``.y`` ``.yT`` ``.t``) are views of ONE
+    scratch per group kind, shared by all layers and shaped exactly like the persistent images of the bf16 engine (so the GEMMs run
+    the same plans on the same bits); ``out`` / ``out.t`` have a scratch of their own, filled once.  A request for another layer than the
+    resident one drops the kind's contents; an orientation is filled on first request by a3v_dequantize_nf4_images (one call per original
+    module, into its row / column window).  In the backward of a recomputed block the forward image and the transposed one are both
+    needed: ``recompute_backward`` fills them by ONE call.  The dequantiser writes only the N x K window, so the adapter blocks in the tails survive a
+    fill; they are copied there from the engine's persistent per-layer A / B / A^T images when the layer or the adapter version changed.
+    The projector images (group ``vp``) are the parent's."""
+
+    _MODS = {"qkv": ("attention.wq", "attention.wk", "attention.wv"), "wo": ("attention.wo",),
+             "w13": ("feed_forward.w1", "feed_forward.w3"), "w2": ("feed_forward.w2",)}
+    _TARGET = {"": "d", "x": "d", "y": "d", "yT": "yT", "t": "t"}
+
+    def __init__(self, eng: "TrainEngine"):
+        super().__init__(eng)
+        assert eng.act == torch.bfloat16, "an NF4 base trains under --precision bf16 (the dequantised images are bf16)"
+        self.kinds: Dict[str, dict] = {}
+
+    def groups(self):                         # the parameter-backed groups (optimizer sinks, adoption): the projector only
+        return ["vp"] if getattr(self.eng.m, "visual_proj", None) is not None else []
+
+    def nbytes(self, head: bool = True) -> int:
+        return sum(t.untyped_storage().nbytes() for kind, st in self.kinds.items() if head or kind != "out" for t in st["buf"].values())
+
+    def _entries(self, kind: str, i: int):
+        q4 = self.eng.m._q4
+        return [q4["output"]] if kind == "out" else [q4[f"layers.{i}.{nm}"] for nm in self._MODS[kind]]
+
+    def _state(self, kind: str) -> dict:
+        st = self.kinds.get(kind)
+        if st is None:
+            ent = self._entries(kind, 0)
+            st = self.kinds[kind] = dict(N=sum(e[2][0] for e in ent), K=ent[0][2][1], ext=self.eng._kext_cols(kind + ".0"), layer=None,
+                                         valid=set(), tails={}, buf={})
+        return st
+
+    def _buffer(self, st: dict, target: str) -> torch.Tensor:
+        b = st["buf"].get(target)
+        if b is None:
+            N, K, ext = st["N"], st["K"], st["ext"]
+            dev = self.eng.m._device
+            if target == "d":                 # [[W, B], [A, 0]] (or plain W): zero once, the corner and the pads are never written again
+                b = torch.zeros(N + ext, K + ext, dtype=torch.bfloat16, device=dev)
+            elif target == "yT":              # [W^T | A^T]
+                b = torch.zeros(K, N + ext, dtype=torch.bfloat16, device=dev)
+            else:                             # W^T [K, N padded to 64], row pitch as _Images._transposed
+                Np = _pad64(N)
+                ld = Np + 64 if (Np * 2) % 4096 == 0 else Np
+                b = torch.zeros(K, ld, dtype=torch.bfloat16, device=dev)[:, :Np]
+            st["buf"][target] = b
+        return b
+
+    def _fill(self, kind: str, i: int, st: dict, targets) -> None:
+        wd = self._buffer(st, "d") if "d" in targets else None
+        for tt in [t for t in ("yT", "t") if t in targets] or [None]:
+            wt = self._buffer(st, tt) if tt is not None else None
+            row = 0
+            for q, sc, (n, k) in self._entries(kind, i):
+                assert row % 8 == 0, "module rows must keep the 16-B alignment of the transposed window"
+                ops.dequantize_nf4_images(q, sc, wd=None if wd is None else wd[row:row + n, :k],
+                                          wt=None if wt is None else wt[:, row:row + n])
+                row += n
+            wd = None                          # (a second transposed target re-reads the codes; the forward image is written once)
+        st["valid"] |= set(targets)
+
+    def recompute_backward(self, i: int) -> None:
+        """The backward of a recomputed block reads the forward image of each of its GEMMs, then the image of its input gradient:
+        both orientations from one read of the codes.  (Only a saving: an orientation this misses is filled on its first request.)"""
+        eng = self.eng
+        with torch.no_grad():
+            for kind in self._MODS:
+                st = self._state(kind)
+                if st["layer"] != i:
+                    st["layer"], st["valid"], st["tails"] = i, set(), {}
+                if st["ext"]:
+                    bwd = "yT" if eng._nt_dgrad(f"{kind}.{i}") else "d"
+                else:
+                    bwd = "d" if eng.nn_dgrad else "t"
+                need = {"d", bwd} - st["valid"]
+                if need:
+                    self._fill(kind, i, st, need)
+
+    def _place_tails(self, kind: str, i: int, st: dict, target: str) -> None:
+        eng = self.eng
+        li = eng._lora_step_images()
+        ver = eng._li_ver
+        # identity on purpose: _lora_step_images / adapters_adopted bind a NEW tuple to _li_ver whenever the adapters changed and keep
+        # the same object otherwise; a miss only copies the blocks again
+        if st["tails"].get(target) is ver:
+            return
+        N, K, ext = st["N"], st["K"], st["ext"]
+        key = f"{kind}.{i}"
+        if target == "d":
+            full = st["buf"]["d"]
+            full[:N, K:].copy_(li[key + ".B"])
+            full[N:, :K].copy_(li[key + ".A"])
+        else:
+            st["buf"]["yT"][:, N:].copy_(li[key + ".At"][:K])
+        st["tails"][target] = ver
+
+    def __getitem__(self, key: str) -> torch.Tensor:
+        if self._group(key) == "vp":
+            return super().__getitem__(key)
+        parts = key.split(".")
+        if parts[0] == "out":
+            kind, i, suffix = "out", 0, ".".join(parts[1:])
+        else:
+            kind, i, suffix = parts[0], int(parts[1]), ".".join(parts[2:])
+        target = self._TARGET[suffix]
+        eng = self.eng
+        st = self._state(kind)
+        with torch.no_grad():
+            if st["layer"] != i:
+                st["layer"], st["valid"], st["tails"] = i, set(), {}
+            if target not in st["valid"]:
+                self._fill(kind, i, st, {target})
+            if st["ext"] and target in ("d", "yT"):
+                self._place_tails(kind, i, st, target)
+        b = st["buf"][target]
+        N, K = st["N"], st["K"]
+        if target != "d":
+            return b
+        return {"": b[:N, :K], "x": b[:N], "y": b[:, :K]}[suffix]
 
 
 class _StepLoss(torch.autograd.Function):

@@ -220,6 +220,12 @@ int a3v_quantize_nf4(const void* W, int N, int K, void* q, float* scales, float*
 /* Wd [N, K] bf16 (row stride ldd elements, ldd % 8 == 0) = bf16(NF4[q] * s_b): the multi-token forward of an NF4 model runs the bf16
  * GEMMs on it (bit-identical to the bf16 model holding Wd). */
 int a3v_dequantize_nf4(const void* q, const float* scales, void* Wd, int64_t ldd, int N, int K, void* stream);
+/* The same values in either orientation from ONE read of the codes and scales (the QLoRA training step: the per-layer GEMM images of
+ * an NF4 base).  Wd [N, K] at row stride ldd and / or Wt [K, N] = Wd^T at row stride ldt (elements); either may be NULL, both NULL is
+ * A3V_ERR_ARG.  Wd is bit-equal to a3v_dequantize_nf4.  ONLY the N x K / K x N windows are written: the destinations are windows of
+ * larger images (ldd > K, ldt > N) whose tail columns hold adapter blocks.  K % 64 == 0, ldd % 8 == 0, ldt % 8 == 0, q / Wd / Wt 16-B
+ * aligned (A3V_ERR_SHAPE before any launch otherwise); N is arbitrary. */
+int a3v_dequantize_nf4_images(const void* q, const float* scales, int N, int K, void* Wd, int64_t ldd, void* Wt, int64_t ldt, void* stream);
 /* Weight-only NF4 decode GEMV, M <= 16, K % 256 == 0: q [N, K/2] (row stride ldw BYTES), scales [N, K/64]; workspace and epilogues
  * (NONE, RESIDUAL, SWIGLU, OUT_F32) as a3v_gemm_skinny; SWIGLU needs K >= 512 (A3V_ERR_SHAPE otherwise, as the fp8 form).  The codes enter the MFMA as bf16 and each 64-k block sum is scaled by s_b in
  * fp32, so results differ from the bf16 GEMV on Wd by rounding only. */
