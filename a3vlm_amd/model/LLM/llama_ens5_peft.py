@@ -24,6 +24,7 @@ import torch.nn as nn
 
 from ... import ops
 from ... import lib as _lib
+from ...train_images import GROUPS, group_modules
 from . import llama_ens5 as base
 from .llama_ens5 import _W
 
@@ -177,9 +178,7 @@ class Transformer(base.Transformer):
     # ------------------------------------------------------------------ fused adapter images
     def lora_groups(self, i: int):
         """(key, [modules sharing the input], interleave16) for layer i, in the row order of the fused base GEMMs."""
-        a, f = self.layers[i].attention, self.layers[i].feed_forward
-        return [(f"qkv.{i}", [a.wq, a.wk, a.wv], False), (f"wo.{i}", [a.wo], False),
-                (f"w13.{i}", [f.w1, f.w3], True), (f"w2.{i}", [f.w2], False)]
+        return [(f"{kind}.{i}", group_modules(self.layers[i], kind), kind == "w13") for kind in GROUPS]
 
     def lora_images(self, dtype: Optional[torch.dtype] = None, interleave_w13: bool = True) -> Dict[str, torch.Tensor]:
         """Per group: ``A`` [Rp, in] (stacked lora_a, zero rows up to Rp = pad64(n*r)) and ``B`` [N, Rp] (block-diagonal

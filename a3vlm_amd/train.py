@@ -19,11 +19,8 @@ from typing import Callable, Dict, List, Optional, Tuple
 import torch
 
 from . import ops
-from .util import install_param_epoch_hook, optimizer_steps, param_state_key
-
-
-def _pad64(n: int) -> int:
-    return (n + 63) // 64 * 64
+from .train_images import GROUPS, _AdapterImages, _Images, _Nf4Images, _pad64, group_modules
+from .util import install_param_epoch_hook
 
 
 def skinny_slices(M: int, N: int, K: int, cus: int) -> int:
@@ -105,6 +102,14 @@ class TrainEngine:
         self._flat_params: Optional[torch.Tensor] = None    # zero1: the sharded parameters' storage (compute dtype, flat-gradient layout)
         self._z1: List[tuple] = []                          # zero1: (bucket, start, end, shard_start, shard_end, [(seg_start, seg_end, name)])
         self._z1_fresh = True                               # zero1: the sharded gradients restart (store / zero) at the next backward
+        self._params: Dict[str, torch.nn.Parameter] = {}    # name -> parameter with gradient storage (ensure_grads)
+        self._offs: Dict[str, Tuple[int, int]] = {}         # name -> (offset, padded length) in the flat gradient buffer
+        self._adapters = _AdapterImages(self)               # LoRA: the adapter images and their validation state
+        self._cu_count: Optional[int] = None                # compute units of the device (_skinny)
+        self._nt_mem_checked = False                        # the transposed images' HBM headroom was checked (first backward)
+        self._opt_stepped = False                           # an optimizer step has happened (its moments are allocated)
+        self._dha_ready = False                             # fp32 stream: the last norm backward left the bf16 copy of dh in place
+        self._dh_full: Optional[torch.Tensor] = None        # bf16 stream + K-ext: [dh | room for dt], see backward
 
     # ------------------------------------------------------------------ buffers
     def _buf(self, name, shape, dtype=None, zero=False):
@@ -168,24 +173,16 @@ class TrainEngine:
 
     def _kext_cols(self, key: str) -> int:
         """Width of the adapter block appended to the image / input of decoder GEMM ``key`` (0: adapters not folded in)."""
-        if not self._kext() or not key.startswith(("qkv.", "wo.", "w13.", "w2.")):
-            return 0
-        n = {"qkv": 3, "wo": 1, "w13": 2, "w2": 1}[key.split(".")[0]]
-        return _pad64(n * int(self.m.lora_rank))
+        kind = key.split(".")[0]
+        return _pad64(len(GROUPS[kind]) * int(self.m.lora_rank)) if self._kext() and kind in GROUPS else 0
 
     def _nt_dgrad(self, key: str) -> bool:
         sel = self.lora_nt_dgrad
         if not self._kext() or sel in ("", "0"):
             return False
-        g = key.split(".")[0]
-        frozen = self._q4base() or not any(q.requires_grad for q in self._group_base_params(key))
+        g, i = key.split(".")[:2]
+        frozen = self._q4base() or not any(mod.weight.requires_grad for mod in group_modules(self.m.layers[int(i)], g))
         return frozen and (sel == "all" or g in sel.split(","))
-
-    def _group_base_params(self, key: str):
-        g, i = key.split(".")[0], int(key.split(".")[1])
-        a, f = self.m.layers[i].attention, self.m.layers[i].feed_forward
-        return {"qkv": (a.wq.weight, a.wk.weight, a.wv.weight), "wo": (a.wo.weight,), "w13": (f.w1.weight, f.w3.weight),
-                "w2": (f.w2.weight,)}[g]
 
     def _kext(self) -> int:
         """Columns appended to the inputs / weight images of the four decoder GEMMs when the adapters ride inside them
@@ -193,6 +190,14 @@ class TrainEngine:
         if not (self.lora and self.lora_kext and self.act == torch.bfloat16):
             return 0
         return _pad64(3 * int(self.m.lora_rank))          # the widest group (wq|wk|wv) sets one width for all four
+
+    def _kx(self, rows: int) -> bool:
+        """This step runs the adapters inside the decoder GEMMs (K-ext): only together with the fused qkv + RoPE GEMM."""
+        return self._kext() > 0 and rows > 16 and self.m.head_dim in (64, 128) and self.fuse_qkv_rope
+
+    def _res_epi(self, out: torch.Tensor) -> int:
+        """Epilogue flag of a residual add into ``out``: fp32 residual / output beside bf16 operands, else the plain one."""
+        return ops.EPI_RES_F32 if out.dtype == torch.float32 and self.act == torch.bfloat16 else 0
 
     def _check_dtypes(self):
         for n, p in self.m.get_trainable_params().items():
@@ -209,23 +214,14 @@ class TrainEngine:
         w = lambda mod: getattr(mod, "weight", None)       # None: an NF4 base matrix (frozen, no bf16 parameter)
         for i, l in enumerate(m.layers):
             p = f"layers.{i}."
-            items.append((f"layer{i}", [
-                (p + "attention.wq.weight", w(l.attention.wq)), (p + "attention.wk.weight", w(l.attention.wk)),
-                (p + "attention.wv.weight", w(l.attention.wv)), (p + "attention.wo.weight", w(l.attention.wo)),
-                (p + "feed_forward.w1.weight", w(l.feed_forward.w1)), (p + "feed_forward.w3.weight", w(l.feed_forward.w3)),
-                (p + "feed_forward.w2.weight", w(l.feed_forward.w2)),
-                (p + "attention_norm.weight", l.attention_norm.weight), (p + "ffn_norm.weight", l.ffn_norm.weight)]))
+            groups = [list(zip(GROUPS[kind], group_modules(l, kind))) for kind in GROUPS]
+            items.append((f"layer{i}", [(p + sub + ".weight", w(mod)) for group in groups for sub, mod in group]
+                          + [(p + "attention_norm.weight", l.attention_norm.weight), (p + "ffn_norm.weight", l.ffn_norm.weight)]))
             if self.lora:
                 # group-major: the lora_a of the modules that share an input are adjacent ([n r, in] as one matrix: the group's dA
                 # GEMM writes the gradients in place), then their lora_b
-                for group in ((("attention.wq", l.attention.wq), ("attention.wk", l.attention.wk), ("attention.wv", l.attention.wv)),
-                              (("attention.wo", l.attention.wo),),
-                              (("feed_forward.w1", l.feed_forward.w1), ("feed_forward.w3", l.feed_forward.w3)),
-                              (("feed_forward.w2", l.feed_forward.w2),)):
-                    for sub, mod in group:
-                        items[-1][1].append((p + sub + ".lora_a.weight", mod.lora_a.weight))
-                    for sub, mod in group:
-                        items[-1][1].append((p + sub + ".lora_b.weight", mod.lora_b.weight))
+                for group in groups:
+                    items[-1][1].extend((f"{p}{sub}.{ab}.weight", getattr(mod, ab).weight) for ab in ("lora_a", "lora_b") for sub, mod in group)
         items.append(("head", [("norm.weight", m.norm.weight), ("output.weight", w(m.output))]))
         if m.with_visual:
             vp0, vp1 = getattr(m.visual_proj, "0"), getattr(m.visual_proj, "1")
@@ -253,14 +249,15 @@ class TrainEngine:
             offs = {}
             self._ranges = []
             zw = self.zero1_world
+            granule = lambda n: (n + 64 * zw - 1) // (64 * zw) * (64 * zw)              # noqa: E731  (ZeRO-1: up to whole 64 N granules)
             for bucket, plist in self._layout():
                 if zw:
-                    total = (total + 64 * zw - 1) // (64 * zw) * (64 * zw)              # a bucket's sharded span starts on a 64 N granule
+                    total = granule(total)                                              # a bucket's sharded span starts on a 64 N granule
                 start = total
                 segs = []
                 for name, p in plist:
                     if zw and p.dtype == torch.float32 and segs and segs[-1] is not None:
-                        total = (total + 64 * zw - 1) // (64 * zw) * (64 * zw)          # end of the bucket's sharded span: whole 64 N granules
+                        total = granule(total)                                          # end of the bucket's sharded span: whole 64 N granules
                         self._z1.append((bucket, segs))
                         segs = [None]                                                   # (closed)
                     offs[name] = (total, p)
@@ -268,7 +265,7 @@ class TrainEngine:
                         segs.append((total, total + p.numel(), name))
                     total += (p.numel() + 63) // 64 * 64
                 if zw and segs and segs[-1] is not None:
-                    total = (total + 64 * zw - 1) // (64 * zw) * (64 * zw)
+                    total = granule(total)
                     self._z1.append((bucket, segs))
                 self._ranges.append((bucket, start, total))
             self._flat = torch.zeros(total, dtype=torch.float32, device=m._device)
@@ -276,8 +273,8 @@ class TrainEngine:
                 self._views[name] = self._flat[o:o + p.numel()].view(p.shape)
             self._params = {name: p for name, (o, p) in offs.items()}
             self._offs = {name: (o, (p.numel() + 63) // 64 * 64) for name, (o, p) in offs.items()}
-            self._gemm_written = {n for n in self._params if n == "output.weight" or (n.startswith("layers.") and n.endswith(
-                ("wq.weight", "wk.weight", "wv.weight", "wo.weight", "w1.weight", "w2.weight", "w3.weight")) and "lora_" not in n)}
+            base = {sub + ".weight" for subs in GROUPS.values() for sub in subs}
+            self._gemm_written = {n for n in self._params if n == "output.weight" or (n.startswith("layers.") and n.split(".", 2)[2] in base)}
             if zw:
                 # the sharded parameters move into ONE flat buffer in the compute dtype with the gradient buffer's layout (their old
                 # storage is released): reduce-scatter / all-gather address it by the same flat ranges as the gradients
@@ -286,7 +283,7 @@ class TrainEngine:
                 for bucket, segs in self._z1:
                     segs = [x for x in segs if x is not None]
                     ss = segs[0][0]
-                    se = (segs[-1][1] + 64 * zw - 1) // (64 * zw) * (64 * zw)
+                    se = granule(segs[-1][1])
                     assert (se - ss) % (64 * zw) == 0 and se <= rng[bucket][1], (bucket, ss, se, rng[bucket])
                     z1.append((bucket, rng[bucket][0], rng[bucket][1], ss, se, segs))
                 self._z1 = z1
@@ -301,6 +298,15 @@ class TrainEngine:
                 if hasattr(m, "invalidate_packed_weights"):
                     m.invalidate_packed_weights()
         runs = []                     # [start, end) float ranges of the flat buffer to zero, adjacent ones merged (one fill per run)
+
+        def add_run(name):            # this gradient restarts: stored by its first wgrad GEMM of the step, else zeroed here
+            if name in self._gemm_written:
+                return self._fresh.add(name)
+            o, n = self._offs[name]
+            if runs and runs[-1][1] == o:
+                runs[-1][1] = o + n
+            else:
+                runs.append([o, o + n])
         for name, p in self._params.items():
             if not p.requires_grad:
                 if p.grad is not None and p.grad.data_ptr() == self._views[name].data_ptr():
@@ -311,26 +317,12 @@ class TrainEngine:
                 # a sharded parameter: its gradient lives in the flat buffer only (torch refuses an fp32 .grad on a bf16 tensor); it
                 # restarts after every Zero1Optimizer.step (zero1_mark_fresh)
                 if self._z1_fresh:
-                    if name in self._gemm_written:
-                        self._fresh.add(name)
-                    else:
-                        o, n = self._offs[name]
-                        if runs and runs[-1][1] == o:
-                            runs[-1][1] = o + n
-                        else:
-                            runs.append([o, o + n])
+                    add_run(name)
                 continue
             if p.grad is None:
                 # big decoder / head matrices are written (not accumulated) by their first weight-gradient GEMM of the
                 # step: no 27 GB zero-fill and no read of the old value.  Everything else is zeroed here.
-                if name in self._gemm_written:
-                    self._fresh.add(name)
-                else:
-                    o, n = self._offs[name]
-                    if runs and runs[-1][1] == o:
-                        runs[-1][1] = o + n
-                    else:
-                        runs.append([o, o + n])
+                add_run(name)
                 p.grad = v
             elif p.grad.data_ptr() != v.data_ptr():
                 raise RuntimeError(f"{name}.grad was replaced by a foreign tensor; use zero_grad(set_to_none=True) or keep the views")
@@ -408,11 +400,11 @@ class TrainEngine:
         K = x.shape[1]
         fresh = store or (bool(names) and all(n in self._fresh for n in names))
         assert fresh or not any(n in self._fresh for n in names), "partially fresh fused gradient view"
+        self._fresh.difference_update(names if fresh else ())
         tn_ok = (self.tn_wgrad and self.act == torch.bfloat16 and N % 8 == 0 and K % 4 == 0 and dy.stride(0) % 8 == 0
                  and x.stride(0) % 8 == 0 and 2 * M * max(dy.stride(0), x.stride(0)) < 2 ** 31)
         if tn_ok and min(N, K) >= 256:
             # both operands as they are (token-major): the TN kernel transposes fragments on the LDS read
-            self._fresh.difference_update(names if fresh else ())
             sink = self.sumsq_sink            # dp.GradSquareSums (one rank): the clip's sum of squares comes out of this GEMM's epilogue
             sq = sink.wgrad_slots(grad, N, K) if sink is not None and grad.is_contiguous() else None
             ops.gemm_tn(dy, x, grad, residual=None if fresh else grad, epilogue=ops.EPI_OUT_F32 if fresh else ops.EPI_RES_F32, sumsq=sq)
@@ -423,7 +415,6 @@ class TrainEngine:
             # grid holds ~2 blocks per CU: fewer slices = less reduce work, tools/lora_skinny_bench.py)
             tiles = (K + 127) // 128
             S = max(1, min(64, (M + 63) // 64, -(-512 // tiles)))
-            self._fresh.difference_update(names if fresh else ())
             ops.gemm_tn_strip(dy, x, grad, self._buf("splitk", (S * N * K,), torch.float32), S, accumulate=not fresh)
             return
         if tn_ok and min(N, K) <= 64 and max(N, K) >= 256:
@@ -432,7 +423,6 @@ class TrainEngine:
             S = 1
             while blocks * S < 256 and S < 16 and 2 * S <= (M + 63) // 64:
                 S *= 2
-            self._fresh.difference_update(names if fresh else ())
             ops.gemm_tn_splitk(dy, x, grad, self._buf("splitk", (S * N * K,), torch.float32), S, accumulate=not fresh)
             return
         Mp = _pad64(M)
@@ -440,17 +430,11 @@ class TrainEngine:
         xt = self._buf("wg_xt" + tag, (K, Mp))
         ops.transpose(dy, dyt, M, N, Mp)
         ops.transpose(x, xt, M, K, Mp)
-        if fresh:
-            self._fresh.difference_update(names)
-            if min(N, K) <= 64:
-                self._skinny(dyt, xt, grad)
-            else:
-                ops.gemm_nt(dyt, xt, grad, epilogue=ops.EPI_OUT_F32 if self.act == torch.bfloat16 else 0)
+        if min(N, K) <= 64:
+            self._skinny(dyt, xt, grad, accumulate=not fresh)
         else:
-            if min(N, K) <= 64:
-                self._skinny(dyt, xt, grad, accumulate=True)
-            else:
-                ops.gemm_nt(dyt, xt, grad, residual=grad, epilogue=ops.EPI_RES_F32 if self.act == torch.bfloat16 else 0)
+            ops.gemm_nt(dyt, xt, grad, residual=None if fresh else grad,
+                        epilogue=(ops.EPI_OUT_F32 if fresh else ops.EPI_RES_F32) if self.act == torch.bfloat16 else 0)
 
     def _skinny(self, a: torch.Tensor, w: torch.Tensor, out: torch.Tensor, accumulate: bool = False):
         """out (+)= a @ w.T for adapter-sized problems (M or N <= 64, long K): split-K planes of the 128x128 kernel + one
@@ -459,17 +443,15 @@ class TrainEngine:
         N = w.shape[0]
         S = skinny_slices(M, N, K, self._cus(a.device) if a.is_cuda else 0)
         if S == 1 or self.act != torch.bfloat16 or K % 64:
-            f32 = out.dtype == torch.float32 and self.act == torch.bfloat16
             ops.gemm_nt(a, w, out, residual=out if accumulate else None,
-                        epilogue=(ops.EPI_RES_F32 if accumulate else ops.EPI_OUT_F32) if f32 else 0)
+                        epilogue=(ops.EPI_RES_F32 if accumulate else ops.EPI_OUT_F32) if self._res_epi(out) else 0)
             return
         ops.gemm_nt_splitk(a, w, out, self._buf("splitk", (S * M * N,), torch.float32), S, accumulate)
 
     def _cus(self, dev) -> int:
-        n = getattr(self, "_cu_count", None)
-        if n is None:
-            n = self._cu_count = int(torch.cuda.get_device_properties(dev).multi_processor_count)
-        return n
+        if self._cu_count is None:
+            self._cu_count = int(torch.cuda.get_device_properties(dev).multi_processor_count)
+        return self._cu_count
 
     def _dgrad_w(self, dy: torch.Tensor, key: str, out: torch.Tensor):
         """out[M,K] = dy[M,N] @ W[N,K] for the weight image ``key``: the NN kernel on the forward image itself (the transposed
@@ -499,130 +481,75 @@ class TrainEngine:
 
     # ------------------------------------------------------------------ LoRA adapters (model/peft.py semantics)
     def _lora_step_images(self):
-        """A [Rp,in], B [N,Rp] (+ transposes for the backward GEMMs) of every adapter group in the compute dtype.  Built once;
-        after an optimizer step only the r rows / columns each adapter owns are re-written in place (one a3v_lora_refresh
-        launch per adapter) -- rebuilding the padded / block-diagonal images from scratch was ~2500 small launches per step."""
-        m = self.m
-        if getattr(self, "_li_checked", False) and self._li_steps == optimizer_steps():
-            return self._li                                # validated for this forward / backward (flag reset at their entry), no step since
-        self._li_steps = optimizer_steps()
-        if getattr(self, "_lora_plist", None) is None:
-            self._lora_plist = [q for n, q in m.named_parameters() if "lora_" in n]
-        ver = tuple(param_state_key(q) for q in self._lora_plist)
-        if getattr(self, "_li_ver", None) == ver:
-            self._li_checked = True
-            return self._li
-        li = getattr(self, "_li", None)
-        if li is not None and getattr(self, "_li_act", None) == self.act:
-            r = m.lora_rank
-            with torch.no_grad():
-                for i in range(m.n_layers):
-                    for key, mods, _ in m.lora_groups(i):
-                        A, Bm, At, Bt = li[key + ".A"], li[key + ".B"], li[key + ".At"], li[key + ".Bt"]
-                        row = 0
-                        for j, mod in enumerate(mods):
-                            wa, wb = mod.lora_a.weight, mod.lora_b.weight          # [r, in], [N_j, r]
-                            nj = wb.shape[0]
-                            if self.act == torch.bfloat16 and wa.dtype == torch.float32 and wa.is_contiguous() and wb.is_contiguous():
-                                ops.lora_refresh(wa, wb, A, At, Bm, Bt, j * r, row)
-                            else:
-                                A[j * r:(j + 1) * r].copy_(wa)
-                                At[:wa.shape[1], j * r:(j + 1) * r].copy_(wa.t())
-                                Bm[row:row + nj, j * r:(j + 1) * r].copy_(wb)
-                                Bt[j * r:(j + 1) * r, row:row + nj].copy_(wb.t())
-                            row += nj
-            self._li_ver = ver
-            self._li_checked = True
-            return li
-        src = m.lora_images(dtype=self.act, interleave_w13=False)
-        li = {}
-        for k, v in src.items():
-            li[k] = v.clone()              # the engine's own copies (updated in place from now on)
-            R, C = v.shape
-            vt = torch.empty(C, _pad64(R), dtype=v.dtype, device=v.device)
-            if _pad64(R) != R:
-                vp = torch.zeros(_pad64(R), C, dtype=v.dtype, device=v.device)
-                vp[:R] = v
-            else:
-                vp = v
-            ops.transpose(vp, vt, _pad64(R), C, _pad64(R))
-            li[k + "t"] = vt
-        if self._kext() and not self._q4base():
-            # (NF4 base: every layer's images share one scratch, so the adapter blocks stay these persistent tensors -- the optimizer
-            # sinks and a3v_lora_refresh write them -- and _Nf4Images copies them into the scratch tails of the layer it serves)
-            im = self._images()
-            for i in range(m.n_layers):
-                for key, _, _ in m.lora_groups(i):
-                    fx, fy = im[key + ".x"], im[key + ".y"]   # [N, K + Rp] = [W | B],  [N + Rp, K] = [W ; A]
-                    Rp = li[key + ".A"].shape[0]
-                    blk = fx[:, fx.shape[1] - Rp:]
-                    blk.copy_(li[key + ".B"])
-                    li[key + ".B"] = blk                        # refreshed in place from now on (row stride K + Rp)
-                    rows_a = fy[fy.shape[0] - Rp:]
-                    rows_a.copy_(li[key + ".A"])
-                    li[key + ".A"] = rows_a
-                    if self._nt_dgrad(key):
-                        ft = im[key + ".yT"]                      # [K, N + Rp]: the A^T block lives in its tail columns
-                        cols_at = ft[:, ft.shape[1] - Rp:]
-                        cols_at.copy_(li[key + ".At"][:cols_at.shape[0]])
-                        li[key + ".At"] = cols_at
-        self._li, self._li_ver, self._li_act = li, ver, self.act
-        self._li_checked = True
-        self._adapter_sinks = None
-        return li
+        return self._adapters.images()
 
     def adapter_sink(self, p: torch.Tensor):
-        """For ``FusedAdamW``'s multi-tensor launch: where the bf16 value of element (i, j) of adapter parameter ``p`` lives inside
-        the fused group images, as (d1, s1r, s1c, d2, s2r, s2c) in element strides -- lora_a [r, in]: its rows of A and its columns
-        of A^T; lora_b [n_j, r]: its columns of B and its rows of B^T.  None when ``p`` is not an adapter or the images are not
-        built yet (first step: a3v_lora_refresh does it)."""
-        li = getattr(self, "_li", None)
-        if li is None or self.act != torch.bfloat16 or getattr(self, "_li_act", None) != self.act:
-            return None
-        sinks = getattr(self, "_adapter_sinks", None)
-        if sinks is None:
-            sinks = {}
-            r = self.m.lora_rank
-            for i in range(self.m.n_layers):
-                for key, mods, _ in self.m.lora_groups(i):
-                    A, Bm, At, Bt = li[key + ".A"], li[key + ".B"], li[key + ".At"], li[key + ".Bt"]
-                    row = 0
-                    for j, mod in enumerate(mods):
-                        wa, wb = mod.lora_a.weight, mod.lora_b.weight
-                        sinks[id(wa)] = (A.data_ptr() + 2 * (j * r) * A.stride(0), A.stride(0), 1,
-                                         At.data_ptr() + 2 * (j * r), 1, At.stride(0))
-                        sinks[id(wb)] = (Bm.data_ptr() + 2 * (row * Bm.stride(0) + j * r), Bm.stride(0), 1,
-                                         Bt.data_ptr() + 2 * ((j * r) * Bt.stride(0) + row), 1, Bt.stride(0))
-                        row += wb.shape[0]
-            self._adapter_sinks = sinks
-        return sinks.get(id(p))
+        return self._adapters.sink(p)
 
     def adapters_adopted(self, written_ids) -> None:
-        """The optimizer wrote every adapter's bf16 values into the group images itself: they are current for the new parameters."""
-        plist = getattr(self, "_lora_plist", None)
-        if plist is None or getattr(self, "_li", None) is None:
-            return
-        if all(id(q) in written_ids for q in plist if q.requires_grad):
-            self._li_ver = tuple(param_state_key(q) for q in plist)
+        self._adapters.adopted(written_ids)
 
-    def _lora_fwd(self, key: str, x: torch.Tensor, y: torch.Tensor, tag: str) -> torch.Tensor:
-        """y += lora_b(lora_a(x)) for a fused adapter group; returns t = lora_a(x) (kept for the backward)."""
-        li = self._lora_step_images()
-        A, Bm = li[key + ".A"], li[key + ".B"]
-        t = self._buf("lora_t." + key.split(".")[0] + tag, (x.shape[0], A.shape[0]))
+    @property
+    def _li_ver(self):
+        return self._adapters.ver
+
+    def _lora_t(self, key: str, x: torch.Tensor, tag: str, t: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """t = lora_a(x) = x . A^T of a fused adapter group (kept for the backward), into ``t`` (K-ext: the tail columns of the GEMM's
+        input) or a buffer of its own."""
+        A = self._lora_step_images()[key + ".A"]
+        if t is None:
+            t = self._buf("lora_t." + key.split(".")[0] + tag, (x.shape[0], A.shape[0]))
         self._skinny(x, A, t)
-        f32 = y.dtype == torch.float32 and self.act == torch.bfloat16
-        ops.gemm_nt(t, Bm, y, residual=y, epilogue=ops.EPI_RES_F32 if f32 else 0)
         return t
 
-    def _kx_group_bwd(self, i: int, key: str, dy_full: torch.Tensor, N: int, x: torch.Tensor, t: torch.Tensor, dx: torch.Tensor,
-                      swiglu_gu: Optional[torch.Tensor] = None):
-        """Input gradient of a decoder GEMM with the adapters inside it: dy_full = [dy | dt] (dt = dy . B in the tail columns)
-        times [W ; A] in ONE NN GEMM (dx = dy W + dt A), then the adapter weight gradients.  ``swiglu_gu`` (w2 only): the product is
-        d(act) of the SwiGLU and ``dx`` the [rows, 2 F] gradient of the gate | up rows -- the SwiGLU backward runs in the GEMM epilogue."""
-        li = self._lora_step_images()
-        dy, dt = dy_full[:, :N], dy_full[:, N:]
-        self._dgrad(dy, li[key + ".Bt"], dt)
+    def _lora_add(self, key: str, t: torch.Tensor, y: torch.Tensor):
+        """y += lora_b(t) for a fused adapter group."""
+        ops.gemm_nt(t, self._lora_step_images()[key + ".B"], y, residual=y, epilogue=self._res_epi(y))
+
+    # ------------------------------------------------------------------ one decoder GEMM group (GROUPS): forward and backward
+    def _x_buf(self, name: str, cols: int, key: str, rows: int, kx: bool):
+        """Input buffer of decoder GEMM ``key``: (x, full, t).  K-ext: ``full`` = [x | t] with room for the adapter projection
+        t = x . A^T behind x; else ``full`` is x itself and t is None."""
+        full = self._buf(name, (rows, cols + (self._lora_step_images()[key + ".A"].shape[0] if kx else 0)))
+        return (full[:, :cols], full, full[:, cols:]) if kx else (full, full, None)
+
+    def _dy_buf(self, name: str, cols: int, key: str, rows: int, kx: bool):
+        """Output-gradient buffer of decoder GEMM ``key``: (dy, full).  K-ext: ``full`` = [dy | dt] (buffer ``name``.x) with room for
+        dt = dy . B behind dy; else full is None."""
+        dy, full, _ = self._x_buf(name + ".x" if kx else name, cols, key, rows, kx)
+        return dy, (full if kx else None)
+
+    def _group_fwd(self, i: int, kind: str, x: torch.Tensor, x_full: torch.Tensor, t: Optional[torch.Tensor], out: torch.Tensor,
+                   residual: Optional[torch.Tensor] = None, epilogue: int = 0, tag: str = "") -> Optional[torch.Tensor]:
+        """out = x . W^T (+ residual) of GEMM group ``kind`` of layer i with its adapters; (x, x_full, t) from ``_x_buf``.  Returns
+        t = lora_a(x) for the backward (None without adapters)."""
+        im, key = self._images(), f"{kind}.{i}"
+        if t is not None:
+            # K-ext, adapters inside the GEMM: t goes into the tail columns of the input, B sits in the tail columns of the image
+            self._lora_t(key, x, tag, t)
+            ops.gemm_nt(x_full, im[key + ".x"], out, residual=residual, epilogue=epilogue)
+            return t
+        ops.gemm_nt(x, im[key], out, residual=residual, epilogue=epilogue)
+        if not self.lora:
+            return None
+        t = self._lora_t(key, x, tag)                     # separate adapters: a read-modify-write pass over the output
+        self._lora_add(key, t, out)
+        return t
+
+    def _group_bwd(self, i: int, kind: str, dy: torch.Tensor, dy_full: Optional[torch.Tensor], x: torch.Tensor, t: Optional[torch.Tensor],
+                   dx: torch.Tensor, swiglu_gu: Optional[torch.Tensor] = None):
+        """dx = dy . W (+ the adapter term) of GEMM group ``kind`` of layer i and its adapter weight gradients; (dy, dy_full) from
+        ``_dy_buf``.  K-ext: dy_full = [dy | dt] (dt = dy . B in the tail columns) times [W ; A] in ONE GEMM (dx = dy W + dt A).
+        ``swiglu_gu`` (K-ext w2 only): the product is d(act) of the SwiGLU and ``dx`` the [rows, 2 F] gradient of the gate | up
+        rows -- the SwiGLU backward runs in the GEMM epilogue."""
+        key = f"{kind}.{i}"
+        if dy_full is None:
+            self._dgrad_w(dy, key, dx)
+            if self.lora:
+                self._lora_bwd(i, key, dy, x, t, dx)
+            return
+        dt = dy_full[:, dy.shape[1]:]
+        self._dgrad(dy, self._lora_step_images()[key + ".Bt"], dt)
         im = self._images()
         if swiglu_gu is not None:
             ops.gemm_nt(dy_full, im[key + ".yT"], dx, residual=swiglu_gu, epilogue=ops.EPI_SWIGLU_BWD)
@@ -631,6 +558,12 @@ class TrainEngine:
         else:
             ops.gemm_nn(dy_full, im[key + ".y"], dx)
         self._lora_bwd(i, key, dy, x, t, None, dt=dt)
+
+    def _group_wgrad(self, i: int, kind: str, dy: torch.Tensor, x: torch.Tensor):
+        """Base weight gradient of GEMM group ``kind`` of layer i, into the fused view of its modules' gradients (none when frozen)."""
+        names = tuple(f"layers.{i}.{sub}.weight" for sub in GROUPS[kind])
+        if self._has(*names):
+            self._wgrad(dy, x, self._gview(names[0], names[-1]), kind, names)
 
     def _lora_bwd(self, i: int, key: str, dy: torch.Tensor, x: torch.Tensor, t: torch.Tensor, dx: Optional[torch.Tensor], dt=None):
         """Adapter gradients of a fused group and the adapter term of the input gradient (dx += (dy B) A)."""
@@ -647,8 +580,7 @@ class TrainEngine:
         # dB is produced transposed ([Rp, N] = t^T dy): the strip with the adapter rank as its ROW index streams dy 1.2-1.5x
         # faster through the TN kernel than the [N, Rp] strip (tools/lora_skinny_bench.py); the r x N_j blocks are added
         # into the [N_j, r] gradient views below
-        names = {"qkv": ["attention.wq", "attention.wk", "attention.wv"], "wo": ["attention.wo"],
-                 "w13": ["feed_forward.w1", "feed_forward.w3"], "w2": ["feed_forward.w2"]}[g]
+        names = GROUPS[g]
         vas = [self._views[f"layers.{i}.{nm}.lora_a.weight"] for nm in names]
         vbs = [self._views[f"layers.{i}.{nm}.lora_b.weight"] for nm in names]
         nr = len(names) * r
@@ -688,101 +620,69 @@ class TrainEngine:
         rows = B * S
         l = m.layers[i]
         spad = _pad64(S)
-        kx = self._kext() > 0 and rows > 16 and hd in (64, 128) and self.fuse_qkv_rope
-        li = self._lora_step_images() if kx else None
-
-        def xbuf(name, cols, key):      # activation buffer with the adapter block t = x . A^T appended (K_ext): full, x view, t view
-            ext = li[key + ".A"].shape[0]
-            full = self._buf(name + tag, (rows, cols + ext))
-            return full, full[:, :cols], full[:, cols:]
-        if kx:
-            xn_full, xn, t_qkv = xbuf("xn", dim, f"qkv.{i}")
-            att_full, att, t_wo = xbuf("att", H * hd, f"wo.{i}")
-        else:
-            xn = self._buf("xn" + tag, (rows, dim))
-            att = self._buf("att" + tag, (rows, H * hd))
+        kx = self._kx(rows)
+        xn, xn_full, t_qkv = self._x_buf("xn" + tag, dim, f"qkv.{i}", rows, kx)
+        att, att_full, t_wo = self._x_buf("att" + tag, H * hd, f"wo.{i}", rows, kx)
         qkv = self._buf("qkv" + tag, (rows, (H + 2 * Hkv) * hd))
         qrot = self._buf("qrot" + tag, (rows, H * hd))
         kc = self._buf("kc" + tag, (B, Hkv, spad, hd))
         vc = self._buf("vc", (B, Hkv, hd, spad))
         lse = self._buf("lse" + tag, (B, H, S), torch.float32)
-        ops.rmsnorm(h, l.attention_norm.weight, xn, a.norm_eps)
         lt = {}
-        if not self.lora and self.act == torch.bfloat16 and hd in (64, 128) and rows > 16 and self.fuse_qkv_rope:
-            # RoPE + K / V^T writes in the GEMM epilogue; v also token-major in its qkv columns for the attention backward
-            ops.gemm_qkv_rope(xn, im[f"qkv.{i}"], qrot, kc, vc, m._cos_sin_dev(), B, S, H, Hkv, hd, 0, 0,
-                              v_rows=qkv[:, (H + Hkv) * hd:])
-        elif kx:
-            # adapters inside the GEMM: t = x . A^T goes into the tail columns of the input, B sits in the tail columns of the image
-            self._skinny(xn, li[f"qkv.{i}.A"], t_qkv)
-            ops.gemm_qkv_rope(xn_full, im[f"qkv.{i}.x"], qrot, kc, vc, m._cos_sin_dev(), B, S, H, Hkv, hd, 0, 0,
-                              v_rows=qkv[:, (H + Hkv) * hd:])
-            lt["qkv"] = t_qkv
-        elif self.lora and self.act == torch.bfloat16 and hd in (64, 128) and rows > 16 and self.fuse_qkv_rope:
-            # adapters: the LoRA term t . B^T is written into the qkv buffer first and enters the fused GEMM as an additive term
-            # before the rotation (the reference's order: linear output + modification, rounded, then RoPE)
-            li = self._lora_step_images()
-            A, Bm = li[f"qkv.{i}.A"], li[f"qkv.{i}.B"]
-            t = self._buf("lora_t.qkv" + tag, (rows, A.shape[0]))
-            self._skinny(xn, A, t)
-            ops.gemm_nt(t, Bm, qkv)
-            ops.gemm_qkv_rope(xn, im[f"qkv.{i}"], qrot, kc, vc, m._cos_sin_dev(), B, S, H, Hkv, hd, 0, 0,
-                              v_rows=qkv[:, (H + Hkv) * hd:], delta=qkv)
-            lt["qkv"] = t
-        else:
-            ops.gemm_nt(xn, im[f"qkv.{i}"], qkv)
-            if self.lora:
-                lt["qkv"] = self._lora_fwd(f"qkv.{i}", xn, qkv, tag)
-            ops.rope_kvcache(qkv, qrot, kc, vc, m._cos_sin_dev(), B, S, H, Hkv, hd, 0, 0)
+        # ---- attention: h_mid = h + wo(attn(rope(qkv(norm(h)))))
+        ops.rmsnorm(h, l.attention_norm.weight, xn, a.norm_eps)
+        lt["qkv"] = self._qkv_fwd(i, xn, xn_full, t_qkv, qkv, qrot, kc, vc, B, S, tag)
         ldo = att.stride(0)
         strides = (S * H * hd, H * hd, hd, Hkv * spad * hd, spad * hd, hd, Hkv * hd * spad, hd * spad, spad, S * ldo, ldo, hd)
         ops.attention_lse(qrot, kc, vc, att, lse, B, S, S, H, Hkv, hd, strides, True)
-        res_flag = ops.EPI_RES_F32 if (self.act == torch.bfloat16 and self.stream == torch.float32) else 0     # bf16 stream: plain bf16 residual
+        res_flag = self._res_epi(h)                       # bf16 stream: plain bf16 residual
         h_mid = self._buf("h_mid" + tag, (rows, dim), self.stream) if keep else h
-        if kx:
-            self._skinny(att, li[f"wo.{i}.A"], t_wo)
-            ops.gemm_nt(att_full, im[f"wo.{i}.x"], h_mid, residual=h, epilogue=res_flag)
-            lt["wo"] = t_wo
-        else:
-            ops.gemm_nt(att, im[f"wo.{i}"], h_mid, residual=h, epilogue=res_flag)
-            if self.lora:
-                lt["wo"] = self._lora_fwd(f"wo.{i}", att, h_mid, tag)
+        lt["wo"] = self._group_fwd(i, "wo", att, att_full, t_wo, h_mid, h, res_flag, tag)
+        # ---- FFN: out = h_mid + w2(silu(g) * u)
         gu = self._buf("gu" + tag, (rows, 2 * F))
-        if kx:
-            xn2_full, xn2, t_w13 = xbuf("xn2", dim, f"w13.{i}")
-            act_full, actb, t_w2 = xbuf("act", F, f"w2.{i}")
-        else:
-            xn2 = self._buf("xn2" + tag, (rows, dim))
-            actb = self._buf("act" + tag, (rows, F))
+        xn2, xn2_full, t_w13 = self._x_buf("xn2" + tag, dim, f"w13.{i}", rows, kx)
+        actb, act_full, t_w2 = self._x_buf("act" + tag, F, f"w2.{i}", rows, kx)
         ops.rmsnorm(h_mid, l.ffn_norm.weight, xn2, a.norm_eps)
-        if kx:
-            self._skinny(xn2, li[f"w13.{i}.A"], t_w13)
-            ops.gemm_nt(xn2_full, im[f"w13.{i}.x"], gu)
-            lt["w13"] = t_w13
-        else:
-            ops.gemm_nt(xn2, im[f"w13.{i}"], gu)
-            if self.lora:
-                lt["w13"] = self._lora_fwd(f"w13.{i}", xn2, gu, tag)
+        lt["w13"] = self._group_fwd(i, "w13", xn2, xn2_full, t_w13, gu, tag=tag)
         ops.swiglu_fwd(gu, actb, F, interleaved=False)
-        if kx:
-            self._skinny(actb, li[f"w2.{i}.A"], t_w2)
-            lt["w2"] = t_w2
-        elif self.lora:                                   # t = lora_a(act) of w2 is needed by the backward even without the output
-            li2 = self._lora_step_images()
-            lt["w2"] = self._buf("lora_t.w2" + tag, (rows, li2[f"w2.{i}.A"].shape[0]))
-            self._skinny(actb, li2[f"w2.{i}.A"], lt["w2"])
+        # w2 is not a _group_fwd: t = lora_a(act) is needed by the backward even when the block output is not computed, so it comes
+        # first and the output GEMM(s) only when there is an output
+        lt["w2"] = self._lora_t(f"w2.{i}", actb, tag, t_w2) if self.lora else None
         kept = dict(xn=xn, qkv=qkv, qrot=qrot, kc=kc, att=att, lse=lse, h_mid=h_mid, xn2=xn2, gu=gu, act=actb, spad=spad, lt=lt)
         if keep and h_out is None:
             return kept                                   # recompute inside backward: the block output is not needed
         out = h_out if keep else h
-        if kx:
-            ops.gemm_nt(act_full, im[f"w2.{i}.x"], out, residual=h_mid, epilogue=res_flag)
-            return kept
-        ops.gemm_nt(actb, im[f"w2.{i}"], out, residual=h_mid, epilogue=res_flag)
-        if self.lora:
-            f32 = out.dtype == torch.float32 and self.act == torch.bfloat16
-            ops.gemm_nt(lt["w2"], self._lora_step_images()[f"w2.{i}.B"], out, residual=out, epilogue=ops.EPI_RES_F32 if f32 else 0)
+        ops.gemm_nt(act_full, im[f"w2.{i}.x" if kx else f"w2.{i}"], out, residual=h_mid, epilogue=res_flag)
+        if self.lora and not kx:
+            self._lora_add(f"w2.{i}", lt["w2"], out)
         return kept
+
+    def _qkv_fwd(self, i: int, xn, xn_full, t, qkv, qrot, kc, vc, B: int, S: int, tag: str) -> Optional[torch.Tensor]:
+        """The qkv step of a block: q (rotated) into ``qrot``, K / V^T into the caches, v token-major in its columns of ``qkv``
+        (attention backward); returns t = lora_a(xn) or None.  Three forms of the GEMM with the RoPE / cache-write epilogue -- plain,
+        K-ext, and adapters as an additive term -- and the un-fused fallback."""
+        m, im, key = self.m, self._images(), f"qkv.{i}"
+        H, Hkv, hd = m.n_heads, m.n_kv_heads, m.head_dim
+        fused = self.act == torch.bfloat16 and hd in (64, 128) and xn.shape[0] > 16 and self.fuse_qkv_rope
+        v_rows = qkv[:, (H + Hkv) * hd:]
+        if fused and not self.lora:
+            ops.gemm_qkv_rope(xn, im[key], qrot, kc, vc, m._cos_sin_dev(), B, S, H, Hkv, hd, 0, 0, v_rows=v_rows)
+            return None
+        if t is not None:
+            # K-ext (implies ``fused``): t = x . A^T in the tail columns of the input, B in the tail columns of the image
+            self._lora_t(key, xn, tag, t)
+            ops.gemm_qkv_rope(xn_full, im[key + ".x"], qrot, kc, vc, m._cos_sin_dev(), B, S, H, Hkv, hd, 0, 0, v_rows=v_rows)
+            return t
+        if fused:
+            # adapters: the LoRA term t . B^T is written into the qkv buffer first and enters the fused GEMM as an additive term
+            # before the rotation (the reference's order: linear output + modification, rounded, then RoPE)
+            t = self._lora_t(key, xn, tag)
+            ops.gemm_nt(t, self._lora_step_images()[key + ".B"], qkv)
+            ops.gemm_qkv_rope(xn, im[key], qrot, kc, vc, m._cos_sin_dev(), B, S, H, Hkv, hd, 0, 0, v_rows=v_rows, delta=qkv)
+            return t
+        t = self._group_fwd(i, "qkv", xn, xn_full, None, qkv, tag=tag)
+        ops.rope_kvcache(qkv, qrot, kc, vc, m._cos_sin_dev(), B, S, H, Hkv, hd, 0, 0)
+        return t
 
     def _block_backward(self, i: int, h_in: torch.Tensor, dh: torch.Tensor, B: int, S: int):
         m, a, im = self.m, self.m.args, self._images()
@@ -793,88 +693,54 @@ class TrainEngine:
         if not self._saved.get("kept"):
             im.recompute_backward(i)     # (NF4 base: the block's forward and input-gradient images from one read of its codes)
         k = self._saved["kept"][i] if self._saved.get("kept") else self._block_forward(i, h_in, B, S, keep=True)
-        # ---- FFN: out = h_mid + w2(silu(g) * u)
-        lt = k.get("lt", {})
-        kx = self._kext() > 0 and rows > 16 and hd in (64, 128) and self.fuse_qkv_rope       # as in _block_forward
-        li = self._lora_step_images() if kx else None
-
-        def ybuf(name, cols, key):      # gradient buffer with room for dt = dy . B behind it: full, dy view
-            full = self._buf(name, (rows, cols + li[key + ".A"].shape[0]))
-            return full, full[:, :cols]
+        lt = k["lt"]
+        kx = self._kx(rows)
         stream_lp = self.stream == torch.bfloat16 and self.act == torch.bfloat16     # dh itself is the bf16 operand of the GEMMs
         if stream_lp:
-            dha = dh
-            dha_full = self._dh_full if kx else None
-        elif kx:
-            dha_full, dha = ybuf("dh_act.x", dim, f"w2.{i}")
+            dha, dha_full = dh, (self._dh_full if kx else None)
         else:
-            dha = self._buf("dh_act", (rows, dim))
+            dha, dha_full = self._dy_buf("dh_act", dim, f"w2.{i}", rows, kx)
         fuse_cast = self.act == torch.bfloat16 and not stream_lp   # fp32 stream: the norm backward that produced dh also wrote its bf16 copy
-        if not stream_lp and not (fuse_cast and getattr(self, "_dha_ready", False)):
+        if not stream_lp and not (fuse_cast and self._dha_ready):
             ops.cast(dh, dha)
         self._dha_ready = False
-        if self._has(pre + "feed_forward.w2.weight"):
-            self._wgrad(dha, k["act"], self._views[pre + "feed_forward.w2.weight"], "w2", (pre + "feed_forward.w2.weight",))
+        # ---- FFN: out = h_mid + w2(silu(g) * u)
+        self._group_wgrad(i, "w2", dha, k["act"])
+        dgu, dgu_full = self._dy_buf("dgu", 2 * F, f"w13.{i}", rows, kx)
+        # w2's input gradient is d(act); three forms keep it out of HBM by applying the SwiGLU backward in the GEMM epilogue
+        # (a3v_swiglu_bwd on the bf16-rounded product, bit for bit), writing d(gate) | d(up) straight into the w1|w3 gradient buffer
+        ft_epi = (not self.lora and self.fuse_swiglu_bwd and self.act == torch.bfloat16 and dim % 64 == 0 and F % 8 == 0
+                  and dha.stride(0) % 8 == 0)
         if kx and self.fuse_swiglu_bwd and self._nt_dgrad(f"w2.{i}") and F % 8 == 0:
-            # d(act) never reaches HBM: the input-gradient GEMM of w2 applies the SwiGLU backward in its epilogue (a3v_swiglu_bwd on
-            # the bf16-rounded product, bit for bit) and writes d(gate) | d(up) straight into the w1|w3 gradient buffer
-            dgu_full, dgu = ybuf("dgu.x", 2 * F, f"w13.{i}")
-            self._kx_group_bwd(i, f"w2.{i}", dha_full, dim, k["act"], lt["w2"], dgu, swiglu_gu=k["gu"])
-        elif (not self.lora and self.fuse_swiglu_bwd and self.nn_dgrad and self.act == torch.bfloat16 and dim % 64 == 0 and F % 8 == 0 and F >= 256
-              and dha.stride(0) % 8 == 0 and 2 * rows * dha.stride(0) < 2 ** 31 and 2 * F * dim < 2 ** 31
+            self._group_bwd(i, "w2", dha, dha_full, k["act"], lt["w2"], dgu, swiglu_gu=k["gu"])       # LoRA K-ext on the NT ring kernel
+        elif (ft_epi and self.nn_dgrad and F >= 256 and 2 * rows * dha.stride(0) < 2 ** 31 and 2 * F * dim < 2 ** 31
               and tuple(im[f"w2.{i}"].shape) == (dim, F)):
             # full fine-tune: the same epilogue on the NN kernel (dX = dY . W on the forward image)
-            dgu = self._buf("dgu", (rows, 2 * F))
             ops.gemm_nn(dha, im[f"w2.{i}"], dgu, residual=k["gu"], epilogue=ops.EPI_SWIGLU_BWD)
-        elif (not self.lora and self.fuse_swiglu_bwd and not self.nn_dgrad and self.act == torch.bfloat16 and dim % 64 == 0 and F % 8 == 0
-              and dha.stride(0) % 8 == 0 and tuple(im[f"w2.{i}.t"].shape) == (F, dim)):
+        elif ft_epi and not self.nn_dgrad and tuple(im[f"w2.{i}.t"].shape) == (F, dim):
             # full fine-tune with input gradients on the NT ring kernel (W^T images): the same epilogue there
-            dgu = self._buf("dgu", (rows, 2 * F))
             ops.gemm_nt(dha, im[f"w2.{i}.t"], dgu, residual=k["gu"], epilogue=ops.EPI_SWIGLU_BWD)
         else:
             dact = self._buf("dact", (rows, F))
-            if kx:
-                self._kx_group_bwd(i, f"w2.{i}", dha_full, dim, k["act"], lt["w2"], dact)
-                dgu_full, dgu = ybuf("dgu.x", 2 * F, f"w13.{i}")
-            else:
-                self._dgrad_w(dha, f"w2.{i}", dact)
-                if self.lora:
-                    self._lora_bwd(i, f"w2.{i}", dha, k["act"], lt["w2"], dact)
-                dgu = self._buf("dgu", (rows, 2 * F))
+            self._group_bwd(i, "w2", dha, dha_full, k["act"], lt["w2"], dact)
             ops.swiglu_bwd(k["gu"], dact, dgu, F, interleaved=False)
-        if self._has(pre + "feed_forward.w1.weight", pre + "feed_forward.w3.weight"):
-            self._wgrad(dgu, k["xn2"], self._gview(pre + "feed_forward.w1.weight", pre + "feed_forward.w3.weight"), "w13",
-                        (pre + "feed_forward.w1.weight", pre + "feed_forward.w3.weight"))
+        self._group_wgrad(i, "w13", dgu, k["xn2"])
         dxn = self._buf("dxn", (rows, dim))
-        if kx:
-            self._kx_group_bwd(i, f"w13.{i}", dgu_full, 2 * F, k["xn2"], lt["w13"], dxn)
-        else:
-            self._dgrad_w(dgu, f"w13.{i}", dxn)
-            if self.lora:
-                self._lora_bwd(i, f"w13.{i}", dgu, k["xn2"], lt["w13"], dxn)
+        self._group_bwd(i, "w13", dgu, dgu_full, k["xn2"], lt["w13"], dxn)
         ops.rmsnorm_bwd(k["h_mid"], l.ffn_norm.weight, dxn, dh, self._views.get(pre + "ffn_norm.weight"), a.norm_eps,
                         dh_lowp=dha if fuse_cast else None)
         # ---- attention: h_mid = h_in + wo(attn(rope(qkv(norm(h_in)))))
         if not fuse_cast and not stream_lp:
             ops.cast(dh, dha)
-        if self._has(pre + "attention.wo.weight"):
-            self._wgrad(dha, k["att"], self._views[pre + "attention.wo.weight"], "wo", (pre + "attention.wo.weight",))
+        self._group_wgrad(i, "wo", dha, k["att"])
         datt = self._buf("datt", (rows, H * hd))
-        if kx:
-            self._kx_group_bwd(i, f"wo.{i}", dha_full, dim, k["att"], lt["wo"], datt)
-        else:
-            self._dgrad_w(dha, f"wo.{i}", datt)
-            if self.lora:
-                self._lora_bwd(i, f"wo.{i}", dha, k["att"], lt["wo"], datt)
+        self._group_bwd(i, "wo", dha, dha_full, k["att"], lt["wo"], datt)
         D = self._buf("attn_D", (B, S, H), torch.float32)
         qkv = k["qkv"]
         ld = qkv.stride(0)
         vrows = qkv[:, (H + Hkv) * hd:]
         spad = k["spad"]
-        if kx:
-            dqkv_full, dqkv = ybuf("dqkv.x", (H + 2 * Hkv) * hd, f"qkv.{i}")
-        else:
-            dqkv = self._buf("dqkv", (rows, (H + 2 * Hkv) * hd))
+        dqkv, dqkv_full = self._dy_buf("dqkv", (H + 2 * Hkv) * hd, f"qkv.{i}", rows, kx)
         if self.act == torch.bfloat16 and hd in (64, 128) and self.packed_attn_bwd:
             # the MFMA kernels rotate dq / dk back and store [dq | dk | dv] straight into the fused-qkv gradient
             ops.attention_bwd_packed(k["qrot"], k["kc"], Hkv * spad * hd, spad * hd, vrows, S * ld, ld, hd, k["att"], datt, k["lse"], D,
@@ -890,15 +756,8 @@ class TrainEngine:
             ops.attention_bwd(k["qrot"], k["kc"], Hkv * spad * hd, spad * hd, vrows, S * ld, ld, hd, att_c, datt, k["lse"], D,
                               dq, dk, dv, B, S, H, Hkv, hd, True, workspace=wsp)
             ops.rope_bwd_pack(dq, dk, dv, dqkv, m._cos_sin_dev(), B, S, H, Hkv, hd, 0)
-        if self._has(pre + "attention.wq.weight", pre + "attention.wk.weight", pre + "attention.wv.weight"):
-            self._wgrad(dqkv, k["xn"], self._gview(pre + "attention.wq.weight", pre + "attention.wv.weight"), "qkv",
-                        (pre + "attention.wq.weight", pre + "attention.wk.weight", pre + "attention.wv.weight"))
-        if kx:
-            self._kx_group_bwd(i, f"qkv.{i}", dqkv_full, (H + 2 * Hkv) * hd, k["xn"], lt["qkv"], dxn)
-        else:
-            self._dgrad_w(dqkv, f"qkv.{i}", dxn)
-            if self.lora:
-                self._lora_bwd(i, f"qkv.{i}", dqkv, k["xn"], lt["qkv"], dxn)
+        self._group_wgrad(i, "qkv", dqkv, k["xn"])
+        self._group_bwd(i, "qkv", dqkv, dqkv_full, k["xn"], lt["qkv"], dxn)
         ops.rmsnorm_bwd(h_in, l.attention_norm.weight, dxn, dh, self._views.get(pre + "attention_norm.weight"), a.norm_eps,
                         dh_lowp=dha if fuse_cast else None)
         self._dha_ready = fuse_cast                        # the next block's backward finds its bf16 operand in place
@@ -908,7 +767,7 @@ class TrainEngine:
     def forward_loss(self, examples: torch.Tensor, labels: torch.Tensor, image: Optional[torch.Tensor] = None,
                      qformer_feats=None, extra_feats=None) -> torch.Tensor:
         self._check_dtypes()
-        self._li_checked = False
+        self._adapters.checked = False
         m, a = self.m, self.m.args
         im = self._images()
         B, T = examples.shape
@@ -971,37 +830,29 @@ class TrainEngine:
     def backward(self, grad_scale: float = 1.0) -> None:
         s = self._saved
         self._dha_ready = False
-        self._li_checked = False
+        self._adapters.checked = False
         assert s is not None, "backward() without forward_loss()"
         m, a = self.m, self.m.args
         self.sync_optimizer()                    # the update reads the gradients this backward overwrites
-        im = self._images()
         self.ensure_grads()
-        if not self.nn_dgrad and not self.lora and not getattr(self, "_nt_mem_checked", False):
+        if not self.nn_dgrad and not self.lora and not self._nt_mem_checked:
             # the transposed images cost 2 B per matrix parameter (12.3 GiB at 7B, 23.9 at 13B): on a replica that would not leave
             # 8 GiB free after them (13B at DP 8 with persistent wire buckets is at 270 of 288 GiB), stay on the NN kernel
             self._nt_mem_checked = True
-            need = 2 * sum(q.numel() for g_ in im.groups() if g_ != "vp" for q in im._params(g_)[0])
-            if not getattr(self, "_opt_stepped", False):          # the AdamW moments (8 B per trainable parameter) are allocated by the first step
-                need += 8 * sum(q.numel() for q in m.parameters() if q.requires_grad)
-            free, _ = torch.cuda.mem_get_info(m._device)
-            free += torch.cuda.memory_reserved(m._device) - torch.cuda.memory_allocated(m._device)
+            # the AdamW moments (8 B per trainable parameter) are allocated by the first optimizer step
+            moments = 0 if self._opt_stepped else 8 * sum(q.numel() for q in m.parameters() if q.requires_grad)
             # (a replica that recomputes its blocks is one sized against the HBM limit -- 13B at micro-batch 4: measured 452.5 / 453.7 ms
             # with the transposed images against 455.5 / 452.4 without, for 24 GiB: not taken there unless A3V_NN_DGRAD=0 asks for it)
-            if free - need < 8 * 2 ** 30 or (self.recompute and "A3V_NN_DGRAD" not in os.environ):
+            if not self._nt_images_fit(moments) or (self.recompute and "A3V_NN_DGRAD" not in os.environ):
                 self.nn_dgrad = True
-        if self.lora and not self._q4base() and not getattr(self, "_nt_mem_checked", False):
+        if self.lora and not self._q4base() and not self._nt_mem_checked:
             # LoRA engines: the input gradients of the frozen matrices run on the NT kernel over transposed images that
             # are built once (2 B per base parameter: 12.3 GiB at 7B) and, with nn_dgrad off, the head's W^T too -- the same headroom
             # rule as the full fine-tune above: without 8 GiB left after them the NN kernel on the forward images is used instead
             self._nt_mem_checked = True
-            if not self.nn_dgrad or self.lora_nt_dgrad not in ("", "0"):
-                need = 2 * sum(q.numel() for g_ in im.groups() if g_ != "vp" for q in im._params(g_)[0])
-                free, _ = torch.cuda.mem_get_info(m._device)
-                free += torch.cuda.memory_reserved(m._device) - torch.cuda.memory_allocated(m._device)
-                if free - need < 8 * 2 ** 30:
-                    self.nn_dgrad = True
-                    self.lora_nt_dgrad = "0"
+            if (not self.nn_dgrad or self.lora_nt_dgrad not in ("", "0")) and not self._nt_images_fit():
+                self.nn_dgrad = True
+                self.lora_nt_dgrad = "0"
         if self.sumsq_sink is not None:
             self.sumsq_sink.begin_backward()
         B, T, W, S = s["B"], s["T"], s["W"], s["S"]
@@ -1013,9 +864,8 @@ class TrainEngine:
             self._wgrad(dlog, s["xt"], self._views["output.weight"], "out", ("output.weight",))
         dxt = self._buf("dxn_text", (B * T, dim))
         self._dgrad_w(dlog, "out", dxt)
-        kx = self._kext() > 0 and rows > 16 and m.head_dim in (64, 128) and self.fuse_qkv_rope       # as in _block_forward
         self._dh_full = None
-        if self.stream == torch.bfloat16 and self.act == torch.bfloat16 and kx:
+        if self.stream == torch.bfloat16 and self.act == torch.bfloat16 and self._kx(rows):
             # bf16 stream + adapters inside the GEMMs: dh IS the dy operand of the wo / w2 groups, so it lives in the first `dim`
             # columns of a buffer with room for dt = dy . B behind it (no copy of dh per layer)
             # (width of the wo / w2 groups' adapter block, pad64(r) -- NOT _kext(), the qkv group's pad64(3 r): the two differ from r = 22 on)
@@ -1041,6 +891,15 @@ class TrainEngine:
         # gradients there, and every rank must hand the same buckets to the collective on the boundary micro-step
         self._notify("vision_proj")
         self._saved = None
+
+    def _nt_images_fit(self, extra: int = 0) -> bool:
+        """Would 8 GiB of HBM stay free after the transposed images of the decoder / head matrices (2 B per parameter) and ``extra``
+        more bytes?  (Memory the caching allocator holds but has not handed out counts as free.)"""
+        im = self._images()
+        need = extra + 2 * sum(q.numel() for g_ in im.groups() if g_ != "vp" for q in im._params(g_)[0])
+        free, _ = torch.cuda.mem_get_info(self.m._device)
+        free += torch.cuda.memory_reserved(self.m._device) - torch.cuda.memory_allocated(self.m._device)
+        return free - need >= 8 * 2 ** 30
 
     def _notify(self, bucket: str):
         if self.on_layer_grads_ready is None:
@@ -1128,305 +987,6 @@ class TrainEngine:
         for j, sl in enumerate(vis["slots"]):
             ops.rows_sum(dh, vis["start_rows"][j], vis["start_rows"][j].numel(), self._views[names[sl][0]].view(-1))
             ops.rows_sum(dh, vis["end_rows"][j], vis["end_rows"][j].numel(), self._views[names[sl][1]].view(-1))
-
-
-class _Images:
-    """dict-like view of the engine's compute-dtype weight images, built per group on demand."""
-
-    def __init__(self, eng: "TrainEngine"):
-        self.eng = eng
-        self.store: Dict[str, torch.Tensor] = {}
-        self.ver: Dict[str, tuple] = {}
-        self.tver: Dict[str, tuple] = {}      # version of each transposed image (built lazily, per key)
-        self._sinks = None                    # id(param) -> (image key, first row), built on first use
-
-    def _group(self, key: str):
-        if key.startswith(("qkv.", "wo.", "w13.", "w2.")):
-            return "L" + key.split(".")[1]
-        return "vp" if key.startswith(("vp", "vq")) else "out"
-
-    def _fused(self, ps):
-        """The fused matrix of consecutive parameters: a VIEW of the flat parameter buffer under ZeRO-1 (always current, no copy: the
-        image IS the parameter storage), else their concatenation."""
-        v = self.eng._pview(list(ps)) if self.eng.zero1_world and not self.eng.lora else None
-        if v is not None:
-            return v
-        return torch.cat(list(ps), dim=0) if len(ps) > 1 else ps[0]
-
-    def _both(self, key, w):      # forward image W [N,K] now; W^T [K, N padded to 64] only when somebody asks for key + ".t"
-        ext = self.eng._kext_cols(key)
-        if ext:                   # LoRA inside the GEMMs: one [N + Rp, K + Rp] image = [[W, B], [A, 0]]; forward reads [W | B] (rows 0..N),
-            N, K = w.shape        # the input gradient reads [W ; A] (columns 0..K); A / B blocks written by _lora_step_images / a3v_lora_refresh
-            full = torch.zeros(N + ext, K + ext, dtype=self.eng.act, device=w.device)
-            full[:N, :K] = w.to(self.eng.act)
-            self.store[key] = full[:N, :K]
-            self.store[key + ".x"] = full[:N]
-            self.store[key + ".y"] = full[:, :K]
-            if self.eng._nt_dgrad(key):
-                # [W^T | A^T]  [K, N + Rp]: dx = [dy | dt] . (this)^T on the NT ring kernel; W is frozen, the A^T block is re-written
-                # with the adapters (a3v_adamw_multi / a3v_lora_refresh)
-                ft = torch.zeros(K, N + ext, dtype=self.eng.act, device=w.device)
-                ft[:, :N] = full[:N, :K].t()
-                self.store[key + ".yT"] = ft
-        else:
-            self.store[key] = w.to(self.eng.act).contiguous()
-
-    def _transposed(self, key: str, ver) -> torch.Tensor:
-        if self.tver.get(key) != ver:
-            act = self.eng.act
-            wa = self.store[key[:-2]]
-            N, K = wa.shape
-            Np = _pad64(N)
-            if Np != N:
-                wp = torch.zeros(Np, K, dtype=act, device=wa.device)
-                wp[:N] = wa
-            else:
-                wp = wa
-            wt = self.store.get(key)
-            if wt is None or wt.shape != (K, Np) or wt.dtype != act:
-                # row pitch off the powers of two: a3v_adamw_scaled_t writes 64 rows of this image per tile, and at an 8-KiB pitch they
-                # all fall on the same HBM channels (w2 / wo at 7B: 281 vs 255 us per update)
-                ld = Np + 64 if (Np * wa.element_size()) % 4096 == 0 else Np
-                wt = torch.empty(K, ld, dtype=act, device=wa.device)[:, :Np]
-            ops.transpose(wp, wt, Np, K, Np)
-            self.store[key] = wt
-            self.tver[key] = ver
-        return self.store[key]
-
-    def _params(self, g: str):
-        """(parameters, [(image key, first row)] in the same order) of image group g."""
-        m = self.eng.m
-        if g.startswith("L"):
-            i = int(g[1:])
-            a, f = m.layers[i].attention, m.layers[i].feed_forward
-            H, Hkv, hd, F = m.n_heads, m.n_kv_heads, m.head_dim, m.ffn
-            return ((a.wq.weight, a.wk.weight, a.wv.weight, a.wo.weight, f.w1.weight, f.w3.weight, f.w2.weight),
-                    ((f"qkv.{i}", 0), (f"qkv.{i}", H * hd), (f"qkv.{i}", (H + Hkv) * hd), (f"wo.{i}", 0), (f"w13.{i}", 0), (f"w13.{i}", F),
-                     (f"w2.{i}", 0)))
-        if g == "out":
-            return (m.output.weight,), (("out", 0),)
-        vp0 = getattr(m.visual_proj, "0")
-        if getattr(m.args, "qformer_tokens", 0):
-            qp0 = getattr(m.qformer_proj, "0")
-            return (vp0.weight, vp0.bias, qp0.weight, qp0.bias), (("vp", 0), ("vp.b", 0), ("vq", 0), ("vq.b", 0))
-        return (vp0.weight, vp0.bias), (("vp", 0), ("vp.b", 0))
-
-    def _key(self, ps) -> tuple:
-        return tuple(param_state_key(q) for q in ps) + (self.eng.act, str(self.eng.m._device))
-
-    def groups(self):
-        m = self.eng.m
-        return [f"L{i}" for i in range(m.n_layers)] + ["out"] + (["vp"] if getattr(m, "visual_proj", None) is not None else [])
-
-    def sink(self, p) -> Optional[torch.Tensor]:
-        """bf16 destination of parameter p inside its (already built) forward image, or None."""
-        if self.eng.act != torch.bfloat16:
-            return None
-        if self._sinks is None:
-            self._sinks = {}
-            for g in self.groups():
-                ps, where = self._params(g)
-                for q, (key, row) in zip(ps, where):
-                    self._sinks[id(q)] = (key, row)
-        ent = self._sinks.get(id(p))
-        if ent is None:
-            return None
-        img = self.store.get(ent[0])
-        if img is None or img.dtype != torch.bfloat16:
-            return None
-        return img[ent[1]:ent[1] + p.shape[0]] if img.dim() == 2 else img
-
-    def sink_t(self, p):
-        """(columns of parameter p inside the transposed image of its fused matrix [K, Np], Np) -- only once that image exists (the
-        first backward built it) and p is a 64-aligned block of it."""
-        if self.eng.act != torch.bfloat16 or p.dim() != 2 or (p.shape[0] & 63) or (p.shape[1] & 63):
-            return None
-        self.sink(p)                                   # (builds the parameter -> (key, row) map)
-        ent = self._sinks.get(id(p))
-        if ent is None or ent[0].endswith(".b"):
-            return None
-        wt = self.store.get(ent[0] + ".t")
-        if wt is None or wt.dtype != torch.bfloat16 or wt.dim() != 2 or wt.shape[0] != p.shape[1] or ent[1] + p.shape[0] > wt.shape[1] \
-                or (ent[1] & 3) or self.tver.get(ent[0] + ".t") is None:
-            return None
-        return wt[:, ent[1]:ent[1] + p.shape[0]], int(wt.stride(0))
-
-    def adopted(self, written_ids, written_t_ids=()) -> None:
-        """The optimizer wrote the bf16 values of these parameters into their images: groups written completely are current (and
-        the transposed image of a fused matrix whose every parameter also went through ``a3v_adamw_scaled_t``)."""
-        for g in self.groups():
-            ps, where = self._params(g)
-            if g in self.ver and all(id(q) in written_ids for q in ps):
-                old = self.ver[g]
-                self.ver[g] = self._key(ps)
-                for key in {k for k, _ in where}:
-                    if self.tver.get(key + ".t") == old and all(id(q) in written_t_ids for q, (k, _) in zip(ps, where) if k == key):
-                        self.tver[key + ".t"] = self.ver[g]
-
-    def recompute_backward(self, i: int) -> None:
-        """Layer i is about to be recomputed and back-propagated (persistent images: nothing to prepare)."""
-
-    def nbytes(self, head: bool = True) -> int:
-        seen = {}
-        for k, t in self.store.items():
-            g = self._group(k)
-            if g.startswith("L") or (head and g == "out"):
-                st = t.untyped_storage()
-                seen[st.data_ptr()] = st.nbytes()
-        return sum(seen.values())
-
-    def __getitem__(self, key: str) -> torch.Tensor:
-        eng, m = self.eng, self.eng.m
-        g = self._group(key)
-        ps, _ = self._params(g)
-        if g.startswith("L"):
-            i = int(g[1:])
-        ver = self._key(ps)
-        if self.ver.get(g) != ver:
-            with torch.no_grad():
-                if g.startswith("L"):
-                    self._both(f"qkv.{i}", self._fused(ps[0:3]))
-                    self._both(f"wo.{i}", self._fused(ps[3:4]))
-                    self._both(f"w13.{i}", self._fused(ps[4:6]))
-                    self._both(f"w2.{i}", self._fused(ps[6:7]))
-                elif g == "out":
-                    self._both("out", self._fused(ps[0:1]))
-                else:
-                    self._both("vp", ps[0])
-                    self.store["vp.b"] = ps[1].to(eng.act)
-                    if len(ps) == 4:
-                        self._both("vq", ps[2])
-                        self.store["vq.b"] = ps[3].to(eng.act)
-            self.ver[g] = ver
-        if key.endswith(".t"):
-            return self._transposed(key, ver)
-        return self.store[key]
-
-
-class _Nf4Images(_Images):
-    """The same keys over an NF4 base (QLoRA): ``qkv.i`` / ``wo.i`` / ``w13.i`` / ``w2.i`` (+ ``.x`` ``.y`` ``.yT`` ``.t``) are views of ONE
-    scratch per group kind, shared by all layers and shaped exactly like the persistent images of the bf16 engine (so the GEMMs run
-    the same plans on the same bits); ``out`` / ``out.t`` have a scratch of their own, filled once.  A request for another layer than the
-    resident one drops the kind's contents; an orientation is filled on first request by a3v_dequantize_nf4_images (one call per original
-    module, into its row / column window).  In the backward of a recomputed block the forward image and the transposed one are both
-    needed: ``recompute_backward`` fills them by ONE call.  The dequantiser writes only the N x K window, so the adapter blocks in the tails survive a
-    fill; they are copied there from the engine's persistent per-layer A / B / A^T images when the layer or the adapter version changed.
-    The projector images (group ``vp``) are the parent's."""
-
-    _MODS = {"qkv": ("attention.wq", "attention.wk", "attention.wv"), "wo": ("attention.wo",),
-             "w13": ("feed_forward.w1", "feed_forward.w3"), "w2": ("feed_forward.w2",)}
-    _TARGET = {"": "d", "x": "d", "y": "d", "yT": "yT", "t": "t"}
-
-    def __init__(self, eng: "TrainEngine"):
-        super().__init__(eng)
-        assert eng.act == torch.bfloat16, "an NF4 base trains under --precision bf16 (the dequantised images are bf16)"
-        self.kinds: Dict[str, dict] = {}
-
-    def groups(self):                         # the parameter-backed groups (optimizer sinks, adoption): the projector only
-        return ["vp"] if getattr(self.eng.m, "visual_proj", None) is not None else []
-
-    def nbytes(self, head: bool = True) -> int:
-        return sum(t.untyped_storage().nbytes() for kind, st in self.kinds.items() if head or kind != "out" for t in st["buf"].values())
-
-    def _entries(self, kind: str, i: int):
-        q4 = self.eng.m._q4
-        return [q4["output"]] if kind == "out" else [q4[f"layers.{i}.{nm}"] for nm in self._MODS[kind]]
-
-    def _state(self, kind: str) -> dict:
-        st = self.kinds.get(kind)
-        if st is None:
-            ent = self._entries(kind, 0)
-            st = self.kinds[kind] = dict(N=sum(e[2][0] for e in ent), K=ent[0][2][1], ext=self.eng._kext_cols(kind + ".0"), layer=None,
-                                         valid=set(), tails={}, buf={})
-        return st
-
-    def _buffer(self, st: dict, target: str) -> torch.Tensor:
-        b = st["buf"].get(target)
-        if b is None:
-            N, K, ext = st["N"], st["K"], st["ext"]
-            dev = self.eng.m._device
-            if target == "d":                 # [[W, B], [A, 0]] (or plain W): zero once, the corner and the pads are never written again
-                b = torch.zeros(N + ext, K + ext, dtype=torch.bfloat16, device=dev)
-            elif target == "yT":              # [W^T | A^T]
-                b = torch.zeros(K, N + ext, dtype=torch.bfloat16, device=dev)
-            else:                             # W^T [K, N padded to 64], row pitch as _Images._transposed
-                Np = _pad64(N)
-                ld = Np + 64 if (Np * 2) % 4096 == 0 else Np
-                b = torch.zeros(K, ld, dtype=torch.bfloat16, device=dev)[:, :Np]
-            st["buf"][target] = b
-        return b
-
-    def _fill(self, kind: str, i: int, st: dict, targets) -> None:
-        wd = self._buffer(st, "d") if "d" in targets else None
-        for tt in [t for t in ("yT", "t") if t in targets] or [None]:
-            wt = self._buffer(st, tt) if tt is not None else None
-            row = 0
-            for q, sc, (n, k) in self._entries(kind, i):
-                assert row % 8 == 0, "module rows must keep the 16-B alignment of the transposed window"
-                ops.dequantize_nf4_images(q, sc, wd=None if wd is None else wd[row:row + n, :k],
-                                          wt=None if wt is None else wt[:, row:row + n])
-                row += n
-            wd = None                          # (a second transposed target re-reads the codes; the forward image is written once)
-        st["valid"] |= set(targets)
-
-    def recompute_backward(self, i: int) -> None:
-        """The backward of a recomputed block reads the forward image of each of its GEMMs, then the image of its input gradient:
-        both orientations from one read of the codes.  (Only a saving: an orientation this misses is filled on its first request.)"""
-        eng = self.eng
-        with torch.no_grad():
-            for kind in self._MODS:
-                st = self._state(kind)
-                if st["layer"] != i:
-                    st["layer"], st["valid"], st["tails"] = i, set(), {}
-                if st["ext"]:
-                    bwd = "yT" if eng._nt_dgrad(f"{kind}.{i}") else "d"
-                else:
-                    bwd = "d" if eng.nn_dgrad else "t"
-                need = {"d", bwd} - st["valid"]
-                if need:
-                    self._fill(kind, i, st, need)
-
-    def _place_tails(self, kind: str, i: int, st: dict, target: str) -> None:
-        eng = self.eng
-        li = eng._lora_step_images()
-        ver = eng._li_ver
-        # identity on purpose: _lora_step_images / adapters_adopted bind a NEW tuple to _li_ver whenever the adapters changed and keep
-        # the same object otherwise; a miss only copies the blocks again
-        if st["tails"].get(target) is ver:
-            return
-        N, K, ext = st["N"], st["K"], st["ext"]
-        key = f"{kind}.{i}"
-        if target == "d":
-            full = st["buf"]["d"]
-            full[:N, K:].copy_(li[key + ".B"])
-            full[N:, :K].copy_(li[key + ".A"])
-        else:
-            st["buf"]["yT"][:, N:].copy_(li[key + ".At"][:K])
-        st["tails"][target] = ver
-
-    def __getitem__(self, key: str) -> torch.Tensor:
-        if self._group(key) == "vp":
-            return super().__getitem__(key)
-        parts = key.split(".")
-        if parts[0] == "out":
-            kind, i, suffix = "out", 0, ".".join(parts[1:])
-        else:
-            kind, i, suffix = parts[0], int(parts[1]), ".".join(parts[2:])
-        target = self._TARGET[suffix]
-        eng = self.eng
-        st = self._state(kind)
-        with torch.no_grad():
-            if st["layer"] != i:
-                st["layer"], st["valid"], st["tails"] = i, set(), {}
-            if target not in st["valid"]:
-                self._fill(kind, i, st, {target})
-            if st["ext"] and target in ("d", "yT"):
-                self._place_tails(kind, i, st, target)
-        b = st["buf"][target]
-        N, K = st["N"], st["K"]
-        if target != "d":
-            return b
-        return {"": b[:N, :K], "x": b[:N], "y": b[:, :K]}[suffix]
 
 
 class _StepLoss(torch.autograd.Function):
