@@ -38,6 +38,8 @@ __device__ __forceinline__ void swiglu_bwd_pair(float g, float u, float da, floa
   dg = da * u * (sig * (1.f + g * (1.f - sig)));
   du = da * (g * sig);
 }
+// x * sigmoid(x) with v_rcp_f32 (1 ulp) instead of the IEEE division sequence: the SwiGLU epilogues of the GEMMs and of the decode GEMVs
+__device__ __forceinline__ float silu(float x) { return x * __builtin_amdgcn_rcpf(1.f + __expf(-x)); }
 // round-trip: the value a bf16 store of v would hold
 __device__ __forceinline__ float rbf(float v) { return (float)((bf16_t)v); }
 
@@ -230,6 +232,8 @@ int a3v_gemv_fused(const void* A, int64_t lda, const void* W, int64_t ldw, const
                    float* ssq_out, int rope, const float* cos_sin, void* k_cache, void* vt_cache, int H, int Hkv, int hd,
                    int Smax, int pos, void* ws, void* stream);
 bool a3v_gemv_supported(int M, int N, int K, int epilogue, int w8);
+// compute units of the current device rounded down to whole XCD rounds (a3v_gemm.hip; 256 without a device): the GEMM and GEMV planners' `cus`
+int a3v_cu_count();
 int a3v_attention_decode_fused(const void* q, const void* k, const void* vt, void* out, int B, int Sk, int H, int Hkv, int hd,
                                const int64_t* strides, float* scratch, int* counters, void* stream);
 // internal (a3v_train.hip): bf16 transposes of n_out x n_in matrices [R, C] -> [C, Rpad] in one launch

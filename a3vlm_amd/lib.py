@@ -58,6 +58,7 @@ SIGNATURES = {
     "a3v_splitk_reduce": (I, [P, I, I, I, P, L, I, I, P]),
     "a3v_gemm_skinny_split": (I, [I, I, I]),
     "a3v_gemm_skinny_ws_bytes": (L, [I, I, I]),
+    "a3v_gemv_plan": (I, [I, I, I, I, I, I, I, I, I, I, P]),
     "a3v_gemm_skinny_fp8": (I, [P, L, P, L, P, P, L, I, I, I, P, L, I, P, P]),
     "a3v_quantize_nf4_ws_bytes": (L, [I, I]),
     "a3v_quantize_nf4": (I, [P, I, I, P, P, P, P]),

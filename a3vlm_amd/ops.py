@@ -181,18 +181,22 @@ def gemm_skinny_workspace(M: int, N: int, K: int, device) -> "torch.Tensor":
     return torch.zeros((gemm_skinny_ws_bytes(M, N, K) + 3) // 4, dtype=torch.float32, device=device)
 
 
-def gemm_skinny(a, w, out, partial, *, residual=None, epilogue: int = 0):
-    _dev(a, w, out, partial, residual)
+def _gemm_skinny(name, a, w, scales, out, workspace, residual, epilogue):
+    """The shared body of gemm_skinny / _fp8 / _nf4: one call of the C-ABI entry `name` (scales: None for bf16 weights)."""
+    _dev(a, w, scales, out, workspace, residual)
     M, K = a.shape
     N = w.shape[0]
-    if partial.numel() * partial.element_size() < gemm_skinny_ws_bytes(M, N, K):
+    if workspace.numel() * workspace.element_size() < gemm_skinny_ws_bytes(M, N, K):
         raise ValueError("gemm_skinny workspace too small (a3v_gemm_skinny_ws_bytes)")
     ep = epilogue | (EPI_RESIDUAL if residual is not None else 0)
-    rc = _l.load().a3v_gemm_skinny(_p(a), a.stride(0), _p(w), w.stride(0), _p(out), out.stride(0), M, N, K,
-                                   _p(residual), residual.stride(0) if residual is not None else 0, ep,
-                                   _p(partial), _stream())
-    _l.check(rc, f"a3v_gemm_skinny(M={M},N={N},K={K},epi={ep})")
+    rc = getattr(_l.load(), name)(_p(a), a.stride(0), _p(w), w.stride(0), *([] if scales is None else [_p(scales)]), _p(out), out.stride(0),
+                                  M, N, K, _p(residual), residual.stride(0) if residual is not None else 0, ep, _p(workspace), _stream())
+    _l.check(rc, f"{name}(M={M},N={N},K={K},epi={ep})")
     return out
+
+
+def gemm_skinny(a, w, out, partial, *, residual=None, epilogue: int = 0):
+    return _gemm_skinny("a3v_gemm_skinny", a, w, None, out, partial, residual, epilogue)
 
 
 def quantize_rows_fp8(x, q, scales, norm_w=None, eps: float = 0.0):
@@ -234,17 +238,8 @@ def gemm_qkv_rope_fp8(xq, sx, wq, sw, qkv, k_cache, vt_cache, cos_sin, B, S, H, 
 
 def gemm_skinny_fp8(a, wq, wscale, out, workspace, *, residual=None, epilogue: int = 0):
     """out = epilogue((a . float(wq)^T) * wscale): weight-only fp8 (torch.float8_e4m3fn / uint8 bytes) decode GEMV."""
-    _dev(a, wq, wscale, out, workspace, residual)
-    M, K = a.shape
-    N = wq.shape[0]
-    assert wq.element_size() == 1 and wscale.dtype == torch.float32 and wscale.numel() == N
-    if workspace.numel() * workspace.element_size() < gemm_skinny_ws_bytes(M, N, K):
-        raise ValueError("gemm_skinny workspace too small (a3v_gemm_skinny_ws_bytes)")
-    ep = epilogue | (EPI_RESIDUAL if residual is not None else 0)
-    rc = _l.load().a3v_gemm_skinny_fp8(_p(a), a.stride(0), _p(wq), wq.stride(0), _p(wscale), _p(out), out.stride(0), M, N, K,
-                                       _p(residual), residual.stride(0) if residual is not None else 0, ep, _p(workspace), _stream())
-    _l.check(rc, f"a3v_gemm_skinny_fp8(M={M},N={N},K={K},epi={ep})")
-    return out
+    assert wq.element_size() == 1 and wscale.dtype == torch.float32 and wscale.numel() == wq.shape[0]
+    return _gemm_skinny("a3v_gemm_skinny_fp8", a, wq, wscale, out, workspace, residual, epilogue)
 
 
 def quantize_nf4(w, q=None, scales=None, ws=None):
@@ -289,17 +284,9 @@ def dequantize_nf4_images(q, scales, wd=None, wt=None):
 
 def gemm_skinny_nf4(a, q, scales, out, workspace, *, residual=None, epilogue: int = 0):
     """out = epilogue(sum_b s_b * (a . NF4[q])^T): weight-only NF4 decode GEMV (M <= 16, K % 256 == 0)."""
-    _dev(a, q, scales, out, workspace, residual)
-    M, K = a.shape
-    N = q.shape[0]
+    N, K = q.shape[0], a.shape[1]
     assert q.dtype == torch.uint8 and q.shape[1] * 2 == K and scales.dtype == torch.float32 and scales.is_contiguous() and scales.numel() == N * K // 64
-    if workspace.numel() * workspace.element_size() < gemm_skinny_ws_bytes(M, N, K):
-        raise ValueError("gemm_skinny workspace too small (a3v_gemm_skinny_ws_bytes)")
-    ep = epilogue | (EPI_RESIDUAL if residual is not None else 0)
-    rc = _l.load().a3v_gemm_skinny_nf4(_p(a), a.stride(0), _p(q), q.stride(0), _p(scales), _p(out), out.stride(0), M, N, K,
-                                       _p(residual), residual.stride(0) if residual is not None else 0, ep, _p(workspace), _stream())
-    _l.check(rc, f"a3v_gemm_skinny_nf4(M={M},N={N},K={K},epi={ep})")
-    return out
+    return _gemm_skinny("a3v_gemm_skinny_nf4", a, q, scales, out, workspace, residual, epilogue)
 
 
 def rmsnorm(x, w, out, eps: float):

@@ -196,6 +196,27 @@ int a3v_splitk_reduce(const float* partial, int S, int M, int N, void* out, int6
  * a3v_gemm_skinny_split reports the split-K factor used.  Epilogues: NONE, RESIDUAL, SWIGLU, OUT_F32. */
 int a3v_gemm_skinny_split(int M, int N, int K);
 int64_t a3v_gemm_skinny_ws_bytes(int M, int N, int K);
+/* Which kernel a3v_gemm_skinny / _fp8 / _nf4 and the decode step's fused GEMVs launch for a problem, on what grid: the plan those
+ * entry points execute, computed by the same host code from values alone (no device, no pointer; A3V_GEMV_KQ applies).  epilogue as
+ * passed to the entry point; format: the weight image; prologue / rope / ssq: the decode step's fused forms (RMSNorm on the way in,
+ * RoPE + KV-cache write, sums of squares on the way out); inblock_ok: A is 16-byte aligned with lda % 8 == 0 and so are the norm
+ * weights, if any; cus: the device's compute units (256 on MI355X).  Writes A3V_GEMV_PLAN_INTS values into `plan` -- kernel, activation
+ * rows of the template form (8 / 16), prologue, format, grid x, block size, dynamic LDS bytes, K slices across blocks (what
+ * a3v_gemm_skinny_split reports), 128-k blocks of K, 64-row groups of W, 128-k blocks of A per slice, K slices as launched (inside the
+ * block for A3V_GEMV_K_KQ), k per wave of the direct kernels -- and returns the kernel (A3V_GEMV_K_*), A3V_ERR_SHAPE where no kernel
+ * can run the problem, or A3V_ERR_ARG.  The direct kernels exist for a3v_gemm_skinny alone: the other entry points answer
+ * A3V_ERR_SHAPE where this names one.  Shapes that the entry point itself refuses are not checked here. */
+enum { A3V_GEMV_BF16 = 0, A3V_GEMV_FP8 = 1, A3V_GEMV_NF4 = 2 };
+enum { A3V_GEMV_PLAN_INTS = 13 };
+enum {
+  A3V_GEMV_K_DMA = 0,           /* gemv_dma_bf16_kernel<arows, prologue, fp8, nf4>: K slices across blocks   */
+  A3V_GEMV_K_KQ,                /* gemv_kq_bf16_kernel<prologue>: K slices inside the block                  */
+  A3V_GEMV_K_DIRECT1,           /* gemm_skinny1_bf16_kernel<1>: direct-to-VGPR                               */
+  A3V_GEMV_K_DIRECT2,           /* gemm_skinny1_bf16_kernel<2>: the same on gate / up row pairs (SwiGLU)     */
+  A3V_GEMV_K_COUNT
+};
+int a3v_gemv_plan(int M, int N, int K, int epilogue, int format, int prologue, int rope, int ssq, int inblock_ok, int cus,
+                  int32_t* plan);
 /* Weight-only fp8 form (BASELINE config 5): Wq [N,K] OCP e4m3fn bytes (row stride ldw in BYTES,
  * % 16 == 0), wscale [N] fp32 per-row dequantisation scales; C = epilogue((A . float(Wq)^T) * wscale), K % 256 == 0.
  * The reference's quantised path is CUDA-only bitsandbytes NF4 (util/quant.py:95-163): there is NO reference oracle for

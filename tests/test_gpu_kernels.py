@@ -184,6 +184,31 @@ def test_gemm_skinny_swiglu_large(M, F_, K):
     assert_close(out, want, rtol=2 ** -6, atol=4e-3, what="skinny swiglu large")
 
 
+@pytest.mark.parametrize("M,N,K,swiglu,kernel", [(3, 48, 96, False, 2), (8, 64, 128, True, 3), (12, 256, 512, False, 0)])
+def test_gemm_skinny_direct_kernels_and_the_16_row_dma_form(M, N, K, swiglu, kernel):
+    """The outcomes of the decode GEMV plan (a3v_gemv_plan) no other case here reaches: K % 128 != 0 -> the direct-to-VGPR kernel, SwiGLU
+    without a split -> its gate / up pair form, 9..16 rows with a short K -> the 16-row LDS-DMA form.  References and tolerances of
+    test_gemm_skinny / test_gemm_skinny_swiglu_large; the arrival counters are left zero."""
+    import ctypes
+    from a3vlm_amd import lib as _l4
+    plan = (ctypes.c_int32 * 13)()
+    assert _l4.load().a3v_gemv_plan(M, N, K, ops.EPI_SWIGLU if swiglu else 0, 0, 0, 0, 0, 1, 256, plan) == kernel
+    assert kernel != 0 or plan[1] == 16
+    a = rt(gen(M, K, seed=23))
+    part = ops.gemm_skinny_workspace(M, N, K, DEV)
+    if swiglu:
+        w1, w3 = rt(gen(N // 2, K, seed=24, scale=0.03)), rt(gen(N // 2, K, seed=25, scale=0.03))
+        out = torch.empty(M, N // 2, dtype=BF, device=DEV)
+        ops.gemm_skinny(a.to(BF).to(DEV), pack_w13(w1, w3).to(BF).to(DEV), out, part, epilogue=ops.EPI_SWIGLU)
+        assert_close(out, rt(rt(F.silu(rt(a @ w1.t()))) * rt(a @ w3.t())), rtol=2 ** -6, atol=4e-3, what="skinny direct swiglu")
+    else:
+        w = rt(gen(N, K, seed=24, scale=0.05))
+        out = torch.empty(M, N, dtype=BF, device=DEV)
+        ops.gemm_skinny(a.to(BF).to(DEV), w.to(BF).to(DEV), out, part)
+        assert_close(out, a @ w.t(), rtol=2 ** -7, atol=2e-3 * math.sqrt(K) * 0.05 + 1e-3, what="skinny direct / 16-row")
+    assert int(part[:4096].view(torch.int32).abs().sum()) == 0
+
+
 @pytest.mark.parametrize("M,N,K", [(70, 96, 64), (64, 64, 16), (130, 200, 640)])
 def test_gemm_f32(M, N, K):
     a, w, bias, res = gen(M, K, seed=16), gen(N, K, seed=17, scale=0.1), gen(N, seed=18), gen(M, N, seed=19)
@@ -1085,15 +1110,23 @@ def test_gemv_k_slices_inside_the_block_equal_the_across_blocks_form(M, N, K, ep
     for mode in ("2", "0"):
         err = float((outs[mode] - y).abs().max() / y.abs().max())
         assert err < 2e-2, (mode, err)
-    same_plan = not (epi == "swiglu" and L_skinny_split(M, N, K) > 6)
-    if same_plan:
+    plans = {}
+    for mode in ("2", "0"):
+        with _l2.env(A3V_GEMV_KQ=mode):
+            plans[mode] = L_gemv_plan(M, N, K, flags)
+    assert plans["2"][0] == 1 and plans["0"][0] == 0                    # in-block against across-blocks
+    if epi != "swiglu" or plans["2"][11] == plans["0"][11]:              # the K slices as launched (SwiGLU in the block: at most 6)
         assert torch.equal(outs["2"], outs["0"])
     assert int((ws.view(torch.int32)[: 4096] != 0).sum()) == 0          # the arrival counters are left at zero by both forms
 
 
-def L_skinny_split(M, N, K):
+def L_gemv_plan(M, N, K, epilogue):
+    """The A3V_GEMV_PLAN_INTS values of a3v_gemv_plan for a public bf16 call with an aligned A on 256 CUs."""
+    import ctypes
     from a3vlm_amd import lib as _l3
-    return int(_l3.load().a3v_gemm_skinny_split(M, N, K))
+    plan = (ctypes.c_int32 * 13)()
+    assert _l3.load().a3v_gemv_plan(M, N, K, epilogue, 0, 0, 0, 0, 1, 256, plan) >= 0
+    return list(plan)
 
 
 def test_wave_reductions_on_the_valu_equal_the_shuffle_forms_bit_for_bit():

@@ -111,7 +111,7 @@ def _perm(s0: int, s1: int, sel: int) -> int:
 
 
 def _gemv_tables():
-    src = open(os.path.join(ROOT, "a3vlm_amd", "csrc", "a3v_gemm.hip")).read()
+    src = open(os.path.join(ROOT, "a3vlm_amd", "csrc", "a3v_gemv.hip")).read()
     body = src[src.index("bf16x8 nf4_bf16x8(uint32_t x)"):]
     body = body[:body.index("return __builtin_bit_cast(bf16x8, r)")]
     he = re.search(r"he = look\(ie, me, (0x\w+)u, (0x\w+)u, (0x\w+)u, (0x\w+)u\)", body).groups()
@@ -120,7 +120,7 @@ def _gemv_tables():
 
 
 def test_gemv_code_book_lookup_emulated():
-    """nf4_bf16x8 (a3v_gemm.hip) restated with its own constants: every code in every position gives bf16(NF4[code])."""
+    """nf4_bf16x8 (a3v_gemv.hip) restated with its own constants: every code in every position gives bf16(NF4[code])."""
     (h0a, h0b, h1a, h1b), (l0a, l0b, l1a, l1b) = _gemv_tables()
     M = 0xFFFFFFFF
 
@@ -147,7 +147,7 @@ def test_gemv_code_book_lookup_emulated():
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
 def test_nf4_gemv_instantiations_use_no_scratch(tmp_path):
-    src = os.path.join(ROOT, "a3vlm_amd", "csrc", "a3v_gemm.hip")
+    src = os.path.join(ROOT, "a3vlm_amd", "csrc", "a3v_gemv.hip")
     r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=on", "--cuda-device-only",
                         "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", str(tmp_path / "g.o")],
                        capture_output=True, text=True, timeout=900)
