@@ -8,12 +8,14 @@ namespace {
 
 // ---------------------------------------------------------------- RMSNorm
 // model/components.py:39,52-53: (x.float() * rsqrt(mean(x^2)+eps)).type_as(x) * weight
-template <typename TX, typename TW, typename TY>
+// IDX (a3v_rmsnorm_rows, an instantiation of its own: the plain kernel is the code it was): y row i = the norm of x row row_idx[i]
+template <typename TX, typename TW, typename TY, bool IDX = false>
 __global__ __launch_bounds__(256) void rmsnorm_kernel(const TX* __restrict__ x, int64_t ldx, const TW* __restrict__ w,
-                                                      TY* __restrict__ y, int64_t ldy, int dim, float eps) {
+                                                      TY* __restrict__ y, int64_t ldy, int dim, float eps,
+                                                      const int32_t* __restrict__ row_idx = nullptr) {
   __shared__ float red[4];
   const int row = blockIdx.x, tid = threadIdx.x;
-  const TX* xr = x + (int64_t)row * ldx;
+  const TX* xr = x + (int64_t)(IDX ? row_idx[row] : row) * ldx;
   TY* yr = y + (int64_t)row * ldy;
   constexpr int MAXV = 4;  // dim <= 256*8*4 = 8192
   float v[MAXV][8];
@@ -821,6 +823,23 @@ extern "C" int a3v_rmsnorm(const void* x, int64_t ldx, const void* w, void* y, i
     case 2: hipLaunchKernelGGL((rmsnorm_kernel<bf16_t, float, bf16_t>), g, b, 0, ST, (const bf16_t*)x, ldx, (const float*)w, (bf16_t*)y, ldy, dim, eps); break;
     default: return A3V_ERR_DTYPE;
   }
+  A3V_LAUNCH_CHECK();
+  return A3V_OK;
+}
+
+// y[i] = rmsnorm(x[row_idx[i]]) * w for i < rows: the rows of a list, gathered by the pass that normalises them (the caller keeps
+// every index inside x).  The training step's dtypes: bf16 x and y, bf16 or fp32 weight.
+extern "C" int a3v_rmsnorm_rows(const void* x, int64_t ldx, const int32_t* row_idx, const void* w, void* y, int64_t ldy, int rows, int dim,
+                                float eps, int x_dtype, int w_dtype, int y_dtype, void* stream) {
+  if (!x || !w || !y || !row_idx || rows <= 0) return A3V_ERR_ARG;
+  if (dim % 8 || dim > 8192 || ldx % 8 || ldy % 8) return A3V_ERR_SHAPE;
+  dim3 g(rows), b(256);
+  if (x_dtype != A3V_BF16 || y_dtype != A3V_BF16) return A3V_ERR_DTYPE;
+  if (w_dtype == A3V_BF16)
+    hipLaunchKernelGGL((rmsnorm_kernel<bf16_t, bf16_t, bf16_t, true>), g, b, 0, ST, (const bf16_t*)x, ldx, (const bf16_t*)w, (bf16_t*)y, ldy, dim, eps, row_idx);
+  else if (w_dtype == A3V_F32)
+    hipLaunchKernelGGL((rmsnorm_kernel<bf16_t, float, bf16_t, true>), g, b, 0, ST, (const bf16_t*)x, ldx, (const float*)w, (bf16_t*)y, ldy, dim, eps, row_idx);
+  else return A3V_ERR_DTYPE;
   A3V_LAUNCH_CHECK();
   return A3V_OK;
 }

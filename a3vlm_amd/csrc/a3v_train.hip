@@ -76,7 +76,8 @@ __global__ __launch_bounds__(256) void transpose_bf16_vec_kernel(const bf16_t* _
 template <typename TA, int RPB, typename TS = float>     // TS: dtype of the residual stream (x and the accumulated dh)
 __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const TS* __restrict__ x, int64_t ldx, const float* __restrict__ w,
                                                           const TA* __restrict__ dy, int64_t lddy, TS* __restrict__ dh,
-                                                          int64_t lddh, float* __restrict__ dw, int rows, int dim, float eps) {
+                                                          int64_t lddh, float* __restrict__ dw, int rows, int dim, float eps,
+                                                          const int32_t* __restrict__ row_idx = nullptr) {
   __shared__ float red[8];
   const int tid = threadIdx.x;
   constexpr int MAXC = 32;                // dim <= 8192
@@ -87,7 +88,8 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const TS* __restrict__
   for (int rr = 0; rr < RPB; ++rr) {
     const int row = row0 + rr;
     if (row >= rows) break;
-    const TS* xr = x + (int64_t)row * ldx;
+    const int srow = row_idx ? row_idx[row] : row;        // (row_idx: x and dh at row row_idx[i], dy at row i)
+    const TS* xr = x + (int64_t)srow * ldx;
     const TA* dyr = dy + (int64_t)row * lddy;
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
@@ -107,7 +109,7 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const TS* __restrict__
     s2 = red[4] + red[5] + red[6] + red[7];
     const float r = rsqrtf(s1 / (float)dim + eps);
     const float k2 = r * r * r * s2 / (float)dim;
-    TS* dhr = dh + (int64_t)row * lddh;
+    TS* dhr = dh + (int64_t)srow * lddh;
 #pragma unroll
     for (int i = 0; i < MAXC; ++i) {
       const int c = tid + i * 256;
@@ -134,7 +136,9 @@ template <typename TA, int RPB, int MAXV, bool PART, typename TS = float>     //
 __global__ __launch_bounds__(256) void rmsnorm_bwd_vec_kernel(const TS* __restrict__ x, int64_t ldx, const float* __restrict__ w,
                                                               const TA* __restrict__ dy, int64_t lddy, TS* __restrict__ dh,
                                                               int64_t lddh, float* __restrict__ dw, int rows, int dim, float eps,
-                                                              bf16_t* __restrict__ dh_bf = nullptr, int64_t ld_bf = 0) {
+                                                              bf16_t* __restrict__ dh_bf = nullptr, int64_t ld_bf = 0,
+                                                              const int32_t* __restrict__ row_idx = nullptr) {
+  // row_idx (a3v_rmsnorm_bwd_rows_bf16): x and dh at row row_idx[i], dy at row i; the weight-gradient partials as without it
   __shared__ float red[2][8];
   const int tid = threadIdx.x;
   const int nv = dim >> 2;
@@ -153,13 +157,14 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_vec_kernel(const TS* __restri
   auto fetch = [&](int row) {
     if constexpr (PF) {
       const int rc = row < rows ? row : rows - 1;
+      const int sc = row_idx ? row_idx[rc] : rc;
 #pragma unroll
       for (int i = 0; i < MAXV; ++i) {
         const int c = tid + i * 256;
         const int cc = c < nv ? c : 0;
-        nx[i] = *reinterpret_cast<const bf16x4*>(reinterpret_cast<const bf16_t*>(x) + (int64_t)rc * ldx + 4 * cc);
+        nx[i] = *reinterpret_cast<const bf16x4*>(reinterpret_cast<const bf16_t*>(x) + (int64_t)sc * ldx + 4 * cc);
         ng[i] = *reinterpret_cast<const bf16x4*>(reinterpret_cast<const bf16_t*>(dy) + (int64_t)rc * lddy + 4 * cc);
-        nh[i] = *reinterpret_cast<const bf16x4*>(reinterpret_cast<const bf16_t*>(dh) + (int64_t)rc * lddh + 4 * cc);
+        nh[i] = *reinterpret_cast<const bf16x4*>(reinterpret_cast<const bf16_t*>(dh) + (int64_t)sc * lddh + 4 * cc);
       }
     }
   };
@@ -167,7 +172,8 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_vec_kernel(const TS* __restri
   for (int rr = 0; rr < RPB; ++rr) {
     const int row = row0 + rr;
     if (row >= rows) break;
-    const TS* xr = x + (int64_t)row * ldx;
+    const int srow = row_idx ? row_idx[row] : row;
+    const TS* xr = x + (int64_t)srow * ldx;
     const TA* dyr = dy + (int64_t)row * lddy;
     f32x4 xv[MAXV], gv[MAXV], hv[MAXV];
     float s1 = 0.f, s2 = 0.f;
@@ -213,7 +219,7 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_vec_kernel(const TS* __restri
     s2 = red[pb][4] + red[pb][5] + red[pb][6] + red[pb][7];
     const float r = rsqrtf(s1 / (float)dim + eps);
     const float k2 = r * r * r * s2 / (float)dim;
-    TS* dhr = dh + (int64_t)row * lddh;
+    TS* dhr = dh + (int64_t)srow * lddh;
 #pragma unroll
     for (int i = 0; i < MAXV; ++i) {
       const int c = tid + i * 256;
@@ -593,9 +599,109 @@ __global__ __launch_bounds__(256) void add2d_kernel(T* __restrict__ dst, int64_t
   }
 }
 
+// ------------------------------------------------------------------ labelled rows (the rows the loss reads) and their gather / scatter
+// The ascending list of positions i = b T + t with lab[i] != 0, as stream rows b S + W + t and as head rows i, the labels themselves, and
+// the count.  ONE block walks the labels in chunks of 256 and places each hit by an exclusive scan (ballot inside a wave, the four
+// wave totals through LDS): the order is the position order whatever the timing, no atomics.
+__global__ __launch_bounds__(256) void label_rows_kernel(const int64_t* __restrict__ lab, int total, int T, int W, int S,
+                                                         int32_t* __restrict__ stream_rows, int32_t* __restrict__ head_rows,
+                                                         int64_t* __restrict__ lab_out, int32_t* __restrict__ count) {
+  __shared__ int wtot[2][4];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  int base = 0, pb = 0;
+  for (int i0 = 0; i0 < total; i0 += 256, pb ^= 1) {
+    const int i = i0 + tid;
+    const int64_t v = i < total ? lab[i] : 0;
+    const bool hit = v != 0;
+    const unsigned long long m = __ballot(hit);
+    if (lane == 0) wtot[pb][wv] = __popcll(m);
+    __syncthreads();                          // (double-buffered totals: one barrier per chunk)
+    int off = base;
+    for (int w2 = 0; w2 < wv; ++w2) off += wtot[pb][w2];
+    if (hit) {
+      const int o = off + __popcll(m & ((1ull << lane) - 1ull));      // o <= i < total: inside the caller's buffers
+      const int b = i / T;
+      stream_rows[o] = b * S + W + (i - b * T);
+      head_rows[o] = i;
+      if (lab_out) lab_out[o] = v;
+    }
+    base += wtot[pb][0] + wtot[pb][1] + wtot[pb][2] + wtot[pb][3];
+  }
+  if (tid == 0) *count = base;
+}
+
+// dst[i, :] = src[idx[i], :] in 16-byte pieces (any dtype: the row is ``vecs`` pieces long, leading dimensions in pieces); an index
+// outside [0, src_rows) reads nothing and gives a zero row
+__global__ __launch_bounds__(256) void gather_rows_kernel(const u32x4* __restrict__ src, int64_t lds_, int src_rows, const int32_t* __restrict__ idx,
+                                                          u32x4* __restrict__ dst, int64_t ldd, int vecs) {
+  const int r = idx[blockIdx.x];
+  const bool ok = r >= 0 && r < src_rows;
+  const u32x4* s = src + (int64_t)(ok ? r : 0) * lds_;
+  u32x4* d = dst + (int64_t)blockIdx.x * ldd;
+  for (int c = threadIdx.x; c < vecs; c += 256) d[c] = ok ? s[c] : u32x4{0u, 0u, 0u, 0u};
+}
+
+// dst[idx[i], :] = src[i, :] for the ascending list idx[0 .. n), and every other row of dst[0 .. dst_rows) = 0, in the same launch:
+// one block per DESTINATION row finds its place in the list by bisection (no row is written twice, none is left as it was)
+__global__ __launch_bounds__(256) void scatter_rows_kernel(const u32x4* __restrict__ src, int64_t lds_, const int32_t* __restrict__ idx, int n,
+                                                           u32x4* __restrict__ dst, int64_t ldd, int vecs) {
+  const int r = blockIdx.x;
+  int lo = 0, hi = n;                          // first position with idx[pos] >= r
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (idx[mid] < r) lo = mid + 1; else hi = mid;
+  }
+  const bool ok = lo < n && idx[lo] == r;
+  const u32x4* s = src + (int64_t)(ok ? lo : 0) * lds_;
+  u32x4* d = dst + (int64_t)r * ldd;
+  for (int c = threadIdx.x; c < vecs; c += 256) d[c] = ok ? s[c] : u32x4{0u, 0u, 0u, 0u};
+}
+
 }  // namespace
 
 #define ST ((hipStream_t)stream)
+
+extern "C" int a3v_label_rows(const int64_t* labels, int B, int T, int W, int S, int32_t* stream_rows, int32_t* head_rows,
+                              int64_t* labels_out, int32_t* count_dev, void* stream) {
+  if (!labels || !stream_rows || !head_rows || !count_dev || B <= 0 || T <= 0 || W < 0 || S < W + T) return A3V_ERR_ARG;
+  if ((int64_t)B * S >= (int64_t)1 << 31) return A3V_ERR_SHAPE;
+  hipLaunchKernelGGL(label_rows_kernel, dim3(1), dim3(256), 0, ST, labels, B * T, T, W, S, stream_rows, head_rows, labels_out, count_dev);
+  A3V_LAUNCH_CHECK();
+  return A3V_OK;
+}
+
+static int rows_vec_geometry(const void* a, int64_t lda, const void* b, int64_t ldb, int cols, int dtype, int* vecs, int64_t* va, int64_t* vb) {
+  const int es = dtype == A3V_BF16 ? 2 : dtype == A3V_F32 ? 4 : 0;
+  if (!es) return A3V_ERR_DTYPE;
+  const int per = 16 / es;
+  if (cols <= 0 || cols % per || lda % per || ldb % per || lda < cols || ldb < cols ||
+      ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15))
+    return A3V_ERR_SHAPE;
+  *vecs = cols / per; *va = lda / per; *vb = ldb / per;
+  return A3V_OK;
+}
+
+extern "C" int a3v_gather_rows(const void* src, int64_t ld_src, int src_rows, const int32_t* row_idx, int n, void* dst, int64_t ld_dst,
+                               int cols, int dtype, void* stream) {
+  if (!src || !dst || !row_idx || n <= 0 || src_rows <= 0) return A3V_ERR_ARG;
+  int vecs; int64_t vs, vd;
+  const int rc = rows_vec_geometry(src, ld_src, dst, ld_dst, cols, dtype, &vecs, &vs, &vd);
+  if (rc != A3V_OK) return rc;
+  hipLaunchKernelGGL(gather_rows_kernel, dim3(n), dim3(256), 0, ST, (const u32x4*)src, vs, src_rows, row_idx, (u32x4*)dst, vd, vecs);
+  A3V_LAUNCH_CHECK();
+  return A3V_OK;
+}
+
+extern "C" int a3v_scatter_rows(const void* src, int64_t ld_src, const int32_t* row_idx, int n, void* dst, int64_t ld_dst, int dst_rows,
+                                int cols, int dtype, void* stream) {
+  if (!src || !dst || !row_idx || n <= 0 || dst_rows <= 0) return A3V_ERR_ARG;
+  int vecs; int64_t vs, vd;
+  const int rc = rows_vec_geometry(src, ld_src, dst, ld_dst, cols, dtype, &vecs, &vs, &vd);
+  if (rc != A3V_OK) return rc;
+  hipLaunchKernelGGL(scatter_rows_kernel, dim3(dst_rows), dim3(256), 0, ST, (const u32x4*)src, vs, row_idx, n, (u32x4*)dst, vd, vecs);
+  A3V_LAUNCH_CHECK();
+  return A3V_OK;
+}
 
 extern "C" int a3v_add2d(void* dst, int64_t ld_dst, const void* src, int64_t ld_src, int rows, int cols, int dtype, void* stream) {
   if (!dst || !src || rows <= 0 || cols <= 0) return A3V_ERR_ARG;
@@ -750,7 +856,8 @@ extern "C" int64_t a3v_rmsnorm_bwd_scratch_floats(int rows, int dim) { return (i
 template <typename TS>
 static int rmsnorm_bwd_impl(const TS* x, int64_t ldx, const float* w, const void* dy, int64_t lddy, TS* dh, int64_t lddh,
                             float* dw, float* dw_scratch, int rows, int dim, float eps, int act_dtype, void* stream, bf16_t* dh_bf,
-                            int64_t ld_bf) {
+                            int64_t ld_bf, const int32_t* row_idx = nullptr) {
+  if (row_idx && dh_bf) return A3V_ERR_ARG;
   if (!x || !w || !dy || !dh || rows <= 0) return A3V_ERR_ARG;
   if (dim > 8192) return A3V_ERR_SHAPE;
   constexpr uintptr_t SMASK = sizeof(TS) == 2 ? 7 : 15;
@@ -762,7 +869,7 @@ static int rmsnorm_bwd_impl(const TS* x, int64_t ldx, const float* w, const void
     dim3 gv(nb);
     const bool part = dw && dw_scratch && (reinterpret_cast<uintptr_t>(dw_scratch) & 15) == 0;
     float* dwo = part ? dw_scratch : dw;
-#define A3V_RB(TT, MV, PP) hipLaunchKernelGGL((rmsnorm_bwd_vec_kernel<TT, RV, MV, PP, TS>), gv, dim3(256), 0, ST, x, ldx, w, (const TT*)dy, lddy, dh, lddh, dwo, rows, dim, eps, dh_bf, ld_bf)
+#define A3V_RB(TT, MV, PP) hipLaunchKernelGGL((rmsnorm_bwd_vec_kernel<TT, RV, MV, PP, TS>), gv, dim3(256), 0, ST, x, ldx, w, (const TT*)dy, lddy, dh, lddh, dwo, rows, dim, eps, dh_bf, ld_bf, row_idx)
     if (dim <= 4096) {
       if (act_dtype == A3V_BF16) { if (part) A3V_RB(bf16_t, 4, true); else A3V_RB(bf16_t, 4, false); }
       else { if (part) A3V_RB(float, 4, true); else A3V_RB(float, 4, false); }
@@ -780,8 +887,8 @@ static int rmsnorm_bwd_impl(const TS* x, int64_t ldx, const float* w, const void
   }
   constexpr int RPB = 16;
   dim3 g((rows + RPB - 1) / RPB);
-  if (act_dtype == A3V_BF16) hipLaunchKernelGGL((rmsnorm_bwd_kernel<bf16_t, RPB, TS>), g, dim3(256), 0, ST, x, ldx, w, (const bf16_t*)dy, lddy, dh, lddh, dw, rows, dim, eps);
-  else if (act_dtype == A3V_F32) hipLaunchKernelGGL((rmsnorm_bwd_kernel<float, RPB, TS>), g, dim3(256), 0, ST, x, ldx, w, (const float*)dy, lddy, dh, lddh, dw, rows, dim, eps);
+  if (act_dtype == A3V_BF16) hipLaunchKernelGGL((rmsnorm_bwd_kernel<bf16_t, RPB, TS>), g, dim3(256), 0, ST, x, ldx, w, (const bf16_t*)dy, lddy, dh, lddh, dw, rows, dim, eps, row_idx);
+  else if (act_dtype == A3V_F32) hipLaunchKernelGGL((rmsnorm_bwd_kernel<float, RPB, TS>), g, dim3(256), 0, ST, x, ldx, w, (const float*)dy, lddy, dh, lddh, dw, rows, dim, eps, row_idx);
   else return A3V_ERR_DTYPE;
   A3V_LAUNCH_CHECK();
   if (dh_bf) {
@@ -808,6 +915,15 @@ extern "C" int a3v_rmsnorm_bwd_cast(const float* x, int64_t ldx, const float* w,
 extern "C" int a3v_rmsnorm_bwd_bf16(const void* x, int64_t ldx, const float* w, const void* dy, int64_t lddy, void* dh, int64_t lddh,
                                     float* dw, float* dw_scratch, int rows, int dim, float eps, void* stream) {
   return rmsnorm_bwd_impl<bf16_t>((const bf16_t*)x, ldx, w, dy, lddy, (bf16_t*)dh, lddh, dw, dw_scratch, rows, dim, eps, A3V_BF16, stream, nullptr, 0);
+}
+
+// The same over the rows of an ascending list: dy row i belongs to x row row_idx[i], and the input gradient is accumulated into dh row
+// row_idx[i] (the list holds no row twice: no two blocks touch one dh row; the caller keeps every index inside x and dh)
+extern "C" int a3v_rmsnorm_bwd_rows_bf16(const void* x, int64_t ldx, const int32_t* row_idx, const float* w, const void* dy, int64_t lddy,
+                                         void* dh, int64_t lddh, float* dw, float* dw_scratch, int rows, int dim, float eps, void* stream) {
+  if (!row_idx) return A3V_ERR_ARG;
+  return rmsnorm_bwd_impl<bf16_t>((const bf16_t*)x, ldx, w, dy, lddy, (bf16_t*)dh, lddh, dw, dw_scratch, rows, dim, eps, A3V_BF16, stream, nullptr, 0,
+                                  row_idx);
 }
 
 static int layernorm_bwd_impl(const void* x, int64_t ldx, const float* w, const void* dy, int dy_dtype, int64_t lddy, const int32_t* row_map,

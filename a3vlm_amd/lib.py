@@ -103,6 +103,11 @@ SIGNATURES = {
     "a3v_attention_bwd_mfma": (I, [P, P, L, L, P, L, L, L, P, P, P, P, P, P, P, I, I, I, I, I, I, P]),
     "a3v_embed_bwd": (I, [P, L, P, P, I, I, I, I, I, P]),
     "a3v_rows_sum": (I, [P, L, P, I, I, P, I, P]),
+    "a3v_rmsnorm_rows": (I, [P, L, P, P, P, L, I, I, F, I, I, I, P]),
+    "a3v_rmsnorm_bwd_rows_bf16": (I, [P, L, P, P, P, L, P, L, P, P, I, I, F, P]),
+    "a3v_label_rows": (I, [P, I, I, I, I, P, P, P, P, P]),
+    "a3v_gather_rows": (I, [P, L, I, P, I, P, L, I, I, P]),
+    "a3v_scatter_rows": (I, [P, L, P, I, P, L, I, I, I, P]),
 }
 
 class LlamaLayer(ctypes.Structure):

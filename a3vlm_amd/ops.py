@@ -289,9 +289,16 @@ def gemm_skinny_nf4(a, q, scales, out, workspace, *, residual=None, epilogue: in
     return _gemm_skinny("a3v_gemm_skinny_nf4", a, q, scales, out, workspace, residual, epilogue)
 
 
-def rmsnorm(x, w, out, eps: float):
-    _dev(x, w, out)
+def rmsnorm(x, w, out, eps: float, row_idx=None):
+    """out = rmsnorm(x) * w; ``row_idx`` (int32 [n]): out row i from x row row_idx[i]."""
+    _dev(x, w, out, row_idx)
     rows, dim = x.shape
+    if row_idx is not None:
+        assert row_idx.dtype == torch.int32 and row_idx.is_contiguous() and out.shape[0] == row_idx.numel()
+        rc = _l.load().a3v_rmsnorm_rows(_p(x), x.stride(0), _p(row_idx), _p(w), _p(out), out.stride(0), row_idx.numel(), dim, eps,
+                                        dt(x), dt(w), dt(out), _stream())
+        _l.check(rc, "a3v_rmsnorm_rows")
+        return out
     rc = _l.load().a3v_rmsnorm(_p(x), x.stride(0), _p(w), _p(out), out.stride(0), rows, dim, eps,
                                dt(x), dt(w), dt(out), _stream())
     _l.check(rc, "a3v_rmsnorm")
@@ -432,6 +439,49 @@ def count_valid(labels, n_valid):
     _l.check(rc, "a3v_count_valid")
 
 
+_count_host = {}
+
+
+def label_rows(labels, W: int, S: int, stream_rows, head_rows, labels_out, count) -> int:
+    """The rows the loss reads (a3v_label_rows) into the caller's buffers (room for B T entries each); returns their number, read
+    back through ONE pinned 4-byte copy -- the caller's only wait for the device."""
+    _dev(labels, stream_rows, head_rows, labels_out, count)
+    B, T = labels.shape
+    assert labels.dtype == torch.int64 and labels.is_contiguous() and stream_rows.dtype == torch.int32 and head_rows.dtype == torch.int32
+    assert min(stream_rows.numel(), head_rows.numel()) >= B * T and (labels_out is None or (labels_out.dtype == torch.int64 and labels_out.numel() >= B * T))
+    assert count.dtype == torch.int32 and stream_rows.is_contiguous() and head_rows.is_contiguous()
+    rc = _l.load().a3v_label_rows(_p(labels), B, T, W, S, _p(stream_rows), _p(head_rows), _p(labels_out), _p(count), _stream())
+    _l.check(rc, "a3v_label_rows")
+    host = _count_host.get(count.device)
+    if host is None:
+        host = _count_host[count.device] = torch.empty(1, dtype=torch.int32, pin_memory=True)
+    host.copy_(count, non_blocking=True)
+    torch.cuda.current_stream().synchronize()
+    return int(host[0])
+
+
+def gather_rows(src, row_idx, out):
+    """out[i] = src[row_idx[i]] (bf16 / fp32 rows in 16-byte pieces)."""
+    _dev(src, row_idx, out)
+    n, cols = out.shape
+    assert row_idx.dtype == torch.int32 and row_idx.is_contiguous() and row_idx.numel() == n and src.shape[1] == cols and src.dtype == out.dtype
+    assert src.stride(1) == 1 and out.stride(1) == 1
+    rc = _l.load().a3v_gather_rows(_p(src), src.stride(0), src.shape[0], _p(row_idx), n, _p(out), out.stride(0), cols, dt(src), _stream())
+    _l.check(rc, "a3v_gather_rows")
+    return out
+
+
+def scatter_rows(src, row_idx, out):
+    """out[row_idx[i]] = src[i] for an ascending list without repeats; every other row of out = 0 (written by the same launch)."""
+    _dev(src, row_idx, out)
+    n, cols = src.shape
+    assert row_idx.dtype == torch.int32 and row_idx.is_contiguous() and row_idx.numel() == n and out.shape[1] == cols and src.dtype == out.dtype
+    assert src.stride(1) == 1 and out.stride(1) == 1 and n <= out.shape[0]
+    rc = _l.load().a3v_scatter_rows(_p(src), src.stride(0), _p(row_idx), n, _p(out), out.stride(0), out.shape[0], cols, dt(src), _stream())
+    _l.check(rc, "a3v_scatter_rows")
+    return out
+
+
 def cross_entropy(logits, labels, row_loss, dlogits=None, n_valid=None, grad_scale: float = 1.0):
     _dev(logits, labels, row_loss, dlogits, n_valid)
     rows, V = logits.shape
@@ -500,11 +550,16 @@ def add2d(dst, src):
 _rb_scratch = {}
 
 
-def rmsnorm_bwd(x, w, dy, dh, dw, eps, dh_lowp=None):
-    """dh += d(rmsnorm)/dx . dy (fp32 stream), dw += ...; ``dh_lowp``: the updated dh also as bf16 (the next GEMMs' operand)."""
-    _dev(x, w, dy, dh, dw, dh_lowp)
+def rmsnorm_bwd(x, w, dy, dh, dw, eps, dh_lowp=None, row_idx=None):
+    """dh += d(rmsnorm)/dx . dy (fp32 stream), dw += ...; ``dh_lowp``: the updated dh also as bf16 (the next GEMMs' operand).
+    ``row_idx`` (int32 [n], no repeats; bf16 stream): dy [n, dim] is compact, its row i belongs to x row row_idx[i] and dh row row_idx[i]."""
+    _dev(x, w, dy, dh, dw, dh_lowp, row_idx)
     assert w.dtype == torch.float32 and x.dtype == dh.dtype and x.dtype in (torch.float32, torch.bfloat16)
     rows, dim = x.shape
+    if row_idx is not None:
+        assert row_idx.dtype == torch.int32 and row_idx.is_contiguous() and x.dtype == torch.bfloat16 and dh_lowp is None
+        rows = row_idx.numel()
+        assert dy.shape[0] == rows
     scratch = None
     if dw is not None:                       # per-device scratch for the weight-gradient partial rows (grown on demand)
         need = int(_l.load().a3v_rmsnorm_bwd_scratch_floats(rows, dim))
@@ -514,6 +569,11 @@ def rmsnorm_bwd(x, w, dy, dh, dw, eps, dh_lowp=None):
             _rb_scratch[x.device] = scratch
     if x.dtype == torch.bfloat16:            # bf16 residual stream: x, dy and the accumulated dh are bf16 (fp32 arithmetic inside)
         assert dh_lowp is None and dy.dtype == torch.bfloat16
+        if row_idx is not None:
+            rc = _l.load().a3v_rmsnorm_bwd_rows_bf16(_p(x), x.stride(0), _p(row_idx), _p(w), _p(dy), dy.stride(0), _p(dh), dh.stride(0), _p(dw),
+                                                     _p(scratch), rows, dim, eps, _stream())
+            _l.check(rc, "a3v_rmsnorm_bwd_rows_bf16")
+            return
         rc = _l.load().a3v_rmsnorm_bwd_bf16(_p(x), x.stride(0), _p(w), _p(dy), dy.stride(0), _p(dh), dh.stride(0), _p(dw), _p(scratch), rows,
                                             dim, eps, _stream())
         _l.check(rc, "a3v_rmsnorm_bwd_bf16")

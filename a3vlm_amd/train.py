@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import os
 
+from contextlib import contextmanager
 from typing import Callable, Dict, List, Optional, Tuple
 
 import torch
@@ -40,6 +41,16 @@ def skinny_slices(M: int, N: int, K: int, cus: int) -> int:
     return S
 
 
+def label_rows_ref(labels: torch.Tensor, W: int, S: int):
+    """What ``ops.label_rows`` (a3v_label_rows) computes, in torch: for the shifted labels [B, T], the positions whose label is not 0 in
+    ascending order -- as rows b S + W + t of the decoder stream, as rows b T + t of the head, and the labels there."""
+    T = labels.shape[1]
+    flat = labels.reshape(-1)
+    pos = torch.nonzero(flat != 0).reshape(-1)
+    b = torch.div(pos, T, rounding_mode="floor")
+    return (b * S + W + (pos - b * T)).to(torch.int32), pos.to(torch.int32), flat[pos]
+
+
 class TrainEngine:
     # A/B and test hooks (environment A3V_FUSE_QKV_ROPE=0 / A3V_TN_WGRAD=0 / A3V_NN_DGRAD=0 flips the default for a whole process)
     fuse_qkv_rope = os.environ.get("A3V_FUSE_QKV_ROPE", "1") != "0"   # qkv GEMM with the RoPE / cache-write epilogue
@@ -53,6 +64,8 @@ class TrainEngine:
     lora_nt_dgrad = os.environ.get("A3V_LORA_NT_DGRAD", "all")
     strip_wgrad = os.environ.get("A3V_STRIP_WGRAD", "1") != "0"        # adapter weight gradients by a3v_gemm_tn_strip (0: the 256 x 256 TN split-K kernel)
     fuse_swiglu_bwd = os.environ.get("A3V_FUSE_SWIGLU_BWD", "1") != "0"   # LoRA: SwiGLU backward in the epilogue of w2's input-gradient GEMM (0: separate pass, A/B)
+    # the last block's wo / FFN branch, the final norm, the head and the loss on the rows with a label only (0: on every row); DESIGN.md 11
+    label_rows = os.environ.get("A3V_LABEL_ROWS", "1") != "0"
 
     def __init__(self, model, compute_dtype: torch.dtype = torch.bfloat16, recompute: Optional[bool] = None,
                  stream_dtype: Optional[torch.dtype] = None, zero1_world: int = 0):
@@ -110,10 +123,13 @@ class TrainEngine:
         self._opt_stepped = False                           # an optimizer step has happened (its moments are allocated)
         self._dha_ready = False                             # fp32 stream: the last norm backward left the bf16 copy of dh in place
         self._dh_full: Optional[torch.Tensor] = None        # bf16 stream + K-ext: [dh | room for dt], see backward
+        self._sel_rows: Optional[Tuple[int, int]] = None    # inside a labelled-row section: (n rows now, at most this many), see _sel_buf
 
     # ------------------------------------------------------------------ buffers
     def _buf(self, name, shape, dtype=None, zero=False):
         dtype = dtype or self.act
+        if self._sel_rows is not None:
+            return self._sel_buf(name, tuple(shape), dtype, zero)
         key = (name, tuple(shape), dtype)
         t = self._ws.get(key)
         if t is None:
@@ -122,6 +138,43 @@ class TrainEngine:
         if zero:
             t.zero_()
         return t
+
+    def _sel_buf(self, name, shape, dtype, zero):
+        """``_buf`` inside a labelled-row section (n rows this step, never more than cap): a buffer of n rows is the first n rows of
+        ONE buffer of cap rows, and any other (split-K planes, pads: sized by their caller's rows) a view of one flat scratch per name
+        that only grows.  So the section keeps one set of buffers however n moves from step to step, and none of them shares a name
+        -- hence storage or size -- with the buffers of the every-row blocks."""
+        n, cap = self._sel_rows
+        if ".sel" not in name:
+            name += ".sel"
+        if shape[0] == n:
+            key = (name, (cap,) + shape[1:], dtype)
+            t = self._ws.get(key)
+            if t is None:
+                t = self._ws[key] = torch.empty(*key[1], dtype=dtype, device=self.m._device)
+            t = t[:n]
+        else:
+            numel = 1
+            for d in shape:
+                numel *= d
+            key = (name, "flat", dtype)
+            t = self._ws.get(key)
+            if t is None or t.numel() < numel:
+                t = self._ws[key] = torch.empty(numel, dtype=dtype, device=self.m._device)
+            t = t[:numel].view(shape)
+        if zero:
+            t.zero_()
+        return t
+
+    @contextmanager
+    def _sel_section(self, n: Optional[int], cap: int = 0):
+        """Buffers asked for inside are labelled-row buffers (``_sel_buf``); n None: no section."""
+        old = self._sel_rows
+        self._sel_rows = (n, cap) if n is not None else old
+        try:
+            yield
+        finally:
+            self._sel_rows = old
 
     # ------------------------------------------------------------------ optimizer hand-off (a3vlm_amd.optim.FusedAdamW(engine=...))
     def image_sink(self, p: torch.Tensor) -> Optional[torch.Tensor]:
@@ -609,12 +662,15 @@ class TrainEngine:
             ops.gemm_nt(dt, At, dx, residual=dx)             # dx += dt @ A
 
     # ------------------------------------------------------------------ one decoder block (forward / recompute)
-    def _block_forward(self, i: int, h: torch.Tensor, B: int, S: int, keep: bool, tag: str = "", h_out: Optional[torch.Tensor] = None):
+    def _block_forward(self, i: int, h: torch.Tensor, B: int, S: int, keep: bool, tag: str = "", h_out: Optional[torch.Tensor] = None,
+                       sel: Optional[dict] = None):
         """One decoder block on the fp32 stream h [B*S, dim].
         keep=False: h is updated in place (checkpointing forward).
         keep=True : h is only read; h_mid goes to its own buffer and the intermediates the backward needs are
         returned; the block output is written to ``h_out`` if given (stored-activation forward, per-layer buffers
-        selected by ``tag``) or not computed at all (recompute inside backward)."""
+        selected by ``tag``) or not computed at all (recompute inside backward).
+        ``sel`` (keep=True with ``h_out``; ``_label_rows``' answer): everything behind the attention -- wo, the FFN branch and the
+        block output -- runs on the stream rows sel["rows"][j] only, in compact [n, ...] buffers (``_sel_buf``); ``h_out`` is [n, dim]."""
         m, a, im = self.m, self.m.args, self._images()
         H, Hkv, hd, dim, F = m.n_heads, m.n_kv_heads, m.head_dim, a.dim, m.ffn
         rows = B * S
@@ -636,26 +692,35 @@ class TrainEngine:
         strides = (S * H * hd, H * hd, hd, Hkv * spad * hd, spad * hd, hd, Hkv * hd * spad, hd * spad, spad, S * ldo, ldo, hd)
         ops.attention_lse(qrot, kc, vc, att, lse, B, S, S, H, Hkv, hd, strides, True)
         res_flag = self._res_epi(h)                       # bf16 stream: plain bf16 residual
-        h_mid = self._buf("h_mid" + tag, (rows, dim), self.stream) if keep else h
-        lt["wo"] = self._group_fwd(i, "wo", att, att_full, t_wo, h_mid, h, res_flag, tag)
-        # ---- FFN: out = h_mid + w2(silu(g) * u)
-        gu = self._buf("gu" + tag, (rows, 2 * F))
-        xn2, xn2_full, t_w13 = self._x_buf("xn2" + tag, dim, f"w13.{i}", rows, kx)
-        actb, act_full, t_w2 = self._x_buf("act" + tag, F, f"w2.{i}", rows, kx)
-        ops.rmsnorm(h_mid, l.ffn_norm.weight, xn2, a.norm_eps)
-        lt["w13"] = self._group_fwd(i, "w13", xn2, xn2_full, t_w13, gu, tag=tag)
-        ops.swiglu_fwd(gu, actb, F, interleaved=False)
-        # w2 is not a _group_fwd: t = lora_a(act) is needed by the backward even when the block output is not computed, so it comes
-        # first and the output GEMM(s) only when there is an output
-        lt["w2"] = self._lora_t(f"w2.{i}", actb, tag, t_w2) if self.lora else None
-        kept = dict(xn=xn, qkv=qkv, qrot=qrot, kc=kc, att=att, lse=lse, h_mid=h_mid, xn2=xn2, gu=gu, act=actb, spad=spad, lt=lt)
-        if keep and h_out is None:
-            return kept                                   # recompute inside backward: the block output is not needed
-        out = h_out if keep else h
-        ops.gemm_nt(act_full, im[f"w2.{i}.x" if kx else f"w2.{i}"], out, residual=h_mid, epilogue=res_flag)
-        if self.lora and not kx:
-            self._lora_add(f"w2.{i}", lt["w2"], out)
-        return kept
+        att_all = att
+        with self._sel_section(sel["n"] if sel is not None else None, sel["cap"] if sel is not None else 0):
+            if sel is not None:
+                # the rows of att and of the block input that the loss reads, side by side: from here on the block is [n, ...]
+                rows, tag, sel = sel["n"], ".sel", sel["rows"]
+                att, att_full, t_wo = self._x_buf("att" + tag, H * hd, f"wo.{i}", rows, kx)
+                ops.gather_rows(att_all, sel, att)
+                h = ops.gather_rows(h, sel, self._buf("h_in" + tag, (rows, dim), self.stream))
+            h_mid = self._buf("h_mid" + tag, (rows, dim), self.stream) if keep else h
+            lt["wo"] = self._group_fwd(i, "wo", att, att_full, t_wo, h_mid, h, res_flag, tag)
+            # ---- FFN: out = h_mid + w2(silu(g) * u)
+            gu = self._buf("gu" + tag, (rows, 2 * F))
+            xn2, xn2_full, t_w13 = self._x_buf("xn2" + tag, dim, f"w13.{i}", rows, kx)
+            actb, act_full, t_w2 = self._x_buf("act" + tag, F, f"w2.{i}", rows, kx)
+            ops.rmsnorm(h_mid, l.ffn_norm.weight, xn2, a.norm_eps)
+            lt["w13"] = self._group_fwd(i, "w13", xn2, xn2_full, t_w13, gu, tag=tag)
+            ops.swiglu_fwd(gu, actb, F, interleaved=False)
+            # w2 is not a _group_fwd: t = lora_a(act) is needed by the backward even when the block output is not computed, so it comes
+            # first and the output GEMM(s) only when there is an output
+            lt["w2"] = self._lora_t(f"w2.{i}", actb, tag, t_w2) if self.lora else None
+            # (att: all rows, for the attention backward; att_wo: wo's input -- the same, or its selected rows)
+            kept = dict(xn=xn, qkv=qkv, qrot=qrot, kc=kc, att=att_all, att_wo=att, lse=lse, h_mid=h_mid, xn2=xn2, gu=gu, act=actb, spad=spad, lt=lt)
+            if keep and h_out is None:
+                return kept                                   # recompute inside backward: the block output is not needed
+            out = h_out if keep else h
+            ops.gemm_nt(act_full, im[f"w2.{i}.x" if kx else f"w2.{i}"], out, residual=h_mid, epilogue=res_flag)
+            if self.lora and not kx:
+                self._lora_add(f"w2.{i}", lt["w2"], out)
+            return kept
 
     def _qkv_fwd(self, i: int, xn, xn_full, t, qkv, qrot, kc, vc, B: int, S: int, tag: str) -> Optional[torch.Tensor]:
         """The qkv step of a block: q (rotated) into ``qrot``, K / V^T into the caches, v token-major in its columns of ``qkv``
@@ -684,7 +749,12 @@ class TrainEngine:
         ops.rope_kvcache(qkv, qrot, kc, vc, m._cos_sin_dev(), B, S, H, Hkv, hd, 0, 0)
         return t
 
-    def _block_backward(self, i: int, h_in: torch.Tensor, dh: torch.Tensor, B: int, S: int):
+    def _block_backward(self, i: int, h_in: torch.Tensor, dh: torch.Tensor, B: int, S: int, sel: Optional[dict] = None,
+                        dh_sel: Optional[torch.Tensor] = None):
+        """Backward of block i; dh [rows, dim] is the stream gradient, updated in place.  ``sel`` / ``dh_sel`` (the block was run with
+        ``_block_forward(sel=...)``): the gradient arrives as the compact rows ``dh_sel`` [n, dim (+ room for dt)] of the stream rows
+        sel["rows"][j]; the FFN branch and wo back-propagate those n rows, then dh_sel and wo's input gradient are scattered into the full
+        dh / datt (zero at every other row, written by the same launches) and the attention runs on every row."""
         m, a, im = self.m, self.m.args, self._images()
         H, Hkv, hd, dim, F = m.n_heads, m.n_kv_heads, m.head_dim, a.dim, m.ffn
         rows = B * S
@@ -696,7 +766,14 @@ class TrainEngine:
         lt = k["lt"]
         kx = self._kx(rows)
         stream_lp = self.stream == torch.bfloat16 and self.act == torch.bfloat16     # dh itself is the bf16 operand of the GEMMs
-        if stream_lp:
+        dh_all, frows, ftag = dh, rows, ""
+        if sel is not None:
+            assert stream_lp and k["h_mid"].shape[0] == sel["n"]
+            frows, ftag = sel["n"], ".sel"
+            self._sel_rows = (sel["n"], sel["cap"])       # a labelled-row section (_sel_buf) until the scatter below
+            dha, dha_full = dh_sel[:, :dim], (dh_sel if kx else None)
+            dh = dha
+        elif stream_lp:
             dha, dha_full = dh, (self._dh_full if kx else None)
         else:
             dha, dha_full = self._dy_buf("dh_act", dim, f"w2.{i}", rows, kx)
@@ -706,14 +783,14 @@ class TrainEngine:
         self._dha_ready = False
         # ---- FFN: out = h_mid + w2(silu(g) * u)
         self._group_wgrad(i, "w2", dha, k["act"])
-        dgu, dgu_full = self._dy_buf("dgu", 2 * F, f"w13.{i}", rows, kx)
+        dgu, dgu_full = self._dy_buf("dgu" + ftag, 2 * F, f"w13.{i}", frows, kx)
         # w2's input gradient is d(act); three forms keep it out of HBM by applying the SwiGLU backward in the GEMM epilogue
         # (a3v_swiglu_bwd on the bf16-rounded product, bit for bit), writing d(gate) | d(up) straight into the w1|w3 gradient buffer
         ft_epi = (not self.lora and self.fuse_swiglu_bwd and self.act == torch.bfloat16 and dim % 64 == 0 and F % 8 == 0
                   and dha.stride(0) % 8 == 0)
         if kx and self.fuse_swiglu_bwd and self._nt_dgrad(f"w2.{i}") and F % 8 == 0:
             self._group_bwd(i, "w2", dha, dha_full, k["act"], lt["w2"], dgu, swiglu_gu=k["gu"])       # LoRA K-ext on the NT ring kernel
-        elif (ft_epi and self.nn_dgrad and F >= 256 and 2 * rows * dha.stride(0) < 2 ** 31 and 2 * F * dim < 2 ** 31
+        elif (ft_epi and self.nn_dgrad and F >= 256 and 2 * frows * dha.stride(0) < 2 ** 31 and 2 * F * dim < 2 ** 31
               and tuple(im[f"w2.{i}"].shape) == (dim, F)):
             # full fine-tune: the same epilogue on the NN kernel (dX = dY . W on the forward image)
             ops.gemm_nn(dha, im[f"w2.{i}"], dgu, residual=k["gu"], epilogue=ops.EPI_SWIGLU_BWD)
@@ -721,20 +798,27 @@ class TrainEngine:
             # full fine-tune with input gradients on the NT ring kernel (W^T images): the same epilogue there
             ops.gemm_nt(dha, im[f"w2.{i}.t"], dgu, residual=k["gu"], epilogue=ops.EPI_SWIGLU_BWD)
         else:
-            dact = self._buf("dact", (rows, F))
+            dact = self._buf("dact" + ftag, (frows, F))
             self._group_bwd(i, "w2", dha, dha_full, k["act"], lt["w2"], dact)
             ops.swiglu_bwd(k["gu"], dact, dgu, F, interleaved=False)
         self._group_wgrad(i, "w13", dgu, k["xn2"])
-        dxn = self._buf("dxn", (rows, dim))
+        dxn = self._buf("dxn" + ftag, (frows, dim))
         self._group_bwd(i, "w13", dgu, dgu_full, k["xn2"], lt["w13"], dxn)
         ops.rmsnorm_bwd(k["h_mid"], l.ffn_norm.weight, dxn, dh, self._views.get(pre + "ffn_norm.weight"), a.norm_eps,
                         dh_lowp=dha if fuse_cast else None)
         # ---- attention: h_mid = h_in + wo(attn(rope(qkv(norm(h_in)))))
         if not fuse_cast and not stream_lp:
             ops.cast(dh, dha)
-        self._group_wgrad(i, "wo", dha, k["att"])
-        datt = self._buf("datt", (rows, H * hd))
-        self._group_bwd(i, "wo", dha, dha_full, k["att"], lt["wo"], datt)
+        self._group_wgrad(i, "wo", dha, k["att_wo"])
+        datt = self._buf("datt" + ftag, (frows, H * hd))
+        self._group_bwd(i, "wo", dha, dha_full, k["att_wo"], lt["wo"], datt)
+        if sel is not None:
+            # back to every row: the attention reads datt and adds into dh at all of them
+            self._sel_rows = None
+            datt = ops.scatter_rows(datt, sel["rows"], self._buf("datt", (rows, H * hd)))
+            ops.scatter_rows(dh, sel["rows"], dh_all)
+            dh, dha, dha_full = dh_all, dh_all, (self._dh_full if kx else None)
+            dxn = self._buf("dxn", (rows, dim))
         D = self._buf("attn_D", (B, S, H), torch.float32)
         qkv = k["qkv"]
         ld = qkv.stride(0)
@@ -762,12 +846,39 @@ class TrainEngine:
                         dh_lowp=dha if fuse_cast else None)
         self._dha_ready = fuse_cast                        # the next block's backward finds its bf16 operand in place
 
+    # ------------------------------------------------------------------ the rows the loss reads
+    def _label_rows_engine(self) -> bool:
+        """This engine may run the row-wise tail of the step -- the last block's wo and FFN branch, the final norm, the head, the loss and
+        their backwards -- on the labelled rows only: stored activations, bf16 stream and operands, replicated parameters."""
+        return bool(self.label_rows and not self.recompute and not self.zero1_world
+                    and self.stream == torch.bfloat16 and self.act == torch.bfloat16)
+
+    @staticmethod
+    def _label_rows_take(n: int, rows: int) -> bool:
+        """... and does so for n labelled rows of ``rows``: not when there is none (nothing of zero size is launched; the full path
+        gives loss 0 and zero gradients) and not when nothing would be left out."""
+        return 0 < n < rows
+
+    def _label_rows(self, lab: torch.Tensor, W: int, S: int) -> Optional[dict]:
+        """The labelled rows of the shifted labels ``lab`` [B, T] (one launch and the step's one host wait, before any decoder launch),
+        or None when the step runs every row."""
+        B, T = lab.shape
+        srows = self._buf("sel_stream_rows", (B * T,), torch.int32)
+        hrows = self._buf("sel_head_rows", (B * T,), torch.int32)
+        labs = self._buf("sel_labels", (B * T,), torch.int64)
+        n_valid = self._buf("n_valid", (1,), torch.int32)
+        n = int(ops.label_rows(lab, W, S, srows, hrows, labs, n_valid))
+        if not self._label_rows_take(n, B * S):
+            return None
+        return dict(n=n, cap=B * T, rows=srows[:n], head=hrows[:n], lab=labs[:n], n_valid=n_valid)
+
     # ------------------------------------------------------------------ forward (loss) and backward
     @torch.no_grad()
     def forward_loss(self, examples: torch.Tensor, labels: torch.Tensor, image: Optional[torch.Tensor] = None,
                      qformer_feats=None, extra_feats=None) -> torch.Tensor:
         self._check_dtypes()
         self._adapters.checked = False
+        self._sel_rows = None
         m, a = self.m, self.m.args
         im = self._images()
         B, T = examples.shape
@@ -793,6 +904,9 @@ class TrainEngine:
             free, _ = torch.cuda.mem_get_info(m._device)
             self.recompute = need > 0.5 * free
         kept = []
+        lab = self._buf("lab", (B, T), torch.int64, zero=True)
+        lab[:, :T - 1].copy_(labels[:, 1:])      # shift (meta.py:256-257); last position predicts nothing
+        sel = self._label_rows(lab, W, S) if self._label_rows_engine() else None
         if self.recompute:
             for i in range(m.n_layers):
                 hs[i].copy_(h)                   # the block input (checkpoint, main_finetune.py:268-276)
@@ -802,19 +916,38 @@ class TrainEngine:
             # stored activations: block i reads hs[i] and writes hs[i + 1] (its w2 GEMM's residual epilogue stores there), so the
             # checkpoints cost no copy (was one 143-MB read + write per layer)
             hs[0].copy_(h)
+            last = m.n_layers - 1
             for i in range(m.n_layers):
                 self.await_weights(f"layer{i}")
-                kept.append(self._block_forward(i, hs[i], B, S, keep=True, tag=f".L{i}", h_out=hs[i + 1]))
-            h = hs[m.n_layers]
+                if sel is not None and i == last:
+                    # the last block's output is read by the final norm at the labelled rows only: it is written compact ([n, dim])
+                    with self._sel_section(sel["n"], sel["cap"]):
+                        h = self._buf("h_out", (sel["n"], dim), self.stream)
+                    kept.append(self._block_forward(i, hs[i], B, S, keep=True, tag=f".L{i}", h_out=h, sel=sel))
+                else:
+                    kept.append(self._block_forward(i, hs[i], B, S, keep=True, tag=f".L{i}", h_out=hs[i + 1]))
+            if sel is None:
+                h = hs[m.n_layers]
         self.sync_optimizer()                    # "head" is last in forward_order: everything has landed from here on
+        if sel is not None:
+            n = sel["n"]
+            with self._sel_section(n, sel["cap"]):
+                xt = self._buf("xn_text", (n, dim))
+                ops.rmsnorm(h, m.norm.weight, xt, a.norm_eps)
+                logits = self._buf("logits", (n, V))
+                ops.gemm_nt(xt, im["out"], logits)
+                row_loss = self._buf("row_loss", (n,), torch.float32)
+                ops.cross_entropy(logits, sel["lab"], row_loss)
+            loss = row_loss.sum() / float(n)                                                              # meta.py:259-262
+            self._saved = dict(B=B, T=T, W=W, S=S, h=h, hs=hs, xt=xt, logits=logits, lab=sel["lab"], n_valid=sel["n_valid"],
+                               tokens=examples.contiguous(), vis=vis, kept=kept, sel=sel)
+            return loss
         xt = self._buf("xn_text", (B * T, dim))
         hv = h.view(B, S, dim)
         for b in range(B):
             ops.rmsnorm(hv[b, W:], m.norm.weight, xt[b * T:(b + 1) * T], a.norm_eps)
         logits = self._buf("logits", (B * T, V))
         ops.gemm_nt(xt, im["out"], logits)
-        lab = self._buf("lab", (B, T), torch.int64, zero=True)
-        lab[:, :T - 1].copy_(labels[:, 1:])      # shift (meta.py:256-257); last position predicts nothing
         lab = lab.view(-1)
         n_valid = self._buf("n_valid", (1,), torch.int32)
         ops.count_valid(lab, n_valid)
@@ -823,13 +956,14 @@ class TrainEngine:
         nv = n_valid.to(torch.float32)[0]
         loss = torch.where(nv > 0, row_loss.sum() / torch.clamp(nv, min=1.0), torch.zeros_like(nv))   # meta.py:259-262
         self._saved = dict(B=B, T=T, W=W, S=S, h=h, hs=hs, xt=xt, logits=logits, lab=lab, n_valid=n_valid, tokens=examples.contiguous(), vis=vis,
-                           kept=kept if not self.recompute else None)
+                           kept=kept if not self.recompute else None, sel=None)
         return loss
 
     @torch.no_grad()
     def backward(self, grad_scale: float = 1.0) -> None:
         s = self._saved
         self._dha_ready = False
+        self._sel_rows = None
         self._adapters.checked = False
         assert s is not None, "backward() without forward_loss()"
         m, a = self.m, self.m.args
@@ -858,28 +992,43 @@ class TrainEngine:
         B, T, W, S = s["B"], s["T"], s["W"], s["S"]
         rows, dim, V = B * S, a.dim, a.vocab_size
         # ---- CE + LM head + final norm
-        dlog = self._buf("dlogits", (B * T, V))
-        ops.cross_entropy(s["logits"], s["lab"], self._buf("row_loss", (B * T,), torch.float32), dlog, s["n_valid"], grad_scale)
-        if self._has("output.weight"):
-            self._wgrad(dlog, s["xt"], self._views["output.weight"], "out", ("output.weight",))
-        dxt = self._buf("dxn_text", (B * T, dim))
-        self._dgrad_w(dlog, "out", dxt)
+        sel = s["sel"]
+        hrows = sel["n"] if sel is not None else B * T       # the head's rows: the labelled ones, or every text row
+        with self._sel_section(hrows if sel is not None else None, sel["cap"] if sel is not None else 0):
+            dlog = self._buf("dlogits", (hrows, V))
+            ops.cross_entropy(s["logits"], s["lab"], self._buf("row_loss", (hrows,), torch.float32), dlog, s["n_valid"], grad_scale)
+            if self._has("output.weight"):
+                self._wgrad(dlog, s["xt"], self._views["output.weight"], "out", ("output.weight",))
+            dxt = self._buf("dxn_text", (hrows, dim))
+            self._dgrad_w(dlog, "out", dxt)
         self._dh_full = None
+        zero_dh = sel is None        # (labelled rows: a3v_scatter_rows writes every row of dh in the last block's backward)
         if self.stream == torch.bfloat16 and self.act == torch.bfloat16 and self._kx(rows):
             # bf16 stream + adapters inside the GEMMs: dh IS the dy operand of the wo / w2 groups, so it lives in the first `dim`
             # columns of a buffer with room for dt = dy . B behind it (no copy of dh per layer)
             # (width of the wo / w2 groups' adapter block, pad64(r) -- NOT _kext(), the qkv group's pad64(3 r): the two differ from r = 22 on)
-            self._dh_full = self._buf("dh.x", (rows, dim + self._kext_cols("w2.0")), self.stream, zero=True)
+            self._dh_full = self._buf("dh.x", (rows, dim + self._kext_cols("w2.0")), self.stream, zero=zero_dh)
             dh = self._dh_full[:, :dim]
         else:
-            dh = self._buf("dh", (rows, dim), self.stream, zero=True)
-        hv, dhv = s["h"].view(B, S, dim), dh.view(B, S, dim)
-        for b in range(B):
-            ops.rmsnorm_bwd(hv[b, W:], m.norm.weight, dxt[b * T:(b + 1) * T], dhv[b, W:], self._views.get("norm.weight"), a.norm_eps)
+            dh = self._buf("dh", (rows, dim), self.stream, zero=zero_dh)
+        dh_sel = None
+        if sel is not None:
+            # the stream gradient of the labelled rows, compact and laid out like dh: what the last block's FFN branch and wo
+            # back-propagate; _block_backward scatters it into dh (every other row of dh is zero) before the attention
+            with self._sel_section(sel["n"], sel["cap"]):
+                dh_sel = self._buf("dh.x" if self._dh_full is not None else "dh", (sel["n"], dh.stride(0)), self.stream, zero=True)
+            ops.rmsnorm_bwd(s["h"], m.norm.weight, dxt, dh_sel[:, :dim], self._views.get("norm.weight"), a.norm_eps)
+        else:
+            hv, dhv = s["h"].view(B, S, dim), dh.view(B, S, dim)
+            for b in range(B):
+                ops.rmsnorm_bwd(hv[b, W:], m.norm.weight, dxt[b * T:(b + 1) * T], dhv[b, W:], self._views.get("norm.weight"), a.norm_eps)
         self._notify("head")
         # ---- decoder blocks, last to first (recompute from the saved block input)
         for i in range(m.n_layers - 1, -1, -1):
-            self._block_backward(i, s["hs"][i], dh, B, S)
+            if dh_sel is not None and i == m.n_layers - 1:
+                self._block_backward(i, s["hs"][i], dh, B, S, sel=sel, dh_sel=dh_sel)
+            else:
+                self._block_backward(i, s["hs"][i], dh, B, S)
             self._notify(f"layer{i}")
         # ---- embeddings and projector
         if self._has("tok_embeddings.weight"):

@@ -262,6 +262,11 @@ int a3v_gemm_skinny(const void* A, int64_t lda, const void* W, int64_t ldw, void
 int a3v_rmsnorm(const void* x, int64_t ldx, const void* w, void* y, int64_t ldy, int rows, int dim,
                 float eps, int x_dtype, int w_dtype, int y_dtype, void* stream);
 
+/* The same over the rows of a list: y[i] = rmsnorm(x[row_idx[i]]) * w for i < rows (int32 indices, every one inside x): the rows
+ * are gathered by the pass that normalises them. */
+int a3v_rmsnorm_rows(const void* x, int64_t ldx, const int32_t* row_idx, const void* w, void* y, int64_t ldy,
+                     int rows, int dim, float eps, int x_dtype, int w_dtype, int y_dtype, void* stream);
+
 /* y[row_map ? row_map[r] : r] = layernorm(x[r]) * w + b   (torch.nn.LayerNorm, eps 1e-5):
  * open_clip ln_pre/ln_1/ln_2/ln_post and the projector LayerNorm (LLM/llama_ens5.py:325-333,
  * 363,370).  row_map (int32, device) lets the projector write straight into the
@@ -460,6 +465,25 @@ int a3v_rmsnorm_bwd_bf16(const void* x, int64_t ldx, const float* w, const void*
                          float* dw, float* dw_scratch, int rows, int dim, float eps, void* stream);
 int a3v_layernorm_bwd_bf16(const void* x, int64_t ldx, const float* w, const void* dy, int64_t lddy, const int32_t* row_map,
                            void* dx, int64_t lddx, float* dw, float* db, int rows, int dim, float eps, void* stream);
+/* a3v_rmsnorm_bwd_bf16 over the rows of a list without repeats: dy row i (compact, i < rows) belongs to x row row_idx[i], and the input
+ * gradient is accumulated into dh row row_idx[i]; dw and its scratch as above. */
+int a3v_rmsnorm_bwd_rows_bf16(const void* x, int64_t ldx, const int32_t* row_idx, const float* w, const void* dy, int64_t lddy,
+                              void* dh, int64_t lddh, float* dw, float* dw_scratch, int rows, int dim, float eps, void* stream);
+
+/* The rows the loss reads (CrossEntropyLoss(ignore_index=0), model/meta.py:67,256-262): for the shifted labels [B, T] (int64), the
+ * ascending list of positions b T + t with a non-zero label -- as rows b S + W + t of the decoder stream [B, S = W + T] in
+ * stream_rows and as rows b T + t of the head in head_rows (int32, room for B T entries each), the labels themselves in labels_out
+ * (int64, may be NULL) and the length of the list in count_dev.  One launch, one block; the order never depends on timing. */
+int a3v_label_rows(const int64_t* labels, int B, int T, int W, int S, int32_t* stream_rows, int32_t* head_rows,
+                   int64_t* labels_out, int32_t* count_dev, void* stream);
+/* dst[i, :] = src[row_idx[i], :], i < n (bf16 / fp32; 16-byte pieces: cols, both leading dimensions and both pointers multiples of
+ * 16 bytes).  An index outside [0, src_rows) reads nothing and gives a zero row. */
+int a3v_gather_rows(const void* src, int64_t ld_src, int src_rows, const int32_t* row_idx, int n, void* dst, int64_t ld_dst,
+                    int cols, int dtype, void* stream);
+/* dst[row_idx[i], :] = src[i, :] for an ASCENDING list without repeats, and every other row of dst[0 .. dst_rows) = 0, written by the
+ * same launch (nothing of dst's old content survives in the first `cols` columns).  Same alignment rules. */
+int a3v_scatter_rows(const void* src, int64_t ld_src, const int32_t* row_idx, int n, void* dst, int64_t ld_dst, int dst_rows,
+                     int cols, int dtype, void* stream);
 int a3v_embed_bwd_bf16(const int64_t* tokens, int64_t ld_tok, const void* dh, float* dtable, int B, int T, int W, int dim,
                        int vocab, void* stream);
 

@@ -86,6 +86,34 @@ def cases():
     return out
 
 
+def label_rows_cases():
+    """The cases of the second table (profiles/label_rows_trace_<sha>.tsv, tests/test_label_rows_trace_cpu.py): engines with
+    ``label_rows`` on -- the last block's wo / FFN branch, the final norm, the head and the loss on the labelled rows -- and the
+    engines that fall back to every row (recompute, fp32 stream, ZeRO-1: their rows are those of the first table)."""
+    out = []
+
+    def add(name, model, dtype="bf16", recompute=False, **kw):
+        out.append((name, dict(model=model, dtype=dtype, recompute=recompute, label_rows=True, **kw)))
+
+    add("lora.r8", "lora", rank=8)
+    add("lora.r24", "lora", rank=24)
+    add("lora.no_kext", "lora", rank=8, lora_kext=False)
+    add("lora.nt_dgrad_0", "lora", rank=8, lora_nt_dgrad="0")
+    add("lora.no_swiglu_bwd", "lora", rank=8, fuse_swiglu_bwd=False)
+    add("lora.no_strip_wgrad", "lora", rank=8, strip_wgrad=False)
+    add("visual.lora", "visual", rank=8)
+    add("nf4", "nf4", rank=8)
+    add("full", "full")
+    add("full.nn_dgrad", "full", nn_dgrad=True)
+    add("lora.recompute", "lora", rank=8, recompute=True)
+    add("lora.stream_f32", "lora", rank=8, stream="f32")
+    add("zero1", "full", zero1=2)
+    return out
+
+
+CASE_SETS = {"step": cases, "label_rows": label_rows_cases}
+
+
 # ---------------------------------------------------------------------------------------------------------------- the recorder
 class Recorder:
     def __init__(self):
@@ -130,7 +158,12 @@ class Recorder:
         return ba.arguments
 
 
-_RETURNS = {"attention_bwd_workspace_bytes": lambda a: 64 * a["B"] * a["H"] * a["S"], "gemm_tn_sumsq_slots": lambda a: 4,
+def _n_labelled(a):
+    from a3vlm_amd.train import label_rows_ref
+    return int(label_rows_ref(a["labels"], a["W"], a["S"])[0].numel())
+
+
+_RETURNS = {"label_rows": _n_labelled, "attention_bwd_workspace_bytes": lambda a: 64 * a["B"] * a["H"] * a["S"], "gemm_tn_sumsq_slots": lambda a: 4,
             "attention_scratch_floats": lambda a: 64, "gemm_skinny_split": lambda a: 1, "gemm_skinny_ws_bytes": lambda a: 64}
 
 
@@ -237,6 +270,7 @@ def trace(spec):
         for k in SWITCHES:
             if k in spec:
                 setattr(eng, k, spec[k])
+        eng.label_rows = bool(spec.get("label_rows", False))     # the first table's engines run every row, as when it was recorded
         undo = watch_images(rec, eng)
         try:
             g = torch.Generator().manual_seed(1)
@@ -269,9 +303,9 @@ def digest(row: str) -> str:
     return hashlib.sha1(row.encode()).hexdigest()[:6]
 
 
-def table(digests: bool = False):
+def table(digests: bool = False, case_set: str = "step"):
     lines = ["# digests"] if digests else []
-    for name, spec in cases():
+    for name, spec in CASE_SETS[case_set]():
         lines.append(f"## {name}\t" + " ".join(f"{k}={v}" for k, v in spec.items()))
         rows = trace(spec)
         lines += [" ".join(map(digest, rows[j:j + 32])) for j in range(0, len(rows), 32)] if digests else rows
@@ -304,10 +338,12 @@ def main():
     ap.add_argument("--tsv", help="write every row of every case (to read, and to diff against the same from another commit)")
     ap.add_argument("--digests", help="write the committed form: per case, six hex digits per row")
     ap.add_argument("--check", metavar="TABLE", help="compare this tree with a table of either form")
+    ap.add_argument("--cases", choices=sorted(CASE_SETS), default="step", help="which table: the step's (default) or the label-rows engines'")
     a = ap.parse_args()
+    cases = CASE_SETS[a.cases]
     if a.tsv or a.digests:
         with open(a.tsv or a.digests, "w") as f:
-            f.write("\n".join(table(digests=bool(a.digests))) + "\n")
+            f.write("\n".join(table(digests=bool(a.digests), case_set=a.cases)) + "\n")
         return 0
     want = read_table(a.check)
     bad = 0
