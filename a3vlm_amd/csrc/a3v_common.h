@@ -43,6 +43,15 @@ __device__ __forceinline__ float silu(float x) { return x * __builtin_amdgcn_rcp
 // round-trip: the value a bf16 store of v would hold
 __device__ __forceinline__ float rbf(float v) { return (float)((bf16_t)v); }
 
+// bitsandbytes' NF4 code book (16 entries, 0 at index 7): one table for the quantiser, the dequantisers and the LoRA merge over an NF4 base
+__device__ __forceinline__ float nf4_value(int i) {
+  constexpr float t[16] = {-1.0f, -0.6961928009986877f, -0.5250730514526367f, -0.39491748809814453f, -0.28444138169288635f,
+                           -0.18477343022823334f, -0.09105003625154495f, 0.0f, 0.07958029955625534f, 0.16093020141124725f,
+                           0.24611230194568634f, 0.33791524171829224f, 0.44070982933044434f, 0.5626170039176941f, 0.7229568362236023f,
+                           1.0f};
+  return t[i];
+}
+
 template <typename T> struct Cvt;
 template <> struct Cvt<float> {
   static __device__ __forceinline__ float ld(const float* p) { return *p; }

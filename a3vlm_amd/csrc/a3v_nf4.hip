@@ -41,15 +41,6 @@ __constant__ float kDynMap[256] = {
     0x1.d133340000000p-1f, 0x1.d866660000000p-1f, 0x1.df999a0000000p-1f, 0x1.e6cccc0000000p-1f, 0x1.ee00000000000p-1f, 0x1.f533340000000p-1f, 0x1.fc66660000000p-1f, 0x1.0000000000000p+0f,
 };
 
-// bitsandbytes' NF4 code book (16 entries, 0 at index 7)
-__device__ __forceinline__ float nf4_value(int i) {
-  constexpr float t[16] = {-1.0f, -0.6961928009986877f, -0.5250730514526367f, -0.39491748809814453f, -0.28444138169288635f,
-                           -0.18477343022823334f, -0.09105003625154495f, 0.0f, 0.07958029955625534f, 0.16093020141124725f,
-                           0.24611230194568634f, 0.33791524171829224f, 0.44070982933044434f, 0.5626170039176941f, 0.7229568362236023f,
-                           1.0f};
-  return t[i];
-}
-
 // nearest NF4 code of x (first minimum on ties, as argmin)
 __device__ __forceinline__ int nf4_nearest(float x) {
   int best = 0;

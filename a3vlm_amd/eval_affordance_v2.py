@@ -130,6 +130,9 @@ def get_args_parser():
     p.add_argument("--preprocess", type=str, choices=["gpu", "cpu"], default="gpu",
                    help="gpu: workers decode only, PadToSquare / bicubic resize / normalise run on the device per batch (a3v_preprocess_batch, "
                         "bit-identical to the PIL transform); cpu: the PIL transform in the workers (data/transform.py:59-68)")
+    p.add_argument("--merge_lora", action="store_true", default=False,
+                   help="a LoRA model (--llama_type llama_ens5_peft): fold the adapters into the base weights after loading (MetaModel.merge_lora), "
+                        "so that decoding takes the single-call step (and --quant of eval_affordance_with_quant applies)")
     return p
 
 
@@ -153,6 +156,8 @@ def main(args):
     torch.set_default_dtype(old)
     if args.pretrained_path:
         print(f"load pretrained from {args.pretrained_path}:", load_tensor_parallel_model_list(model, args.pretrained_path))
+    if getattr(args, "merge_lora", False):
+        model.merge_lora()
     if getattr(args, "quant", False):     # eval_affordance_with_quant.py --quant: NF4 decoder linears + LM head (bf16 weights freed)
         model.llma.quantize_decode_weights("nf4")
     model.eval()

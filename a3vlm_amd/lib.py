@@ -64,6 +64,7 @@ SIGNATURES = {
     "a3v_quantize_nf4": (I, [P, I, I, P, P, P, P]),
     "a3v_dequantize_nf4": (I, [P, P, P, L, I, I, P]),
     "a3v_dequantize_nf4_images": (I, [P, P, I, I, P, L, P, L, P]),
+    "a3v_lora_merge": (I, [P, L, P, P, P, L, P, L, P, L, I, I, I, I, P]),
     "a3v_gemm_skinny_nf4": (I, [P, L, P, L, P, P, L, I, I, I, P, L, I, P, P]),
     "a3v_gemm_skinny": (I, [P, L, P, L, P, L, I, I, I, P, L, I, P, P]),
     "a3v_rmsnorm": (I, [P, L, P, P, L, I, I, F, I, I, I, P]),

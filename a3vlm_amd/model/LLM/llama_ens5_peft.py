@@ -16,7 +16,7 @@ reference's rounding order) -- so an adapter group costs two skinny-N / skinny-K
 """
 from __future__ import annotations
 
-from dataclasses import dataclass
+from dataclasses import dataclass, fields
 from typing import Dict, Optional
 
 import torch
@@ -45,6 +45,12 @@ def base_shape(mod) -> tuple:
     return tuple(mod.weight.shape) if q4 is None else q4[2]
 
 
+def merged_args(args: ModelArgs) -> base.ModelArgs:
+    """The base plugin's ModelArgs of a merged model: the peft-only fields (``lora_rank``, ``bias_tuning``) are dropped, since the base
+    ``ModelArgs`` -- and ``MetaModel`` reading a ``config.json`` for it -- rejects fields it does not know."""
+    return base.ModelArgs(**{f.name: getattr(args, f.name) for f in fields(base.ModelArgs)})
+
+
 class Transformer(base.Transformer):
     is_peft = True
 
@@ -67,11 +73,14 @@ class Transformer(base.Transformer):
         self._lora_img: Dict[str, torch.Tensor] = {}
         self._lora_ver = None
         self._q4: Optional[Dict[str, tuple]] = None      # quantize_base_weights: module name -> (nibbles, scales, (N, K))
+        self._merged = False                             # merge_adapters: from then on every override below defers to the base class
 
     def quantize_decode_weights(self, mode: str = "fp8", prefill: bool = False) -> None:
+        if self._merged:
+            return super().quantize_decode_weights(mode, prefill)
         if mode == "nf4":
             # the reference keeps the LoRA adapters unquantised beside the NF4 base (llama_ens5.py:541-550, QLoRA): a follow-up
-            raise NotImplementedError("NF4 weights with LoRA adapters (QLoRA) are not implemented")
+            raise NotImplementedError("NF4 decode weights beside LoRA adapters are not implemented: merge_adapters() first")
         super().quantize_decode_weights(mode, prefill)
 
     def quantize_base_weights(self, mode: str = "nf4") -> None:
@@ -89,6 +98,8 @@ class Transformer(base.Transformer):
         Needs bf16 base matrices on the GPU and K % 64 == 0 for every module (the format); none of the NF4 decode GEMV's limits."""
         if mode != "nf4":
             raise ValueError("only 'nf4' base weights are implemented")
+        if self._merged:
+            raise RuntimeError("the adapters are merged: this is a plain llama_ens5 model now (quantize_decode_weights quantises it for inference)")
         if self._q4 is not None:
             raise RuntimeError("the base weights are already NF4")
         named = []
@@ -114,6 +125,66 @@ class Transformer(base.Transformer):
         self._q4 = q4
         self._packed, self._packed_version = {}, None
         self._lora_ver = None
+
+    def merge_adapters(self) -> None:
+        """Fold every adapter into its base matrix, ``weight <- weight + lora_b . lora_a`` (a3v_lora_merge: fp32 accumulation, the base
+        added in fp32, ONE rounding), and drop the adapters.  In place and irreversible.  Afterwards the object behaves as a
+        ``llama_ens5.Transformer``: no ``lora_a`` / ``lora_b`` modules, the state-dict keys and ``args`` of the base plugin, ``is_peft``
+        false, and forward, prefill, decode (the single-call step) and ``quantize_decode_weights("fp8" | "nf4")`` are the base
+        class's; ``quantize_base_weights`` and a second ``merge_adapters`` raise ``RuntimeError``.
+
+        The adapters are cast to the dtype of the base matrices first, as ``lora_images`` does for the adapter GEMMs (a trainer
+        keeps them in fp32).  The merge works on the original modules in module row order.  Over ``quantize_base_weights("nf4")``
+        the base of a module is its Wd = bf16(NF4[q] * s_b) -- what the QLoRA run trained against -- read straight from the NF4
+        image: each freed ``weight`` comes back as a bf16 parameter, bit-equal to merging a bf16 model that holds Wd, and the
+        image of a module is dropped as soon as it is merged, so the bf16 decoder is never alive twice.  ``output`` has no adapter
+        and is dequantised.  Re-quantising such a model (``quantize_decode_weights("nf4")``) quantises W' afresh: a second
+        quantisation error on top of the one inside Wd.
+
+        Needs the model on the GPU and bf16 or fp32 base matrices of one dtype."""
+        if self._merged:
+            raise RuntimeError("the adapters are already merged")
+        named = []
+        for i, lyr in enumerate(self.layers):
+            at, f = lyr.attention, lyr.feed_forward
+            named += [(f"layers.{i}.attention.{n}", getattr(at, n)) for n in ("wq", "wk", "wv", "wo")]
+            named += [(f"layers.{i}.feed_forward.{n}", getattr(f, n)) for n in ("w1", "w3", "w2")]
+        q4 = self._q4
+        dtypes = set()
+        for name, mod in named:
+            for t in (mod.lora_a.weight, mod.lora_b.weight) + (() if q4 is not None else (mod.weight,)):
+                if t.device.type != "cuda":
+                    raise ValueError(f"merge_adapters needs the model on the GPU (merge after .to(device)); {name} is on {t.device}")
+            dtypes.add(torch.bfloat16 if q4 is not None else mod.weight.dtype)
+        if len(dtypes) != 1 or not dtypes <= {torch.bfloat16, torch.float32}:
+            raise ValueError(f"merge_adapters needs bf16 or fp32 base matrices of one dtype, got {sorted(map(str, dtypes))}")
+        dtype = dtypes.pop()
+        with torch.no_grad():
+            for name, mod in named:
+                lb = mod.lora_b.weight.detach().to(dtype).contiguous()
+                la = mod.lora_a.weight.detach().to(dtype).contiguous()
+                if q4 is None:
+                    ops.lora_merge(mod.weight.data, lb, la)
+                else:
+                    q, sc, _ = q4.pop(name)
+                    mod.weight = nn.Parameter(ops.lora_merge((q, sc), lb, la), requires_grad=False)
+                    del mod.q4, q, sc
+                del mod.lora_a, mod.lora_b
+            if q4 is not None:
+                q, sc, (n, k) = q4.pop("output")
+                w = torch.empty(n, k, dtype=torch.bfloat16, device=q.device)
+                ops.dequantize_nf4_images(q, sc, wd=w)
+                self.output.weight = nn.Parameter(w, requires_grad=False)
+                del self.output.q4
+        self._q4 = None
+        self._merged = True
+        self.is_peft = False
+        del self._per_kernel_decode
+        self.args = merged_args(self.args)
+        self._packed, self._packed_version = {}, None
+        self._lora_img, self._lora_ver = {}, None
+        for key in [k for k in self._ws if k[0] in ("q4_scratch", "q4_head", "lora_t", "lora_o")]:
+            del self._ws[key]
 
     def _pack(self, check: bool = False) -> Dict[str, torch.Tensor]:
         if self._q4 is None:
@@ -165,6 +236,8 @@ class Transformer(base.Transformer):
         self._linear(xn, self._head_weight(), logits, epilogue=ops.EPI_OUT_F32)
 
     def get_trainable_params(self, pretrain_stage: bool = False):
+        if self._merged:
+            return super().get_trainable_params(pretrain_stage)
         frozen_pre = ("qformer.", "openclip_convnext_xxl.", "clip.", "dinov2_vitg14.", "tok_embeddings.", "output.")
         out = {}
         for n, p in self.named_parameters():
@@ -222,6 +295,8 @@ class Transformer(base.Transformer):
     # ------------------------------------------------------------------ decoder stack with adapters
     def _decoder_layers(self, h: torch.Tensor, B: int, S: int, start_pos: int, rope_pos0: int,
                         k_caches, vt_caches, causal: bool) -> None:
+        if self._merged:
+            return super()._decoder_layers(h, B, S, start_pos, rope_pos0, k_caches, vt_caches, causal)
         a = self.args
         H, Hkv, hd, dim = self.n_heads, self.n_kv_heads, self.head_dim, a.dim
         rows = B * S

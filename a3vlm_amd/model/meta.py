@@ -193,6 +193,21 @@ class MetaModel(nn.Module):
         if eng is not None:
             eng.sync_optimizer()
 
+    def merge_lora(self) -> None:
+        """Fold the LoRA adapters into the base matrices (``Transformer.merge_adapters``: W' = W + lora_b . lora_a, one rounding) and
+        become a plain ``llama_ens5`` model: ``llama_type`` and ``is_peft`` say so, ``save_checkpoint`` writes a folder that
+        ``from_pretrained`` loads without a ``llama_type``, and every inference path of the base plugin (the single-call decode
+        step, ``quantize_decode_weights``) applies.  A live ``TrainEngine`` is joined first, so the adapters merged are the ones the
+        last optimizer step wrote, and dropped (its weight images describe the adapter model).  In place and irreversible."""
+        if not self.is_peft or not hasattr(self.llma, "merge_adapters"):
+            raise RuntimeError(f"merge_lora needs a model with LoRA adapters; this is a {self.llama_type} model without any")
+        self._sync_engine()
+        self._engine = None
+        self.llma.merge_adapters()
+        self.llama_type = "llama_ens5"
+        self.is_peft = False
+        self._set_default_trainability()
+
     def zero_grad(self, set_to_none: bool = True):
         """``set_to_none=False`` WRITES the gradients: an overlapped optimizer step (``FusedAdamW.step(overlap=True)``) may still
         be reading them on its own stream, so it is joined first (``set_to_none=True`` only drops references)."""

@@ -282,6 +282,33 @@ def dequantize_nf4_images(q, scales, wd=None, wt=None):
     _l.check(rc, f"a3v_dequantize_nf4_images(N={N},K={K})")
 
 
+def lora_merge(base, lora_b, lora_a, out=None):
+    """out = round(base + lora_b . lora_a), fp32 accumulation and ONE rounding (a3v_lora_merge).  ``base``: a bf16 / fp32 matrix [N, K]
+    (unit column stride, any row stride) or an NF4 image ``(q [N, K/2] uint8, scales [N, K/64] fp32)`` of ``quantize_nf4``; ``lora_b``
+    [N, R] and ``lora_a`` [R, K] in the dtype of ``out``.  ``out=None``: in place into ``base`` (a new bf16 matrix for an NF4 base).
+    Only the N x K window of ``out`` is written."""
+    R, K = lora_a.shape
+    N = lora_b.shape[0]
+    if isinstance(base, (tuple, list)):
+        w, (q, scales) = None, base[:2]
+        _dev(q, scales)
+        assert q.dtype == torch.uint8 and q.is_contiguous() and tuple(q.shape) == (N, K // 2)
+        assert scales.dtype == torch.float32 and scales.is_contiguous() and scales.numel() == N * (K // 64)
+        if out is None:
+            out = torch.empty(N, K, dtype=torch.bfloat16, device=q.device)
+    else:
+        w, q, scales = base, None, None
+        out = w if out is None else out
+        assert tuple(w.shape) == (N, K) and w.stride(1) == 1 and w.dtype == out.dtype
+    _dev(w, lora_b, lora_a, out)
+    assert lora_b.shape[1] == R and tuple(out.shape) == (N, K) and out.stride(1) == 1 and lora_a.stride(1) == 1 and lora_b.stride(1) == 1
+    assert lora_a.dtype == out.dtype and lora_b.dtype == out.dtype
+    rc = _l.load().a3v_lora_merge(_p(w), w.stride(0) if w is not None else 0, _p(q), _p(scales), _p(lora_b), lora_b.stride(0),
+                                  _p(lora_a), lora_a.stride(0), _p(out), out.stride(0), N, K, R, dt(out), _stream())
+    _l.check(rc, f"a3v_lora_merge(N={N},K={K},R={R})")
+    return out
+
+
 def gemm_skinny_nf4(a, q, scales, out, workspace, *, residual=None, epilogue: int = 0):
     """out = epilogue(sum_b s_b * (a . NF4[q])^T): weight-only NF4 decode GEMV (M <= 16, K % 256 == 0)."""
     N, K = q.shape[0], a.shape[1]

@@ -247,6 +247,22 @@ int a3v_dequantize_nf4(const void* q, const float* scales, void* Wd, int64_t ldd
  * larger images (ldd > K, ldt > N) whose tail columns hold adapter blocks.  K % 64 == 0, ldd % 8 == 0, ldt % 8 == 0, q / Wd / Wt 16-B
  * aligned (A3V_ERR_SHAPE before any launch otherwise); N is arbitrary. */
 int a3v_dequantize_nf4_images(const void* q, const float* scales, int N, int K, void* Wd, int64_t ldd, void* Wt, int64_t ldt, void* stream);
+/* LoRA merge: the adapters of one linear folded into its base matrix, W' = W + lora_b . lora_a (no alpha / rank scaling, as the
+ * adapter forward y = W x + lora_b(lora_a(x))).
+ *   out[n,k] = round_to_dtype( fp32(base[n,k]) + sum_r fp32(B[n,r]) * fp32(A[r,k]) )
+ * The sum over r is accumulated in fp32 (ascending r in 32-wide MFMA steps; the order does not depend on the base format), the base is
+ * added in fp32 and the result is rounded ONCE (not bf16(acc) + base as the residual epilogue of a3v_gemm_nt rounds: a merged weight is
+ * written once and read forever).  Base: either W [N, K] (row stride ldw elements) or, with W NULL, the NF4 image (q [N, K/2],
+ * scales [N, K/64]) of a3v_quantize_nf4, for which base[n,k] is Wd = bf16(NF4[q] * s_b) exactly as a3v_dequantize_nf4 writes it: a
+ * merge over an NF4 base is bit-equal to a merge over a bf16 base that holds Wd.
+ * dtype A3V_BF16: B [N, R], A [R, K], out [N, K] and a non-NULL W are bf16; the product runs on MFMA.  dtype A3V_F32 (parity path):
+ * fp32 storage, plain FMA, no NF4 base (A3V_ERR_ARG).  out == W (in place) is allowed and is the normal use; any other overlap of out
+ * with an input is undefined.  Only the N x K window of out is written (ldo > K: the columns beyond K are untouched).
+ * Limits (A3V_ERR_SHAPE before any launch; a NULL B / A / out, both or neither of W / q, or q without scales: A3V_ERR_ARG):
+ * R % 8 == 0 and 8 <= R <= 256; K % 8 == 0 (K % 64 == 0 for an NF4 base); ldw, ldo >= K, lda >= K, ldb >= R, all multiples of 8
+ * elements; every pointer 16-B aligned; N arbitrary (<= 65535 * 128 rows).  Allocates nothing. */
+int a3v_lora_merge(const void* W, int64_t ldw, const void* q, const float* scales, const void* B, int64_t ldb, const void* A, int64_t lda,
+                   void* out, int64_t ldo, int N, int K, int R, int dtype, void* stream);
 /* Weight-only NF4 decode GEMV, M <= 16, K % 256 == 0: q [N, K/2] (row stride ldw BYTES), scales [N, K/64]; workspace and epilogues
  * (NONE, RESIDUAL, SWIGLU, OUT_F32) as a3v_gemm_skinny; SWIGLU needs K >= 512 (A3V_ERR_SHAPE otherwise, as the fp8 form).  The codes enter the MFMA as bf16 and each 64-k block sum is scaled by s_b in
  * fp32, so results differ from the bf16 GEMV on Wd by rounding only. */
