@@ -145,8 +145,7 @@ class TrainEngine:
         that only grows.  So the section keeps one set of buffers however n moves from step to step, and none of them shares a name
         -- hence storage or size -- with the buffers of the every-row blocks."""
         n, cap = self._sel_rows
-        if ".sel" not in name:
-            name += ".sel"
+        name += ".sel"
         if shape[0] == n:
             key = (name, (cap,) + shape[1:], dtype)
             t = self._ws.get(key)
@@ -167,10 +166,10 @@ class TrainEngine:
         return t
 
     @contextmanager
-    def _sel_section(self, n: Optional[int], cap: int = 0):
-        """Buffers asked for inside are labelled-row buffers (``_sel_buf``); n None: no section."""
+    def _sel_section(self, sel: dict):
+        """One step on the labelled rows ``sel`` (``_label_rows``' answer): buffers asked for inside are labelled-row buffers (``_sel_buf``)."""
         old = self._sel_rows
-        self._sel_rows = (n, cap) if n is not None else old
+        self._sel_rows = (sel["n"], sel["cap"])
         try:
             yield
         finally:
@@ -661,66 +660,84 @@ class TrainEngine:
         if dx is not None:
             ops.gemm_nt(dt, At, dx, residual=dx)             # dx += dt @ A
 
-    # ------------------------------------------------------------------ one decoder block (forward / recompute)
-    def _block_forward(self, i: int, h: torch.Tensor, B: int, S: int, keep: bool, tag: str = "", h_out: Optional[torch.Tensor] = None,
-                       sel: Optional[dict] = None):
-        """One decoder block on the fp32 stream h [B*S, dim].
+    # ------------------------------------------------------------------ one decoder block: the attention half, then the row-wise tail
+    def _block_forward(self, i: int, h: torch.Tensor, B: int, S: int, keep: bool, tag: str = "", h_out: Optional[torch.Tensor] = None):
+        """One decoder block on the stream h [B*S, dim], every row.
         keep=False: h is updated in place (checkpointing forward).
         keep=True : h is only read; h_mid goes to its own buffer and the intermediates the backward needs are
         returned; the block output is written to ``h_out`` if given (stored-activation forward, per-layer buffers
-        selected by ``tag``) or not computed at all (recompute inside backward).
-        ``sel`` (keep=True with ``h_out``; ``_label_rows``' answer): everything behind the attention -- wo, the FFN branch and the
-        block output -- runs on the stream rows sel["rows"][j] only, in compact [n, ...] buffers (``_sel_buf``); ``h_out`` is [n, dim]."""
-        m, a, im = self.m, self.m.args, self._images()
-        H, Hkv, hd, dim, F = m.n_heads, m.n_kv_heads, m.head_dim, a.dim, m.ffn
+        selected by ``tag``) or not computed at all (recompute inside backward)."""
+        kept, att = self._attn_forward(i, h, B, S, tag)
+        return self._tail_forward(i, h, att, keep, tag, h_out, kept)
+
+    def _attn_forward(self, i: int, h: torch.Tensor, B: int, S: int, tag: str):
+        """The attention half of block i, on every row: att = attn(rope(qkv(norm(h)))).  Returns what the backward keeps of it and
+        ``att`` as wo's input (x, full, t) from ``_x_buf``."""
+        m, a = self.m, self.m.args
+        H, Hkv, hd, dim = m.n_heads, m.n_kv_heads, m.head_dim, a.dim
         rows = B * S
-        l = m.layers[i]
         spad = _pad64(S)
         kx = self._kx(rows)
         xn, xn_full, t_qkv = self._x_buf("xn" + tag, dim, f"qkv.{i}", rows, kx)
-        att, att_full, t_wo = self._x_buf("att" + tag, H * hd, f"wo.{i}", rows, kx)
+        att3 = self._x_buf("att" + tag, H * hd, f"wo.{i}", rows, kx)
+        att = att3[0]
         qkv = self._buf("qkv" + tag, (rows, (H + 2 * Hkv) * hd))
         qrot = self._buf("qrot" + tag, (rows, H * hd))
         kc = self._buf("kc" + tag, (B, Hkv, spad, hd))
         vc = self._buf("vc", (B, Hkv, hd, spad))
         lse = self._buf("lse" + tag, (B, H, S), torch.float32)
-        lt = {}
-        # ---- attention: h_mid = h + wo(attn(rope(qkv(norm(h)))))
-        ops.rmsnorm(h, l.attention_norm.weight, xn, a.norm_eps)
-        lt["qkv"] = self._qkv_fwd(i, xn, xn_full, t_qkv, qkv, qrot, kc, vc, B, S, tag)
+        ops.rmsnorm(h, m.layers[i].attention_norm.weight, xn, a.norm_eps)
+        t = self._qkv_fwd(i, xn, xn_full, t_qkv, qkv, qrot, kc, vc, B, S, tag)
         ldo = att.stride(0)
         strides = (S * H * hd, H * hd, hd, Hkv * spad * hd, spad * hd, hd, Hkv * hd * spad, hd * spad, spad, S * ldo, ldo, hd)
         ops.attention_lse(qrot, kc, vc, att, lse, B, S, S, H, Hkv, hd, strides, True)
+        return dict(xn=xn, qkv=qkv, qrot=qrot, kc=kc, att=att, lse=lse, spad=spad, lt={"qkv": t}), att3
+
+    def _tail_forward(self, i: int, h: torch.Tensor, att3, keep: bool, tag: str, h_out: Optional[torch.Tensor], kept: dict):
+        """The row-wise tail of block i: h_mid = h + wo(att), out = h_mid + w2(silu(g) * u) with g | u = w1|w3(norm(h_mid)), on the rows
+        of its operands -- h [rows, dim] and ``att3`` = (att, full, t) from ``_x_buf``: every row of the stream, or any rows of it side by
+        side.  keep / tag / h_out as in ``_block_forward``; returns ``kept`` with what the tail's backward needs added."""
+        m, a, im = self.m, self.m.args, self._images()
+        dim, F = a.dim, m.ffn
+        rows = h.shape[0]
+        l = m.layers[i]
+        att, att_full, t_wo = att3
+        kx = t_wo is not None
+        lt = kept["lt"]
         res_flag = self._res_epi(h)                       # bf16 stream: plain bf16 residual
-        att_all = att
-        with self._sel_section(sel["n"] if sel is not None else None, sel["cap"] if sel is not None else 0):
-            if sel is not None:
-                # the rows of att and of the block input that the loss reads, side by side: from here on the block is [n, ...]
-                rows, tag, sel = sel["n"], ".sel", sel["rows"]
-                att, att_full, t_wo = self._x_buf("att" + tag, H * hd, f"wo.{i}", rows, kx)
-                ops.gather_rows(att_all, sel, att)
-                h = ops.gather_rows(h, sel, self._buf("h_in" + tag, (rows, dim), self.stream))
-            h_mid = self._buf("h_mid" + tag, (rows, dim), self.stream) if keep else h
-            lt["wo"] = self._group_fwd(i, "wo", att, att_full, t_wo, h_mid, h, res_flag, tag)
-            # ---- FFN: out = h_mid + w2(silu(g) * u)
-            gu = self._buf("gu" + tag, (rows, 2 * F))
-            xn2, xn2_full, t_w13 = self._x_buf("xn2" + tag, dim, f"w13.{i}", rows, kx)
-            actb, act_full, t_w2 = self._x_buf("act" + tag, F, f"w2.{i}", rows, kx)
-            ops.rmsnorm(h_mid, l.ffn_norm.weight, xn2, a.norm_eps)
-            lt["w13"] = self._group_fwd(i, "w13", xn2, xn2_full, t_w13, gu, tag=tag)
-            ops.swiglu_fwd(gu, actb, F, interleaved=False)
-            # w2 is not a _group_fwd: t = lora_a(act) is needed by the backward even when the block output is not computed, so it comes
-            # first and the output GEMM(s) only when there is an output
-            lt["w2"] = self._lora_t(f"w2.{i}", actb, tag, t_w2) if self.lora else None
-            # (att: all rows, for the attention backward; att_wo: wo's input -- the same, or its selected rows)
-            kept = dict(xn=xn, qkv=qkv, qrot=qrot, kc=kc, att=att_all, att_wo=att, lse=lse, h_mid=h_mid, xn2=xn2, gu=gu, act=actb, spad=spad, lt=lt)
-            if keep and h_out is None:
-                return kept                                   # recompute inside backward: the block output is not needed
-            out = h_out if keep else h
-            ops.gemm_nt(act_full, im[f"w2.{i}.x" if kx else f"w2.{i}"], out, residual=h_mid, epilogue=res_flag)
-            if self.lora and not kx:
-                self._lora_add(f"w2.{i}", lt["w2"], out)
-            return kept
+        h_mid = self._buf("h_mid" + tag, (rows, dim), self.stream) if keep else h
+        lt["wo"] = self._group_fwd(i, "wo", att, att_full, t_wo, h_mid, h, res_flag, tag)
+        gu = self._buf("gu" + tag, (rows, 2 * F))
+        xn2, xn2_full, t_w13 = self._x_buf("xn2" + tag, dim, f"w13.{i}", rows, kx)
+        actb, act_full, t_w2 = self._x_buf("act" + tag, F, f"w2.{i}", rows, kx)
+        ops.rmsnorm(h_mid, l.ffn_norm.weight, xn2, a.norm_eps)
+        lt["w13"] = self._group_fwd(i, "w13", xn2, xn2_full, t_w13, gu, tag=tag)
+        ops.swiglu_fwd(gu, actb, F, interleaved=False)
+        # w2 is not a _group_fwd: t = lora_a(act) is needed by the backward even when the block output is not computed, so it comes
+        # first and the output GEMM(s) only when there is an output
+        lt["w2"] = self._lora_t(f"w2.{i}", actb, tag, t_w2) if self.lora else None
+        # (att_wo: wo's input here; kept["att"]: every row of it, for the attention backward -- the same buffer in an every-row block)
+        kept.update(att_wo=att, h_mid=h_mid, xn2=xn2, gu=gu, act=actb)
+        if keep and h_out is None:
+            return kept                                   # recompute inside backward: the block output is not needed
+        out = h_out if keep else h
+        ops.gemm_nt(act_full, im[f"w2.{i}.x" if kx else f"w2.{i}"], out, residual=h_mid, epilogue=res_flag)
+        if self.lora and not kx:
+            self._lora_add(f"w2.{i}", lt["w2"], out)
+        return kept
+
+    def _last_block_forward_rows(self, i: int, h: torch.Tensor, B: int, S: int, tag: str, sel: dict):
+        """The last block when the loss reads the rows ``sel`` only (stored activations): the attention half on every row, then the
+        rows sel["rows"][j] of att and of the block input side by side and the tail on those n rows, in labelled-row buffers.  Returns
+        (kept, the block output at those rows [n, dim])."""
+        m, n = self.m, sel["n"]
+        kept, (att_all, _, t_wo) = self._attn_forward(i, h, B, S, tag)
+        with self._sel_section(sel):
+            att3 = self._x_buf("att", m.n_heads * m.head_dim, f"wo.{i}", n, t_wo is not None)     # (K-ext: the block's answer at B S rows)
+            ops.gather_rows(att_all, sel["rows"], att3[0])
+            h_in = ops.gather_rows(h, sel["rows"], self._buf("h_in", (n, m.args.dim), self.stream))
+            h_out = self._buf("h_out", (n, m.args.dim), self.stream)
+            return self._tail_forward(i, h_in, att3, True, "", h_out, kept), h_out
 
     def _qkv_fwd(self, i: int, xn, xn_full, t, qkv, qrot, kc, vc, B: int, S: int, tag: str) -> Optional[torch.Tensor]:
         """The qkv step of a block: q (rotated) into ``qrot``, K / V^T into the caches, v token-major in its columns of ``qkv``
@@ -749,48 +766,59 @@ class TrainEngine:
         ops.rope_kvcache(qkv, qrot, kc, vc, m._cos_sin_dev(), B, S, H, Hkv, hd, 0, 0)
         return t
 
-    def _block_backward(self, i: int, h_in: torch.Tensor, dh: torch.Tensor, B: int, S: int, sel: Optional[dict] = None,
-                        dh_sel: Optional[torch.Tensor] = None):
-        """Backward of block i; dh [rows, dim] is the stream gradient, updated in place.  ``sel`` / ``dh_sel`` (the block was run with
-        ``_block_forward(sel=...)``): the gradient arrives as the compact rows ``dh_sel`` [n, dim (+ room for dt)] of the stream rows
-        sel["rows"][j]; the FFN branch and wo back-propagate those n rows, then dh_sel and wo's input gradient are scattered into the full
-        dh / datt (zero at every other row, written by the same launches) and the attention runs on every row."""
-        m, a, im = self.m, self.m.args, self._images()
-        H, Hkv, hd, dim, F = m.n_heads, m.n_kv_heads, m.head_dim, a.dim, m.ffn
-        rows = B * S
-        l = m.layers[i]
-        pre = f"layers.{i}."
+    def _block_backward(self, i: int, h_in: torch.Tensor, dh: torch.Tensor, B: int, S: int):
+        """Backward of block i on every row: the tail, then the attention half; dh [rows, dim] is the stream gradient, updated in place."""
+        rows, dim = B * S, self.m.args.dim
         if not self._saved.get("kept"):
-            im.recompute_backward(i)     # (NF4 base: the block's forward and input-gradient images from one read of its codes)
+            self._images().recompute_backward(i)     # (NF4 base: the block's forward and input-gradient images from one read of its codes)
         k = self._saved["kept"][i] if self._saved.get("kept") else self._block_forward(i, h_in, B, S, keep=True)
-        lt = k["lt"]
         kx = self._kx(rows)
-        stream_lp = self.stream == torch.bfloat16 and self.act == torch.bfloat16     # dh itself is the bf16 operand of the GEMMs
-        dh_all, frows, ftag = dh, rows, ""
-        if sel is not None:
-            assert stream_lp and k["h_mid"].shape[0] == sel["n"]
-            frows, ftag = sel["n"], ".sel"
-            self._sel_rows = (sel["n"], sel["cap"])       # a labelled-row section (_sel_buf) until the scatter below
-            dha, dha_full = dh_sel[:, :dim], (dh_sel if kx else None)
-            dh = dha
-        elif stream_lp:
-            dha, dha_full = dh, (self._dh_full if kx else None)
+        if self.stream == torch.bfloat16 and self.act == torch.bfloat16:
+            dha, dha_full = dh, (self._dh_full if kx else None)         # dh itself is the bf16 operand of the GEMMs
         else:
             dha, dha_full = self._dy_buf("dh_act", dim, f"w2.{i}", rows, kx)
+        datt = self._tail_backward(i, k, dh, dha, dha_full)
+        self._attn_backward(i, k, h_in, dh, dha, datt, B, S)
+
+    def _last_block_backward_rows(self, i: int, h_in: torch.Tensor, dh: torch.Tensor, dh_sel: torch.Tensor, B: int, S: int, sel: dict):
+        """Backward of the block ``_last_block_forward_rows`` ran: the tail back-propagates the compact stream gradient ``dh_sel``
+        [n, dim (+ room for dt)] of the rows sel["rows"][j]; then dh_sel and wo's input gradient are scattered into the every-row dh /
+        datt (zero at every other row, written by the same launches) and the attention half runs on every row."""
+        m, k = self.m, self._saved["kept"][i]
+        rows, dim = B * S, m.args.dim
+        kx = self._kx(rows)
+        assert k["h_mid"].shape[0] == sel["n"]
+        with self._sel_section(sel):
+            datt_sel = self._tail_backward(i, k, dh_sel[:, :dim], dh_sel[:, :dim], dh_sel if kx else None)
+        datt = ops.scatter_rows(datt_sel, sel["rows"], self._buf("datt", (rows, m.n_heads * m.head_dim)))
+        ops.scatter_rows(dh_sel[:, :dim], sel["rows"], dh)
+        self._attn_backward(i, k, h_in, dh, dh, datt, B, S)
+
+    def _tail_backward(self, i: int, k: dict, dh: torch.Tensor, dha: torch.Tensor, dha_full: Optional[torch.Tensor]) -> torch.Tensor:
+        """Backward of ``_tail_forward`` on the rows of its operands: dh [rows, dim] is the stream gradient of those rows, updated in
+        place to that of h_mid; dha its operand form for the GEMMs -- dh itself (bf16 stream) or a bf16 buffer this pass fills -- and
+        dha_full = [dha | room for dt] under K-ext (``_dy_buf``), else None.  Returns wo's input gradient datt [rows, H hd]."""
+        m, a, im = self.m, self.m.args, self._images()
+        H, hd, dim, F = m.n_heads, m.head_dim, a.dim, m.ffn
+        rows = dha.shape[0]
+        l = m.layers[i]
+        lt = k["lt"]
+        kx = dha_full is not None
+        stream_lp = self.stream == torch.bfloat16 and self.act == torch.bfloat16
         fuse_cast = self.act == torch.bfloat16 and not stream_lp   # fp32 stream: the norm backward that produced dh also wrote its bf16 copy
         if not stream_lp and not (fuse_cast and self._dha_ready):
             ops.cast(dh, dha)
         self._dha_ready = False
         # ---- FFN: out = h_mid + w2(silu(g) * u)
         self._group_wgrad(i, "w2", dha, k["act"])
-        dgu, dgu_full = self._dy_buf("dgu" + ftag, 2 * F, f"w13.{i}", frows, kx)
+        dgu, dgu_full = self._dy_buf("dgu", 2 * F, f"w13.{i}", rows, kx)
         # w2's input gradient is d(act); three forms keep it out of HBM by applying the SwiGLU backward in the GEMM epilogue
         # (a3v_swiglu_bwd on the bf16-rounded product, bit for bit), writing d(gate) | d(up) straight into the w1|w3 gradient buffer
         ft_epi = (not self.lora and self.fuse_swiglu_bwd and self.act == torch.bfloat16 and dim % 64 == 0 and F % 8 == 0
                   and dha.stride(0) % 8 == 0)
         if kx and self.fuse_swiglu_bwd and self._nt_dgrad(f"w2.{i}") and F % 8 == 0:
             self._group_bwd(i, "w2", dha, dha_full, k["act"], lt["w2"], dgu, swiglu_gu=k["gu"])       # LoRA K-ext on the NT ring kernel
-        elif (ft_epi and self.nn_dgrad and F >= 256 and 2 * frows * dha.stride(0) < 2 ** 31 and 2 * F * dim < 2 ** 31
+        elif (ft_epi and self.nn_dgrad and F >= 256 and 2 * rows * dha.stride(0) < 2 ** 31 and 2 * F * dim < 2 ** 31
               and tuple(im[f"w2.{i}"].shape) == (dim, F)):
             # full fine-tune: the same epilogue on the NN kernel (dX = dY . W on the forward image)
             ops.gemm_nn(dha, im[f"w2.{i}"], dgu, residual=k["gu"], epilogue=ops.EPI_SWIGLU_BWD)
@@ -798,27 +826,30 @@ class TrainEngine:
             # full fine-tune with input gradients on the NT ring kernel (W^T images): the same epilogue there
             ops.gemm_nt(dha, im[f"w2.{i}.t"], dgu, residual=k["gu"], epilogue=ops.EPI_SWIGLU_BWD)
         else:
-            dact = self._buf("dact" + ftag, (frows, F))
+            dact = self._buf("dact", (rows, F))
             self._group_bwd(i, "w2", dha, dha_full, k["act"], lt["w2"], dact)
             ops.swiglu_bwd(k["gu"], dact, dgu, F, interleaved=False)
         self._group_wgrad(i, "w13", dgu, k["xn2"])
-        dxn = self._buf("dxn" + ftag, (frows, dim))
+        dxn = self._buf("dxn", (rows, dim))
         self._group_bwd(i, "w13", dgu, dgu_full, k["xn2"], lt["w13"], dxn)
-        ops.rmsnorm_bwd(k["h_mid"], l.ffn_norm.weight, dxn, dh, self._views.get(pre + "ffn_norm.weight"), a.norm_eps,
+        ops.rmsnorm_bwd(k["h_mid"], l.ffn_norm.weight, dxn, dh, self._views.get(f"layers.{i}.ffn_norm.weight"), a.norm_eps,
                         dh_lowp=dha if fuse_cast else None)
-        # ---- attention: h_mid = h_in + wo(attn(rope(qkv(norm(h_in)))))
+        # ---- wo: h_mid = h_in + wo(att)
         if not fuse_cast and not stream_lp:
             ops.cast(dh, dha)
         self._group_wgrad(i, "wo", dha, k["att_wo"])
-        datt = self._buf("datt" + ftag, (frows, H * hd))
+        datt = self._buf("datt", (rows, H * hd))
         self._group_bwd(i, "wo", dha, dha_full, k["att_wo"], lt["wo"], datt)
-        if sel is not None:
-            # back to every row: the attention reads datt and adds into dh at all of them
-            self._sel_rows = None
-            datt = ops.scatter_rows(datt, sel["rows"], self._buf("datt", (rows, H * hd)))
-            ops.scatter_rows(dh, sel["rows"], dh_all)
-            dh, dha, dha_full = dh_all, dh_all, (self._dh_full if kx else None)
-            dxn = self._buf("dxn", (rows, dim))
+        return datt
+
+    def _attn_backward(self, i: int, k: dict, h_in: torch.Tensor, dh: torch.Tensor, dha: torch.Tensor, datt: torch.Tensor, B: int, S: int):
+        """Backward of ``_attn_forward``, on every row: att = attn(rope(qkv(norm(h_in)))) from its output gradient datt; adds the
+        result into dh (fp32 stream: and leaves its bf16 copy in dha for the next block, ``_dha_ready``)."""
+        m, a = self.m, self.m.args
+        H, Hkv, hd, dim = m.n_heads, m.n_kv_heads, m.head_dim, a.dim
+        rows = B * S
+        kx = self._kx(rows)
+        fuse_cast = self.act == torch.bfloat16 and self.stream != torch.bfloat16
         D = self._buf("attn_D", (B, S, H), torch.float32)
         qkv = k["qkv"]
         ld = qkv.stride(0)
@@ -841,8 +872,9 @@ class TrainEngine:
                               dq, dk, dv, B, S, H, Hkv, hd, True, workspace=wsp)
             ops.rope_bwd_pack(dq, dk, dv, dqkv, m._cos_sin_dev(), B, S, H, Hkv, hd, 0)
         self._group_wgrad(i, "qkv", dqkv, k["xn"])
-        self._group_bwd(i, "qkv", dqkv, dqkv_full, k["xn"], lt["qkv"], dxn)
-        ops.rmsnorm_bwd(h_in, l.attention_norm.weight, dxn, dh, self._views.get(pre + "attention_norm.weight"), a.norm_eps,
+        dxn = self._buf("dxn", (rows, dim))
+        self._group_bwd(i, "qkv", dqkv, dqkv_full, k["xn"], k["lt"]["qkv"], dxn)
+        ops.rmsnorm_bwd(h_in, m.layers[i].attention_norm.weight, dxn, dh, self._views.get(f"layers.{i}.attention_norm.weight"), a.norm_eps,
                         dh_lowp=dha if fuse_cast else None)
         self._dha_ready = fuse_cast                        # the next block's backward finds its bf16 operand in place
 
@@ -880,13 +912,11 @@ class TrainEngine:
         self._adapters.checked = False
         self._sel_rows = None
         m, a = self.m, self.m.args
-        im = self._images()
         B, T = examples.shape
         n_img = 0 if image is None else (len(image) if isinstance(image, (list, tuple)) else 1)
         W = m.words_per_image * n_img if n_img else 0
         S = T + W
-        rows = B * S
-        dim, V = a.dim, a.vocab_size
+        rows, dim = B * S, a.dim
         h = self._buf("h", (rows, dim), self.stream)
         if self.lora or self.act != torch.bfloat16:
             self.sync_optimizer()          # adapter / fp32 images are rebuilt from all parameters at once
@@ -920,43 +950,47 @@ class TrainEngine:
             for i in range(m.n_layers):
                 self.await_weights(f"layer{i}")
                 if sel is not None and i == last:
-                    # the last block's output is read by the final norm at the labelled rows only: it is written compact ([n, dim])
-                    with self._sel_section(sel["n"], sel["cap"]):
-                        h = self._buf("h_out", (sel["n"], dim), self.stream)
-                    kept.append(self._block_forward(i, hs[i], B, S, keep=True, tag=f".L{i}", h_out=h, sel=sel))
+                    # the last block's output is read by the final norm at the labelled rows only: it comes out compact ([n, dim])
+                    k, h = self._last_block_forward_rows(i, hs[i], B, S, f".L{i}", sel)
                 else:
-                    kept.append(self._block_forward(i, hs[i], B, S, keep=True, tag=f".L{i}", h_out=hs[i + 1]))
-            if sel is None:
-                h = hs[m.n_layers]
+                    k, h = self._block_forward(i, hs[i], B, S, keep=True, tag=f".L{i}", h_out=hs[i + 1]), hs[i + 1]
+                kept.append(k)
         self.sync_optimizer()                    # "head" is last in forward_order: everything has landed from here on
-        if sel is not None:
-            n = sel["n"]
-            with self._sel_section(n, sel["cap"]):
-                xt = self._buf("xn_text", (n, dim))
-                ops.rmsnorm(h, m.norm.weight, xt, a.norm_eps)
-                logits = self._buf("logits", (n, V))
-                ops.gemm_nt(xt, im["out"], logits)
-                row_loss = self._buf("row_loss", (n,), torch.float32)
-                ops.cross_entropy(logits, sel["lab"], row_loss)
-            loss = row_loss.sum() / float(n)                                                              # meta.py:259-262
-            self._saved = dict(B=B, T=T, W=W, S=S, h=h, hs=hs, xt=xt, logits=logits, lab=sel["lab"], n_valid=sel["n_valid"],
-                               tokens=examples.contiguous(), vis=vis, kept=kept, sel=sel)
-            return loss
-        xt = self._buf("xn_text", (B * T, dim))
-        hv = h.view(B, S, dim)
-        for b in range(B):
-            ops.rmsnorm(hv[b, W:], m.norm.weight, xt[b * T:(b + 1) * T], a.norm_eps)
-        logits = self._buf("logits", (B * T, V))
+        step = dict(B=B, T=T, W=W, S=S, hs=hs, tokens=examples.contiguous(), vis=vis, kept=kept)
+        if sel is None:
+            return self._head_forward(h, lab, None, step)
+        with self._sel_section(sel):
+            return self._head_forward(h, lab, sel, step)
+
+    def _head_forward(self, h: torch.Tensor, lab: torch.Tensor, sel: Optional[dict], step: dict) -> torch.Tensor:
+        """Final norm, LM head and loss of the step ``step`` (what ``backward`` needs of the forward so far; completed here into
+        ``_saved``).  ``sel`` None: h is the stream [B S, dim] and the head runs on its B T text rows against the shifted labels
+        ``lab`` [B, T]; else h is [n, dim], the labelled rows only, and so are the head's buffers (the caller's section)."""
+        m, a, im = self.m, self.m.args, self._images()
+        B, T, W, S = step["B"], step["T"], step["W"], step["S"]
+        dim, V = a.dim, a.vocab_size
+        n = B * T if sel is None else sel["n"]
+        xt = self._buf("xn_text", (n, dim))
+        if sel is None:
+            hv = h.view(B, S, dim)
+            for b in range(B):
+                ops.rmsnorm(hv[b, W:], m.norm.weight, xt[b * T:(b + 1) * T], a.norm_eps)
+            lab, n_valid = lab.view(-1), self._buf("n_valid", (1,), torch.int32)
+        else:
+            ops.rmsnorm(h, m.norm.weight, xt, a.norm_eps)
+            lab, n_valid = sel["lab"], sel["n_valid"]
+        logits = self._buf("logits", (n, V))
         ops.gemm_nt(xt, im["out"], logits)
-        lab = lab.view(-1)
-        n_valid = self._buf("n_valid", (1,), torch.int32)
-        ops.count_valid(lab, n_valid)
-        row_loss = self._buf("row_loss", (B * T,), torch.float32)
+        row_loss = self._buf("row_loss", (n,), torch.float32)
+        if sel is None:
+            ops.count_valid(lab, n_valid)
         ops.cross_entropy(logits, lab, row_loss)
-        nv = n_valid.to(torch.float32)[0]
-        loss = torch.where(nv > 0, row_loss.sum() / torch.clamp(nv, min=1.0), torch.zeros_like(nv))   # meta.py:259-262
-        self._saved = dict(B=B, T=T, W=W, S=S, h=h, hs=hs, xt=xt, logits=logits, lab=lab, n_valid=n_valid, tokens=examples.contiguous(), vis=vis,
-                           kept=kept if not self.recompute else None, sel=None)
+        if sel is None:                                                                                   # meta.py:259-262
+            nv = n_valid.to(torch.float32)[0]
+            loss = torch.where(nv > 0, row_loss.sum() / torch.clamp(nv, min=1.0), torch.zeros_like(nv))
+        else:
+            loss = row_loss.sum() / float(n)
+        self._saved = dict(step, h=h, xt=xt, logits=logits, lab=lab, n_valid=n_valid, sel=sel)
         return loss
 
     @torch.no_grad()
@@ -989,44 +1023,13 @@ class TrainEngine:
                 self.lora_nt_dgrad = "0"
         if self.sumsq_sink is not None:
             self.sumsq_sink.begin_backward()
-        B, T, W, S = s["B"], s["T"], s["W"], s["S"]
-        rows, dim, V = B * S, a.dim, a.vocab_size
-        # ---- CE + LM head + final norm
-        sel = s["sel"]
-        hrows = sel["n"] if sel is not None else B * T       # the head's rows: the labelled ones, or every text row
-        with self._sel_section(hrows if sel is not None else None, sel["cap"] if sel is not None else 0):
-            dlog = self._buf("dlogits", (hrows, V))
-            ops.cross_entropy(s["logits"], s["lab"], self._buf("row_loss", (hrows,), torch.float32), dlog, s["n_valid"], grad_scale)
-            if self._has("output.weight"):
-                self._wgrad(dlog, s["xt"], self._views["output.weight"], "out", ("output.weight",))
-            dxt = self._buf("dxn_text", (hrows, dim))
-            self._dgrad_w(dlog, "out", dxt)
-        self._dh_full = None
-        zero_dh = sel is None        # (labelled rows: a3v_scatter_rows writes every row of dh in the last block's backward)
-        if self.stream == torch.bfloat16 and self.act == torch.bfloat16 and self._kx(rows):
-            # bf16 stream + adapters inside the GEMMs: dh IS the dy operand of the wo / w2 groups, so it lives in the first `dim`
-            # columns of a buffer with room for dt = dy . B behind it (no copy of dh per layer)
-            # (width of the wo / w2 groups' adapter block, pad64(r) -- NOT _kext(), the qkv group's pad64(3 r): the two differ from r = 22 on)
-            self._dh_full = self._buf("dh.x", (rows, dim + self._kext_cols("w2.0")), self.stream, zero=zero_dh)
-            dh = self._dh_full[:, :dim]
-        else:
-            dh = self._buf("dh", (rows, dim), self.stream, zero=zero_dh)
-        dh_sel = None
-        if sel is not None:
-            # the stream gradient of the labelled rows, compact and laid out like dh: what the last block's FFN branch and wo
-            # back-propagate; _block_backward scatters it into dh (every other row of dh is zero) before the attention
-            with self._sel_section(sel["n"], sel["cap"]):
-                dh_sel = self._buf("dh.x" if self._dh_full is not None else "dh", (sel["n"], dh.stride(0)), self.stream, zero=True)
-            ops.rmsnorm_bwd(s["h"], m.norm.weight, dxt, dh_sel[:, :dim], self._views.get("norm.weight"), a.norm_eps)
-        else:
-            hv, dhv = s["h"].view(B, S, dim), dh.view(B, S, dim)
-            for b in range(B):
-                ops.rmsnorm_bwd(hv[b, W:], m.norm.weight, dxt[b * T:(b + 1) * T], dhv[b, W:], self._views.get("norm.weight"), a.norm_eps)
+        B, T, W, S, dim = s["B"], s["T"], s["W"], s["S"], a.dim
+        dh, dh_sel = self._head_backward(s, grad_scale)
         self._notify("head")
         # ---- decoder blocks, last to first (recompute from the saved block input)
         for i in range(m.n_layers - 1, -1, -1):
             if dh_sel is not None and i == m.n_layers - 1:
-                self._block_backward(i, s["hs"][i], dh, B, S, sel=sel, dh_sel=dh_sel)
+                self._last_block_backward_rows(i, s["hs"][i], dh, dh_sel, B, S, s["sel"])
             else:
                 self._block_backward(i, s["hs"][i], dh, B, S)
             self._notify(f"layer{i}")
@@ -1040,6 +1043,44 @@ class TrainEngine:
         # gradients there, and every rank must hand the same buckets to the collective on the boundary micro-step
         self._notify("vision_proj")
         self._saved = None
+
+    def _head_grads(self, s: dict, n: int, grad_scale: float) -> torch.Tensor:
+        """CE and LM head backward on the head's n rows: the head's weight gradient; returns the final norm's output gradient [n, dim]."""
+        dlog = self._buf("dlogits", (n, self.m.args.vocab_size))
+        ops.cross_entropy(s["logits"], s["lab"], self._buf("row_loss", (n,), torch.float32), dlog, s["n_valid"], grad_scale)
+        if self._has("output.weight"):
+            self._wgrad(dlog, s["xt"], self._views["output.weight"], "out", ("output.weight",))
+        dxt = self._buf("dxn_text", (n, self.m.args.dim))
+        self._dgrad_w(dlog, "out", dxt)
+        return dxt
+
+    def _head_backward(self, s: dict, grad_scale: float):
+        """Backward of ``_head_forward``.  Returns (dh, dh_sel): the stream gradient dh [B S, dim] the blocks update in place, and --
+        when the head ran on the labelled rows -- the gradient of those rows, compact and laid out like dh, for the last block's tail
+        (``_last_block_backward_rows``, whose scatter writes every row of dh: it is not zeroed here); else None."""
+        m, a = self.m, self.m.args
+        B, T, W, S, sel = s["B"], s["T"], s["W"], s["S"], s["sel"]
+        rows, dim = B * S, a.dim
+        # bf16 stream + adapters inside the GEMMs: dh IS the dy operand of the wo / w2 groups, so it lives in the first `dim` columns
+        # of a buffer with room for dt = dy . B behind it (no copy of dh per layer)
+        # (width of the wo / w2 groups' adapter block, pad64(r) -- NOT _kext(), the qkv group's pad64(3 r): the two differ from r = 22 on)
+        wide = self.stream == torch.bfloat16 and self.act == torch.bfloat16 and self._kx(rows)
+        name, cols = ("dh.x", dim + self._kext_cols("w2.0")) if wide else ("dh", dim)
+        norm_dw = self._views.get("norm.weight")
+        if sel is None:
+            dxt = self._head_grads(s, B * T, grad_scale)
+            dh_full, dh_sel = self._buf(name, (rows, cols), self.stream, zero=True), None
+            hv, dhv = s["h"].view(B, S, dim), dh_full[:, :dim].view(B, S, dim)
+            for b in range(B):
+                ops.rmsnorm_bwd(hv[b, W:], m.norm.weight, dxt[b * T:(b + 1) * T], dhv[b, W:], norm_dw, a.norm_eps)
+        else:
+            with self._sel_section(sel):
+                dxt = self._head_grads(s, sel["n"], grad_scale)
+                dh_sel = self._buf(name, (sel["n"], cols), self.stream, zero=True)
+            dh_full = self._buf(name, (rows, cols), self.stream)
+            ops.rmsnorm_bwd(s["h"], m.norm.weight, dxt, dh_sel[:, :dim], norm_dw, a.norm_eps)
+        self._dh_full = dh_full if wide else None
+        return dh_full[:, :dim], dh_sel
 
     def _nt_images_fit(self, extra: int = 0) -> bool:
         """Would 8 GiB of HBM stay free after the transposed images of the decoder / head matrices (2 B per parameter) and ``extra``

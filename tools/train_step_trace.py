@@ -108,6 +108,12 @@ def label_rows_cases():
     add("lora.recompute", "lora", rank=8, recompute=True)
     add("lora.stream_f32", "lora", rank=8, stream="f32")
     add("zero1", "full", zero1=2)
+    add("lora.no_packed_attn_bwd", "lora", rank=8, packed_attn_bwd=False)
+    add("lora.no_kext.no_fuse_qkv_rope", "lora", rank=8, lora_kext=False, fuse_qkv_rope=False)
+    add("lora.hd32", "lora", rank=8, heads=8)
+    add("lora.nt_dgrad_wo_w2", "lora", rank=8, lora_nt_dgrad="wo,w2")
+    add("lora.low_hbm", "lora", rank=8, free_gib=1)
+    add("nf4.nt_dgrad_0", "nf4", rank=8, lora_nt_dgrad="0")
     return out
 
 
