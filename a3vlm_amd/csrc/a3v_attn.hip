@@ -441,66 +441,6 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_bf16_kernel(AttnArgs p) {
   }
 }
 
-// Fused combine of the wave-streaming decode kernel (all threads of the block call it; `po` = this block's partial, already written with plain stores)
-template <int HD>
-__device__ __forceinline__ void decode_combine_tail(const AttnArgs& p, float* part, float* po, int nsplit, int* counters, int b, int h, int tid) {
-  // Fused combine (decode step): the block that arrives last at the (batch, head) counter merges the nsplit partials.
-  // The splits of a head may run on different XCDs (private L2s), so the hand-off uses agent-coherent accesses: this
-  // block re-writes its HD+2 partial values with sc0 sc1 stores (write-through), waits for the acknowledgement, bumps
-  // the counter; the last block reads all partials with sc0 sc1 loads.  (An agent-scope fence instead = L2 write-back
-  // + invalidate per wave: measured 5x slower on the GEMV that uses the same scheme.)
-  __shared__ int last_s;
-  __syncthreads();                                    // po[] of this block is complete (plain stores, same CU)
-  if (tid < HD + 2) st_agent(po + tid, po[tid]);      // L1 is write-through: the value read back is this block's own
-  agent_wait();
-  __syncthreads();
-  if (tid == 0) {
-    int* ctr = counters + b * p.H + h;
-    const int old = __hip_atomic_fetch_add(ctr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    last_s = old == nsplit - 1;
-    if (old == nsplit - 1) __hip_atomic_store(ctr, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  __syncthreads();
-  if (!last_s || tid >= HD) return;
-  const float* pp = part + (int64_t)(b * p.H + h) * nsplit * (HD + 2);
-  float acc = 0.f, l = 0.f;
-  if (nsplit <= 8) {                                  // all loads in flight at once: one memory round trip
-    float mv[8], av[8], lv[8];
-#pragma unroll
-    for (int s = 0; s < 8; ++s) {
-      const float* q = pp + (s < nsplit ? s : nsplit - 1) * (HD + 2);
-      mv[s] = ld_agent_issue(q + HD);
-      av[s] = ld_agent_issue(q + tid);
-      lv[s] = ld_agent_issue(q + HD + 1);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" : "+v"(mv[0]), "+v"(mv[1]), "+v"(mv[2]), "+v"(mv[3]), "+v"(mv[4]), "+v"(mv[5]), "+v"(mv[6]), "+v"(mv[7])::"memory");
-    asm volatile("" : "+v"(av[0]), "+v"(av[1]), "+v"(av[2]), "+v"(av[3]), "+v"(av[4]), "+v"(av[5]), "+v"(av[6]), "+v"(av[7]));
-    asm volatile("" : "+v"(lv[0]), "+v"(lv[1]), "+v"(lv[2]), "+v"(lv[3]), "+v"(lv[4]), "+v"(lv[5]), "+v"(lv[6]), "+v"(lv[7]));
-    float m = -INFINITY;
-#pragma unroll
-    for (int s = 0; s < 8; ++s) if (s < nsplit) m = fmaxf(m, mv[s]);
-#pragma unroll
-    for (int s = 0; s < 8; ++s)
-      if (s < nsplit) {
-        const float w = (mv[s] == -INFINITY) ? 0.f : __expf(mv[s] - m);
-        acc += w * av[s];
-        l += w * lv[s];
-      }
-  } else {
-    float m = -INFINITY;
-    for (int s = 0; s < nsplit; ++s) m = fmaxf(m, ld_agent(pp + s * (HD + 2) + HD));
-    for (int s = 0; s < nsplit; ++s) {
-      const float ms = ld_agent(pp + s * (HD + 2) + HD);
-      const float a1 = ld_agent(pp + s * (HD + 2) + tid);
-      const float l1 = ld_agent(pp + s * (HD + 2) + HD + 1);
-      const float w = (ms == -INFINITY) ? 0.f : __expf(ms - m);
-      acc += w * a1;
-      l += w * l1;
-    }
-  }
-  ((bf16_t*)p.out)[b * p.o_sb + h * p.o_sh + tid] = f2bf(acc / l);
-}
-
 // ------------------------------------------------------------------------------------
 // Decode (Sq == 1): grid (nsplit, H, B); block 256.  part[b][h][split] = {o[HD], m, l}
 // ------------------------------------------------------------------------------------
@@ -751,7 +691,7 @@ __global__ __launch_bounds__(512) void attn_decode_wave_kernel(AttnArgs p, float
     }
   }
   if (!counters || nsplit == 1) return;
-  decode_combine_tail<HD>(p, part, po, nsplit, counters, b, h, tid);
+  decode_combine_tail<HD>(p.out, p.o_sb, p.o_sh, p.H, part, po, nsplit, counters, b, h, tid);
 }
 
 template <int HD>

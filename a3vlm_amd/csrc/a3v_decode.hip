@@ -43,9 +43,14 @@ static int decode_step_form(int B, int dim, int H, int Hkv, int hd, int ffn, int
 }
 extern "C" int a3v_llama_decode_step_form(int B, int dim, int H, int Hkv, int hd, int ffn, int w8) { return decode_step_form(B, dim, H, Hkv, hd, ffn, w8); }
 
-extern "C" int a3v_llama_decode_step(const a3v_llama_layer* layers, int n_layers, void* h, void* xn, void* qkv, void* att,
-                                     void* act, float* attn_scratch, void* skinny_ws, const float* cos_sin, int B, int dim, int H, int Hkv,
-                                     int hd, int ffn, int Smax, int pos, float eps, void* stream) {
+// The step behind a3v_llama_decode_step (kv8 == NULL: bf16 KV caches of `layers`) and a3v_llama_decode_step_kv8 (fp8 caches of `kv8`,
+// fused form only: the qkv GEMV's RoPE epilogue writes the new position into the staging pair as a cache of Smax = 1 at pos 0, one
+// more launch quantises it into the fp8 cache at `pos`, and the attention reads the fp8 cache -- SIX launches per layer; the S = 1
+// quantisation is not folded into a neighbour: the GEMV's epilogue is a3v_gemv.hip's, and inside the attention launch the blocks of
+// the heads that share a kv-head would have to wait for the one that writes the row they all read back).
+static int decode_step_impl(const a3v_llama_layer* layers, const a3v_kv8_layer* kv8, int n_layers, void* h, void* xn, void* qkv, void* att,
+                            void* act, float* attn_scratch, void* skinny_ws, const float* cos_sin, void* stage_k, void* stage_vt, int B,
+                            int dim, int H, int Hkv, int hd, int ffn, int Smax, int pos, float eps, void* stream) {
   if (!layers || n_layers <= 0 || !h || !xn || !qkv || !att || !act || !attn_scratch || !skinny_ws || !cos_sin) return A3V_ERR_ARG;
   if (B <= 0 || B > 32 || pos < 0 || pos >= Smax) return A3V_ERR_SHAPE;   // the plugin contract's max_batch_size = 32 (meta.py:34-52)
   const int64_t ldq = (int64_t)(H + 2 * Hkv) * hd;
@@ -70,6 +75,12 @@ extern "C" int a3v_llama_decode_step(const a3v_llama_layer* layers, int n_layers
   const int form = decode_step_form(B, dim, H, Hkv, hd, ffn, w8);
   if (!form) return A3V_ERR_SHAPE;                 // fp8 / NF4 images and 17..32 rows exist only in the fused form (the host takes its general path)
   const bool fused = form == 2;
+  if (kv8) {
+    if (!fused || Smax % 64) return A3V_ERR_SHAPE;
+    if (!stage_k || !stage_vt) return A3V_ERR_ARG;
+    for (int i = 0; i < n_layers; ++i)
+      if (!kv8[i].k_q || !kv8[i].vt_q || !kv8[i].k_scale || !kv8[i].v_scale) return A3V_ERR_ARG;
+  }
   if (fused) {
     float* ssq = (float*)((char*)skinny_ws + A3V_WS_SSQ);
     int* actr = (int*)((char*)skinny_ws + A3V_WS_ATTN_COUNTERS);
@@ -95,11 +106,21 @@ extern "C" int a3v_llama_decode_step(const a3v_llama_layer* layers, int n_layers
         const float* s13 = q4 ? L.w13_n4s : L.w13_s;
         const float* s2 = q4 ? L.w2_n4s : L.w2_s;
         const int dv = q4 ? 2 : 1;
-        bf16_t* kc = (bf16_t*)L.k_cache + b0 * kv_b;
-        bf16_t* vc = (bf16_t*)L.vt_cache + b0 * kv_b;
+        // the cache the qkv GEMV's epilogue writes: the layer's bf16 cache at `pos`, or the staging pair (a cache of one position)
+        bf16_t* kc = kv8 ? (bf16_t*)stage_k + (int64_t)b0 * Hkv * hd : (bf16_t*)L.k_cache + b0 * kv_b;
+        bf16_t* vc = kv8 ? (bf16_t*)stage_vt + (int64_t)b0 * Hkv * hd : (bf16_t*)L.vt_cache + b0 * kv_b;
         if ((rc = a3v_gemv_fused(hc, dim, wqkv, dim / dv, sqkv, q4, qc, ldq, nb, (int)ldq, dim, nullptr, 0, 0, L.attn_norm_w, ssq, eps,
-                                 nullptr, 1, cos_sin, kc, vc, H, Hkv, hd, Smax, pos, skinny_ws, stream))) return rc;
-        if ((rc = a3v_attention_decode_fused(qc, kc, vc, ac, nb, pos + 1, H, Hkv, hd, strides, attn_scratch, actr, stream))) return rc;
+                                 nullptr, 1, kv8 ? cos_sin + (int64_t)pos * hd : cos_sin, kc, vc, H, Hkv, hd, kv8 ? 1 : Smax, kv8 ? 0 : pos,
+                                 skinny_ws, stream))) return rc;     // (the epilogue has ONE position for angle and cache row: row `pos` of the table is handed in as row 0)
+        if (kv8) {
+          uint8_t* kq = (uint8_t*)kv8[i].k_q + b0 * kv_b;
+          uint8_t* vq = (uint8_t*)kv8[i].vt_q + b0 * kv_b;
+          float* ksc = kv8[i].k_scale + (int64_t)b0 * Hkv * Smax;
+          float* vsc = kv8[i].v_scale + (int64_t)b0 * Hkv * Smax;
+          if ((rc = a3v_kv_quantize_fp8(kc, vc, 1, 0, kq, vq, ksc, vsc, nb, Hkv, hd, 1, Smax, pos, stream))) return rc;
+          if ((rc = a3v_attention_decode_fp8kv(qc, ldq, kq, vq, ksc, vsc, ac, (int64_t)H * hd, nb, pos + 1, H, Hkv, hd, Smax, attn_scratch,
+                                               actr, stream))) return rc;
+        } else if ((rc = a3v_attention_decode_fused(qc, kc, vc, ac, nb, pos + 1, H, Hkv, hd, strides, attn_scratch, actr, stream))) return rc;
         if ((rc = a3v_gemv_fused(ac, (int64_t)H * hd, wo, (int64_t)H * hd / dv, so, q4, hc, dim, nb, dim, H * hd, hc, dim, A3V_EPI_RESIDUAL,
                                  nullptr, nullptr, eps, ssq, 0, nullptr, nullptr, nullptr, H, Hkv, hd, Smax, pos, skinny_ws, stream))) return rc;
         if ((rc = a3v_gemv_fused(hc, dim, w13, dim / dv, s13, q4, fc, ffn, nb, 2 * ffn, dim, nullptr, 0, A3V_EPI_SWIGLU, L.ffn_norm_w, ssq,
@@ -122,4 +143,20 @@ extern "C" int a3v_llama_decode_step(const a3v_llama_layer* layers, int n_layers
     if ((rc = a3v_gemm_skinny(act, ffn, L.w2, ffn, h, dim, B, dim, ffn, h, dim, A3V_EPI_RESIDUAL, skinny_ws, stream))) return rc;
   }
   return A3V_OK;
+}
+
+extern "C" int a3v_llama_decode_step(const a3v_llama_layer* layers, int n_layers, void* h, void* xn, void* qkv, void* att,
+                                     void* act, float* attn_scratch, void* skinny_ws, const float* cos_sin, int B, int dim, int H, int Hkv,
+                                     int hd, int ffn, int Smax, int pos, float eps, void* stream) {
+  return decode_step_impl(layers, nullptr, n_layers, h, xn, qkv, att, act, attn_scratch, skinny_ws, cos_sin, nullptr, nullptr, B, dim, H, Hkv,
+                          hd, ffn, Smax, pos, eps, stream);
+}
+
+extern "C" int a3v_llama_decode_step_kv8(const a3v_llama_layer* layers, const a3v_kv8_layer* kv8, int n_layers, void* h, void* xn, void* qkv,
+                                         void* att, void* act, float* attn_scratch, void* skinny_ws, const float* cos_sin, void* stage_k,
+                                         void* stage_vt, int B, int dim, int H, int Hkv, int hd, int ffn, int Smax, int pos, float eps,
+                                         void* stream) {
+  if (!kv8) return A3V_ERR_ARG;
+  return decode_step_impl(layers, kv8, n_layers, h, xn, qkv, att, act, attn_scratch, skinny_ws, cos_sin, stage_k, stage_vt, B, dim, H, Hkv, hd,
+                          ffn, Smax, pos, eps, stream);
 }

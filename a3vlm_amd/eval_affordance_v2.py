@@ -133,6 +133,9 @@ def get_args_parser():
     p.add_argument("--merge_lora", action="store_true", default=False,
                    help="a LoRA model (--llama_type llama_ens5_peft): fold the adapters into the base weights after loading (MetaModel.merge_lora), "
                         "so that decoding takes the single-call step (and --quant of eval_affordance_with_quant applies)")
+    p.add_argument("--kv_quant", type=str, choices=["fp8"], default=None,
+                   help="keep the KV cache in fp8 e4m3 with per-position scales (Transformer.quantize_kv_cache): half the cache memory and half "
+                        "the cache bytes per decode step; independent of --quant, applied after --merge_lora")
     return p
 
 
@@ -160,6 +163,8 @@ def main(args):
         model.merge_lora()
     if getattr(args, "quant", False):     # eval_affordance_with_quant.py --quant: NF4 decoder linears + LM head (bf16 weights freed)
         model.llma.quantize_decode_weights("nf4")
+    if getattr(args, "kv_quant", None):
+        model.llma.quantize_kv_cache(args.kv_quant)
     model.eval()
 
     name = os.path.basename(args.dataset).split(".")[0]

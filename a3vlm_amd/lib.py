@@ -109,6 +109,10 @@ SIGNATURES = {
     "a3v_label_rows": (I, [P, I, I, I, I, P, P, P, P, P]),
     "a3v_gather_rows": (I, [P, L, I, P, I, P, L, I, I, P]),
     "a3v_scatter_rows": (I, [P, L, P, I, P, L, I, I, I, P]),
+    "a3v_kv_quantize_fp8": (I, [P, P, I, I, P, P, P, P, I, I, I, I, I, I, P]),
+    "a3v_kv_dequantize_fp8": (I, [P, P, P, P, I, P, P, I, I, I, I, I, P]),
+    "a3v_attention_decode_fp8kv": (I, [P, L, P, P, P, P, P, L, I, I, I, I, I, I, P, P, P]),
+    "a3v_attention_decode_fp8kv_splits": (I, [I, I, I]),
 }
 
 class LlamaLayer(ctypes.Structure):
@@ -118,6 +122,11 @@ class LlamaLayer(ctypes.Structure):
                                         "wqkv_n4", "wqkv_n4s", "wo_n4", "wo_n4s", "w13_n4", "w13_n4s", "w2_n4", "w2_n4s")]
 
 
+class Kv8Layer(ctypes.Structure):
+    """a3v_kv8_layer of include/a3vlm_hip.h"""
+    _fields_ = [(n, c_void_p) for n in ("k_q", "vt_q", "k_scale", "v_scale")]
+
+
 class ImageDesc(ctypes.Structure):
     """a3v_image_desc of include/a3vlm_hip.h"""
     _fields_ = [("src", c_void_p), ("coeffs", c_void_p), ("bounds", c_void_p), ("H", c_int), ("W", c_int), ("side", c_int), ("pad_x", c_int),
@@ -125,6 +134,8 @@ class ImageDesc(ctypes.Structure):
 
 
 SIGNATURES["a3v_llama_decode_step"] = (I, [ctypes.POINTER(LlamaLayer), I, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, F, P])
+SIGNATURES["a3v_llama_decode_step_kv8"] = (I, [ctypes.POINTER(LlamaLayer), ctypes.POINTER(Kv8Layer), I, P, P, P, P, P, P, P, P, P, P,
+                                               I, I, I, I, I, I, I, I, F, P])
 SIGNATURES["a3v_llama_decode_step_form"] = (I, [I, I, I, I, I, I, I])
 
 _lib = None

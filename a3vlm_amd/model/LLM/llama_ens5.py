@@ -227,6 +227,8 @@ class Transformer(nn.Module):
         self._k_cache: List[torch.Tensor] = []
         self._vt_cache: List[torch.Tensor] = []
         self._cache_shape = None
+        self._kv_quant: Optional[str] = None        # quantize_kv_cache: None = bf16 caches, "fp8" = e4m3 caches + per-position scales
+        self._kv8: Optional[Dict[str, object]] = None
         self._ws: Dict[tuple, torch.Tensor] = {}
         self._row_maps: Dict[tuple, tuple] = {}
 
@@ -337,10 +339,30 @@ class Transformer(nn.Module):
     def _allocate_kv_cache(self, bsz: int) -> None:
         """llama_ens5.py:171-176,533-535 (re-allocated only when the shape changes)."""
         smax = (self.args.max_seq_len + 63) // 64 * 64
-        shape = (bsz, self.n_kv_heads, smax, self.head_dim, self._dtype, str(self._device))
+        shape = (bsz, self.n_kv_heads, smax, self.head_dim, self._dtype, str(self._device), self._kv_quant)
         if self._cache_shape == shape:
             return
         dev, dtp = self._device, self._dtype
+        if self._kv_quant == "fp8":
+            # e4m3 caches and per-(batch, kv-head, position) scales per layer; ONE bf16 K / V^T pair at full Smax shared by all layers
+            # (the multi-token forward runs unchanged on it, layer after layer) and one single-position staging pair for decode
+            if dtp != torch.bfloat16:
+                raise RuntimeError("the fp8 KV cache needs a bf16 model")
+            Hkv, hd, L = self.n_kv_heads, self.head_dim, self.n_layers
+            self._destroy_kv_cache()
+            pair_k = torch.zeros(bsz, Hkv, smax, hd, dtype=dtp, device=dev)
+            pair_vt = torch.zeros(bsz, Hkv, hd, smax, dtype=dtp, device=dev)
+            self._kv8 = dict(
+                k_q=[torch.zeros(bsz, Hkv, smax, hd, dtype=torch.uint8, device=dev) for _ in range(L)],
+                vt_q=[torch.zeros(bsz, Hkv, hd, smax, dtype=torch.uint8, device=dev) for _ in range(L)],
+                k_scale=[torch.zeros(bsz, Hkv, smax, dtype=torch.float32, device=dev) for _ in range(L)],
+                v_scale=[torch.zeros(bsz, Hkv, smax, dtype=torch.float32, device=dev) for _ in range(L)],
+                stage_k=torch.zeros(bsz, Hkv, 1, hd, dtype=dtp, device=dev),
+                stage_vt=torch.zeros(bsz, Hkv, hd, 1, dtype=dtp, device=dev))
+            self._k_cache, self._vt_cache = [pair_k] * L, [pair_vt] * L
+            self._cache_shape = shape
+            return
+        self._kv8 = None
         self._k_cache = [torch.zeros(bsz, self.n_kv_heads, smax, self.head_dim, dtype=dtp, device=dev)
                          for _ in range(self.n_layers)]
         self._vt_cache = [torch.zeros(bsz, self.n_kv_heads, self.head_dim, smax, dtype=dtp, device=dev)
@@ -348,7 +370,24 @@ class Transformer(nn.Module):
         self._cache_shape = shape
 
     def _destroy_kv_cache(self) -> None:
-        self._k_cache, self._vt_cache, self._cache_shape = [], [], None
+        self._k_cache, self._vt_cache, self._cache_shape, self._kv8 = [], [], None, None
+
+    def quantize_kv_cache(self, mode: Optional[str] = "fp8") -> None:
+        """Opt-in fp8 (OCP e4m3fn) KV cache for ``forward_inference`` (format: include/a3vlm_hip.h, "fp8 KV cache"): half the cache
+        bytes a decode step reads and half the cache allocation.  ``None`` restores the bf16 cache.  Any allocated cache is dropped
+        (the next prefill allocates the new kind).  Independent of ``quantize_decode_weights`` -- either order.
+
+        Prefill is bit-identical to the bf16-cache model: every layer runs the unchanged bf16 kernels on one shared bf16 K / V^T pair
+        and a3v_kv_quantize_fp8 then moves the layer's new positions into its fp8 cache.  Decode (one token) quantises the new
+        position and runs a3v_attention_decode_fp8kv -- inside a3v_llama_decode_step_kv8 where the fused step form exists.  A
+        multi-token continuation dequantises each layer's prefix into the shared pair first.  bf16 models, head_dim 64 or 128."""
+        if mode not in (None, "fp8"):
+            raise ValueError(f"unknown KV-cache format {mode!r}: only 'fp8' (OCP e4m3fn, per-position scales) or None (bf16) exist")
+        if mode == "fp8" and self.head_dim not in (64, 128):
+            raise ValueError(f"the fp8 KV cache needs head_dim 64 or 128, this model has {self.head_dim}")
+        self._kv_quant = mode
+        self._destroy_kv_cache()
+        self._layer_tab_key = None
 
     # ------------------------------------------------------------------ linear dispatch
     def _skinny_ws(self, M: int, N: int, K: int) -> torch.Tensor:
@@ -392,6 +431,22 @@ class Transformer(nn.Module):
         w8a8 = (q8 is not None and getattr(self, "_fp8_prefill", False) and rows > 16 and h.dtype == torch.bfloat16
                 and hd in (64, 128))
         n4 = getattr(self, "_n4", None)
+        # fp8 KV cache (quantize_kv_cache): k_caches / vt_caches then hold the ONE shared bf16 pair.  S > 1: the layer runs unchanged on
+        # the pair (a continuation dequantises the layer's prefix into it first) and its new positions are quantised afterwards;
+        # S == 1: the new position goes through the staging pair into the fp8 cache and the attention reads the fp8 cache.
+        kv8 = self._kv8 if k_caches is self._k_cache else None
+        stage = kv8 is not None and S == 1
+        cpos = 0 if stage else start_pos             # where the qkv epilogue / rope kernel writes in the cache it is handed
+
+        def attend(i, kc, vc, strides):
+            if kv8 is None:
+                return ops.attention(qkv, kc, vc, att, B, S, Sk, H, Hkv, hd, strides, causal and S > 1, scratch)
+            fp8c = (kv8["k_q"][i], kv8["vt_q"][i], kv8["k_scale"][i], kv8["v_scale"][i])
+            if stage:
+                ops.kv_quantize_fp8(kc, vc, 0, *fp8c, 1, start_pos)
+                return ops.attention_decode_fp8kv(qkv, *fp8c, att, B, Sk, H, Hkv, hd, scratch)
+            ops.attention(qkv, kc, vc, att, B, S, Sk, H, Hkv, hd, strides, causal and S > 1, scratch)
+            ops.kv_quantize_fp8(kc, vc, start_pos, *fp8c, S, start_pos)
         if w8a8:
             if q8[0] != self._packed_version:
                 raise RuntimeError("parameters changed after quantize_decode_weights(): call it again (or with mode=None)")
@@ -400,6 +455,10 @@ class Transformer(nn.Module):
             sx = self._buf("fp8_sx", (rows,), torch.float32)
         for i, lyr in enumerate(self.layers):
             kc, vc = k_caches[i], vt_caches[i]
+            if stage:
+                kc, vc = kv8["stage_k"], kv8["stage_vt"]
+            elif kv8 is not None and start_pos > 0:
+                ops.kv_dequantize_fp8(kv8["k_q"][i], kv8["vt_q"][i], kv8["k_scale"][i], kv8["v_scale"][i], kc, vc, start_pos)
             smax = kc.shape[2]
             strides = (S * ldq, ldq, hd,                       # q: view into the qkv buffer
                        Hkv * smax * hd, smax * hd, hd,         # k cache
@@ -410,8 +469,8 @@ class Transformer(nn.Module):
                 # token on the fly (the RMSNorm output never exists in bf16), weights per output row, MX-scaled MFMA
                 (wqkv_q, wqkv_s), (wo_q, wo_s), (w13_q, w13_s), (w2_q, w2_s) = q8[1][i]
                 ops.quantize_rows_fp8(h, xq[:, :dim], sx, lyr.attention_norm.weight, a.norm_eps)
-                ops.gemm_qkv_rope_fp8(xq[:, :dim], sx, wqkv_q, wqkv_s, qkv, kc, vc, cs, B, S, H, Hkv, hd, start_pos, rope_pos0)
-                ops.attention(qkv, kc, vc, att, B, S, Sk, H, Hkv, hd, strides, causal and S > 1, scratch)
+                ops.gemm_qkv_rope_fp8(xq[:, :dim], sx, wqkv_q, wqkv_s, qkv, kc, vc, cs, B, S, H, Hkv, hd, cpos, rope_pos0)
+                attend(i, kc, vc, strides)
                 ops.quantize_rows_fp8(att, xq[:, :H * hd], sx)
                 ops.gemm_nt_fp8(xq[:, :H * hd], sx, wo_q, wo_s, h, residual=h)
                 ops.quantize_rows_fp8(h, xq[:, :dim], sx, lyr.ffn_norm.weight, a.norm_eps)
@@ -428,11 +487,11 @@ class Transformer(nn.Module):
             ops.rmsnorm(h, lyr.attention_norm.weight, xn, a.norm_eps)
             if rows > 16 and h.dtype == torch.bfloat16 and hd in (64, 128) and self._fuse_qkv_rope:
                 # rotary embedding + cache write in the GEMM epilogue: qkv never makes a second trip through HBM
-                ops.gemm_qkv_rope(xn, wqkv, qkv, kc, vc, cs, B, S, H, Hkv, hd, start_pos, rope_pos0)
+                ops.gemm_qkv_rope(xn, wqkv, qkv, kc, vc, cs, B, S, H, Hkv, hd, cpos, rope_pos0)
             else:
                 self._linear(xn, wqkv, qkv)
-                ops.rope_kvcache(qkv, qkv, kc, vc, cs, B, S, H, Hkv, hd, start_pos, rope_pos0)
-            ops.attention(qkv, kc, vc, att, B, S, Sk, H, Hkv, hd, strides, causal and S > 1, scratch)
+                ops.rope_kvcache(qkv, qkv, kc, vc, cs, B, S, H, Hkv, hd, cpos, rope_pos0)
+            attend(i, kc, vc, strides)
             self._linear(att, wo, h, residual=h)
             ops.rmsnorm(h, lyr.ffn_norm.weight, xn, a.norm_eps)
             self._linear(xn, w13, act, epilogue=ops.EPI_SWIGLU)
@@ -573,9 +632,16 @@ class Transformer(nn.Module):
         if q8 is not None and q8[0] != self._packed_version:
             raise RuntimeError("parameters changed after quantize_decode_weights(): call it again (or with mode=None)")
         n4 = getattr(self, "_n4", None)
+        kv8 = self._kv8
         key = (self._packed_version, self._cache_shape, q8 is not None, n4 is not None)
         if getattr(self, "_layer_tab_key", None) != key:
             tab = (_l.LlamaLayer * self.n_layers)()
+            self._kv8_tab = None
+            if kv8 is not None:            # fp8 KV cache: the k_cache / vt_cache fields below (the shared bf16 pair) are not read by the step
+                self._kv8_tab = (_l.Kv8Layer * self.n_layers)()
+                for i in range(self.n_layers):
+                    for f in ("k_q", "vt_q", "k_scale", "v_scale"):
+                        setattr(self._kv8_tab[i], f, kv8[f][i].data_ptr())
             for i, lyr in enumerate(self.layers):
                 if n4 is not None:         # NF4 images only: the bf16 fields stay NULL
                     (tab[i].wqkv_n4, tab[i].wqkv_n4s), (tab[i].wo_n4, tab[i].wo_n4s), (tab[i].w13_n4, tab[i].w13_n4s), (tab[i].w2_n4, tab[i].w2_n4s) = \
@@ -608,6 +674,14 @@ class Transformer(nn.Module):
         sws = self._skinny_ws(Bc, max((H + 2 * Hkv) * hd, 2 * self.ffn, a.dim), max(a.dim, self.ffn))
         for (n_, k_) in (((H + 2 * Hkv) * hd, a.dim), (a.dim, H * hd), (2 * self.ffn, a.dim), (a.dim, self.ffn)):
             sws = self._skinny_ws(Bc, n_, k_)
+        if kv8 is not None:
+            rc = _l.load().a3v_llama_decode_step_kv8(self._layer_tab, self._kv8_tab, self.n_layers, h.data_ptr(), xn.data_ptr(), qkv.data_ptr(),
+                                                     att.data_ptr(), act.data_ptr(), scratch.data_ptr(), sws.data_ptr(),
+                                                     self._cos_sin_dev().data_ptr(), kv8["stage_k"].data_ptr(), kv8["stage_vt"].data_ptr(),
+                                                     B, a.dim, H, Hkv, hd, self.ffn, smax, pos, a.norm_eps,
+                                                     torch.cuda.current_stream().cuda_stream)
+            _l.check(rc, "a3v_llama_decode_step_kv8")
+            return
         rc = _l.load().a3v_llama_decode_step(self._layer_tab, self.n_layers, h.data_ptr(), xn.data_ptr(), qkv.data_ptr(),
                                              att.data_ptr(), act.data_ptr(), scratch.data_ptr(), sws.data_ptr(), self._cos_sin_dev().data_ptr(),
                                              B, a.dim, H, Hkv, hd, self.ffn, smax, pos, a.norm_eps,
@@ -846,7 +920,9 @@ class Transformer(nn.Module):
             # chunks); a geometry they do not take goes through the general kernels -- decided BEFORE h or the KV cache are touched, an
             # error from inside the step is never papered over
             w8 = 2 if getattr(self, "_n4", None) is not None else 1 if getattr(self, "_q8", None) is not None else 0
-            if _lib.load().a3v_llama_decode_step_form(B, a.dim, a.n_heads, self.n_kv_heads, self.head_dim, self.ffn, w8) or (B <= 16 and w8 != 2):
+            form = _lib.load().a3v_llama_decode_step_form(B, a.dim, a.n_heads, self.n_kv_heads, self.head_dim, self.ffn, w8)
+            # (an fp8 KV cache has the fused form only: elsewhere the per-kernel sequence of _decoder_layers)
+            if form == 2 or (self._kv8 is None and (form or (B <= 16 and w8 != 2))):
                 self._decode_step(h, B, start_pos)
             else:
                 self._decoder_layers(h, B, S, start_pos, rope0, self._k_cache, self._vt_cache, True)

@@ -83,6 +83,13 @@ class Transformer(base.Transformer):
             raise NotImplementedError("NF4 decode weights beside LoRA adapters are not implemented: merge_adapters() first")
         super().quantize_decode_weights(mode, prefill)
 
+    def quantize_kv_cache(self, mode: Optional[str] = "fp8") -> None:
+        if mode is not None and not self._merged:
+            # decode beside adapters runs kernel by kernel with the adapter hooks (no fused step): the fp8 cache is not wired into it
+            raise NotImplementedError("the fp8 KV cache is not implemented beside LoRA adapters: merge_adapters() first "
+                                      "(MetaModel.merge_lora / --merge_lora), then quantize_kv_cache('fp8')")
+        super().quantize_kv_cache(mode)
+
     def quantize_base_weights(self, mode: str = "nf4") -> None:
         """QLoRA (the reference's ``main_finetune.py --quant``: bf16 model, checkpoint, ``quantize(model, nf4)``, then train what is left
         trainable; util/quant.py:95-163 skips every ``lora`` module).  The seven decoder linears of every layer and ``output`` are

@@ -72,7 +72,7 @@ class MetaModel(nn.Module):
     @classmethod
     def from_pretrained(cls, pretrained_path, llama_type: Optional[str] = None, llama_config=None,
                         tokenizer_path: Optional[str] = None, with_visual: bool = False, max_seq_len: int = 4096,
-                        mp_group=None, dtype=torch.bfloat16, device="cuda", quant=False) -> "MetaModel":
+                        mp_group=None, dtype=torch.bfloat16, device="cuda", quant=False, kv_quant: Optional[str] = None) -> "MetaModel":
         """Build the model a checkpoint folder describes and load it (reference: model/meta.py:88-222).
 
         What is not given is looked up in the LAST folder of ``pretrained_path``: ``llama_type`` in ``meta.json``,
@@ -83,7 +83,9 @@ class MetaModel(nn.Module):
         package's weight-only fp8 decoder images (``Transformer.quantize_decode_weights("fp8")``) instead of bitsandbytes NF4.
         ``quant="nf4"`` is the reference's 4-bit mode (meta.py:197-219, util/quant.py:95-163): the bf16 checkpoint is loaded,
         then every decoder linear and the LM head is quantised to NF4 layer by layer and its bf16 weight freed
-        (``Transformer.quantize_decode_weights("nf4")``; inference only, irreversible)."""
+        (``Transformer.quantize_decode_weights("nf4")``; inference only, irreversible).
+        ``kv_quant="fp8"`` (no reference counterpart) keeps the KV cache of ``generate`` in fp8 e4m3 with per-position scales
+        (``Transformer.quantize_kv_cache``); independent of ``quant``."""
         import os
         import warnings
         from ..checkpoint import load_tensor_parallel_model_list
@@ -128,6 +130,8 @@ class MetaModel(nn.Module):
             model.llma.quantize_decode_weights("nf4")
         elif quant:
             model.llma.quantize_decode_weights("fp8")
+        if kv_quant is not None:
+            model.llma.quantize_kv_cache(kv_quant)
         model.eval()
         return model
 

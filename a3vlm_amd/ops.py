@@ -383,6 +383,49 @@ def attention(q, k, vt, out, B, Sq, Sk, H, Hkv, hd, strides, causal: bool, scrat
     return out
 
 
+def kv_quantize_fp8(k_src, vt_src, src_pos: int, k_q, vt_q, k_scale, v_scale, S: int, dst_pos: int):
+    """Positions src_pos .. src_pos+S-1 of a bf16 K [B,Hkv,Smax_src,hd] / V^T [B,Hkv,hd,Smax_src] pair -> positions dst_pos .. of the fp8
+    caches (uint8, same layouts) and their per-(batch, kv-head, position) fp32 scales."""
+    _dev(k_src, vt_src, k_q, vt_q, k_scale, v_scale)
+    B, Hkv, Smax, hd = k_q.shape
+    assert k_src.dtype == vt_src.dtype == torch.bfloat16 and k_q.dtype == vt_q.dtype == torch.uint8
+    assert k_src.is_contiguous() and vt_src.is_contiguous() and k_q.is_contiguous() and vt_q.is_contiguous()
+    assert k_src.shape[0] >= B and tuple(vt_q.shape) == (B, Hkv, hd, Smax) and tuple(k_scale.shape) == tuple(v_scale.shape) == (B, Hkv, Smax)
+    assert tuple(k_src.shape[1:]) == (Hkv, k_src.shape[2], hd) and tuple(vt_src.shape[1:]) == (Hkv, hd, k_src.shape[2])
+    rc = _l.load().a3v_kv_quantize_fp8(_p(k_src), _p(vt_src), k_src.shape[2], src_pos, _p(k_q), _p(vt_q), _p(k_scale), _p(v_scale),
+                                       B, Hkv, hd, S, Smax, dst_pos, _stream())
+    _l.check(rc, f"a3v_kv_quantize_fp8(B={B},Hkv={Hkv},hd={hd},S={S},dst_pos={dst_pos},Smax={Smax})")
+
+
+def kv_dequantize_fp8(k_q, vt_q, k_scale, v_scale, k_dst, vt_dst, n: int):
+    """Positions 0 .. n-1 of the fp8 caches -> the same positions of a bf16 K / V^T pair: bf16(float(q) * scale)."""
+    _dev(k_q, vt_q, k_scale, v_scale, k_dst, vt_dst)
+    B, Hkv, Smax, hd = k_q.shape
+    assert k_dst.dtype == vt_dst.dtype == torch.bfloat16 and k_q.dtype == vt_q.dtype == torch.uint8
+    assert k_dst.is_contiguous() and vt_dst.is_contiguous() and k_q.is_contiguous() and vt_q.is_contiguous()
+    assert tuple(k_dst.shape) == (B, Hkv, k_dst.shape[2], hd) and tuple(vt_dst.shape) == (B, Hkv, hd, k_dst.shape[2])
+    rc = _l.load().a3v_kv_dequantize_fp8(_p(k_q), _p(vt_q), _p(k_scale), _p(v_scale), Smax, _p(k_dst), _p(vt_dst), k_dst.shape[2],
+                                         B, Hkv, hd, n, _stream())
+    _l.check(rc, f"a3v_kv_dequantize_fp8(B={B},Hkv={Hkv},hd={hd},n={n})")
+
+
+def attention_decode_fp8kv_splits(B: int, H: int, Sk: int) -> int:
+    return _l.load().a3v_attention_decode_fp8kv_splits(B, H, Sk)
+
+
+def attention_decode_fp8kv(q, k_q, vt_q, k_scale, v_scale, out, B, Sk, H, Hkv, hd, scratch, counters=None):
+    """Decode attention over an fp8 KV cache: q bf16 [B, ldq] (head h at column h*hd; a view into the qkv buffer), out bf16
+    [B, >= H*hd].  counters (int32 [>= B*H], zero; left zero): the split partials are merged inside the launch."""
+    _dev(q, k_q, vt_q, k_scale, v_scale, out, scratch, counters)
+    assert q.dtype == out.dtype == torch.bfloat16 and k_q.dtype == vt_q.dtype == torch.uint8 and scratch.dtype == torch.float32
+    assert k_q.is_contiguous() and vt_q.is_contiguous() and k_scale.is_contiguous() and v_scale.is_contiguous()
+    assert scratch.numel() >= attention_scratch_floats(B, H, hd, Sk) and (counters is None or counters.numel() >= B * H)
+    rc = _l.load().a3v_attention_decode_fp8kv(_p(q), q.stride(0), _p(k_q), _p(vt_q), _p(k_scale), _p(v_scale), _p(out), out.stride(0),
+                                              B, Sk, H, Hkv, hd, k_q.shape[2], _p(scratch), _p(counters), _stream())
+    _l.check(rc, f"a3v_attention_decode_fp8kv(B={B},Sk={Sk},H={H},hd={hd})")
+    return out
+
+
 def embed_assemble(tokens, table, h, B, T, W, dim):
     _dev(tokens, table, h)
     assert tokens.dtype == torch.int64 and tokens.stride(1) == 1

@@ -443,7 +443,51 @@ int a3v_llama_decode_step(const a3v_llama_layer* layers, int n_layers, void* h, 
 int a3v_llama_decode_step_form(int B, int dim, int H, int Hkv, int hd, int ffn, int w8);   /* w8: 0 bf16, 1 fp8, 2 NF4 images */
 
 /* ---------------------------------------------------------------------------------------
- * Training (backward) entry points.  Reference: autograd through the same modules under
+ * fp8 KV cache (opt-in; no reference counterpart: the reference's cache is bf16, LLM/llama_ens5.py:171-176).  Format:
+ *   k_q  [B,Hkv,Smax,hd] and vt_q [B,Hkv,hd,Smax]: OCP e4m3fn bytes in the layouts of the bf16 caches, Smax % 64 == 0;
+ *   k_scale, v_scale [B,Hkv,Smax] fp32: one scale per (batch, kv-head, position) for K and one for V;
+ *   over the hd values x of one head at one position (K: after RoPE), as a3v_quantize_rows_fp8 / oracle.quant_fp8:
+ *   scale = max(max|x|, 1e-12) / 448, q = e4m3(x / scale) (round to nearest even, saturating); a zero row stays finite;
+ *   the dequantised value is float(q) * scale.
+ * hd must be 64 or 128: anything else is A3V_ERR_SHAPE before any launch.  Every cache / scale pointer 16-B aligned.
+ *
+ * a3v_kv_quantize_fp8: positions src_pos .. src_pos+S-1 of a bf16 K / V^T pair (k_src [B,Hkv,Smax_src,hd], vt_src
+ * [B,Hkv,hd,Smax_src]) -> positions dst_pos .. dst_pos+S-1 of the fp8 caches and their scales, one launch for S = 1 (decode,
+ * Smax_src = 1) as for a prefill.  Nothing outside the S positions is written.
+ * a3v_kv_dequantize_fp8: positions 0 .. n-1 -> the same positions of a bf16 pair (k_dst [B,Hkv,Smax_dst,hd], vt_dst
+ * [B,Hkv,hd,Smax_dst]), each value bf16(float(q) * scale); nothing else is written. */
+int a3v_kv_quantize_fp8(const void* k_src, const void* vt_src, int Smax_src, int src_pos, void* k_q, void* vt_q, float* k_scale,
+                        float* v_scale, int B, int Hkv, int hd, int S, int Smax, int dst_pos, void* stream);
+int a3v_kv_dequantize_fp8(const void* k_q, const void* vt_q, const float* k_scale, const float* v_scale, int Smax, void* k_dst,
+                          void* vt_dst, int Smax_dst, int B, int Hkv, int hd, int n, void* stream);
+/* Decode attention (one query row per batch row) over an fp8 cache: out[b, h*hd ..] = softmax((q . kq) k_scale softmax_scale) .
+ * (vq v_scale) over keys 0 .. Sk-1, every factor applied in fp32.  q bf16 [B, ldq] (head h at column h*hd), out bf16 [B, ldo].
+ * Cache positions >= Sk and their scales may hold anything (NaN codes, inf).  scratch: a3v_attention_scratch_floats(B, H, hd, Sk)
+ * floats.  counters: NULL = the split partials are merged by a second launch; else B*H zero-initialised ints (left zero) and the
+ * last-arriving block of a (batch, head) merges them in the same launch -- both forms give the same bits.
+ * a3v_attention_decode_fp8kv_splits: the number of key ranges a (batch, head) is split into (> 1: partials are merged). */
+int a3v_attention_decode_fp8kv(const void* q, int64_t ldq, const void* k_q, const void* vt_q, const float* k_scale,
+                               const float* v_scale, void* out, int64_t ldo, int B, int Sk, int H, int Hkv, int hd, int Smax,
+                               float* scratch, int* counters, void* stream);
+int a3v_attention_decode_fp8kv_splits(int B, int H, int Sk);
+/* a3v_llama_decode_step over an fp8 KV cache: the same arguments (the k_cache / vt_cache fields of `layers` are not read) plus one
+ * a3v_kv8_layer per layer and ONE bf16 staging pair stage_k [B,Hkv,1,hd] / stage_vt [B,Hkv,hd,1] shared by all layers.  Fused
+ * form only (a3v_llama_decode_step_form == 2, else A3V_ERR_SHAPE with nothing touched), SIX launches per layer: the qkv GEMV
+ * writes the rotated k / v of the new position into the staging pair, a3v_kv_quantize_fp8 (S = 1) moves it to `pos`,
+ * a3v_attention_decode_fp8kv reads pos + 1 keys -- the new one from the fp8 cache like every other -- then wo, w1|w3, w2. */
+typedef struct a3v_kv8_layer {
+  void* k_q;          /* [B,Hkv,Smax,hd] e4m3 */
+  void* vt_q;         /* [B,Hkv,hd,Smax] e4m3 */
+  float* k_scale;     /* [B,Hkv,Smax] */
+  float* v_scale;     /* [B,Hkv,Smax] */
+} a3v_kv8_layer;
+int a3v_llama_decode_step_kv8(const a3v_llama_layer* layers, const a3v_kv8_layer* kv8, int n_layers, void* h, void* xn, void* qkv,
+                              void* att, void* act, float* attn_scratch, void* skinny_ws, const float* cos_sin, void* stage_k,
+                              void* stage_vt, int B, int dim, int H, int Hkv, int hd, int ffn, int Smax, int pos, float eps,
+                              void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Training (backward) entry points. Reference: autograd through the same modules under
  * autocast(bf16) with fp32 master weights (engine_finetune.py:44-68, main_finetune.py:212-217).
  * Convention: activations and their grads use `act_dtype` (bf16 / f32 parity); the residual
  * stream h, master weights and weight grads are fp32.  GEMM-shaped backward work goes through
