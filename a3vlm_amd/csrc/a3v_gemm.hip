@@ -2450,6 +2450,23 @@ extern "C" int a3v_gemm_qkv_rope_fp8(const void* Aq, int64_t lda, const float* s
   return gemm_nt_fp8_impl(Aq, lda, sa, Wq, ldw, sw, q_out, ldq, B * S, (H + 2 * Hkv) * hd, K, nullptr, nullptr, 0, 0, stream, &rk);
 }
 
+// The training form: a3v_gemm_qkv_rope_fp8 with the two operands of a3v_gemm_qkv_rope the training forward needs -- v_rows and delta,
+// through the same epilogue code (the fp8 kernels scale their accumulators in front of the bf16 kernels' epilogues).
+extern "C" int a3v_gemm_qkv_rope_fp8_train(const void* Aq, int64_t lda, const float* sa, const void* Wq, int64_t ldw, const float* sw, int K,
+                                           void* q_out, int64_t ldq, void* k_cache, void* vt_cache, void* v_rows, int64_t ldv,
+                                           const void* delta, int64_t ldd, const float* cos_sin, int B, int S, int H, int Hkv, int hd,
+                                           int Smax, int start_pos, int rope_pos0, void* stream) {
+  if (!q_out || !k_cache || !vt_cache || !cos_sin || B <= 0 || S <= 0 || H <= 0 || Hkv <= 0) return A3V_ERR_ARG;
+  if ((hd != 64 && hd != 128) || ldq % 4 || (v_rows && ldv % 4) || (delta && ldd % 4) || start_pos < 0 || start_pos + S > Smax) return A3V_ERR_SHAPE;
+  RopeKvArgs rk{};
+  rk.q_out = (bf16_t*)q_out; rk.k_cache = (bf16_t*)k_cache; rk.vt_cache = (bf16_t*)vt_cache; rk.cos_sin = cos_sin;
+  rk.v_rows = (bf16_t*)v_rows; rk.ldv = ldv;
+  rk.ldq = ldq; rk.S = S; rk.H = H; rk.Hkv = Hkv; rk.hd_shift = hd == 128 ? 7 : 6; rk.Smax = Smax;
+  rk.start_pos = start_pos; rk.rope_pos0 = rope_pos0; rk.m_off = 0;
+  return gemm_nt_fp8_impl(Aq, lda, sa, Wq, ldw, sw, q_out, ldq, B * S, (H + 2 * Hkv) * hd, K, nullptr, delta, ldd,
+                          delta ? A3V_EPI_RESIDUAL : 0, stream, &rk);
+}
+
 // "NN" GEMM: C[M,N] = epilogue(A . Wt) with A [M, K] row-major and Wt [K, N] row-major (the contracted index is Wt's ROW index) --
 // the input gradient dX = dY . W on the weight image the forward pass uses, without a transposed copy of W.  K % 64 == 0.
 extern "C" int a3v_gemm_nn(const void* A, int64_t lda, const void* Wt, int64_t ldw, void* C, int64_t ldc, int M, int N, int K,

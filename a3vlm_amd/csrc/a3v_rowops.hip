@@ -119,6 +119,67 @@ __global__ __launch_bounds__(256) void rows_quant_fp8_kernel(const TX* __restric
   }
 }
 
+// The column-scaled form (fp8 frozen base, the input gradient dX = (dY * sw) . Wq): y[row][c] = fl32(x[row][c] * cs[c]), then scale /
+// bytes exactly as rows_quant_fp8_kernel; every row gets cols_pad >= cols bytes, zero beyond cols (the contraction length of the GEMM
+// that follows is a multiple of 128 without a padded copy of x).  One pass: a lane keeps 16 columns per step, one 16-byte store each;
+// MAXV steps: 4 for rows up to 16384 columns, 8 up to 32768 (the gradient of the fused w1|w3 output at 7B / 13B is 22016 / 27648 wide).
+template <typename TX, int MAXV>
+__global__ __launch_bounds__(256) void rows_quant_fp8_cs_kernel(const TX* __restrict__ x, int64_t ldx, const float* __restrict__ cs,
+                                                                uint8_t* __restrict__ q, int64_t ldq, float* __restrict__ scales, int cols,
+                                                                int cols_pad) {
+  __shared__ float red[4];
+  const int row = blockIdx.x, tid = threadIdx.x;
+  const TX* xr = x + (int64_t)row * ldx;
+  float v[MAXV][16];      // cols_pad <= 256 * 16 * MAXV
+  float amax = 0.f;
+#pragma unroll
+  for (int i = 0; i < MAXV; ++i) {
+    const int c = (tid + i * 256) * 16;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      float* vh = v[i] + h * 8;
+      if (c + h * 8 < cols) {               // cols % 8 == 0: a group of 8 is inside the row or beyond it
+        float sc[8];
+        load8(xr + c + h * 8, vh);
+        load8(cs + c + h * 8, sc);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          vh[e] *= sc[e];
+          amax = fmaxf(amax, fabsf(vh[e]));
+        }
+      } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) vh[e] = 0.f;
+      }
+    }
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
+  if ((tid & 63) == 0) red[tid >> 6] = amax;
+  __syncthreads();
+  amax = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  const float scale = fmaxf(amax, 1e-12f) * (1.f / 448.f);
+  const float rs = 1.f / scale;
+  if (tid == 0) scales[row] = scale;
+  uint8_t* qr = q + (int64_t)row * ldq;
+#pragma unroll
+  for (int i = 0; i < MAXV; ++i) {
+    const int c = (tid + i * 256) * 16;
+    if (c < cols_pad) {
+      int w[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        float t[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) t[e] = fminf(fmaxf(v[i][k * 4 + e] * rs, -448.f), 448.f);
+        w[k] = __builtin_amdgcn_cvt_pk_fp8_f32(t[0], t[1], 0, false);
+        w[k] = __builtin_amdgcn_cvt_pk_fp8_f32(t[2], t[3], w[k], true);
+      }
+      *reinterpret_cast<int4*>(qr + c) = make_int4(w[0], w[1], w[2], w[3]);
+    }
+  }
+}
+
 // ---------------------------------------------------------------- LayerNorm (torch.nn.LayerNorm)
 template <typename T, typename TP, typename TY>
 __global__ __launch_bounds__(256) void layernorm_kernel(const T* __restrict__ x, int64_t ldx, const TP* __restrict__ w,
@@ -1200,6 +1261,27 @@ extern "C" int a3v_quantize_rows_fp8(const void* x, int64_t ldx, const void* nor
   if (x_dtype == A3V_BF16) {
     if (norm_w) hipLaunchKernelGGL((rows_quant_fp8_kernel<bf16_t, bf16_t, true>), g, b, 0, ST, (const bf16_t*)x, ldx, (const bf16_t*)norm_w, (uint8_t*)q, ldq, scales, dim, eps);
     else hipLaunchKernelGGL((rows_quant_fp8_kernel<bf16_t, bf16_t, false>), g, b, 0, ST, (const bf16_t*)x, ldx, (const bf16_t*)nullptr, (uint8_t*)q, ldq, scales, dim, eps);
+  } else {
+    return A3V_ERR_DTYPE;
+  }
+  A3V_LAUNCH_CHECK();
+  return A3V_OK;
+}
+
+extern "C" int a3v_quantize_rows_fp8_cs(const void* x, int64_t ldx, const float* cs, void* q, int64_t ldq, float* scales, int rows,
+                                        int cols, int cols_pad, int x_dtype, void* stream) {
+  if (!x || !cs || !q || !scales || rows <= 0 || cols <= 0) return A3V_ERR_ARG;
+  if (cols % 8 || cols_pad < cols || cols_pad % 16 || cols_pad > 32768 || ldx % 8 || ldx < cols || ldq % 16 || ldq < cols_pad ||
+      (reinterpret_cast<uintptr_t>(q) & 15) || (reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(cs) & 15))
+    return A3V_ERR_SHAPE;
+  dim3 g(rows), b(256);
+  const bool wide = cols_pad > 16384;
+  if (x_dtype == A3V_BF16) {
+    if (wide) hipLaunchKernelGGL((rows_quant_fp8_cs_kernel<bf16_t, 8>), g, b, 0, ST, (const bf16_t*)x, ldx, cs, (uint8_t*)q, ldq, scales, cols, cols_pad);
+    else hipLaunchKernelGGL((rows_quant_fp8_cs_kernel<bf16_t, 4>), g, b, 0, ST, (const bf16_t*)x, ldx, cs, (uint8_t*)q, ldq, scales, cols, cols_pad);
+  } else if (x_dtype == A3V_F32) {
+    if (wide) hipLaunchKernelGGL((rows_quant_fp8_cs_kernel<float, 8>), g, b, 0, ST, (const float*)x, ldx, cs, (uint8_t*)q, ldq, scales, cols, cols_pad);
+    else hipLaunchKernelGGL((rows_quant_fp8_cs_kernel<float, 4>), g, b, 0, ST, (const float*)x, ldx, cs, (uint8_t*)q, ldq, scales, cols, cols_pad);
   } else {
     return A3V_ERR_DTYPE;
   }

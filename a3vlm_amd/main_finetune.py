@@ -16,7 +16,9 @@ checkpoint loaded, the decoder linears and the LM head quantised to NF4 (``quant
 broadcast) and what is left trainable -- adapters, norms, projectors -- trained; it needs a peft ``--llama_type``,
 ``--only_save_trainable`` and ``--precision bf16``, and does not combine with ``--zero1``.  To resume, give the base
 checkpoint as ``--pretrained_path`` and the adapter checkpoint as ``--resume``: the base is quantised before the adapters are loaded by
-name.  ``--synthetic N`` substitutes a seeded synthetic dataset of N
+name.  ``--base_fp8`` is the same flow on a frozen fp8 (e4m3, per-row scales) base: the seven decoder linears of every layer are quantised
+after the checkpoint (``quantize_base_weights("fp8")``) and the base GEMMs of the LoRA step run on fp8 operands, adapters in bf16
+(DESIGN.md 7c); same requirements, and it does not combine with ``--quant``.  ``--synthetic N`` substitutes a seeded synthetic dataset of N
 items of the dialog dataset's output shape (the real dataset classes are the next host-side row).
 """
 from __future__ import annotations
@@ -77,6 +79,9 @@ def get_args_parser():
     p.add_argument("--precision", type=str, choices=["fp16", "bf16", "tf32"], default="bf16")
     p.add_argument("--checkpointing", action="store_true", default=False)
     p.add_argument("--quant", action="store_true", default=False)
+    p.add_argument("--base_fp8", action="store_true", default=False,
+                   help="LoRA fine-tune on a frozen fp8 (e4m3, per-row scales) base: the base GEMMs of the step run on fp8 operands, "
+                        "the adapters stay bf16 (quantize_base_weights('fp8'), DESIGN.md 7c)")
     p.add_argument("--synthetic", type=int, default=0, help="use a seeded synthetic dataset of this many items")
     p.add_argument("--max_seq_len", type=int, default=None)
     p.add_argument("--zero1", action="store_true", default=False,
@@ -145,6 +150,18 @@ def main(args):
             raise SystemExit("--quant needs --precision bf16 (NF4 weights dequantise to bf16 GEMM images)")
         if args.zero1:
             raise SystemExit("--quant does not combine with --zero1: ZeRO-1 shards compute-dtype base matrices, and an NF4 base has none")
+    if args.base_fp8:
+        # LoRA fine-tune on a frozen fp8 base (no reference counterpart); refused up front, before the GPU is touched
+        if args.quant:
+            raise SystemExit("--base_fp8 does not combine with --quant: the frozen base is either fp8 or NF4")
+        if "peft" not in args.llama_type:
+            raise SystemExit(f"--base_fp8 trains adapters on a frozen fp8 base: it needs a peft --llama_type (llama_ens5_peft), not {args.llama_type}")
+        if not args.only_save_trainable:
+            raise SystemExit("--base_fp8 needs --only_save_trainable: the fp8 base matrices are not in state_dict()")
+        if args.precision != "bf16":
+            raise SystemExit("--base_fp8 needs --precision bf16 (the fp8 base GEMMs produce bf16 activations)")
+        if args.zero1:
+            raise SystemExit("--base_fp8 does not combine with --zero1: ZeRO-1 shards compute-dtype base matrices, and an fp8 base has none")
     if os.environ.get("A3V_ONE_DEVICE") == "1":      # tests: several ranks on a single-GPU box (with A3V_DIST_BACKEND=gloo)
         local = 0
     torch.cuda.set_device(local)
@@ -170,6 +187,8 @@ def main(args):
             dist.broadcast(p.data, src=0)
     if args.quant:                                                       # :200-209, after the checkpoint: each rank quantises its own copy
         model.llma.quantize_base_weights("nf4")
+    if args.base_fp8:                                                    # likewise after the checkpoint, on every rank
+        model.llma.quantize_base_weights("fp8")
     model.llma.invalidate_packed_weights()
     if args.precision == "tf32":
         model.train_compute_dtype = torch.float32

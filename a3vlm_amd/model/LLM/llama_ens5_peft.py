@@ -42,7 +42,10 @@ def _pad64(n: int) -> int:
 def base_shape(mod) -> tuple:
     """(out, in) of a decoder linear's base matrix, also after ``quantize_base_weights`` freed its bf16 ``weight``."""
     q4 = getattr(mod, "q4", None)
-    return tuple(mod.weight.shape) if q4 is None else q4[2]
+    if q4 is not None:
+        return q4[2]
+    q8 = getattr(mod, "q8_shape", None)
+    return tuple(mod.weight.shape) if q8 is None else q8
 
 
 def merged_args(args: ModelArgs) -> base.ModelArgs:
@@ -73,6 +76,7 @@ class Transformer(base.Transformer):
         self._lora_img: Dict[str, torch.Tensor] = {}
         self._lora_ver = None
         self._q4: Optional[Dict[str, tuple]] = None      # quantize_base_weights: module name -> (nibbles, scales, (N, K))
+        self._q8base: Optional[Dict[str, tuple]] = None  # quantize_base_weights("fp8"): "<kind>.<layer>" -> (Wq, sw, WqT) of the fused group
         self._merged = False                             # merge_adapters: from then on every override below defers to the base class
 
     def quantize_decode_weights(self, mode: str = "fp8", prefill: bool = False) -> None:
@@ -102,13 +106,26 @@ class Transformer(base.Transformer):
         layer's Wd in a reused scratch, then the bf16 kernels plus adapters of the unquantised plugin -- bit-identical to the bf16 model
         holding Wd, but every decode step dequantises every layer again: decode speed on this path is not a goal.
 
-        Needs bf16 base matrices on the GPU and K % 64 == 0 for every module (the format); none of the NF4 decode GEMV's limits."""
-        if mode != "nf4":
-            raise ValueError("only 'nf4' base weights are implemented")
+        Needs bf16 base matrices on the GPU and K % 64 == 0 for every module (the format); none of the NF4 decode GEMV's limits.
+
+        ``mode="fp8"``: the frozen base as OCP e4m3fn bytes for the LoRA step's base GEMMs.  Each fused GEMM group of a
+        layer (``GROUPS``: wq|wk|wv, wo, w1|w3, w2; rows in image order) is quantised per output row by a3v_quantize_rows_fp8 into
+        ``Wq`` [N, K] bytes and ``sw`` [N] fp32, and ``WqT`` [K, N padded to 128] is the byte transpose of Wq (zero pad; not a second
+        quantisation) for the input gradient; ``self._q8base["<kind>.<layer>"] = (Wq, sw, WqT)``.  The bf16 ``weight`` of the seven
+        linears is freed as above; ``output``, norms, embeddings, projectors, tags and adapters are untouched.  Training runs the base
+        products on a3v_gemm_nt_fp8 (``TrainEngine``); inference dequantises a layer's Wd = bf16(Wq * sw) into the reused scratch and
+        runs the unquantised plugin's kernels -- bit-identical to the bf16 model holding Wd.  Needs bf16 base matrices on the GPU,
+        K % 128 == 0 for every decoder linear (the fp8 MFMA's K step) and head_dim 64 or 128."""
+        if mode not in ("nf4", "fp8"):
+            raise ValueError("only 'nf4' and 'fp8' base weights are implemented")
         if self._merged:
             raise RuntimeError("the adapters are merged: this is a plain llama_ens5 model now (quantize_decode_weights quantises it for inference)")
         if self._q4 is not None:
             raise RuntimeError("the base weights are already NF4")
+        if self._q8base is not None:
+            raise RuntimeError("the base weights are already fp8")
+        if mode == "fp8":
+            return self._quantize_base_fp8()
         named = []
         for i, lyr in enumerate(self.layers):
             at, f = lyr.attention, lyr.feed_forward
@@ -133,6 +150,63 @@ class Transformer(base.Transformer):
         self._packed, self._packed_version = {}, None
         self._lora_ver = None
 
+    def _quantize_base_fp8(self) -> None:
+        if self.head_dim not in (64, 128):
+            raise ValueError(f"fp8 base weights need head_dim 64 or 128 (the fused qkv GEMM); got {self.head_dim}")
+        for i, lyr in enumerate(self.layers):
+            for kind, names in GROUPS.items():
+                for nm, mod in zip(names, group_modules(lyr, kind)):
+                    w = mod.weight
+                    if w.dtype != torch.bfloat16 or w.device.type != "cuda":
+                        raise ValueError(f"fp8 base weights need a bf16 model on the GPU (quantise after .to(device)); layers.{i}.{nm}.weight "
+                                         f"is {w.dtype} on {w.device}")
+                    if w.shape[1] % 128:
+                        raise ValueError(f"fp8 base weights need K % 128 == 0 for every decoder linear; layers.{i}.{nm}.weight is {tuple(w.shape)}")
+        q8: Dict[str, tuple] = {}
+        with torch.no_grad():
+            for i, lyr in enumerate(self.layers):
+                for kind in GROUPS:
+                    mods = group_modules(lyr, kind)
+                    w = torch.cat([mod.weight.data for mod in mods], dim=0) if len(mods) > 1 else mods[0].weight.data.contiguous()
+                    N, K = w.shape
+                    wq = torch.empty(N, K, dtype=torch.uint8, device=w.device)
+                    sw = torch.empty(N, dtype=torch.float32, device=w.device)
+                    ops.quantize_rows_fp8(w, wq, sw)
+                    wqt = torch.zeros(K, (N + 127) // 128 * 128, dtype=torch.uint8, device=w.device)
+                    wqt[:, :N] = wq.t()                      # the byte transpose (runs once per model: data movement only)
+                    q8[f"{kind}.{i}"] = (wq, sw, wqt)
+                    for mod in mods:
+                        mod.q8_shape = tuple(mod.weight.shape)
+                        del mod.weight
+                    del w
+        self._q8base = q8
+        self._packed, self._packed_version = {}, None
+        self._lora_ver = None
+
+    def _q8_dequantize(self, key: str, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Wd = bf16(float(Wq) * sw) of fused group ``key`` [N, K] (a torch cast and multiply: correctness paths only)."""
+        wq, sw, _ = self._q8base[key]
+        wd = (wq.view(torch.float8_e4m3fn).float() * sw[:, None]).to(torch.bfloat16)
+        return wd if out is None else out.copy_(wd)
+
+    def _q8_layer_weights(self, i: int):
+        """Wd of layer i in the reused scratch, in the row orders of ``_pack``: (wqkv, wo, w13 in 16-row blocks, w2)."""
+        a = self.args
+        H, Hkv, hd, F, dim = self.n_heads, self.n_kv_heads, self.head_dim, self.ffn, a.dim
+        shapes = (((H + 2 * Hkv) * hd, dim), (dim, H * hd), (2 * F, dim), (dim, F))
+        buf = self._buf("q4_scratch", (sum(n * k for n, k in shapes),), torch.bfloat16)
+        views, o = [], 0
+        for n, k in shapes:
+            views.append(buf[o:o + n * k].view(n, k))
+            o += n * k
+        wqkv, wo, w13, w2 = views
+        self._q8_dequantize(f"qkv.{i}", wqkv)
+        self._q8_dequantize(f"wo.{i}", wo)
+        self._q8_dequantize(f"w2.{i}", w2)
+        tmp = self._q8_dequantize(f"w13.{i}")
+        w13.view(F // 16, 2, 16, dim).copy_(tmp.view(2, F // 16, 16, dim).transpose(0, 1))     # data movement only (the SwiGLU row order)
+        return wqkv, wo, w13, w2
+
     def merge_adapters(self) -> None:
         """Fold every adapter into its base matrix, ``weight <- weight + lora_b . lora_a`` (a3v_lora_merge: fp32 accumulation, the base
         added in fp32, ONE rounding), and drop the adapters.  In place and irreversible.  Afterwards the object behaves as a
@@ -151,6 +225,20 @@ class Transformer(base.Transformer):
         Needs the model on the GPU and bf16 or fp32 base matrices of one dtype."""
         if self._merged:
             raise RuntimeError("the adapters are already merged")
+        if self._q8base is not None:
+            # fp8 base: every freed ``weight`` comes back as its bf16 Wd (one fused group alive at a time), then the bf16 route below
+            with torch.no_grad():
+                for i, lyr in enumerate(self.layers):
+                    for kind in GROUPS:
+                        wd, row = self._q8_dequantize(f"{kind}.{i}"), 0
+                        del self._q8base[f"{kind}.{i}"]
+                        for mod in group_modules(lyr, kind):
+                            n = mod.q8_shape[0]
+                            mod.weight = nn.Parameter(wd[row:row + n].clone(), requires_grad=False)
+                            del mod.q8_shape
+                            row += n
+                        del wd
+            self._q8base = None
         named = []
         for i, lyr in enumerate(self.layers):
             at, f = lyr.attention, lyr.feed_forward
@@ -194,12 +282,12 @@ class Transformer(base.Transformer):
             del self._ws[key]
 
     def _pack(self, check: bool = False) -> Dict[str, torch.Tensor]:
-        if self._q4 is None:
+        if self._q4 is None and self._q8base is None:
             return super()._pack(check)
         if self._packed_version is not None and not check:
             return self._packed
         ver = self._weights_version()
-        if self._packed_version != ver:              # NF4 base: the decoder matrices live only as NF4 images
+        if self._packed_version != ver:              # NF4 / fp8 base: the decoder matrices live only as quantised images
             with torch.no_grad():
                 self._packed = self._pack_vision() if self.with_visual else {}
             self._packed_version = ver
@@ -323,7 +411,9 @@ class Transformer(base.Transformer):
         for i, lyr in enumerate(self.layers):
             kc, vc = k_caches[i], vt_caches[i]
             smax = kc.shape[2]
-            if self._q4 is None:
+            if self._q8base is not None:       # fp8 base: likewise, Wd = bf16(Wq * sw)
+                wqkv, wo, w13, w2 = self._q8_layer_weights(i)
+            elif self._q4 is None:
                 wqkv, wo, w13, w2 = pk[f"wqkv.{i}"], lyr.attention.wo.weight, pk[f"w13.{i}"], lyr.feed_forward.w2.weight
             else:                              # NF4 base: the layer's Wd in a reused scratch, then the bf16 kernels unchanged
                 wqkv, wo, w13, w2 = self._q4_layer_weights(i)

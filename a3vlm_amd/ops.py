@@ -236,6 +236,32 @@ def gemm_qkv_rope_fp8(xq, sx, wq, sw, qkv, k_cache, vt_cache, cos_sin, B, S, H, 
     _l.check(rc, "a3v_gemm_qkv_rope_fp8")
 
 
+def quantize_rows_fp8_cs(x, cs, q, scales, cols_pad: Optional[int] = None):
+    """q[r, :cols] = fp8(y[r] / scales[r]) with y = x * cs[None, :] (fp32) and scales[r] = max|y[r]| / 448; q[r, cols:cols_pad] = 0."""
+    _dev(x, cs, q, scales)
+    rows, cols = x.shape
+    cols_pad = q.shape[1] if cols_pad is None else cols_pad
+    assert q.dtype == torch.uint8 and q.shape[0] >= rows and q.shape[1] >= cols_pad and q.stride(1) == 1 and x.stride(1) == 1
+    assert scales.dtype == torch.float32 and scales.numel() >= rows and scales.is_contiguous()
+    assert cs.dtype == torch.float32 and cs.numel() >= cols and cs.is_contiguous()
+    rc = _l.load().a3v_quantize_rows_fp8_cs(_p(x), x.stride(0), _p(cs), _p(q), q.stride(0), _p(scales), rows, cols, cols_pad, dt(x), _stream())
+    _l.check(rc, f"a3v_quantize_rows_fp8_cs(rows={rows},cols={cols},cols_pad={cols_pad})")
+    return q, scales
+
+
+def gemm_qkv_rope_fp8_train(xq, sx, wq, sw, q_out, k_cache, vt_cache, cos_sin, B, S, H, Hkv, hd, start_pos, rope_pos0, v_rows=None, delta=None):
+    """gemm_qkv_rope_fp8 with the training operands of gemm_qkv_rope: ``v_rows`` (v token-major) and ``delta`` (bf16 additive term)."""
+    _dev(xq, sx, wq, sw, q_out, k_cache, vt_cache, cos_sin, v_rows, delta)
+    assert xq.shape[0] == B * S and wq.shape[0] == (H + 2 * Hkv) * hd and xq.dtype == torch.uint8 and wq.dtype == torch.uint8
+    assert wq.shape[1] == xq.shape[1]
+    _ensure_gemm_workspace(xq.device)
+    rc = _l.load().a3v_gemm_qkv_rope_fp8_train(_p(xq), xq.stride(0), _p(sx), _p(wq), wq.stride(0), _p(sw), xq.shape[1], _p(q_out),
+                                               q_out.stride(0), _p(k_cache), _p(vt_cache), _p(v_rows), v_rows.stride(0) if v_rows is not None else 0,
+                                               _p(delta), delta.stride(0) if delta is not None else 0, _p(cos_sin), B, S, H, Hkv, hd,
+                                               k_cache.shape[2], start_pos, rope_pos0, _stream())
+    _l.check(rc, "a3v_gemm_qkv_rope_fp8_train")
+
+
 def gemm_skinny_fp8(a, wq, wscale, out, workspace, *, residual=None, epilogue: int = 0):
     """out = epilogue((a . float(wq)^T) * wscale): weight-only fp8 (torch.float8_e4m3fn / uint8 bytes) decode GEMV."""
     assert wq.element_size() == 1 and wscale.dtype == torch.float32 and wscale.numel() == wq.shape[0]

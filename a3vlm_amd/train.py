@@ -20,7 +20,7 @@ from typing import Callable, Dict, List, Optional, Tuple
 import torch
 
 from . import ops
-from .train_images import GROUPS, _AdapterImages, _Images, _Nf4Images, _pad64, group_modules
+from .train_images import GROUPS, _AdapterImages, _Fp8Images, _Images, _Nf4Images, _pad64, group_modules
 from .util import install_param_epoch_hook
 
 
@@ -112,6 +112,11 @@ class TrainEngine:
             self.nn_dgrad = bool(self.zero1_world)
         if self._q4base() and self.zero1_world:
             raise ValueError("ZeRO-1 shards compute-dtype base matrices; an NF4 base (quantize_base_weights) has none")
+        if self._q8base():
+            if self.zero1_world:
+                raise ValueError("ZeRO-1 shards compute-dtype base matrices; an fp8 base (quantize_base_weights) has none")
+            if compute_dtype != torch.bfloat16:
+                raise ValueError(f"an fp8 base trains under the bf16 compute dtype (the products of its GEMMs are bf16); got {compute_dtype}")
         self._flat_params: Optional[torch.Tensor] = None    # zero1: the sharded parameters' storage (compute dtype, flat-gradient layout)
         self._z1: List[tuple] = []                          # zero1: (bucket, start, end, shard_start, shard_end, [(seg_start, seg_end, name)])
         self._z1_fresh = True                               # zero1: the sharded gradients restart (store / zero) at the next backward
@@ -218,9 +223,15 @@ class TrainEngine:
         of one layer at a time are dequantised into a reused scratch (``_Nf4Images``)."""
         return getattr(self.m, "_q4", None) is not None
 
+    def _q8base(self) -> bool:
+        """The base matrices are fp8 (``quantize_base_weights("fp8")``): no bf16 ``weight`` exists; the base products of
+        the decoder GEMM groups run on a3v_gemm_nt_fp8 over the persistent e4m3 images (``_Fp8Images``), adapters beside them."""
+        return getattr(self.m, "_q8base", None) is not None
+
     def weight_image_bytes(self, head: bool = True) -> int:
-        """Bytes of compute-dtype weight images the engine holds right now (decoder GEMM images and their transposes; ``head``: also
-        the LM head's).  bf16 base: grows with the layers served so far.  NF4 base: one layer's worth whatever the depth."""
+        """Bytes of weight images the engine holds right now (decoder GEMM images and their transposes; ``head``: also the LM
+        head's).  bf16 base: grows with the layers served so far.  NF4 base: one layer's worth whatever the depth.  fp8 base: the
+        e4m3 image, its byte transpose and the row scales of every layer (2 B per decoder parameter), from the start."""
         return self._images().nbytes(head)
 
     def _kext_cols(self, key: str) -> int:
@@ -239,8 +250,8 @@ class TrainEngine:
     def _kext(self) -> int:
         """Columns appended to the inputs / weight images of the four decoder GEMMs when the adapters ride inside them
         (LoRA, bf16): y = [x | t] . [W | B]^T with t = x . A^T -- no separate read-modify-write pass over y."""
-        if not (self.lora and self.lora_kext and self.act == torch.bfloat16):
-            return 0
+        if not (self.lora and self.lora_kext and self.act == torch.bfloat16) or self._q8base():
+            return 0                                       # (fp8 base: the adapters stay bf16 and separate, beside the fp8 product)
         return _pad64(3 * int(self.m.lora_rank))          # the widest group (wq|wk|wv) sets one width for all four
 
     def _kx(self, rows: int) -> bool:
@@ -252,6 +263,8 @@ class TrainEngine:
         return ops.EPI_RES_F32 if out.dtype == torch.float32 and self.act == torch.bfloat16 else 0
 
     def _check_dtypes(self):
+        if self._q8base() and (self.act != torch.bfloat16 or self.zero1_world):
+            raise TypeError("an fp8 base (quantize_base_weights) trains under the bf16 compute dtype and without ZeRO-1")
         for n, p in self.m.get_trainable_params().items():
             if p.requires_grad and p.dtype != torch.float32 and not (self.zero1_world and p.dtype == self.act):
                 raise TypeError(f"trainable parameter {n} must be fp32 (promote_trainable_params_to_fp32, "
@@ -442,7 +455,9 @@ class TrainEngine:
         is (re)built on first use after its parameters changed.  (Issuing the AdamW update per layer on a side stream under the
         next forward was tried on top of this and measured no gain: the 256x256 GEMM leaves no VGPRs for a co-resident kernel.)"""
         if self._img is None or not isinstance(self._img, _Images):
-            self._img = _Nf4Images(self) if self._q4base() else _Images(self)
+            self._img = _Nf4Images(self) if self._q4base() else _Fp8Images(self) if self._q8base() else _Images(self)
+        if self._q8base() and not isinstance(self._img, _Fp8Images):
+            self._img = _Fp8Images(self)                  # (the model was quantised after this engine first ran)
         return self._img
 
     # ------------------------------------------------------------------ GEMM helpers
@@ -511,6 +526,15 @@ class TrainEngine:
         to the NT kernel on the transposed image for shapes / dtypes the NN kernel does not take."""
         im = self._images()
         M, N = dy.shape
+        if self._q8base() and key.split(".")[0] in GROUPS:
+            # fp8 base: dx = (dy * sw) . Wq -- the row scales of W folded into dy, quantised per row into the zero-padded width of the
+            # byte transpose, then the fp8 NT GEMM over it (weight-side scale 1)
+            wqt = im[key + ".qT"]
+            gq = self._buf("q8_g", (M, wqt.shape[1]), torch.uint8)
+            sg = self._buf("q8_sg", (M,), torch.float32)
+            ops.quantize_rows_fp8_cs(dy, im[key + ".s"], gq, sg)
+            ops.gemm_nt_fp8(gq, sg, wqt, im[key + ".one"], out)
+            return
         if self.nn_dgrad and self.act == torch.bfloat16 and N % 64 == 0 and dy.stride(0) % 8 == 0:
             w = im[key]
             if w.shape[0] == N and w.shape[1] % 8 == 0 and w.shape[1] >= 256 and 2 * M * dy.stride(0) < 2 ** 31 and 2 * w.numel() < 2 ** 31:
@@ -571,6 +595,15 @@ class TrainEngine:
         dy, full, _ = self._x_buf(name + ".x" if kx else name, cols, key, rows, kx)
         return dy, (full if kx else None)
 
+    def _base_fwd_fp8(self, key: str, x: torch.Tensor, out: torch.Tensor, residual: Optional[torch.Tensor] = None, epilogue: int = 0):
+        """out = epilogue((quant_rows(x) . Wq^T) * sx[m] * sw[n]): the base product of decoder GEMM ``key`` over an fp8 base."""
+        im = self._images()
+        xq = self._buf("q8_x", tuple(x.shape), torch.uint8)
+        sx = self._buf("q8_sx", (x.shape[0],), torch.float32)
+        ops.quantize_rows_fp8(x, xq, sx)
+        ops.gemm_nt_fp8(xq, sx, im[key + ".q"], im[key + ".s"], out, residual=residual, epilogue=epilogue)
+        return xq, sx
+
     def _group_fwd(self, i: int, kind: str, x: torch.Tensor, x_full: torch.Tensor, t: Optional[torch.Tensor], out: torch.Tensor,
                    residual: Optional[torch.Tensor] = None, epilogue: int = 0, tag: str = "") -> Optional[torch.Tensor]:
         """out = x . W^T (+ residual) of GEMM group ``kind`` of layer i with its adapters; (x, x_full, t) from ``_x_buf``.  Returns
@@ -581,7 +614,10 @@ class TrainEngine:
             self._lora_t(key, x, tag, t)
             ops.gemm_nt(x_full, im[key + ".x"], out, residual=residual, epilogue=epilogue)
             return t
-        ops.gemm_nt(x, im[key], out, residual=residual, epilogue=epilogue)
+        if self._q8base():
+            self._base_fwd_fp8(key, x, out, residual, epilogue)
+        else:
+            ops.gemm_nt(x, im[key], out, residual=residual, epilogue=epilogue)
         if not self.lora:
             return None
         t = self._lora_t(key, x, tag)                     # separate adapters: a read-modify-write pass over the output
@@ -721,7 +757,10 @@ class TrainEngine:
         if keep and h_out is None:
             return kept                                   # recompute inside backward: the block output is not needed
         out = h_out if keep else h
-        ops.gemm_nt(act_full, im[f"w2.{i}.x" if kx else f"w2.{i}"], out, residual=h_mid, epilogue=res_flag)
+        if self._q8base():
+            self._base_fwd_fp8(f"w2.{i}", actb, out, h_mid, res_flag)
+        else:
+            ops.gemm_nt(act_full, im[f"w2.{i}.x" if kx else f"w2.{i}"], out, residual=h_mid, epilogue=res_flag)
         if self.lora and not kx:
             self._lora_add(f"w2.{i}", lt["w2"], out)
         return kept
@@ -754,6 +793,16 @@ class TrainEngine:
             # K-ext (implies ``fused``): t = x . A^T in the tail columns of the input, B in the tail columns of the image
             self._lora_t(key, xn, tag, t)
             ops.gemm_qkv_rope(xn_full, im[key + ".x"], qrot, kc, vc, m._cos_sin_dev(), B, S, H, Hkv, hd, 0, 0, v_rows=v_rows)
+            return t
+        if fused and self._q8base():
+            # fp8 base: the same additive form on the fp8 product (a3v_gemm_qkv_rope_fp8_train: v_rows and delta as the bf16 entry)
+            t = self._lora_t(key, xn, tag)
+            ops.gemm_nt(t, self._lora_step_images()[key + ".B"], qkv)
+            xq = self._buf("q8_x", tuple(xn.shape), torch.uint8)
+            sx = self._buf("q8_sx", (xn.shape[0],), torch.float32)
+            ops.quantize_rows_fp8(xn, xq, sx)
+            ops.gemm_qkv_rope_fp8_train(xq, sx, im[key + ".q"], im[key + ".s"], qrot, kc, vc, m._cos_sin_dev(), B, S, H, Hkv, hd, 0, 0,
+                                        v_rows=v_rows, delta=qkv)
             return t
         if fused:
             # adapters: the LoRA term t . B^T is written into the qkv buffer first and enters the fused GEMM as an additive term
@@ -1013,7 +1062,7 @@ class TrainEngine:
             # with the transposed images against 455.5 / 452.4 without, for 24 GiB: not taken there unless A3V_NN_DGRAD=0 asks for it)
             if not self._nt_images_fit(moments) or (self.recompute and "A3V_NN_DGRAD" not in os.environ):
                 self.nn_dgrad = True
-        if self.lora and not self._q4base() and not self._nt_mem_checked:
+        if self.lora and not self._q4base() and not self._q8base() and not self._nt_mem_checked:
             # LoRA engines: the input gradients of the frozen matrices run on the NT kernel over transposed images that
             # are built once (2 B per base parameter: 12.3 GiB at 7B) and, with nn_dgrad off, the head's W^T too -- the same headroom
             # rule as the full fine-tune above: without 8 GiB left after them the NN kernel on the forward images is used instead
@@ -1202,14 +1251,16 @@ def step_loss(engine: TrainEngine, anchor: torch.Tensor, examples, labels, image
 
 def hbm_budget(dim: int, n_layers: int, n_heads: int, ffn: int, vocab: int, batch: int, seq: int, text: int, n_kv_heads: Optional[int] = None,
                vit_params: int = 304_000_000, proj_in: int = 1024, world: int = 1, wire_bytes: int = 2, recompute: bool = False,
-               stream_bytes: int = 2, zero1: bool = False, transposed_images: bool = False) -> Dict[str, int]:
+               stream_bytes: int = 2, zero1: bool = False, transposed_images: bool = False, base_bytes: Optional[int] = None) -> Dict[str, int]:
     """Bytes of one pure-DP replica of the FULL fine-tune (every rank of a DP job holds exactly this; SURVEY 7 "13B full fine-tune
     memory", main_finetune.py:241-276): what ``TrainEngine`` + ``FusedAdamW`` + ``dp.GradReducer`` allocate, from their own layouts.
     fp32 masters / flat gradient buffer / two AdamW moments of every trainable parameter, the bf16 GEMM images of the decoder and
     head matrices, the frozen bf16 ViT, the reducer's persistent wire buckets (``wire_bytes`` per gradient element when world > 1
     and the wire dtype is not fp32), the residual-stream checkpoints [L+1, rows, dim] (``stream_bytes`` per element: 2 = the bf16 stream
     of round 3 on, 4 = the fp32 stream of rounds 1-2), the block intermediates (per layer when activations are stored, once when
-    blocks are recomputed), and the CE buffers; ``transposed_images``: + the W^T images of the round-5 default.  Checked against the measured peaks of the bench
+    blocks are recomputed), and the CE buffers; ``transposed_images``: + the W^T images of the round-5 default; ``base_bytes``: the
+    decoder matrices' images, both orientations together, cost this many bytes per parameter instead (a frozen fp8 base,
+    ``quantize_base_weights("fp8")``: 2 = e4m3 image + byte transpose, plus 4 B per output row of scales; the head's stay bf16).  Checked against the measured peaks of the bench
     (tests/test_dp_cpu.py::test_dp_replica_fits_288_gib)."""
     hkv = n_kv_heads or n_heads
     hd = dim // n_heads
@@ -1246,5 +1297,11 @@ def hbm_budget(dim: int, n_layers: int, n_heads: int, ffn: int, vocab: int, batc
         "backward_workspace": bwd_ws,
         "ce_buffers": batch * text * vocab * 2 * 2 + batch * text * dim * 2 * 2,
     })
+    if base_bytes is not None and not zero1:
+        p_dec = n_layers * p_layer
+        out["images_bf16"] = 2 * (p_mat - p_dec)
+        if "images_t_bf16" in out:
+            out["images_t_bf16"] = 2 * (p_mat - p_dec)
+        out["images_base"] = base_bytes * p_dec + 4 * n_layers * (qkv + 2 * dim + 2 * ffn)
     out["total"] = sum(out.values())
     return out

@@ -1,5 +1,5 @@
 """Compute-dtype operand images of the training step (``a3vlm_amd.train.TrainEngine``): the weight images of the decoder / head /
-projector GEMMs (``_Images``; over an NF4 base ``_Nf4Images``) and the adapter images of a LoRA step (``_AdapterImages``), and the one
+projector GEMMs (``_Images``; over an NF4 base ``_Nf4Images``, over an fp8 base ``_Fp8Images``) and the adapter images of a LoRA step (``_AdapterImages``), and the one
 table of the decoder's four GEMM groups that they, the engine and the LoRA plugin share."""
 from __future__ import annotations
 
@@ -317,6 +317,42 @@ class _Nf4Images(_Images):
         if target != "d":
             return b
         return {"": b[:N, :K], "x": b[:N], "y": b[:, :K]}[suffix]
+
+
+class _Fp8Images(_Images):
+    """The same keys over an fp8 base (``quantize_base_weights("fp8")``): for each decoder group ``qkv.i`` / ``wo.i`` /
+    ``w13.i`` / ``w2.i`` the model's persistent images -- ``.q`` Wq [N, K] e4m3 bytes, ``.s`` sw [N] fp32, ``.qT`` the byte transpose
+    [K, N padded to 128] -- with no scratch and nothing to rebuild (the base is frozen and has no bf16 form); ``.one`` is a vector
+    of K ones, the weight-side scale of the input-gradient GEMM (sw is folded into the gradient rows instead).  The head and the
+    projector images (``out``, ``vp``) are the parent's."""
+
+    _SLOT = {"q": 0, "s": 1, "qT": 2}
+
+    def __init__(self, eng: "TrainEngine"):
+        super().__init__(eng)
+        assert eng.act == torch.bfloat16, "an fp8 base trains under --precision bf16"
+        self.ones: Dict[int, torch.Tensor] = {}
+
+    def groups(self):                         # the parameter-backed groups (optimizer sinks, adoption): the head and the projector
+        return ["out"] + (["vp"] if getattr(self.eng.m, "visual_proj", None) is not None else [])
+
+    def nbytes(self, head: bool = True) -> int:
+        q8 = self.eng.m._q8base
+        n = sum(t.untyped_storage().nbytes() for ent in q8.values() for t in ent)
+        return n + (super().nbytes(True) if head else 0)
+
+    def __getitem__(self, key: str) -> torch.Tensor:
+        parts = key.split(".")
+        if parts[0] not in GROUPS:
+            return super().__getitem__(key)
+        ent = self.eng.m._q8base[f"{parts[0]}.{parts[1]}"]
+        if parts[2] == "one":
+            K = ent[0].shape[1]
+            one = self.ones.get(K)
+            if one is None:
+                one = self.ones[K] = torch.ones(K, dtype=torch.float32, device=ent[0].device)
+            return one
+        return ent[self._SLOT[parts[2]]]
 
 
 class _AdapterImages:

@@ -111,6 +111,23 @@ int a3v_gemm_qkv_rope_fp8(const void* Aq, int64_t lda, const float* sa, const vo
  * dim % 8 == 0, dim <= 16384. */
 int a3v_quantize_rows_fp8(const void* x, int64_t ldx, const void* norm_w, float eps, void* q, int64_t ldq, float* scales,
                           int rows, int dim, int x_dtype, void* stream);
+/* The column-scaled row quantiser of the fp8 frozen base (no reference counterpart, as above): the input gradient of a
+ * base linear whose weight is Wq[n,k] * sw[n] is dX = (dY * sw) . Wq, so the row scales of W are folded into dY before it is
+ * quantised: y[r,c] = fl32(x[r,c] * cs[c]), scales[r] = max|y[r,:]| / 448, q[r,c] = fp8(y[r,c] / scales[r]) with the rounding and the
+ * all-zero-row rule of a3v_quantize_rows_fp8.  x [rows, cols] bf16 or fp32 (x_dtype), cs [cols] fp32; q gets cols_pad >= cols bytes
+ * per row, ZERO beyond cols (cols_pad % 128 == 0 makes q the A operand of a3v_gemm_nt_fp8 over a zero-padded W^T without a padded
+ * copy of x).  cols % 8 == 0, cols_pad % 16 == 0, cols_pad <= 32768, ldx % 8 == 0, ldq % 16 == 0, ldq >= cols_pad; x, cs, q 16-byte
+ * aligned.  Anything else: A3V_ERR_*, nothing written. */
+int a3v_quantize_rows_fp8_cs(const void* x, int64_t ldx, const float* cs, void* q, int64_t ldq, float* scales, int rows, int cols,
+                             int cols_pad, int x_dtype, void* stream);
+/* The training form of a3v_gemm_qkv_rope_fp8: the same fp8 product ((Aq . Wq^T) * sa[m] * sw[n]) with the epilogue contract of
+ * a3v_gemm_qkv_rope -- the scaled accumulator is rounded to bf16, + delta (optional, bf16 [B*S, ldd]: the LoRA branch) is rounded,
+ * then the rotation, the cache writes and v_rows (optional, [B*S, ldv]: v token-major for the attention backward); delta may alias
+ * v_rows' buffer.  Value for value a3v_gemm_nt_fp8, the bf16 add of delta, a3v_rope_kvcache and the token-major copy of v. */
+int a3v_gemm_qkv_rope_fp8_train(const void* Aq, int64_t lda, const float* sa, const void* Wq, int64_t ldw, const float* sw, int K,
+                                void* q_out, int64_t ldq, void* k_cache, void* vt_cache, void* v_rows, int64_t ldv,
+                                const void* delta, int64_t ldd, const float* cos_sin, int B, int S, int H, int Hkv, int hd, int Smax,
+                                int start_pos, int rope_pos0, void* stream);
 
 /* "TN" GEMM: C[M,N] = epilogue(At^T . Wt) with At [K, M] and Wt [K, N] (the contracted index is the ROW index of both
  * operands): the weight gradient dW = dY^T . X on the token-major activations autograd holds (engine_finetune.py:55-57
