@@ -496,7 +496,7 @@ def generate_step(logits, sampled, tokens, text_mask, cur_pos: int, stop_seq, st
     _dev(tokens, text_mask, stopped, stop_pos, live)
     B = tokens.shape[0]
     assert tokens.dtype == torch.int64 and text_mask.dtype == torch.bool and stopped.dtype == torch.bool and stop_pos.dtype == torch.int64
-    assert tokens.stride(1) == 1 and text_mask.stride(1) == 1 and live.dtype == torch.int32
+    assert tokens.stride(1) == 1 and text_mask.stride(1) == 1 and (live is None or live.dtype == torch.int32)      # live is optional in the C ABI
     if sampled is None:
         assert logits.dtype == torch.float32 and logits.stride(1) == 1 and logits.shape[0] == B
         lp, ld, V = _p(logits), logits.stride(0), logits.shape[1]
