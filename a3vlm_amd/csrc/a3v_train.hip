@@ -856,7 +856,8 @@ extern "C" int64_t a3v_rmsnorm_bwd_scratch_floats(int rows, int dim) { return (i
 template <typename TS>
 static int rmsnorm_bwd_impl(const TS* x, int64_t ldx, const float* w, const void* dy, int64_t lddy, TS* dh, int64_t lddh,
                             float* dw, float* dw_scratch, int rows, int dim, float eps, int act_dtype, void* stream, bf16_t* dh_bf,
-                            int64_t ld_bf, const int32_t* row_idx = nullptr) {
+                            int64_t ld_bf, const int32_t* row_idx = nullptr, bool parts_only = false) {
+  // parts_only: dw_scratch receives the partial rows and is NOT column-summed here (a3v_grad_finish_multi does that later)
   if (row_idx && dh_bf) return A3V_ERR_ARG;
   if (!x || !w || !dy || !dh || rows <= 0) return A3V_ERR_ARG;
   if (dim > 8192) return A3V_ERR_SHAPE;
@@ -867,7 +868,8 @@ static int rmsnorm_bwd_impl(const TS* x, int64_t ldx, const float* w, const void
     constexpr int RV = 8;
     const int nb = (rows + RV - 1) / RV;
     dim3 gv(nb);
-    const bool part = dw && dw_scratch && (reinterpret_cast<uintptr_t>(dw_scratch) & 15) == 0;
+    const bool part = (dw || parts_only) && dw_scratch && (reinterpret_cast<uintptr_t>(dw_scratch) & 15) == 0;
+    if (parts_only && !part) return A3V_ERR_SHAPE;
     float* dwo = part ? dw_scratch : dw;
 #define A3V_RB(TT, MV, PP) hipLaunchKernelGGL((rmsnorm_bwd_vec_kernel<TT, RV, MV, PP, TS>), gv, dim3(256), 0, ST, x, ldx, w, (const TT*)dy, lddy, dh, lddh, dwo, rows, dim, eps, dh_bf, ld_bf, row_idx)
     if (dim <= 4096) {
@@ -879,12 +881,13 @@ static int rmsnorm_bwd_impl(const TS* x, int64_t ldx, const float* w, const void
     }
 #undef A3V_RB
     A3V_LAUNCH_CHECK();
-    if (part) {
+    if (part && !parts_only) {
       hipLaunchKernelGGL(colsum_add_kernel, dim3((dim + 255) / 256, 16), dim3(256), 0, ST, dw_scratch, nb, dim, dw);
       A3V_LAUNCH_CHECK();
     }
     return A3V_OK;
   }
+  if (parts_only) return A3V_ERR_SHAPE;       // the scalar form has no partial rows
   constexpr int RPB = 16;
   dim3 g((rows + RPB - 1) / RPB);
   if (act_dtype == A3V_BF16) hipLaunchKernelGGL((rmsnorm_bwd_kernel<bf16_t, RPB, TS>), g, dim3(256), 0, ST, x, ldx, w, (const bf16_t*)dy, lddy, dh, lddh, dw, rows, dim, eps, row_idx);
@@ -924,6 +927,15 @@ extern "C" int a3v_rmsnorm_bwd_rows_bf16(const void* x, int64_t ldx, const int32
   if (!row_idx) return A3V_ERR_ARG;
   return rmsnorm_bwd_impl<bf16_t>((const bf16_t*)x, ldx, w, dy, lddy, (bf16_t*)dh, lddh, dw, dw_scratch, rows, dim, eps, A3V_BF16, stream, nullptr, 0,
                                   row_idx);
+}
+
+// a3v_rmsnorm_bwd_bf16 / a3v_rmsnorm_bwd_rows_bf16 (row_idx non-NULL) without the column sum: the weight gradient stays as
+// ceil(rows / 8) partial rows of dim floats in `parts`, to be summed into dw by an A3V_FINISH_COLSUM job of a3v_grad_finish_multi
+extern "C" int a3v_rmsnorm_bwd_parts_bf16(const void* x, int64_t ldx, const int32_t* row_idx, const float* w, const void* dy, int64_t lddy,
+                                          void* dh, int64_t lddh, float* parts, int rows, int dim, float eps, void* stream) {
+  if (!parts) return A3V_ERR_ARG;
+  return rmsnorm_bwd_impl<bf16_t>((const bf16_t*)x, ldx, w, dy, lddy, (bf16_t*)dh, lddh, nullptr, parts, rows, dim, eps, A3V_BF16, stream, nullptr, 0,
+                                  row_idx, true);
 }
 
 static int layernorm_bwd_impl(const void* x, int64_t ldx, const float* w, const void* dy, int dy_dtype, int64_t lddy, const int32_t* row_map,

@@ -72,6 +72,10 @@ class GradReducer:
         self.wire_bytes_last_step = 0              # bytes handed to the collective since the last finish()
         self._wire_bytes = 0
         engine.on_layer_grads_ready = self._on_ready
+        # buckets leave for the wire while the backward still runs: the engine must finish every gradient where it is produced
+        # (TrainEngine._fin_begin; on one rank nothing is sent and the engine may defer)
+        if self.world > 1 or reduce_single_rank:
+            engine.bucket_overlap = True
 
     def _side_stream(self, device):
         if self._stream is None:

@@ -42,6 +42,8 @@ SIGNATURES = {
     "a3v_gemm_tn_strip": (I, [P, L, P, L, P, I, I, I, I, P]),
     "a3v_lora_gb_scatter": (I, [P, L, I, I, P, P, P, P]),
     "a3v_adamw_multi": (I, [P, I, L, F, F, F, F, F, L, P, P]),
+    "a3v_grad_finish_multi": (I, [P, I, L, I, P]),
+    "a3v_rmsnorm_bwd_parts_bf16": (I, [P, L, P, P, P, L, P, L, P, I, I, F, P]),
     "a3v_scale_cast": (I, [P, I, P, I, L, F, P]),
     "a3v_sumsq_partials": (I, [P, L, P, P]),
     "a3v_grad_bucket_allreduce": (I, [P, P, L, P, I, P]),

@@ -770,6 +770,42 @@ def lora_gb_scatter(gbt, r: int, views, row0s):
     _l.check(rc, "a3v_lora_gb_scatter")
 
 
+def grad_finish_multi(table, n_jobs: int, total_units: int, max_blocks: int = 0):
+    """One launch over a device table of a3v_finish_job descriptors (int64 [n_jobs, 22], built by a3vlm_amd.grad_finish): every split-K
+    plane set and RMSNorm partial-row block of a backward becomes its gradient.  ``max_blocks``: grid size (0: four blocks per CU)."""
+    _dev(table)
+    assert table.dtype == torch.int64 and table.is_contiguous() and tuple(table.shape) == (n_jobs, 22)
+    rc = _l.load().a3v_grad_finish_multi(_p(table), int(n_jobs), int(total_units), int(max_blocks), _stream())
+    _l.check(rc, f"a3v_grad_finish_multi(jobs={n_jobs},units={total_units})")
+
+
+def rmsnorm_bwd_parts(x, w, dy, dh, parts, eps, row_idx=None):
+    """``rmsnorm_bwd`` on the bf16 stream without the column sum of the weight gradient: ``parts`` (fp32, ceil(rows / 8) * dim floats)
+    receives the partial rows, which an A3V_FINISH_COLSUM job of ``grad_finish_multi`` adds into dw."""
+    _dev(x, w, dy, dh, parts, row_idx)
+    assert w.dtype == torch.float32 and x.dtype == dh.dtype == dy.dtype == torch.bfloat16 and parts.dtype == torch.float32
+    rows, dim = x.shape
+    if row_idx is not None:
+        assert row_idx.dtype == torch.int32 and row_idx.is_contiguous()
+        rows = row_idx.numel()
+        assert dy.shape[0] == rows
+    assert parts.is_contiguous() and parts.numel() >= (rows + 7) // 8 * dim
+    rc = _l.load().a3v_rmsnorm_bwd_parts_bf16(_p(x), x.stride(0), _p(row_idx), _p(w), _p(dy), dy.stride(0), _p(dh), dh.stride(0), _p(parts),
+                                              rows, dim, eps, _stream())
+    _l.check(rc, "a3v_rmsnorm_bwd_parts_bf16")
+
+
+def gemm_tn_strip_planes(t, x, planes, S: int):
+    """The launch of ``gemm_tn_strip`` alone: planes[s] ([R, N] fp32, s < S) = the product over token slice s, left un-summed."""
+    _dev(t, x, planes)
+    Kt, R = t.shape
+    N = x.shape[1]
+    assert x.shape[0] == Kt and t.stride(1) == 1 and x.stride(1) == 1 and t.stride(0) >= 64
+    assert planes.dtype == torch.float32 and planes.is_contiguous() and planes.numel() >= S * R * N
+    rc = _l.load().a3v_gemm_tn_strip(_p(t), t.stride(0), _p(x), x.stride(0), _p(planes), R, N, Kt, S, _stream())
+    _l.check(rc, f"a3v_gemm_tn_strip(R={R},N={N},Kt={Kt},S={S})")
+
+
 def lora_refresh(wa, wb, A, At, B, Bt, col0: int, row0: int):
     """One adapter's rows / columns of the fused group images (A, At, B, Bt; bf16) from its fp32 lora_a [r, in], lora_b [nj, r]."""
     _dev(wa, wb, A, At, B, Bt)

@@ -19,7 +19,7 @@ from typing import Callable, Dict, List, Optional, Tuple
 
 import torch
 
-from . import ops
+from . import grad_finish, ops
 from .train_images import GROUPS, _AdapterImages, _Fp8Images, _Images, _Nf4Images, _pad64, group_modules
 from .util import install_param_epoch_hook
 
@@ -66,6 +66,10 @@ class TrainEngine:
     fuse_swiglu_bwd = os.environ.get("A3V_FUSE_SWIGLU_BWD", "1") != "0"   # LoRA: SwiGLU backward in the epilogue of w2's input-gradient GEMM (0: separate pass, A/B)
     # the last block's wo / FFN branch, the final norm, the head and the loss on the rows with a label only (0: on every row); DESIGN.md 11
     label_rows = os.environ.get("A3V_LABEL_ROWS", "1") != "0"
+    # LoRA: the adapter strips' split-K planes and the RMSNorm partial rows stay in a step-long arena and ONE a3v_grad_finish_multi launch
+    # after the last block's backward turns them into gradients (0: every product finishes its own sums, A/B); DESIGN.md 5, 11
+    finish_defer = os.environ.get("A3V_FINISH_DEFER", "1") != "0"
+    finish_budget = int(float(os.environ.get("A3V_FINISH_BUDGET_MB", grad_finish.DEFAULT_BUDGET // 2 ** 20)) * 2 ** 20)   # bytes of arena at most
 
     def __init__(self, model, compute_dtype: torch.dtype = torch.bfloat16, recompute: Optional[bool] = None,
                  stream_dtype: Optional[torch.dtype] = None, zero1_world: int = 0):
@@ -129,6 +133,10 @@ class TrainEngine:
         self._dha_ready = False                             # fp32 stream: the last norm backward left the bf16 copy of dh in place
         self._dh_full: Optional[torch.Tensor] = None        # bf16 stream + K-ext: [dh | room for dt], see backward
         self._sel_rows: Optional[Tuple[int, int]] = None    # inside a labelled-row section: (n rows now, at most this many), see _sel_buf
+        self.bucket_overlap = False                         # a DP reducer sends gradient buckets while the backward runs (dp.GradReducer)
+        self._fin: Optional[grad_finish.GradFinisher] = None    # deferred gradient finish: plan, arena, tables (_fin_begin)
+        self._fin_mode: Optional[str] = None                # this backward: "plan" (record the producer calls), "defer", None (off)
+        self._fin_hold: Optional[List[str]] = None          # buckets announced while their gradients wait for the finish launch
 
     # ------------------------------------------------------------------ buffers
     def _buf(self, name, shape, dtype=None, zero=False):
@@ -476,12 +484,10 @@ class TrainEngine:
             sq = sink.wgrad_slots(grad, N, K) if sink is not None and grad.is_contiguous() else None
             ops.gemm_tn(dy, x, grad, residual=None if fresh else grad, epilogue=ops.EPI_OUT_F32 if fresh else ops.EPI_RES_F32, sumsq=sq)
             return
-        if (tn_ok and self.strip_wgrad and N <= 64 and N % 4 == 0 and K >= 256 and dy.stride(0) >= 64
-                and (dy.data_ptr() | x.data_ptr()) % 16 == 0):
+        if tn_ok and self._strip_ok(dy, x):
             # adapter gradients [N <= 64, K]: the small-block streaming kernel (three blocks per CU; token slices chosen so that the
             # grid holds ~2 blocks per CU: fewer slices = less reduce work, tools/lora_skinny_bench.py)
-            tiles = (K + 127) // 128
-            S = max(1, min(64, (M + 63) // 64, -(-512 // tiles)))
+            S = self._strip_slices(M, K)
             ops.gemm_tn_strip(dy, x, grad, self._buf("splitk", (S * N * K,), torch.float32), S, accumulate=not fresh)
             return
         if tn_ok and min(N, K) <= 64 and max(N, K) >= 256:
@@ -502,6 +508,107 @@ class TrainEngine:
         else:
             ops.gemm_nt(dyt, xt, grad, residual=None if fresh else grad,
                         epilogue=(ops.EPI_OUT_F32 if fresh else ops.EPI_RES_F32) if self.act == torch.bfloat16 else 0)
+
+    def _strip_ok(self, dy: torch.Tensor, x: torch.Tensor) -> bool:
+        """``_wgrad`` of dy [M, N], x [M, K] (both taken by the TN kernels) runs on a3v_gemm_tn_strip."""
+        N, K = dy.shape[1], x.shape[1]
+        return bool(self.strip_wgrad and N <= 64 and N % 4 == 0 and K >= 256 and dy.stride(0) >= 64
+                    and (dy.data_ptr() | x.data_ptr()) % 16 == 0)
+
+    @staticmethod
+    def _strip_slices(M: int, K: int) -> int:
+        """Token slices of a strip product over M tokens with K output columns (at most ``_strip_slices(1 << 30, K)``)."""
+        return max(1, min(64, (M + 63) // 64, -(-512 // ((K + 127) // 128))))
+
+    # ------------------------------------------------------------------ deferred gradient finish (a3v_grad_finish_multi)
+    def _fin_begin(self) -> None:
+        """Start of a backward: does this one leave its adapter / norm gradient partials to one finish launch?  Not under the engines
+        whose gradients leave before the backward ends or restart differently (recompute, ZeRO-1, DP bucket overlap), and only on the
+        bf16 stream the headline runs.  The engine's FIRST such backward only records what its producer calls need (``plan``); the
+        arena is allocated behind it if it fits ``finish_budget``, and later backwards defer."""
+        self._fin_mode, self._fin_hold = None, None
+        flat = self._flat
+        if not (self.finish_defer and self.lora and not self.recompute and not self.zero1_world and not self.bucket_overlap
+                and self.stream == torch.bfloat16 and self.act == torch.bfloat16 and flat is not None and flat.is_cuda):
+            return
+        if self._fin is None or self._fin.flat_ptr != flat.data_ptr() or self._fin.plan.budget_bytes != self.finish_budget:
+            self._fin = grad_finish.GradFinisher(self.finish_budget, flat.data_ptr())
+            self._fin_mode = "plan"
+        elif self._fin.arena is not None:
+            self._fin.pending = {}
+            self._fin_mode, self._fin_hold = "defer", []
+
+    def _fin_end(self) -> None:
+        """After the last block's backward: the finish launch, then the bucket announcements that waited for it (whoever takes sums of
+        squares of a bucket, or sends it, must see finished gradients)."""
+        if self._fin_mode == "plan":
+            self._fin.commit(self._flat.device)
+        elif self._fin_mode == "defer":
+            self._fin.launch()
+        self._fin_mode = None
+        held, self._fin_hold = self._fin_hold, None
+        for bucket in held or ():
+            self._notify(bucket)
+
+    def _fin_slot(self, key, add, signature: tuple, count: int):
+        """The arena slot of producer call ``key`` for ``count`` planes / partial rows, or None: the call finishes its own sums (not
+        deferring, the recording backward -- ``add(plan)`` registers the call there --, or a call the plan does not cover)."""
+        if self._fin_mode == "plan":
+            try:
+                add(self._fin.plan)
+            except ValueError:
+                pass                                      # a shape the finish kernel does not take: stays on its own reduce
+            return None
+        if self._fin_mode != "defer":
+            return None
+        slot = self._fin.plan.slots.get(key)
+        if slot is None or slot.signature() != signature or count > slot.count_cap or key in self._fin.pending:
+            return None
+        return slot
+
+    def _wgrad_deferred(self, key, dy: torch.Tensor, x: torch.Tensor, dst=None, scatter=None) -> bool:
+        """``_wgrad`` of an adapter strip with its sum left to the finish launch: the planes of dy^T x go into the call's arena slice.
+        ``dst``: the [N, K] gradient view they are added into; ``scatter`` = (r, views, row0s): the blocks are added, transposed, into
+        the modules' [n_j, r] views.  False: nothing was launched (the caller runs ``_wgrad``)."""
+        if self._fin_mode is None or self.act != torch.bfloat16 or not self.tn_wgrad or not self._strip_ok(dy, x):
+            return False
+        (M, N), K = dy.shape, x.shape[1]
+        if dy.stride(0) % 8 or x.stride(0) % 8 or 2 * M * max(dy.stride(0), x.stride(0)) >= 2 ** 31:
+            return False
+        S, S_cap = self._strip_slices(M, K), self._strip_slices(1 << 30, K)
+        if scatter is None:
+            sig = (grad_finish.PLANES, N, K, (dst.data_ptr(),), dst.stride(0), True, 0, (), ())
+            add = lambda plan: plan.add_planes(key, N, K, S_cap, dst.data_ptr(), dst.stride(0), True)      # noqa: E731
+        else:
+            r, views, row0s = scatter
+            ptrs, njs = tuple(v.data_ptr() for v in views), tuple(int(v.shape[0]) for v in views)
+            if not all(v.is_contiguous() and v.shape[1] == r for v in views):
+                return False
+            sig = (grad_finish.SCATTER, N, K, ptrs, 0, True, r, tuple(row0s), njs)
+            add = lambda plan: plan.add_scatter(key, N, K, S_cap, r, ptrs, row0s, njs)                     # noqa: E731
+        slot = self._fin_slot(key, add, sig, S)
+        if slot is None:
+            return False
+        ops.gemm_tn_strip_planes(dy, x, self._fin.slice_of(slot, S * N * K), S)
+        self._fin.pending[key] = S
+        return True
+
+    def _norm_bwd(self, key, x: torch.Tensor, w: torch.Tensor, dy: torch.Tensor, dh: torch.Tensor, dw: Optional[torch.Tensor], eps: float,
+                  dh_lowp: Optional[torch.Tensor] = None):
+        """``ops.rmsnorm_bwd``; when this backward defers, the weight gradient's partial rows stay in the call's arena slice."""
+        rows, dim = x.shape
+        if (self._fin_mode is not None and dw is not None and dh_lowp is None and x.dtype == torch.bfloat16 and dy.dtype == torch.bfloat16
+                and dim % 4 == 0 and dim <= 8192 and x.stride(0) % 4 == 0 and dy.stride(0) % 4 == 0 and dh.stride(0) % 4 == 0
+                and (x.data_ptr() | dh.data_ptr() | dy.data_ptr()) % 8 == 0 and w.data_ptr() % 16 == 0):
+            nb = (rows + 7) // 8                             # partial rows now; the slice holds those of a section's row cap
+            cap = max(nb, (self._sel_rows[1] + 7) // 8 if self._sel_rows is not None else 0)
+            sig = (grad_finish.COLSUM, 0, dim, (dw.data_ptr(),), 0, True, 0, (), ())
+            slot = self._fin_slot(key, lambda plan: plan.add_colsum(key, cap, dim, dw.data_ptr()), sig, nb)
+            if slot is not None:
+                ops.rmsnorm_bwd_parts(x, w, dy, dh, self._fin.slice_of(slot, nb * dim), eps)
+                self._fin.pending[key] = nb
+                return
+        ops.rmsnorm_bwd(x, w, dy, dh, dw, eps, dh_lowp=dh_lowp)
 
     def _skinny(self, a: torch.Tensor, w: torch.Tensor, out: torch.Tensor, accumulate: bool = False):
         """out (+)= a @ w.T for adapter-sized problems (M or N <= 64, long K): split-K planes of the 128x128 kernel + one
@@ -672,23 +779,30 @@ class TrainEngine:
         vas = [self._views[f"layers.{i}.{nm}.lora_a.weight"] for nm in names]
         vbs = [self._views[f"layers.{i}.{nm}.lora_b.weight"] for nm in names]
         nr = len(names) * r
-        gBt = self._buf("lora_gBt." + g, (Rp, N), torch.float32)
-        self._wgrad(t, dy, gBt, "lb", store=True)
+        row0s, row = [], 0
+        for vb in vbs:
+            row0s.append(row)
+            row += vb.shape[0]
+        # (deferred finish: only the nr rows that hold adapter blocks are produced, and the finish launch adds the blocks)
+        gBt = None
+        if not (t.is_cuda and nr % 4 == 0 and self._wgrad_deferred((i, g, "gB"), t[:, :nr], dy, scatter=(r, vbs, row0s))):
+            gBt = self._buf("lora_gBt." + g, (Rp, N), torch.float32)
+            self._wgrad(t, dy, gBt, "lb", store=True)
         # dA of the whole group straight into the flat gradient buffer: the group's lora_a gradients are adjacent = ONE [n r, in] matrix
         adjacent = all(vas[j + 1].data_ptr() == vas[j].data_ptr() + 4 * vas[j].numel() for j in range(len(vas) - 1))
         if adjacent and dt.stride(0) % 8 == 0:
             off = (vas[0].data_ptr() - self._flat.data_ptr()) // 4
-            self._wgrad(dt[:, :nr], x, self._flat[off:off + nr * x.shape[1]].view(nr, x.shape[1]), "la", store=False)
+            gA = self._flat[off:off + nr * x.shape[1]].view(nr, x.shape[1])
+            if not self._wgrad_deferred((i, g, "gA"), dt[:, :nr], x, dst=gA):
+                self._wgrad(dt[:, :nr], x, gA, "la", store=False)
         else:
             gA = self._buf("lora_gA." + g, (Rp, x.shape[1]), torch.float32)
             self._wgrad(dt, x, gA, "la", store=True)
             for j, va in enumerate(vas):
                 ops.add2d(va, gA[j * r:(j + 1) * r])
-        row0s, row = [], 0
-        for vb in vbs:
-            row0s.append(row)
-            row += vb.shape[0]
-        if gBt.is_cuda:
+        if gBt is None:
+            pass
+        elif gBt.is_cuda:
             ops.lora_gb_scatter(gBt, r, vbs, row0s)          # one launch: each module's [n_j, r] += its diagonal block transposed
         else:
             for j, vb in enumerate(vbs):
@@ -881,8 +995,8 @@ class TrainEngine:
         self._group_wgrad(i, "w13", dgu, k["xn2"])
         dxn = self._buf("dxn", (rows, dim))
         self._group_bwd(i, "w13", dgu, dgu_full, k["xn2"], lt["w13"], dxn)
-        ops.rmsnorm_bwd(k["h_mid"], l.ffn_norm.weight, dxn, dh, self._views.get(f"layers.{i}.ffn_norm.weight"), a.norm_eps,
-                        dh_lowp=dha if fuse_cast else None)
+        self._norm_bwd((i, "ffn_norm"), k["h_mid"], l.ffn_norm.weight, dxn, dh, self._views.get(f"layers.{i}.ffn_norm.weight"), a.norm_eps,
+                       dh_lowp=dha if fuse_cast else None)
         # ---- wo: h_mid = h_in + wo(att)
         if not fuse_cast and not stream_lp:
             ops.cast(dh, dha)
@@ -923,8 +1037,8 @@ class TrainEngine:
         self._group_wgrad(i, "qkv", dqkv, k["xn"])
         dxn = self._buf("dxn", (rows, dim))
         self._group_bwd(i, "qkv", dqkv, dqkv_full, k["xn"], k["lt"]["qkv"], dxn)
-        ops.rmsnorm_bwd(h_in, m.layers[i].attention_norm.weight, dxn, dh, self._views.get(f"layers.{i}.attention_norm.weight"), a.norm_eps,
-                        dh_lowp=dha if fuse_cast else None)
+        self._norm_bwd((i, "attention_norm"), h_in, m.layers[i].attention_norm.weight, dxn, dh,
+                       self._views.get(f"layers.{i}.attention_norm.weight"), a.norm_eps, dh_lowp=dha if fuse_cast else None)
         self._dha_ready = fuse_cast                        # the next block's backward finds its bf16 operand in place
 
     # ------------------------------------------------------------------ the rows the loss reads
@@ -1072,6 +1186,7 @@ class TrainEngine:
                 self.lora_nt_dgrad = "0"
         if self.sumsq_sink is not None:
             self.sumsq_sink.begin_backward()
+        self._fin_begin()
         B, T, W, S, dim = s["B"], s["T"], s["W"], s["S"], a.dim
         dh, dh_sel = self._head_backward(s, grad_scale)
         self._notify("head")
@@ -1082,6 +1197,7 @@ class TrainEngine:
             else:
                 self._block_backward(i, s["hs"][i], dh, B, S)
             self._notify(f"layer{i}")
+        self._fin_end()
         # ---- embeddings and projector
         if self._has("tok_embeddings.weight"):
             ops.embed_bwd(s["tokens"], dh, self._views["tok_embeddings.weight"], B, T, W, dim)
@@ -1127,7 +1243,8 @@ class TrainEngine:
                 dxt = self._head_grads(s, sel["n"], grad_scale)
                 dh_sel = self._buf(name, (sel["n"], cols), self.stream, zero=True)
             dh_full = self._buf(name, (rows, cols), self.stream)
-            ops.rmsnorm_bwd(s["h"], m.norm.weight, dxt, dh_sel[:, :dim], norm_dw, a.norm_eps)
+            with self._sel_section(sel):                    # (its partial-row slice is sized for every labelled-row count)
+                self._norm_bwd("norm", s["h"], m.norm.weight, dxt, dh_sel[:, :dim], norm_dw, a.norm_eps)
         self._dh_full = dh_full if wide else None
         return dh_full[:, :dim], dh_sel
 
@@ -1143,6 +1260,8 @@ class TrainEngine:
     def _notify(self, bucket: str):
         if self.on_layer_grads_ready is None:
             return
+        if self._fin_hold is not None:
+            return self._fin_hold.append(bucket)           # its adapter / norm gradients are final after the finish launch (_fin_end)
         for name, st, en in self._ranges:
             if name == bucket:
                 self.on_layer_grads_ready(name, st, en)

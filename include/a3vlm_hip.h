@@ -546,6 +546,11 @@ int a3v_layernorm_bwd_bf16(const void* x, int64_t ldx, const float* w, const voi
  * gradient is accumulated into dh row row_idx[i]; dw and its scratch as above. */
 int a3v_rmsnorm_bwd_rows_bf16(const void* x, int64_t ldx, const int32_t* row_idx, const float* w, const void* dy, int64_t lddy,
                               void* dh, int64_t lddh, float* dw, float* dw_scratch, int rows, int dim, float eps, void* stream);
+/* Either of the two (row_idx NULL: every row) WITHOUT the column sum: the weight gradient stays as ceil(rows / 8) partial rows of dim
+ * floats in `parts` (a3v_rmsnorm_bwd_scratch_floats(rows, dim) floats, 16-byte aligned), for an A3V_FINISH_COLSUM job of
+ * a3v_grad_finish_multi.  A3V_ERR_SHAPE where the kernel with partial rows does not apply (dim or a row stride no multiple of 4). */
+int a3v_rmsnorm_bwd_parts_bf16(const void* x, int64_t ldx, const int32_t* row_idx, const float* w, const void* dy, int64_t lddy,
+                               void* dh, int64_t lddh, float* parts, int rows, int dim, float eps, void* stream);
 
 /* The rows the loss reads (CrossEntropyLoss(ignore_index=0), model/meta.py:67,256-262): for the shifted labels [B, T] (int64), the
  * ascending list of positions b T + t with a non-zero label -- as rows b S + W + t of the decoder stream [B, S = W + T] in
@@ -677,6 +682,31 @@ typedef struct {
 } a3v_adamw_tensor;
 int a3v_adamw_multi(const a3v_adamw_tensor* table, int n_tensors, int64_t max_n, float lr, float beta1, float beta2, float eps,
                     float weight_decay, int64_t step, const float* grad_scale, void* stream);
+
+/* Every fp32 gradient partial of a LoRA backward finished in ONE launch (was one a3v_splitk_reduce per adapter strip, one
+ * a3v_lora_gb_scatter per fused group and one column-sum launch per RMSNorm: ~450 launches of 1 - 17 MB per 7B step).  `table` is a
+ * DEVICE array of n_jobs descriptors (every field 8 bytes; built once by the host, a3vlm_amd/grad_finish.py), each one of
+ *   A3V_FINISH_PLANES   dst[0][r * ldo + c] (+)= rbf(sum_s src[s][r][c]), S planes [R][N]: what a3v_splitk_reduce does into fp32;
+ *   A3V_FINISH_SCATTER  dst[j][n * r + c] += rbf(sum_s src[s][j * r + c][row0[j] + n]), n < nj[j], j < n_mods <= 4: that reduce
+ *                       followed by a3v_lora_gb_scatter (only the diagonal blocks of the planes are read);
+ *   A3V_FINISH_COLSUM   dst[0][c] += sum_r src[r][c], R partial rows of N columns, summed in 16 row chunks with one atomic per column
+ *                       and chunk: the column sum behind a3v_rmsnorm_bwd's partial rows.
+ * Planes are summed in ascending s; results equal those of the kernels named, element for element.  Every pointer 16-byte aligned;
+ * N, ldo, r, row0[j], nj[j] multiples of 4; r <= 64.  unit0 = the running sum of the units of the jobs before this one, a job having
+ * ceil(R * (N / 4) / 256) / sum_j ceil(nj[j] / 64) / 16 * ceil(N / 1024) units; total_units = the sum over all jobs.  The grid is
+ * max_blocks blocks (0: four per compute unit), never more than total_units, striding over the units. */
+enum { A3V_FINISH_PLANES = 0, A3V_FINISH_SCATTER = 1, A3V_FINISH_COLSUM = 2 };
+typedef struct {
+  int64_t kind;
+  const float* src;
+  int64_t S, R, N;
+  int64_t ldo, accumulate;
+  int64_t r, n_mods;
+  float* dst[4];
+  int64_t row0[4], nj[4];
+  int64_t unit0;
+} a3v_finish_job;
+int a3v_grad_finish_multi(const a3v_finish_job* table, int n_jobs, int64_t total_units, int max_blocks, void* stream);
 
 /* dst[i] = (dst_dtype)(src[i] * scale), n contiguous elements, both 16-B aligned: the wire-dtype conversions of the DP gradient
  * reducer (fp32 bucket -> bf16 wire bucket pre-scaled by 1/world, and back) -- FSDP's reduce_dtype = bf16 averaging
