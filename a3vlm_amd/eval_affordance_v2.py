@@ -136,6 +136,10 @@ def get_args_parser():
     p.add_argument("--kv_quant", type=str, choices=["fp8"], default=None,
                    help="keep the KV cache in fp8 e4m3 with per-position scales (Transformer.quantize_kv_cache): half the cache memory and half "
                         "the cache bytes per decode step; independent of --quant, applied after --merge_lora")
+    p.add_argument("--continuous_rows", type=int, default=0,
+                   help="N > 0: answers come from MetaModel.generate_many on N KV-cache rows (every row at its own position, a finished "
+                        "row is refilled with the next prompt); the loader then hands over 4 N samples at a time and --batch_size is "
+                        "not used.  0 (default): generate() per batch.  Not with --kv_quant or an unmerged LoRA model")
     return p
 
 
@@ -178,7 +182,8 @@ def main(args):
                          decode_only=on_gpu)
     pre = GpuPaddedResize(args.input_size, dev, torch.float32) if on_gpu else None
     idx = list(shard_range(len(dataset), world, rank))
-    loader = torch.utils.data.DataLoader(torch.utils.data.Subset(dataset, idx), batch_size=args.batch_size, shuffle=False,
+    rows = getattr(args, "continuous_rows", 0)
+    loader = torch.utils.data.DataLoader(torch.utils.data.Subset(dataset, idx), batch_size=4 * rows if rows > 0 else args.batch_size, shuffle=False,
                                          num_workers=args.num_workers, pin_memory=True, drop_last=False, collate_fn=collate_fn)
     outputs = []
     # the sampled recipe (default: temperature 0.1 / top-p 0.75) draws its uniform numbers from torch's device generator inside
@@ -188,7 +193,11 @@ def main(args):
     with torch.no_grad():
         for image, qids, prompts, annotations, paths in loader:
             image = pre.batch(image) if isinstance(image, list) else image.to(dev)
-            answers = model.generate(prompts, image, max_gen_len=args.max_gen_len, temperature=args.temperature, top_p=args.top_p)
+            if rows > 0:           # a chunk of a few batches at a time: the loader's workers stay ahead of the decode
+                answers = model.generate_many(prompts, image, batch_rows=rows, max_gen_len=args.max_gen_len, temperature=args.temperature,
+                                              top_p=args.top_p)
+            else:
+                answers = model.generate(prompts, image, max_gen_len=args.max_gen_len, temperature=args.temperature, top_p=args.top_p)
             for answer, annotation, question, path in zip(answers, annotations, prompts, paths):
                 answer = postprocess_answer(answer)
                 box = format_bounding_box(answer)

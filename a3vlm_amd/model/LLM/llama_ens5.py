@@ -622,11 +622,10 @@ class Transformer(nn.Module):
         for r0 in range(0, xn.shape[0], 16):
             self._linear(xn[r0:r0 + 16], n4["output"], logits[r0:r0 + 16], epilogue=ops.EPI_OUT_F32)
 
-    def _decode_step(self, h: torch.Tensor, B: int, pos: int) -> None:
-        """seqlen == 1, bf16: the whole layer stack from one C call (a3v_llama_decode_step)."""
-        import ctypes
+    def _llama_layer_table(self):
+        """The a3v_llama_layer table of the C step entries (and the a3v_kv8_layer table of an fp8 KV cache), rebuilt when weights,
+        caches or weight images change."""
         from ... import lib as _l
-        a = self.args
         pk = self._pack()
         q8 = getattr(self, "_q8", None)
         if q8 is not None and q8[0] != self._packed_version:
@@ -663,8 +662,12 @@ class Transformer(nn.Module):
                 tab[i].k_cache = self._k_cache[i].data_ptr()
                 tab[i].vt_cache = self._vt_cache[i].data_ptr()
             self._layer_tab, self._layer_tab_key = tab, key
+        return self._layer_tab
+
+    def _decode_step_buffers(self, B: int):
+        """xn, qkv, att, act, attention scratch and GEMV workspace of a C step call at B rows."""
+        a = self.args
         H, Hkv, hd = self.n_heads, self.n_kv_heads, self.head_dim
-        smax = self._k_cache[0].shape[2]
         xn = self._buf("xn", (B, a.dim))
         qkv = self._buf("qkv", (B, (H + 2 * Hkv) * hd))
         att = self._buf("att", (B, H * hd))
@@ -674,6 +677,17 @@ class Transformer(nn.Module):
         sws = self._skinny_ws(Bc, max((H + 2 * Hkv) * hd, 2 * self.ffn, a.dim), max(a.dim, self.ffn))
         for (n_, k_) in (((H + 2 * Hkv) * hd, a.dim), (a.dim, H * hd), (2 * self.ffn, a.dim), (a.dim, self.ffn)):
             sws = self._skinny_ws(Bc, n_, k_)
+        return xn, qkv, att, act, scratch, sws
+
+    def _decode_step(self, h: torch.Tensor, B: int, pos: int) -> None:
+        """seqlen == 1, bf16: the whole layer stack from one C call (a3v_llama_decode_step)."""
+        from ... import lib as _l
+        a = self.args
+        self._llama_layer_table()
+        kv8 = self._kv8
+        H, Hkv, hd = self.n_heads, self.n_kv_heads, self.head_dim
+        smax = self._k_cache[0].shape[2]
+        xn, qkv, att, act, scratch, sws = self._decode_step_buffers(B)
         if kv8 is not None:
             rc = _l.load().a3v_llama_decode_step_kv8(self._layer_tab, self._kv8_tab, self.n_layers, h.data_ptr(), xn.data_ptr(), qkv.data_ptr(),
                                                      att.data_ptr(), act.data_ptr(), scratch.data_ptr(), sws.data_ptr(),
@@ -939,3 +953,134 @@ class Transformer(nn.Module):
         # the reference returns a fresh tensor (output(h[:, -1, :]).float(), llama_ens5.py:530-531); `logits` is a cached workspace
         # that the next call overwrites, so hand out a copy (B x V fp32 = 1 MB at bs 8: microseconds next to a 4 ms step)
         return logits.clone()
+
+    # ------------------------------------------------------------------ ragged decode (every cache row at its own position)
+    def _ragged_check(self) -> None:
+        """Refusals of the ragged path, raised before anything is launched."""
+        if self._kv_quant == "fp8":
+            raise RuntimeError("ragged decode (prefill_row / forward_inference_rows / generate_many) has no fp8 KV-cache form yet: "
+                               "call quantize_kv_cache(None) for the bf16 cache, or use generate()")
+
+    def allocate_rows(self, batch_rows: int) -> None:
+        """The KV cache of ``batch_rows`` independent rows for prefill_row / forward_inference_rows."""
+        self._ragged_check()
+        assert 0 < batch_rows <= self.args.max_batch_size, (batch_rows, self.args.max_batch_size)
+        self._allocate_kv_cache(batch_rows)
+        self._pack(check=True)
+
+    @torch.no_grad()
+    def prefill_row(self, row: int, tokens: torch.Tensor, image: Optional[torch.Tensor] = None, *,
+                    qformer_feats=None, extra_feats=None) -> torch.Tensor:
+        """The multi-token forward of ONE prompt (tokens [1, T], with its image words if ``image`` is given) on cache row ``row``
+        of a cache made by ``allocate_rows``: the other rows are not touched.  Returns that row's last-position logits [1, V] fp32."""
+        self._ragged_check()
+        a = self.args
+        assert tokens.dim() == 2 and tokens.shape[0] == 1, tuple(tokens.shape)
+        assert self._k_cache and 0 <= row < self._k_cache[0].shape[0], "allocate_rows(batch_rows) first"
+        T = tokens.shape[1]
+        W = 0
+        if image is not None:
+            W = self.words_per_image
+            assert W == self.image_words
+        self.cache_image_words = W
+        S = T + W
+        assert S <= self._k_cache[0].shape[2], (S, self._k_cache[0].shape[2])
+        h = self._buf("h", (S, a.dim))
+        ops.embed_assemble(tokens.contiguous(), self.tok_embeddings.weight, h, 1, T, W, a.dim)
+        if image is not None:
+            self.encode_image_into(h, [image], 1, S, qformer_feats, extra_feats, (0,))
+        # the batch is the outermost dimension of both caches: one row of them is a contiguous cache of batch 1
+        kc = [k[row:row + 1] for k in self._k_cache]
+        vc = [v[row:row + 1] for v in self._vt_cache]
+        self._decoder_layers(h, 1, S, 0, 0, kc, vc, True)
+        xn = self._buf("xn_last", (1, a.dim))
+        ops.rmsnorm(h[S - 1:S], self.norm.weight, xn, a.norm_eps)
+        logits = torch.empty(1, a.vocab_size, dtype=torch.float32, device=self._device)
+        if self._dtype == torch.float32:
+            ops.gemm_nt(xn, self.output.weight, logits)
+        else:
+            self._lm_head_f32(xn, logits)
+        return logits
+
+    def _decode_step_rows(self, h: torch.Tensor, B: int, pos: torch.Tensor, pos_max: int) -> None:
+        """One bf16 decode step with row b at cache position pos[b] from one C call (a3v_llama_decode_step_rows)."""
+        from ... import lib as _l
+        a = self.args
+        tab = self._llama_layer_table()
+        H, Hkv, hd = self.n_heads, self.n_kv_heads, self.head_dim
+        xn, qkv, att, act, scratch, sws = self._decode_step_buffers(B)
+        rc = _l.load().a3v_llama_decode_step_rows(tab, self.n_layers, h.data_ptr(), xn.data_ptr(), qkv.data_ptr(), att.data_ptr(),
+                                                  act.data_ptr(), scratch.data_ptr(), sws.data_ptr(), self._cos_sin_dev().data_ptr(),
+                                                  pos.data_ptr(), pos_max, B, a.dim, H, Hkv, hd, self.ffn, self._k_cache[0].shape[2],
+                                                  a.norm_eps, torch.cuda.current_stream().cuda_stream)
+        _l.check(rc, "a3v_llama_decode_step_rows")
+
+    def _decoder_layers_rows(self, h: torch.Tensor, B: int, pos: torch.Tensor, pos_max: int) -> None:
+        """The ragged step kernel by kernel: _decoder_layers at S = 1 with a3v_rope_kvcache_rows / a3v_attention_decode_rows."""
+        a = self.args
+        H, Hkv, hd, dim = self.n_heads, self.n_kv_heads, self.head_dim, a.dim
+        pk = self._pack()
+        cs = self._cos_sin_dev()
+        xn = self._buf("xn", (B, dim))
+        qkv = self._buf("qkv", (B, (H + 2 * Hkv) * hd))
+        att = self._buf("att", (B, H * hd))
+        act = self._buf("act", (B, self.ffn))
+        scratch = counters = None
+        if h.dtype == torch.bfloat16 and hd in (64, 128):
+            scratch = self._buf("attn_scratch", (2 * ops.attention_scratch_floats(B, H, hd, a.max_seq_len + 64),), torch.float32)
+            counters = self._ws.get("rows_counters")
+            if counters is None or counters.numel() < B * H:
+                counters = self._ws["rows_counters"] = torch.zeros(B * H, dtype=torch.int32, device=self._device)
+        sk = self._buf("rows_sk", (B,), torch.int32)
+        torch.add(pos, 1, out=sk)                      # keys of row b (idle rows: <= 0)
+        ldq = qkv.stride(0)
+        n4 = getattr(self, "_n4", None)
+        for i, lyr in enumerate(self.layers):
+            kc, vc = self._k_cache[i], self._vt_cache[i]
+            smax = kc.shape[2]
+            strides = (ldq, ldq, hd, Hkv * smax * hd, smax * hd, hd, Hkv * hd * smax, hd * smax, smax, H * hd, H * hd, hd)
+            if n4 is None:
+                wqkv, wo, w13, w2 = pk[f"wqkv.{i}"], lyr.attention.wo.weight, pk[f"w13.{i}"], lyr.feed_forward.w2.weight
+            elif B <= 16 and a.dim >= 512:
+                wqkv, wo, w13, w2 = (n4[f"{k}.{i}"] for k in ("wqkv", "wo", "w13", "w2"))
+            else:
+                wqkv, wo, w13, w2 = self._nf4_dequant_layer(i)
+            ops.rmsnorm(h, lyr.attention_norm.weight, xn, a.norm_eps)
+            self._linear(xn, wqkv, qkv)
+            ops.rope_kvcache_rows(qkv, qkv, kc, vc, cs, pos, B, H, Hkv, hd)
+            ops.attention_decode_rows(qkv, kc, vc, att, sk, pos_max + 1, B, H, Hkv, hd, strides, scratch, counters)
+            self._linear(att, wo, h, residual=h)
+            ops.rmsnorm(h, lyr.ffn_norm.weight, xn, a.norm_eps)
+            self._linear(xn, w13, act, epilogue=ops.EPI_SWIGLU)
+            self._linear(act, w2, h, residual=h)
+
+    @torch.no_grad()
+    def forward_inference_rows(self, next_tok: torch.Tensor, pos: torch.Tensor, pos_max: int,
+                               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """One decode step with every cache row at its own position: next_tok [B] (int64, device) is embedded, row b is written at
+        cache position pos[b] (int32, device, image words included; negative = idle row: nothing written, its logits are not
+        meaningful) and attends to pos[b] + 1 keys.  ``pos_max`` = the largest position (host value).  fp32 logits [B, V] (into
+        ``out`` if given).  bf16 and fp32 streams."""
+        self._ragged_check()
+        a = self.args
+        B = next_tok.shape[0]
+        assert self._k_cache and self._k_cache[0].shape[0] == B, "allocate_rows(batch_rows) first; one token per cache row"
+        assert next_tok.dtype == torch.int64 and pos.dtype == torch.int32 and pos.numel() == B and pos.is_contiguous()
+        assert 0 <= pos_max < min(self._k_cache[0].shape[2], self._cos_sin_cpu.shape[0]), pos_max
+        h = self._buf("h", (B, a.dim))
+        ops.embed_assemble(next_tok.view(B, 1).contiguous(), self.tok_embeddings.weight, h, B, 1, 0, a.dim)
+        w8 = 2 if getattr(self, "_n4", None) is not None else 1 if getattr(self, "_q8", None) is not None else 0
+        fused = (self._dtype == torch.bfloat16 and not getattr(self, "_per_kernel_decode", False)
+                 and _lib.load().a3v_llama_decode_step_rows_form(B, a.dim, a.n_heads, self.n_kv_heads, self.head_dim, self.ffn, w8) == 2)
+        if fused:
+            self._decode_step_rows(h, B, pos, pos_max)
+        else:
+            self._decoder_layers_rows(h, B, pos, pos_max)
+        xn = self._buf("xn_last", (B, a.dim))
+        ops.rmsnorm(h, self.norm.weight, xn, a.norm_eps)
+        logits = out if out is not None else torch.empty(B, a.vocab_size, dtype=torch.float32, device=self._device)
+        if self._dtype == torch.float32:
+            ops.gemm_nt(xn, self.output.weight, logits)
+        else:
+            self._lm_head_f32(xn, logits)
+        return logits

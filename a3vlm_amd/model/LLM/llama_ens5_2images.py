@@ -33,6 +33,10 @@ class Transformer(_Base):
     def _image_slots(self):
         return [(self.start_img, self.end_img), (self.start_depth_img, self.end_depth_img)]
 
+    def _ragged_check(self) -> None:
+        raise NotImplementedError("ragged decode (prefill_row / forward_inference_rows / generate_many) is not implemented for the "
+                                  "two-image plugin: use generate(), which takes the depth images")
+
     def forward(self, examples: torch.Tensor, image: Optional[torch.Tensor] = None, depth_imgs: Optional[torch.Tensor] = None, *,
                 qformer_feats=None, extra_feats=None) -> torch.Tensor:
         images, slots = [], []

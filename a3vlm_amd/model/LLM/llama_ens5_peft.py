@@ -87,6 +87,13 @@ class Transformer(base.Transformer):
             raise NotImplementedError("NF4 decode weights beside LoRA adapters are not implemented: merge_adapters() first")
         super().quantize_decode_weights(mode, prefill)
 
+    def _ragged_check(self) -> None:
+        if not self._merged:
+            # the ragged step has no adapter hooks: it would silently decode with the base weights alone
+            raise NotImplementedError("ragged decode (prefill_row / forward_inference_rows / generate_many) is not implemented beside "
+                                      "LoRA adapters: merge_adapters() first (MetaModel.merge_lora / --merge_lora), or use generate()")
+        super()._ragged_check()
+
     def quantize_kv_cache(self, mode: Optional[str] = "fp8") -> None:
         if mode is not None and not self._merged:
             # decode beside adapters runs kernel by kernel with the adapter hooks (no fused step): the fp8 cache is not wired into it

@@ -379,6 +379,114 @@ class MetaModel(nn.Module):
         return (decoded, ids) if return_ids else decoded
 
     @torch.no_grad()
+    def generate_many(self, prompts: List[str], images: Optional[torch.Tensor] = None, *, batch_rows: int,
+                      max_gen_len=512, temperature: float = 0.0, top_p: float = 0.95,
+                      additional_stop_symbols: Iterable[str] = (), return_ids: bool = False, poll_every: int = 4,
+                      sample_uniforms: Optional[torch.Tensor] = None):
+        """Any number of prompts through ``batch_rows`` KV-cache rows (no reference counterpart; opt-in): every row decodes at its
+        own position, and a row whose answer is finished is prefilled with the next prompt while the others keep decoding, so a
+        short answer does not hold its row until the longest answer of a batch is done.  Answers come back in input order.
+
+        ``max_gen_len``: an int, or one int per prompt.  Per prompt the truncation and the length limit are ``generate``'s for a
+        batch of one (prompt cut to its last ``max_seq_len - max_gen_len`` tokens, ``max_seq_len`` less the image words; at most
+        ``min(max_seq_len, max_gen_len + len(prompt))`` tokens in all); generation starts behind the truncated prompt.
+        ``images`` [N, ...]: one image per prompt, or None.  ``temperature > 0``: uniforms are indexed [prompt, generated index]
+        (drawn up front, or ``sample_uniforms`` [N, >= max steps]), so an answer does not depend on ``batch_rows`` or on the row it
+        ran in.  ``stopped`` is read back every ``poll_every`` steps; a stopped row is not touched by later steps.
+        Not for the fp8 KV cache, LoRA models before ``merge_lora()`` or the two-image plugin (each raises, naming the way out)."""
+        from .ragged import RowScheduler
+        if isinstance(prompts, str):
+            raise ValueError(f"{self.__class__}.generate_many expects a LIST of prompts, but str is given")
+        llma = self.llma
+        llma._ragged_check()                                  # before anything is allocated or launched
+        dev = self._device
+        N = len(prompts)
+        args = llma.args
+        R = int(batch_rows)
+        assert 0 < R <= args.max_batch_size, (R, args.max_batch_size)
+        mgl = [int(max_gen_len)] * N if isinstance(max_gen_len, int) else [int(x) for x in max_gen_len]
+        assert len(mgl) == N, (len(mgl), N)
+        if images is not None:
+            images = images.to(dev)
+            assert images.shape[0] == N, (tuple(images.shape), N)
+        max_seq_len = args.max_seq_len - (llma.image_words if images is not None else 0)
+        W = llma.image_words if images is not None else 0
+        prompt_tokens, limits = [], []
+        for x, mg in zip(prompts, mgl):
+            t = self.tokenizer.encode(x, bos=True, eos=False)
+            limits.append(min(max_seq_len, mg + len(t)))
+            prompt_tokens.append(t[-(max_seq_len - mg):])
+        lens = [len(t) for t in prompt_tokens]
+        if N == 0:
+            return ([], []) if return_ids else []
+
+        l_stop = [[self.tokenizer.eos_id]]
+        l_stop += [self.tokenizer.encode_segment(s) for s in additional_stop_symbols]
+        l_stop += [self.tokenizer.encode_wo_prefix_space(s) for s in additional_stop_symbols]
+        offs = [0]
+        for st in l_stop:
+            offs.append(offs[-1] + len(st))
+        stop_seq = torch.tensor([t for st in l_stop for t in st], dtype=torch.long, device=dev)
+        stop_off = torch.tensor(offs, dtype=torch.int32, device=dev)
+
+        width = max(max(limits), max(lens), 1)
+        tokens = torch.zeros((R, width), dtype=torch.long, device=dev)
+        cur = torch.zeros(R, dtype=torch.int32, device=dev)
+        limit = torch.zeros(R, dtype=torch.int32, device=dev)
+        stopped = torch.ones(R, dtype=torch.bool, device=dev)            # an empty row is a stopped row: no step touches it
+        stop_pos = torch.zeros(R, dtype=torch.long, device=dev)
+        next_tok = torch.zeros(R, dtype=torch.long, device=dev)
+        pos = torch.full((R,), -1, dtype=torch.int32, device=dev)
+        logits = torch.zeros((R, args.vocab_size), dtype=torch.float32, device=dev)
+        uni = sampled = ubase = None
+        if temperature > 0:
+            n_steps = max(max(lim - ln for lim, ln in zip(limits, lens)), 1)
+            uni = (torch.rand(N, n_steps, device=dev, dtype=torch.float32) if sample_uniforms is None
+                   else sample_uniforms.to(device=dev, dtype=torch.float32).contiguous())
+            assert uni.shape[0] == N and uni.shape[1] >= n_steps, (tuple(uni.shape), N, n_steps)
+            n_uni = uni.shape[1]
+            uni = uni.reshape(-1)
+            sampled = torch.zeros(R, dtype=torch.long, device=dev)
+            ubase = torch.zeros(R, dtype=torch.long, device=dev)         # index of the row's uniform at scheduler step 0
+
+        sched = RowScheduler(lens, limits, R, W)
+        ids: List[Optional[List[int]]] = [None] * N
+        llma.allocate_rows(R)
+        while True:
+            for row, i in sched.refill():
+                t = torch.tensor(prompt_tokens[i], dtype=torch.long, device=dev)
+                logits[row].copy_(llma.prefill_row(row, t[None], None if images is None else images[i:i + 1])[0])
+                tokens[row].zero_()
+                tokens[row, :lens[i]] = t
+                cur[row], limit[row], stopped[row], stop_pos[row] = lens[i], limits[i], False, lens[i] + 1
+                if ubase is not None:
+                    ubase[row] = i * n_uni - sched.steps
+            for i in sched.finished_at_once:
+                ids[i] = []
+            sched.finished_at_once.clear()
+            if not sched.occupied():
+                break
+            if temperature > 0:
+                u = uni[(ubase + sched.steps).clamp_(0, uni.numel() - 1)]
+                self._sample_into(logits, temperature, top_p, u, sampled)
+            ops.generate_step_rows(logits, sampled, tokens, cur, limit, W, stop_seq, stop_off, len(l_stop), stopped, stop_pos, None,
+                                   next_tok, pos)
+            pos_max = sched.advance()
+            if sched.steps % poll_every == 0 or all(sched.generated[r] >= limits[i] - lens[i] for r, i in sched.occupied()):
+                st = stopped.tolist()
+                fin = [(r, i) for r, i in sched.occupied() if st[r]]
+                if fin:
+                    sp = stop_pos.tolist()
+                    for r, i in fin:
+                        ids[i] = tokens[r, lens[i]:sp[r]].tolist()
+                        sched.release(r)
+                    if not sched.occupied():
+                        continue                                         # refill (or leave) before another step
+            llma.forward_inference_rows(next_tok, pos, pos_max, out=logits)
+        decoded = [self.tokenizer.decode(t) for t in ids]
+        return (decoded, ids) if return_ids else decoded
+
+    @torch.no_grad()
     def stream_generate(self, prompt: str, image: Optional[torch.Tensor] = None, max_gen_len: int = 512,
                         temperature: float = 0.0, top_p: float = 0.95,
                         additional_stop_symbols: Iterable[str] = ()):

@@ -452,6 +452,56 @@ def attention_decode_fp8kv(q, k_q, vt_q, k_scale, v_scale, out, B, Sk, H, Hkv, h
     return out
 
 
+def rope_kvcache_rows(qkv, q_out, k_cache, vt_cache, cos_sin, pos, B, H, Hkv, hd):
+    """rope_kvcache at S = 1 with row b at cache position pos[b] (device int32 [B]; outside [0, Smax) = idle row: no cache write,
+    zero q row)."""
+    _dev(qkv, q_out, k_cache, vt_cache, cos_sin, pos)
+    assert pos.dtype == torch.int32 and pos.is_contiguous() and pos.numel() >= B
+    assert k_cache.is_contiguous() and vt_cache.is_contiguous() and k_cache.shape[0] >= B and k_cache.dtype == vt_cache.dtype == qkv.dtype
+    rc = _l.load().a3v_rope_kvcache_rows(_p(qkv), qkv.stride(0), _p(q_out), q_out.stride(0), _p(k_cache), _p(vt_cache), _p(cos_sin),
+                                         _p(pos), B, H, Hkv, hd, k_cache.shape[2], dt(qkv), _stream())
+    _l.check(rc, f"a3v_rope_kvcache_rows(B={B},H={H},Hkv={Hkv},hd={hd})")
+
+
+def attention_decode_rows_splits(B: int, H: int, sk_max: int) -> int:
+    return _l.load().a3v_attention_decode_rows_splits(B, H, sk_max)
+
+
+def attention_decode_rows(q, k, vt, out, sk, sk_max: int, B, H, Hkv, hd, strides, scratch=None, counters=None):
+    """Decode attention with sk[b] keys for row b (device int32 [B]; <= 0 = idle row, zero output); strides as ``attention`` at
+    Sq = 1.  bf16 at hd 64 / 128 needs scratch (attention_scratch_floats(B, H, hd, sk_max) floats) and counters (int32 [>= B*H],
+    zero; left zero)."""
+    _dev(q, k, vt, out, sk, scratch, counters)
+    assert sk.dtype == torch.int32 and sk.is_contiguous() and sk.numel() >= B
+    assert scratch is None or (scratch.dtype == torch.float32 and scratch.numel() >= attention_scratch_floats(B, H, hd, sk_max))
+    assert counters is None or (counters.dtype == torch.int32 and counters.numel() >= B * H)
+    rc = _l.load().a3v_attention_decode_rows(_p(q), _p(k), _p(vt), _p(out), _p(sk), int(sk_max), B, H, Hkv, hd, _Strides(*strides),
+                                             _p(scratch), _p(counters), dt(q), _stream())
+    _l.check(rc, f"a3v_attention_decode_rows(B={B},sk_max={sk_max},H={H},hd={hd})")
+    return out
+
+
+def generate_step_rows(logits, sampled, tokens, cur, limit, pos_base: int, stop_seq, stop_off, n_stop: int, stopped, stop_pos, live,
+                       next_tok, pos):
+    """One launch = one step of generate_many's bookkeeping (a3v_generate_step_rows): per row argmax (or the sampled id), the
+    tokens[b, cur[b]] write, stop-sequence match, cur[b] += 1, the row's limit, and the (next id, cache position) pair."""
+    _dev(tokens, cur, limit, stopped, stop_pos, live, next_tok, pos)
+    B = tokens.shape[0]
+    assert tokens.dtype == torch.int64 and tokens.stride(1) == 1 and stopped.dtype == torch.bool and stop_pos.dtype == torch.int64
+    assert cur.dtype == limit.dtype == pos.dtype == torch.int32 and next_tok.dtype == torch.int64 and (live is None or live.dtype == torch.int32)
+    assert all(t.is_contiguous() and t.numel() >= B for t in (cur, limit, pos, next_tok, stopped, stop_pos))
+    if sampled is None:
+        assert logits.dtype == torch.float32 and logits.stride(1) == 1 and logits.shape[0] == B
+        lp, ld, V = _p(logits), logits.stride(0), logits.shape[1]
+    else:
+        assert sampled.dtype == torch.int64 and sampled.is_contiguous() and sampled.numel() == B
+        lp, ld, V = None, 0, 1
+    rc = _l.load().a3v_generate_step_rows(lp, ld, _p(sampled), B, V, _p(tokens), tokens.stride(0), _p(cur), _p(limit), int(pos_base),
+                                          _p(stop_seq), _p(stop_off), int(n_stop), _p(stopped), _p(stop_pos), _p(live), _p(next_tok),
+                                          _p(pos), _stream())
+    _l.check(rc, "a3v_generate_step_rows")
+
+
 def embed_assemble(tokens, table, h, B, T, W, dim):
     _dev(tokens, table, h)
     assert tokens.dtype == torch.int64 and tokens.stride(1) == 1

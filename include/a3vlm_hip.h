@@ -1,7 +1,7 @@
 /*
  * a3vlm_hip.h -- C ABI of liba3vlm_hip.so: the MI355X (gfx950 / CDNA4) kernels of the
  * A3VLM multimodal hot path (ViT patch-embed + encoder -> projector -> Llama decoder
- * -> LM head / CE / greedy decode).
+ * -> LM head / CE / greedy decode; opt-in: NF4 / fp8 weights, fp8 KV cache, ragged decode with one cache position per batch row).
  *
  * The reference (changhaonan/A3VLM) is pure Python on PyTorch and has no FFI of its
  * own: its "native" layer is whatever ATen/cuBLAS/flash-attn kernel each torch call
@@ -502,6 +502,49 @@ int a3v_llama_decode_step_kv8(const a3v_llama_layer* layers, const a3v_kv8_layer
                               void* att, void* act, float* attn_scratch, void* skinny_ws, const float* cos_sin, void* stage_k,
                               void* stage_vt, int B, int dim, int H, int Hkv, int hd, int ffn, int Smax, int pos, float eps,
                               void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Ragged decode (opt-in; no reference counterpart: model/meta.py:413-485 keeps every batch row at one cache position).  Each
+ * batch row decodes at its own position; every position array is a DEVICE int32[B].  An idle row (a negative position, or one
+ * outside the cache) writes nothing into any cache and its outputs are zeros, never NaN.  bf16 KV cache only.
+ *
+ * a3v_rope_kvcache_rows: a3v_rope_kvcache at S = 1 with start_pos = rope_pos0 = pos[b] per row, one launch, bf16 and fp32, the
+ * per-element arithmetic of that entry (a row is bit-equal to the uniform call at its position).  pos[b] outside [0, Smax) is an
+ * idle row (bounded by the kernel: the host cannot see a device array): its q_out row is zeros.
+ * a3v_attention_decode_rows: decode attention over sk[b] keys for row b, 0 < sk[b] <= sk_max <= Smax (strides as a3v_attention
+ * with Sq = 1; sk[b] above sk_max is read as sk_max); sk[b] <= 0: the row's output is zeros.  bf16 at hd 64 / 128: the
+ * wave-streaming kernel of a3v_attention_decode_fused with the split plan of that entry at Sk = sk_max (counters: B*H
+ * zero-initialised ints, left zero; key ranges beyond sk[b] contribute nothing).  fp32 (any hd <= 256; also bf16 at other head
+ * dims): one wave per (batch, head), counters unused.  scratch: a3v_attention_scratch_floats(B, H, hd, sk_max) floats.
+ * a3v_attention_decode_rows_splits: the number of key ranges of that plan.
+ * a3v_generate_step_rows: a3v_generate_step with per-row state and no text_mask (a refilled row was prefilled with its whole
+ * prompt).  cur[b] (in/out): the index of tokens[b] this step writes; limit[b]: one past the last writable index; pos_base: the
+ * image words in the cache.  A row with stopped[b] set on entry is not touched.  Otherwise: next = argmax (or sampled[b]);
+ * tokens[b, cur] = next; stop_pos / stopped / live as a3v_generate_step at cur_pos = cur[b]; cur[b] += 1; cur[b] == limit[b] stops
+ * the row (stop_pos stays cur[b]).  Outputs: next_tok[b] (int64) = the id to embed next and pos[b] = pos_base + cur[b] - 1, its
+ * cache position, for a row that still runs; 0 and -1 for a row that is stopped on entry or stops in this step.  A cur[b]
+ * outside [0, min(limit[b], ld_tok)) stops the row without a write.  Integer work: bit-identical to tests/ragged_ref.py.
+ * a3v_llama_decode_step_rows: a3v_llama_decode_step with row b at cache position pos[b] (idle rows: pos[b] < 0), pos_max = the
+ * largest of them (host value, 0 <= pos_max < Smax).  Fused form only (a3v_llama_decode_step_rows_form == 2: bf16, fp8 or NF4
+ * weight images, 17..32 rows as two chunks; else the form query says 0, the call returns A3V_ERR_SHAPE with nothing touched and
+ * the host runs kernel by kernel).  SIX launches per layer: the qkv GEMV with the RMSNorm prologue and a plain store,
+ * a3v_rope_kvcache_rows on the qkv buffer in place, a3v_attention_decode_rows over pos[b] + 1 keys (sk_max = pos_max + 1; the kernel
+ * adds the one to pos[b] itself, there is no second array), wo, w1|w3, w2.  The GEMV's RoPE epilogue has one position for
+ * angle and cache row, so it is not used: q and k are rounded to bf16 once more than in a3v_llama_decode_step (GEMV store, then
+ * the rotation's store).  The step therefore equals the per-kernel sequence bit for bit, not the uniform fused step. */
+int a3v_rope_kvcache_rows(const void* qkv, int64_t ldqkv, void* q_out, int64_t ldq, void* k_cache, void* vt_cache,
+                          const float* cos_sin, const int32_t* pos, int B, int H, int Hkv, int hd, int Smax, int dtype, void* stream);
+int a3v_attention_decode_rows(const void* q, const void* k, const void* vt, void* out, const int32_t* sk, int sk_max, int B, int H,
+                              int Hkv, int hd, const int64_t* strides, float* scratch, int* counters, int dtype, void* stream);
+int a3v_attention_decode_rows_splits(int B, int H, int sk_max);
+int a3v_generate_step_rows(const float* logits, int64_t ld, const int64_t* sampled, int B, int V, int64_t* tokens, int64_t ld_tok,
+                           int32_t* cur, const int32_t* limit, int pos_base, const int64_t* stop_seq, const int32_t* stop_off,
+                           int n_stop, uint8_t* stopped, int64_t* stop_pos, int32_t* live, int64_t* next_tok, int32_t* pos,
+                           void* stream);
+int a3v_llama_decode_step_rows(const a3v_llama_layer* layers, int n_layers, void* h, void* xn, void* qkv, void* att, void* act,
+                               float* attn_scratch, void* skinny_ws, const float* cos_sin, const int32_t* pos, int pos_max, int B,
+                               int dim, int H, int Hkv, int hd, int ffn, int Smax, float eps, void* stream);
+int a3v_llama_decode_step_rows_form(int B, int dim, int H, int Hkv, int hd, int ffn, int w8);
 
 /* ---------------------------------------------------------------------------------------
  * Training (backward) entry points. Reference: autograd through the same modules under
