@@ -52,6 +52,18 @@ __device__ __forceinline__ float nf4_value(int i) {
   return t[i];
 }
 
+// One element of the AdamW update (torch.optim.AdamW, decoupled weight decay; the host scalars are derived in a3v_adamw_scaled):
+//   p *= 1 - lr*wd;  m += (1-b1)(g - m);  v = b2 v + (1-b2) g^2;  p -= (lr / (1-b1^t)) * m / (sqrt(v)/sqrt(1-b2^t) + eps)
+// adamw_kernel (a3v_train.hip, fp32 moments) and adamw8_kernel (a3v_adam8.hip, e4m3 moments) share these statements, so both are
+// contracted into the same fma sequence and the 8-bit step equals dequantise -> a3v_adamw_scaled -> quantise bit for bit.
+__device__ __forceinline__ void adamw_update(float& p, float g, float& m, float& v, float decay, float b1, float b2, float step_size,
+                                             float inv_bc2_sqrt, float eps) {
+  p *= decay;
+  m += (1.f - b1) * (g - m);
+  v = b2 * v + (1.f - b2) * g * g;
+  p -= step_size * m / (sqrtf(v) * inv_bc2_sqrt + eps);
+}
+
 template <typename T> struct Cvt;
 template <> struct Cvt<float> {
   static __device__ __forceinline__ float ld(const float* p) { return *p; }

@@ -1125,10 +1125,9 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
     f32x4 vv = (NT & 1) ? __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(v) + i) : reinterpret_cast<const f32x4*>(v)[i];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      pp[e] *= decay;
-      mm[e] += (1.f - b1) * (gg[e] - mm[e]);
-      vv[e] = b2 * vv[e] + (1.f - b2) * gg[e] * gg[e];
-      pp[e] -= step_size * mm[e] / (sqrtf(vv[e]) * inv_bc2_sqrt + eps);
+      float pe = pp[e], me = mm[e], ve = vv[e];
+      adamw_update(pe, gg[e], me, ve, decay, b1, b2, step_size, inv_bc2_sqrt, eps);       // a3v_common.h: shared with adamw8_kernel
+      pp[e] = pe; mm[e] = me; vv[e] = ve;
     }
     if (NT & 2) {
       __builtin_nontemporal_store(pp, reinterpret_cast<f32x4*>(p) + i);

@@ -51,6 +51,7 @@ def train_one_epoch(model, data_loader, optimizer, epoch: int, start_iter: int, 
     model.train(True)
     accum_iter = args.accum_iter
     print_freq = getattr(args, "print_freq", 10)
+    loss_trace = getattr(args, "loss_trace", None)   # a list: gets (optimizer step, loss as read back) at every logged step, unrounded
     model.zero_grad(set_to_none=True)
     dev = next(model.parameters()).device
     n_iter = len(data_loader)                      # the FULL epoch, also when resuming at start_iter (sampler contract)
@@ -148,6 +149,8 @@ def train_one_epoch(model, data_loader, optimizer, epoch: int, start_iter: int, 
                 if not math.isfinite(lv):
                     log(f"Loss is {lv}, stopping training")
                     sys.exit(1)
+                if loss_trace is not None:
+                    loss_trace.append((step + 1, lv))
                 stats["closs"] += lv
                 stats["n"] += 1
                 gn = float(stats["grad_norm"]) if torch.is_tensor(stats["grad_norm"]) else stats["grad_norm"]

@@ -18,8 +18,11 @@ broadcast) and what is left trainable -- adapters, norms, projectors -- trained;
 checkpoint as ``--pretrained_path`` and the adapter checkpoint as ``--resume``: the base is quantised before the adapters are loaded by
 name.  ``--base_fp8`` is the same flow on a frozen fp8 (e4m3, per-row scales) base: the seven decoder linears of every layer are quantised
 after the checkpoint (``quantize_base_weights("fp8")``) and the base GEMMs of the LoRA step run on fp8 operands, adapters in bf16
-(DESIGN.md 7c); same requirements, and it does not combine with ``--quant``.  ``--synthetic N`` substitutes a seeded synthetic dataset of N
-items of the dialog dataset's output shape (the real dataset classes are the next host-side row).
+(DESIGN.md 7c); same requirements, and it does not combine with ``--quant``.  ``--adam8bit`` keeps the AdamW moments of the big
+matrices as blockwise e4m3 codes (``FusedAdamW(moments="e4m3")``, DESIGN.md 5a: 2.03 B per parameter instead of 8) and runs the
+input gradients in the NN form, without transposed weight images; its checkpoints hold the 8-bit state, which the optimizer
+reloads bit for bit, and a checkpoint of either form resumes under either setting; it does not combine with ``--zero1``.
+``--synthetic N`` substitutes a seeded synthetic dataset of N items of the dialog dataset's output shape (the real dataset classes are the next host-side row).
 """
 from __future__ import annotations
 
@@ -87,7 +90,19 @@ def get_args_parser():
     p.add_argument("--zero1", action="store_true", default=False,
                    help="shard the fp32 masters and the AdamW state of the big matrices over the DP ranks (reduce-scatter -> AdamW on 1/N -> "
                         "all-gather of bf16 parameters): the reference's FSDP(SHARD_GRAD_OP) sizing for the 13B full fine-tune (configs[3])")
+    p.add_argument("--adam8bit", action="store_true", default=False,
+                   help="keep the AdamW moments of the big matrices as blockwise e4m3 codes (FusedAdamW(moments='e4m3'), DESIGN.md 5a): "
+                        "2.03 B per parameter instead of 8; input gradients in the NN form (no transposed weight images)")
     return p
+
+
+def check_args(args) -> None:
+    """Flag combinations that are refused before anything else happens (the parser's job: no GPU is needed to hear about them)."""
+    if getattr(args, "adam8bit", False) and args.zero1:
+        raise SystemExit("--adam8bit does not combine with --zero1: the ZeRO-1 slices have their own fp32 update (a3vlm_amd/zero1.py); "
+                         "use one or the other")
+    if getattr(args, "adam8bit", False) and os.environ.get("A3V_TORCH_ADAMW", "0") == "1":
+        raise SystemExit("--adam8bit is FusedAdamW(moments='e4m3'): it does not combine with A3V_TORCH_ADAMW=1")
 
 
 class _OneRank:
@@ -138,6 +153,7 @@ def main(args):
     rank = int(os.environ.get("RANK", 0))
     world = int(os.environ.get("WORLD_SIZE", 1))
     local = int(os.environ.get("LOCAL_RANK", 0))
+    check_args(args)
     if args.model_parallel_size != 1:
         raise SystemExit("tensor parallelism is not part of this build (DP replicas only, SURVEY 8(e)): use --model_parallel_size 1")
     if args.quant:
@@ -211,7 +227,13 @@ def main(args):
         optimizer = torch.optim.AdamW(add_weight_decay(model, args.weight_decay), lr=args.lr, betas=(0.9, 0.95), fused=True)
     else:
         from .optim import FusedAdamW
-        optimizer = FusedAdamW(add_weight_decay(model, args.weight_decay), lr=args.lr, betas=(0.9, 0.95), engine=model.train_engine())
+        eng = model.train_engine()
+        if args.adam8bit and not eng.lora:
+            # no 8-bit form of a3v_adamw_scaled_t: the NN input-gradient form (as under ZeRO-1 / recompute), which also drops the
+            # 2 B per parameter of transposed images
+            eng.nn_dgrad = True
+        optimizer = FusedAdamW(add_weight_decay(model, args.weight_decay), lr=args.lr, betas=(0.9, 0.95), engine=eng,
+                               moments="e4m3" if args.adam8bit else "fp32")
     # gradient wire dtype = FSDP's MixedPrecision(reduce_dtype) of the reference (:251-255): bf16 under --precision bf16
     if reducer is None:
         reducer = GradReducer(model.train_engine(), dist, reduce_dtype=torch.bfloat16 if args.precision == "bf16" else None) if distributed else None
@@ -267,8 +289,12 @@ def main(args):
                     print(f"resume: {opt_path} holds {'ZeRO-1' if is_zero1 else 'replicated AdamW'} optimizer state but this run is "
                           f"{'--zero1' if args.zero1 else 'not --zero1'}: the optimizer state is NOT loaded")
                 opt_sd, have_full, have_legacy = None, False, False
+        if have_full and not hasattr(optimizer, "moments") and any(g.get("moments") for g in opt_sd.get("param_groups", [])):
+            # torch.optim.AdamW (A3V_TORCH_ADAMW=1) would cast the e4m3 codes to floats without a word
+            raise SystemExit(f"resume: {opt_path} holds 8-bit AdamW moments ({opt_sd['param_groups'][0]['moments']}): resume it with FusedAdamW "
+                             "(with or without --adam8bit), not with A3V_TORCH_ADAMW=1")
         if have_full:
-            optimizer.load_state_dict(opt_sd)
+            optimizer.load_state_dict(opt_sd)        # FusedAdamW takes the fp32 and the 8-bit layout under either setting (optim.py)
         elif have_legacy:
             optimizer.load_state_dict(torch.load(legacy, weights_only=False)["optimizer"])
         else:

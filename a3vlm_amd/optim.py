@@ -20,7 +20,18 @@ Skipped steps: a negative or NaN ``grad_scale`` makes ``a3v_adamw_scaled`` a no-
 device-side non-finite guard).  The host cannot know that without reading the flag, so ``state[p]["step"]`` counts LAUNCHES, not
 applied updates, and the weight images are marked current either way (they are: nothing changed).  The trainer reads the flag at
 its logging / checkpoint / epoch boundaries and exits there, before anything is saved, so a skipped step is never followed by a
-step whose bias correction would be off by one."""
+step whose bias correction would be off by one.
+
+``moments="e4m3"`` (opt-in): the moments of the big tensors -- ``numel() > multi_threshold`` and ``numel() % 256 == 0`` -- are kept as
+blockwise e4m3 codes (include/a3vlm_hip.h, "8-bit AdamW moments": one byte per element and one fp32 scale per 256, 2.03 B per parameter
+for both moments instead of 8) and updated by ``a3v_adamw8_scaled``; their state is ``step`` / ``exp_avg_q`` / ``exp_avg_scale`` /
+``exp_avg_sq_q`` / ``exp_avg_sq_scale``.  Every other tensor (adapters, norms, odd sizes) keeps fp32 moments and the paths above, the
+multi-tensor launch included.  ``state_dict()`` writes that native state and marks every group with ``"moments": "e4m3x256"``;
+``load_state_dict`` of either mode takes either layout and converts tensor by tensor (a stock fp32 state is quantised on load, a
+native one dequantised by an fp32 optimizer), so no whole-model fp32 copy of the moments exists at any time.
+``a3v_adamw8_scaled`` has no scalar form for misaligned data: a parameter that does not start on 16 bytes keeps fp32 moments, and a
+GRADIENT that does not (a view at an odd offset of a flat buffer) is an explicit ``A3V_ERR_SHAPE`` at the step.  There is no 8-bit form of
+``a3v_adamw_scaled_t``: an engine that keeps transposed weight images is refused (build it in the NN input-gradient form)."""
 from __future__ import annotations
 
 import os
@@ -31,11 +42,46 @@ import torch
 from . import lib as _l
 
 
+MOMENTS_TAG = "e4m3x256"                    # param-group marker of a state_dict with 8-bit moments
+BLOCK = 256                                 # elements per scale of the 8-bit moments
+_F32_KEYS = ("exp_avg", "exp_avg_sq")
+_Q_KEYS = ("exp_avg_q", "exp_avg_scale", "exp_avg_sq_q", "exp_avg_sq_scale")
+_ZERO_SCALE = 1e-30 / 448.0                 # the scale of an all-zero block
+
+
+def _quantize_state(m: torch.Tensor, v: torch.Tensor):
+    """fp32 device moments of one tensor -> (exp_avg_q, exp_avg_scale, exp_avg_sq_q, exp_avg_sq_scale) by ``a3v_adam8_quantize``."""
+    if not m.is_cuda:
+        raise RuntimeError("8-bit AdamW moments are quantised by a HIP kernel: the parameter must be on the GPU (no CPU fallback)")
+    m, v = m.contiguous(), v.contiguous()
+    n = m.numel()
+    mq, rq = torch.empty(m.shape, dtype=torch.uint8, device=m.device), torch.empty(m.shape, dtype=torch.uint8, device=m.device)
+    ms, rs = torch.empty(n // BLOCK, dtype=torch.float32, device=m.device), torch.empty(n // BLOCK, dtype=torch.float32, device=m.device)
+    rc = _l.load().a3v_adam8_quantize(m.data_ptr(), v.data_ptr(), mq.data_ptr(), ms.data_ptr(), rq.data_ptr(), rs.data_ptr(), n,
+                                      torch.cuda.current_stream().cuda_stream)
+    _l.check(rc, "a3v_adam8_quantize")
+    return mq, ms, rq, rs
+
+
+def _dequantize_state(mq: torch.Tensor, ms: torch.Tensor, rq: torch.Tensor, rs: torch.Tensor):
+    """The inverse: the codes and scales of one tensor -> fp32 (exp_avg, exp_avg_sq) by ``a3v_adam8_dequantize``."""
+    if not mq.is_cuda:
+        raise RuntimeError("8-bit AdamW moments are dequantised by a HIP kernel: the parameter must be on the GPU (no CPU fallback)")
+    m, v = torch.empty(mq.shape, dtype=torch.float32, device=mq.device), torch.empty(mq.shape, dtype=torch.float32, device=mq.device)
+    rc = _l.load().a3v_adam8_dequantize(mq.data_ptr(), ms.data_ptr(), rq.data_ptr(), rs.data_ptr(), m.data_ptr(), v.data_ptr(), mq.numel(),
+                                        torch.cuda.current_stream().cuda_stream)
+    _l.check(rc, "a3v_adam8_dequantize")
+    return m, v
+
+
 class FusedAdamW(torch.optim.Optimizer):
     bumps_version = True        # parameters' Tensor._version is incremented by step(): version-keyed caches need no extra hook
 
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
-                 image_of: Optional[Callable[[torch.Tensor], Optional[torch.Tensor]]] = None, engine=None):
+                 image_of: Optional[Callable[[torch.Tensor], Optional[torch.Tensor]]] = None, engine=None, moments: str = "fp32"):
+        if moments not in ("fp32", "e4m3"):
+            raise ValueError(f"unknown AdamW moment format {moments!r}: 'fp32' or 'e4m3'")
+        self.moments = moments
         if lr < 0 or eps < 0 or not 0 <= betas[0] < 1 or not 0 <= betas[1] < 1 or weight_decay < 0:
             raise ValueError("invalid AdamW hyper-parameter")
         super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay))
@@ -52,13 +98,65 @@ class FusedAdamW(torch.optim.Optimizer):
     def state_dict(self):
         if self.engine is not None:
             self.engine.sync_optimizer()
-        return super().state_dict()
+        sd = super().state_dict()
+        if self.moments == "e4m3":
+            sd["param_groups"] = [{**g, "moments": MOMENTS_TAG} for g in sd["param_groups"]]
+        return sd
+
+    def _is8(self, p: torch.Tensor) -> bool:
+        """Whether p's moments are kept as e4m3 codes: the big tensors only (bitsandbytes' ``min_8bit_size`` idea)."""
+        return self.moments == "e4m3" and p.numel() > self.multi_threshold and p.numel() % BLOCK == 0 and p.data_ptr() % 16 == 0
+
+    def _convert_moments(self, p: torch.Tensor, saved: dict) -> dict:
+        """The moments of one saved entry in the layout this optimizer keeps for p, on p's device; copies, never views of ``saved``."""
+        want8, dev, n = self._is8(p), p.device, p.numel()
+        if all(k in saved for k in _Q_KEYS):
+            q = {k: saved[k].to(dev, copy=True) for k in _Q_KEYS}
+            if q["exp_avg_q"].dtype != torch.uint8 or q["exp_avg_sq_q"].dtype != torch.uint8 or q["exp_avg_q"].numel() != n \
+                    or q["exp_avg_sq_q"].numel() != n or n % BLOCK or q["exp_avg_scale"].numel() != n // BLOCK or q["exp_avg_sq_scale"].numel() != n // BLOCK:
+                raise ValueError(f"8-bit AdamW state of a {tuple(p.shape)} parameter has the wrong sizes or dtypes")
+            if want8:
+                return {"exp_avg_q": q["exp_avg_q"].view(p.shape), "exp_avg_scale": q["exp_avg_scale"].float().reshape(-1),
+                        "exp_avg_sq_q": q["exp_avg_sq_q"].view(p.shape), "exp_avg_sq_scale": q["exp_avg_sq_scale"].float().reshape(-1)}
+            m, v = _dequantize_state(q["exp_avg_q"].view(p.shape), q["exp_avg_scale"], q["exp_avg_sq_q"].view(p.shape), q["exp_avg_sq_scale"])
+            return {"exp_avg": m, "exp_avg_sq": v}
+        if all(k in saved for k in _F32_KEYS):
+            m, v = (saved[k].to(dev, dtype=torch.float32, copy=True).view(p.shape) for k in _F32_KEYS)
+            if not want8:
+                return {"exp_avg": m, "exp_avg_sq": v}
+            return dict(zip(_Q_KEYS, _quantize_state(m, v)))           # m and v die here: one tensor's fp32 moments at a time
+        if any(k in saved for k in _Q_KEYS + _F32_KEYS):
+            raise ValueError(f"incomplete AdamW state: {sorted(saved)}")
+        return {}
 
     def load_state_dict(self, state_dict):
-        """The device tables of the multi-tensor launch hold raw pointers of the moment tensors, which a load replaces."""
+        """The device tables of the multi-tensor launch hold raw pointers of the moment tensors, which a load replaces.
+        Takes the stock layout (``exp_avg`` / ``exp_avg_sq``, ``torch.optim.AdamW``'s and the fp32 mode's) and the native 8-bit one
+        (groups marked ``"moments": "e4m3x256"``), whichever mode this optimizer is in; see the module docstring."""
         if self.engine is not None:
             self.engine.sync_optimizer()
-        super().load_state_dict(state_dict)
+        groups = state_dict["param_groups"]
+        tags = {g.get("moments") for g in groups} - {None}
+        if tags - {MOMENTS_TAG}:
+            raise ValueError(f"optimizer state with unknown moment format {sorted(tags - {MOMENTS_TAG})}: this build reads fp32 and {MOMENTS_TAG!r}")
+        if self.moments == "fp32" and not tags:
+            super().load_state_dict(state_dict)
+            self._tables.clear()
+            return
+        # torch's loader casts every state tensor of a floating-point parameter to the parameter's dtype -- codes included -- and
+        # copies all of them at once: it gets the groups and the step counts, the moments are placed here, one tensor at a time
+        saved = state_dict["state"]
+        moment_keys = _Q_KEYS + _F32_KEYS
+        super().load_state_dict({"state": {i: {k: x for k, x in st.items() if k not in moment_keys} for i, st in saved.items()},
+                                 "param_groups": [{k: x for k, x in g.items() if k != "moments"} for g in groups]})
+        ids = [i for g in groups for i in g["params"]]
+        params = [p for g in self.param_groups for p in g["params"]]
+        for i, p in zip(ids, params):
+            if i in saved:
+                st = self.state[p]
+                if torch.is_tensor(st.get("step")):
+                    st["step"] = st["step"].clone()          # torch hands a host ``step`` through as it is: never share it with the source
+                st.update(self._convert_moments(p, saved[i]))
         self._tables.clear()
 
     def add_param_group(self, param_group):
@@ -98,7 +196,12 @@ class FusedAdamW(torch.optim.Optimizer):
                     or not p.grad.is_contiguous():
                 raise RuntimeError("FusedAdamW takes contiguous fp32 device parameters and gradients (no CPU fallback)")
             st = self.state[p]
-            if len(st) == 0:
+            if len(st) == 0 and self._is8(p):
+                st["step"] = torch.tensor(0.0, dtype=torch.float32)
+                for k in ("exp_avg", "exp_avg_sq"):                          # the all-zero state of the format: codes 0, scale 1e-30 / 448
+                    st[k + "_q"] = torch.zeros_like(p, dtype=torch.uint8, memory_format=torch.preserve_format)
+                    st[k + "_scale"] = torch.full((p.numel() // BLOCK,), _ZERO_SCALE, dtype=torch.float32, device=p.device)
+            elif len(st) == 0:
                 st["step"] = torch.tensor(0.0, dtype=torch.float32)          # torch.optim.AdamW's (non-capturable) layout
                 st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                 st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
@@ -162,7 +265,18 @@ class FusedAdamW(torch.optim.Optimizer):
             if img is not None and (img.dtype != torch.bfloat16 or img.shape != p.shape or not img.is_contiguous()):
                 raise RuntimeError("image_of must return a contiguous bf16 tensor of the parameter's shape")
             imgt = self.engine.image_sink_t(p) if (img is not None and self.engine is not None and hasattr(self.engine, "image_sink_t")) else None
-            if imgt is not None and p.is_contiguous():
+            if "exp_avg_q" in st:
+                if imgt is not None:
+                    raise RuntimeError("FusedAdamW(moments='e4m3'): the engine keeps a transposed bf16 image of this matrix current in the "
+                                       "optimizer pass (a3v_adamw_scaled_t), and that pass has no 8-bit form: build the engine in the NN "
+                                       "input-gradient form (engine.nn_dgrad = True before the first step, or A3V_NN_DGRAD=1; "
+                                       "main_finetune --adam8bit does)")
+                rc = lib.a3v_adamw8_scaled(p.data_ptr(), p.grad.data_ptr(), st["exp_avg_q"].data_ptr(), st["exp_avg_scale"].data_ptr(),
+                                           st["exp_avg_sq_q"].data_ptr(), st["exp_avg_sq_scale"].data_ptr(), p.numel(), float(group["lr"]),
+                                           float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]), int(st["step"].item()),
+                                           img.data_ptr() if img is not None else None, gs_ptr, stream)
+                _l.check(rc, "a3v_adamw8_scaled")
+            elif imgt is not None and p.is_contiguous():
                 # full fine-tune with input gradients on the NT kernel: the same pass also writes p's columns of the transposed image
                 rc = lib.a3v_adamw_scaled_t(p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
                                             p.shape[0], p.shape[1], float(group["lr"]), float(b1), float(b2), float(group["eps"]),

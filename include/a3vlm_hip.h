@@ -726,6 +726,44 @@ typedef struct {
 int a3v_adamw_multi(const a3v_adamw_tensor* table, int n_tensors, int64_t max_n, float lr, float beta1, float beta2, float eps,
                     float weight_decay, int64_t step, const float* grad_scale, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * 8-bit AdamW moments (opt-in; no reference counterpart: the reference's optimizer is torch.optim.AdamW with fp32 state,
+ * main_finetune.py:138; the idea is bitsandbytes' 8-bit optimizers, here with the project's fp8 convention of
+ * a3v_quantize_rows_fp8 / the fp8 KV cache instead of a dynamic code book).  Format:
+ *   a parameter tensor of n elements, n % 256 == 0, is viewed flat as n / 256 blocks of 256 consecutive elements;
+ *   exp_avg m:    m_q uint8[n] (OCP e4m3fn codes) and m_scale float[n / 256]; per block scale = max(max|m|, 1e-30) / 448,
+ *                 q = e4m3(m / scale) with a true division, round to nearest even, saturating; stored value float(q) * scale;
+ *   exp_avg_sq v: what is stored is r = sqrtf(v), as r_q / r_scale by the same rule; stored value v^ = (float(q) * scale)^2.  The
+ *                 square root halves the exponent range one block scale has to span: e4m3 reaches from 448 down to 2^-9, a ratio of
+ *                 2^17.8 in |g| inside one block;
+ *   for r only:   a NON-ZERO r whose quotient rounds to code 0 is stored as code 0x01 (value 2^-9 * scale), so that an element that
+ *                 has seen a gradient never gets the denominator 0 + eps; m may round to zero;
+ *   an all-zero block stays finite: codes 0, scale 1e-30 / 448.
+ * The floor of the scale is 1e-30, not the KV cache's 1e-12: moments of small gradients are legitimately far below 1e-12 (a floor
+ * of 1e-12 would store every block of a layer whose gradients are ~1e-8 as zeros).  Below r ~ 1e-19 the square v^ underflows in
+ * fp32 whatever the code: such elements are, as in the fp32 optimizer, indistinguishable from zero.
+ * NaN / inf are NOT kept: the block maximum and the saturating clamp are fmaxf / fminf, which drop a NaN operand, so a NaN or inf that
+ * reaches a moment (a non-finite gradient with grad_scale NULL) is stored as finite codes (+-448 or 0) and a finite scale -- the fp32
+ * state would stay visibly NaN.  The parameter still turns NaN in that step; the trainer's device-side guard (a negative grad_scale)
+ * keeps such a step from being applied at all.
+ *
+ * Argument checks, before any launch: a NULL required pointer, n <= 0 (step < 1): A3V_ERR_ARG; n % 256 != 0 or any pointer not 16-B
+ * aligned (scales and grad_scale: 4-B): A3V_ERR_SHAPE.
+ * a3v_adam8_quantize: (m, m_q, m_scale) and (v, r_q, r_scale); either triple may be NULL as a whole (that moment is skipped).
+ * a3v_adam8_dequantize: the element-wise inverse, m[i] = float(m_q[i]) * m_scale[i / 256], v[i] = (float(r_q[i]) * r_scale[i / 256])^2
+ * (every product rounded to fp32); either triple may be NULL. */
+int a3v_adam8_quantize(const float* m, const float* v, uint8_t* m_q, float* m_scale, uint8_t* r_q, float* r_scale, int64_t n,
+                       void* stream);
+int a3v_adam8_dequantize(const uint8_t* m_q, const float* m_scale, const uint8_t* r_q, const float* r_scale, float* m, float* v,
+                         int64_t n, void* stream);
+/* a3v_adamw_scaled on 8-bit moments: bit for bit the sequence a3v_adam8_dequantize -> a3v_adamw_scaled -> a3v_adam8_quantize on the
+ * parameter, the optional bf16 image, the codes and the scales, in ONE pass that reads and writes every byte once (18.06 B per
+ * parameter with the image, against 30).  grad_scale as in a3v_adamw_scaled: a negative or NaN *grad_scale is a no-op on the
+ * parameter, the codes, the scales and the image. */
+int a3v_adamw8_scaled(float* param, const float* grad, uint8_t* m_q, float* m_scale, uint8_t* r_q, float* r_scale, int64_t n, float lr,
+                      float beta1, float beta2, float eps, float weight_decay, int64_t step, void* bf16_image, const float* grad_scale,
+                      void* stream);
+
 /* Every fp32 gradient partial of a LoRA backward finished in ONE launch (was one a3v_splitk_reduce per adapter strip, one
  * a3v_lora_gb_scatter per fused group and one column-sum launch per RMSNorm: ~450 launches of 1 - 17 MB per 7B step).  `table` is a
  * DEVICE array of n_jobs descriptors (every field 8 bytes; built once by the host, a3vlm_amd/grad_finish.py), each one of
