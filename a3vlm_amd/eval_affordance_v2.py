@@ -165,8 +165,8 @@ def main(args):
         print(f"load pretrained from {args.pretrained_path}:", load_tensor_parallel_model_list(model, args.pretrained_path))
     if getattr(args, "merge_lora", False):
         model.merge_lora()
-    if getattr(args, "quant", False):     # eval_affordance_with_quant.py --quant: NF4 decoder linears + LM head (bf16 weights freed)
-        model.llma.quantize_decode_weights("nf4")
+    if getattr(args, "quant", False):     # eval_affordance_with_quant.py --quant: 4-bit decoder linears + LM head, NF4 or --quant_format mxfp4 (bf16 weights freed)
+        model.llma.quantize_decode_weights(getattr(args, "quant_format", "nf4"))
     if getattr(args, "kv_quant", None):
         model.llma.quantize_kv_cache(args.kv_quant)
     model.eval()

@@ -71,6 +71,11 @@ SIGNATURES = {
     "a3v_lora_merge": (I, [P, L, P, P, P, L, P, L, P, L, I, I, I, I, P]),
     "a3v_gemm_skinny_nf4": (I, [P, L, P, L, P, P, L, I, I, I, P, L, I, P, P]),
     "a3v_gemm_skinny": (I, [P, L, P, L, P, L, I, I, I, P, L, I, P, P]),
+    "a3v_quantize_mxfp4": (I, [P, L, P, L, P, I, I, P]),
+    "a3v_dequantize_mxfp4": (I, [P, L, P, P, L, I, I, P]),
+    "a3v_mx4_gemv_plan": (I, [I, I, I, I, I, P]),
+    "a3v_gemm_skinny_mxfp4_ws_bytes": (L, [I, I, I]),
+    "a3v_gemm_skinny_mxfp4": (I, [P, L, P, L, P, P, L, I, I, I, P, L, I, P, P]),
     "a3v_rmsnorm": (I, [P, L, P, P, L, I, I, F, I, I, I, P]),
     "a3v_layernorm": (I, [P, L, P, P, P, L, P, I, I, F, I, I, I, P]),
     "a3v_rope_kvcache": (I, [P, L, P, L, P, P, P, I, I, I, I, I, I, I, I, I, P]),

@@ -22,6 +22,7 @@ Differences from the reference that are deliberate and documented in DESIGN.md:
 """
 from __future__ import annotations
 
+import collections
 import math
 from dataclasses import dataclass
 from typing import Callable, Dict, List, Optional
@@ -31,6 +32,9 @@ from torch import nn
 
 from ... import lib as _lib
 from ... import ops
+
+# one MXFP4 weight image: codes [N, K/2] uint8 and e8m0 block scales [N, K/32] uint8 (ops.quantize_mxfp4)
+Mx4Image = collections.namedtuple("Mx4Image", "q s")
 
 
 @dataclass
@@ -285,8 +289,8 @@ class Transformer(nn.Module):
         pk: Dict[str, torch.Tensor] = {}
         with torch.no_grad():
             for i, lyr in enumerate(self.layers):
-                if getattr(self, "_n4", None) is not None:
-                    break                  # NF4 model: the decoder weights live only as NF4 images (self._n4)
+                if getattr(self, "_n4", None) is not None or getattr(self, "_mx4", None) is not None:
+                    break                  # NF4 / MXFP4 model: the decoder weights live only as images (self._n4 / self._mx4)
                 a, f = lyr.attention, lyr.feed_forward
                 pk[f"wqkv.{i}"] = torch.cat([a.wq.weight, a.wk.weight, a.wv.weight], dim=0).to(dtp).contiguous()
                 w1, w3 = f.w1.weight, f.w3.weight
@@ -399,7 +403,24 @@ class Transformer(nn.Module):
             self._ws["skinny_ws"] = ws
         return ws
 
+    def _mx4_ws(self, M: int, N: int, K: int) -> torch.Tensor:
+        """The GEMV workspace, large enough for the MXFP4 GEMV of this shape (same layout, same buffer as _skinny_ws)."""
+        need = ops.gemm_skinny_mxfp4_ws_bytes(M, N, K)
+        ws = self._ws.get("skinny_ws")
+        if ws is None or ws.numel() * 4 < need:
+            ws = torch.zeros((need + 3) // 4, dtype=torch.float32, device=self._device)
+            self._ws["skinny_ws"] = ws
+        return ws
+
     def _linear(self, x, w, out, **kw):
+        if isinstance(w, Mx4Image):        # MXFP4 image (codes, e8m0 block scales): the scaled-MFMA GEMV, <= 16 rows per call
+            if x.shape[0] > 32:
+                raise RuntimeError("an MXFP4 image takes at most 32 rows: larger products run on the dequantised layer")
+            for r0 in range(0, x.shape[0], 16):
+                res = kw.get("residual")
+                ops.gemm_skinny_mxfp4(x[r0:r0 + 16], w.q, w.s, out[r0:r0 + 16], self._mx4_ws(min(16, x.shape[0] - r0), w.q.shape[0], x.shape[1]),
+                                      residual=None if res is None else res[r0:r0 + 16], epilogue=kw.get("epilogue", 0))
+            return out
         if isinstance(w, tuple):           # NF4 image (nibbles, block scales): weight-only NF4 GEMV, <= 16 rows
             q, sc = w
             return ops.gemm_skinny_nf4(x, q, sc, out, self._skinny_ws(x.shape[0], q.shape[0], x.shape[1]), residual=kw.get("residual"),
@@ -431,6 +452,7 @@ class Transformer(nn.Module):
         w8a8 = (q8 is not None and getattr(self, "_fp8_prefill", False) and rows > 16 and h.dtype == torch.bfloat16
                 and hd in (64, 128))
         n4 = getattr(self, "_n4", None)
+        mx4 = getattr(self, "_mx4", None)
         # fp8 KV cache (quantize_kv_cache): k_caches / vt_caches then hold the ONE shared bf16 pair.  S > 1: the layer runs unchanged on
         # the pair (a continuation dequantises the layer's prefix into it first) and its new positions are quantised afterwards;
         # S == 1: the new position goes through the staging pair into the fp8 cache and the attention reads the fp8 cache.
@@ -478,14 +500,16 @@ class Transformer(nn.Module):
                 ops.quantize_rows_fp8(act, aq, sx)
                 ops.gemm_nt_fp8(aq, sx, w2_q, w2_s, h, residual=h)
                 continue
-            if n4 is None:
+            if mx4 is not None:            # decode rows on the images; every multi-token forward on the layer's Wd (weight-only)
+                wqkv, wo, w13, w2 = (mx4[f"{k}.{i}"] for k in ("wqkv", "wo", "w13", "w2")) if S == 1 and rows <= 32 else self._mx4_dequant_layer(i)
+            elif n4 is None:
                 wqkv, wo, w13, w2 = pk[f"wqkv.{i}"], lyr.attention.wo.weight, pk[f"w13.{i}"], lyr.feed_forward.w2.weight
             elif rows <= 16 and a.dim >= 512:   # NF4 decode GEMV on the images (its SwiGLU form needs K = dim >= 512: two K slices)
                 wqkv, wo, w13, w2 = (n4[f"{k}.{i}"] for k in ("wqkv", "wo", "w13", "w2"))
             else:                          # multi-token: the layer's Wd in a reused bf16 scratch, then the bf16 GEMMs unchanged
                 wqkv, wo, w13, w2 = self._nf4_dequant_layer(i)
             ops.rmsnorm(h, lyr.attention_norm.weight, xn, a.norm_eps)
-            if rows > 16 and h.dtype == torch.bfloat16 and hd in (64, 128) and self._fuse_qkv_rope:
+            if rows > 16 and h.dtype == torch.bfloat16 and hd in (64, 128) and self._fuse_qkv_rope and not isinstance(wqkv, Mx4Image):
                 # rotary embedding + cache write in the GEMM epilogue: qkv never makes a second trip through HBM
                 ops.gemm_qkv_rope(xn, wqkv, qkv, kc, vc, cs, B, S, H, Hkv, hd, cpos, rope_pos0)
             else:
@@ -508,14 +532,25 @@ class Transformer(nn.Module):
         weight is FREED (as the reference's ``del module.weight``): irreversible, and gone from ``state_dict()``.  Decode
         streams the NF4 images (a3v_gemm_skinny_nf4 / the fused step); the multi-token forward dequantises one layer at a time
         into a reused bf16 scratch (a3v_dequantize_nf4) and runs the bf16 GEMMs on it.  Quantise after ``.to(device)``:
-        the images are not module buffers and do not move with the model.  Decode batches above 32 rows have no GEMV form (as
+        the images are not module buffers and do not move with the model.
+
+        ``mode="mxfp4"``: the chip's own 4-bit format (OCP MXFP4, include/a3vlm_hip.h "MXFP4 weights"): the NF4 flow with
+        a3v_quantize_mxfp4; decode rows (<= 32) run a3v_gemm_skinny_mxfp4 kernel by kernel (MXFP8 activations inside the GEMV),
+        every multi-token forward dequantises one layer (a3v_dequantize_mxfp4) and is weight-only.  Needs a bf16 model on the GPU
+        and dim, ffn, n_heads*head_dim multiples of 128, vocab_size % 16 == 0.  Decode batches above 32 rows have no GEMV form (as
         for bf16 / fp8) and take the multi-token path: every generated token then dequantises every layer again (~400 MB
         written per layer at 7B), far slower than decoding the same batch in bf16."""
         if getattr(self, "_n4", None) is not None:
             raise RuntimeError("this model holds NF4 weights: quantize_decode_weights('nf4') freed its bf16 decoder weights and "
                                "cannot be undone or combined with another mode; reload the checkpoint instead")
+        if getattr(self, "_mx4", None) is not None:
+            raise RuntimeError("this model holds MXFP4 weights: quantize_decode_weights('mxfp4') freed its bf16 decoder weights and "
+                               "cannot be undone or combined with another mode; reload the checkpoint instead")
         if mode == "nf4":
             self._quantize_nf4()
+            return
+        if mode == "mxfp4":
+            self._quantize_mx4()
             return
         self._q8 = None
         self._fp8_prefill = bool(prefill) and mode is not None
@@ -579,6 +614,59 @@ class Transformer(nn.Module):
         self._packed_version = None
         self._ws.pop("nf4_scratch", None)
 
+    def _quantize_mx4(self) -> None:
+        a = self.args
+        H, Hkv, hd = self.n_heads, self.n_kv_heads, self.head_dim
+        if self._dtype != torch.bfloat16:
+            raise ValueError(f"MXFP4 weights need a bf16 model, this one is {self._dtype} (fp32 models are refused)")
+        if self._device.type != "cuda":
+            raise ValueError("MXFP4 weights need the model on the GPU (quantise after .to(device))")
+        if a.dim % 128 or self.ffn % 128 or (H * hd) % 128:
+            raise ValueError(f"MXFP4 weights need dim, ffn and n_heads*head_dim multiples of 128 (got {a.dim}, {self.ffn}, {H * hd})")
+        if a.vocab_size % 16 or (Hkv * hd) % 16 or a.vocab_size > 65536 or 2 * self.ffn > 65536 or max(a.dim, self.ffn) > 16384:
+            raise ValueError("MXFP4 weights need vocab_size and n_kv_heads*head_dim multiples of 16, vocab_size, 2*ffn <= 65536 and dim, ffn <= 16384")
+        self._q8, self._fp8_prefill, self._layer_tab_key = None, False, None
+        mx: Dict[str, Mx4Image] = {}
+
+        def quant(mod):                    # one original module -> (codes, scales); its bf16 weight is dropped
+            q, sc = ops.quantize_mxfp4(mod.weight.data.contiguous())
+            del mod.weight
+            return q, sc
+
+        def rows16(x, y):                  # w1 / w3 interleaved in 16-row blocks (the SwiGLU GEMV row order, as _pack)
+            nb = x.shape[0] // 16
+            return torch.stack([x.view(nb, 16, -1), y.view(nb, 16, -1)], dim=1).reshape(2 * x.shape[0], -1).contiguous()
+        with torch.no_grad():
+            for i, lyr in enumerate(self.layers):
+                at, f = lyr.attention, lyr.feed_forward
+                (qq, sq), (qk, sk), (qv, sv) = quant(at.wq), quant(at.wk), quant(at.wv)
+                mx[f"wqkv.{i}"] = Mx4Image(torch.cat([qq, qk, qv]), torch.cat([sq, sk, sv]))
+                mx[f"wo.{i}"] = Mx4Image(*quant(at.wo))
+                (q1, s1), (q3, s3) = quant(f.w1), quant(f.w3)
+                mx[f"w13.{i}"] = Mx4Image(rows16(q1, q3), rows16(s1, s3))
+                mx[f"w2.{i}"] = Mx4Image(*quant(f.w2))
+                del qq, qk, qv, sq, sk, sv, q1, q3, s1, s3
+                self._packed.pop(f"wqkv.{i}", None)
+                self._packed.pop(f"w13.{i}", None)
+            mx["output"] = Mx4Image(*quant(self.output))
+        self._mx4 = mx
+        self._packed_version = None
+        self._ws.pop("nf4_scratch", None)
+
+    def _mx4_dequant_layer(self, i: int):
+        """Wd of layer i's four (packed) matrices in the reused scratch: views (wqkv, wo, w13, w2)."""
+        a = self.args
+        shapes = (((self.n_heads + 2 * self.n_kv_heads) * self.head_dim, a.dim), (a.dim, self.n_heads * self.head_dim),
+                  (2 * self.ffn, a.dim), (a.dim, self.ffn))
+        buf = self._nf4_scratch(sum(n * k for n, k in shapes))
+        out, o = [], 0
+        for key, (n, k) in zip(("wqkv", "wo", "w13", "w2"), shapes):
+            w = buf[o:o + n * k].view(n, k)
+            ops.dequantize_mxfp4(*self._mx4[f"{key}.{i}"], w)
+            out.append(w)
+            o += n * k
+        return out
+
     def _nf4_scratch(self, n: int) -> torch.Tensor:
         buf = self._ws.get("nf4_scratch")
         if buf is None or buf.numel() < n:
@@ -611,11 +699,24 @@ class Transformer(nn.Module):
 
     def _head_weight(self) -> torch.Tensor:
         """The LM head as a bf16 GEMM operand (an NF4 model: dequantised into the reused scratch)."""
+        mx4 = getattr(self, "_mx4", None)
+        if mx4 is not None:
+            a = self.args
+            return ops.dequantize_mxfp4(*mx4["output"], self._nf4_scratch(a.vocab_size * a.dim)[:a.vocab_size * a.dim].view(a.vocab_size, a.dim))
         return self.output.weight if getattr(self, "_n4", None) is None else self._nf4_output_weight()
 
+    def _lm_head_last(self, xn: torch.Tensor, logits: torch.Tensor, decode: bool) -> None:
+        """_lm_head_f32 for the last rows of a forward.  An MXFP4 model runs its GEMV (MXFP8 activations) where its decoder layers do,
+        on decode steps of at most 32 rows (``decode``): after a multi-token forward, or a decode step of more rows, the rows take
+        the dequantised head, so such a forward is weight-only from end to end."""
+        if getattr(self, "_mx4", None) is not None and not decode:
+            self._linear(xn, self._head_weight(), logits, epilogue=ops.EPI_OUT_F32)
+        else:
+            self._lm_head_f32(xn, logits)
+
     def _lm_head_f32(self, xn: torch.Tensor, logits: torch.Tensor) -> None:
-        """fp32 logits of bf16 rows xn: the NF4 GEMV in chunks of 16 rows on an NF4 model, the bf16 path otherwise."""
-        n4 = getattr(self, "_n4", None)
+        """fp32 logits of bf16 rows xn: the NF4 / MXFP4 GEMV in chunks of 16 rows on such a model, the bf16 path otherwise."""
+        n4 = getattr(self, "_n4", None) or getattr(self, "_mx4", None)
         if n4 is None:
             self._linear(xn, self.output.weight, logits, epilogue=ops.EPI_OUT_F32)
             return
@@ -929,6 +1030,7 @@ class Transformer(nn.Module):
             self.encode_image_into(h, image, B, S, qformer_feats, extra_feats, slots)
         if (S == 1 and (B <= 16 or (B <= 32 and a.dim % 128 == 0 and self.ffn % 128 == 0)) and self._dtype == torch.bfloat16
                 and self.head_dim in (64, 128) and a.dim % 32 == 0 and self.ffn % 32 == 0
+                and getattr(self, "_mx4", None) is None                  # MXFP4 images: the kernel-by-kernel form only
                 and not getattr(self, "_per_kernel_decode", False)):     # test hook: run the step kernel by kernel
             # the C entry says up front which form it takes (a3v_llama_decode_step_form): 17..32 rows need the fused GEMV forms (two row
             # chunks); a geometry they do not take goes through the general kernels -- decided BEFORE h or the KV cache are touched, an
@@ -949,7 +1051,7 @@ class Transformer(nn.Module):
         if self._dtype == torch.float32:
             ops.gemm_nt(xn, self.output.weight, logits)
         else:
-            self._lm_head_f32(xn, logits)
+            self._lm_head_last(xn, logits, S == 1 and B <= 32)     # (an MXFP4 model: the head as the layers, GEMV up to 32 rows)
         # the reference returns a fresh tensor (output(h[:, -1, :]).float(), llama_ens5.py:530-531); `logits` is a cached workspace
         # that the next call overwrites, so hand out a copy (B x V fp32 = 1 MB at bs 8: microseconds next to a 4 ms step)
         return logits.clone()
@@ -999,7 +1101,7 @@ class Transformer(nn.Module):
         if self._dtype == torch.float32:
             ops.gemm_nt(xn, self.output.weight, logits)
         else:
-            self._lm_head_f32(xn, logits)
+            self._lm_head_last(xn, logits, False)
         return logits
 
     def _decode_step_rows(self, h: torch.Tensor, B: int, pos: torch.Tensor, pos_max: int) -> None:
@@ -1035,11 +1137,14 @@ class Transformer(nn.Module):
         torch.add(pos, 1, out=sk)                      # keys of row b (idle rows: <= 0)
         ldq = qkv.stride(0)
         n4 = getattr(self, "_n4", None)
+        mx4 = getattr(self, "_mx4", None)
         for i, lyr in enumerate(self.layers):
             kc, vc = self._k_cache[i], self._vt_cache[i]
             smax = kc.shape[2]
             strides = (ldq, ldq, hd, Hkv * smax * hd, smax * hd, hd, Hkv * hd * smax, hd * smax, smax, H * hd, H * hd, hd)
-            if n4 is None:
+            if mx4 is not None:
+                wqkv, wo, w13, w2 = (mx4[f"{k}.{i}"] for k in ("wqkv", "wo", "w13", "w2")) if B <= 32 else self._mx4_dequant_layer(i)
+            elif n4 is None:
                 wqkv, wo, w13, w2 = pk[f"wqkv.{i}"], lyr.attention.wo.weight, pk[f"w13.{i}"], lyr.feed_forward.w2.weight
             elif B <= 16 and a.dim >= 512:
                 wqkv, wo, w13, w2 = (n4[f"{k}.{i}"] for k in ("wqkv", "wo", "w13", "w2"))
@@ -1070,7 +1175,7 @@ class Transformer(nn.Module):
         h = self._buf("h", (B, a.dim))
         ops.embed_assemble(next_tok.view(B, 1).contiguous(), self.tok_embeddings.weight, h, B, 1, 0, a.dim)
         w8 = 2 if getattr(self, "_n4", None) is not None else 1 if getattr(self, "_q8", None) is not None else 0
-        fused = (self._dtype == torch.bfloat16 and not getattr(self, "_per_kernel_decode", False)
+        fused = (self._dtype == torch.bfloat16 and not getattr(self, "_per_kernel_decode", False) and getattr(self, "_mx4", None) is None
                  and _lib.load().a3v_llama_decode_step_rows_form(B, a.dim, a.n_heads, self.n_kv_heads, self.head_dim, self.ffn, w8) == 2)
         if fused:
             self._decode_step_rows(h, B, pos, pos_max)
@@ -1082,5 +1187,5 @@ class Transformer(nn.Module):
         if self._dtype == torch.float32:
             ops.gemm_nt(xn, self.output.weight, logits)
         else:
-            self._lm_head_f32(xn, logits)
+            self._lm_head_last(xn, logits, B <= 32)
         return logits

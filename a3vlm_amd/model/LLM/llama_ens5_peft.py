@@ -85,6 +85,8 @@ class Transformer(base.Transformer):
         if mode == "nf4":
             # the reference keeps the LoRA adapters unquantised beside the NF4 base (llama_ens5.py:541-550, QLoRA): a follow-up
             raise NotImplementedError("NF4 decode weights beside LoRA adapters are not implemented: merge_adapters() first")
+        if mode == "mxfp4":
+            raise NotImplementedError("MXFP4 decode weights beside LoRA adapters are not implemented: merge_adapters() first")
         super().quantize_decode_weights(mode, prefill)
 
     def _ragged_check(self) -> None:

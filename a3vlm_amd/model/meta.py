@@ -84,6 +84,8 @@ class MetaModel(nn.Module):
         ``quant="nf4"`` is the reference's 4-bit mode (meta.py:197-219, util/quant.py:95-163): the bf16 checkpoint is loaded,
         then every decoder linear and the LM head is quantised to NF4 layer by layer and its bf16 weight freed
         (``Transformer.quantize_decode_weights("nf4")``; inference only, irreversible).
+        ``quant="mxfp4"`` is the same flow in the chip's own 4-bit format (OCP MXFP4 on the scaled MFMA,
+        ``Transformer.quantize_decode_weights("mxfp4")``; no reference counterpart).
         ``kv_quant="fp8"`` (no reference counterpart) keeps the KV cache of ``generate`` in fp8 e4m3 with per-position scales
         (``Transformer.quantize_kv_cache``); independent of ``quant``."""
         import os
@@ -126,8 +128,8 @@ class MetaModel(nn.Module):
             warnings.warn(f"checkpoint and model mismatch: \n{load_result}")
         else:
             print("all params match perfectly!")
-        if quant == "nf4":
-            model.llma.quantize_decode_weights("nf4")
+        if quant in ("nf4", "mxfp4"):
+            model.llma.quantize_decode_weights(quant)
         elif quant:
             model.llma.quantize_decode_weights("fp8")
         if kv_quant is not None:
@@ -182,6 +184,8 @@ class MetaModel(nn.Module):
         from ..train import TrainEngine
         if getattr(self.llma, "_n4", None) is not None:
             raise RuntimeError("this model holds NF4 weights (inference only): training needs the bf16 checkpoint")
+        if getattr(self.llma, "_mx4", None) is not None:
+            raise RuntimeError("this model holds MXFP4 weights (inference only): training needs the bf16 checkpoint")
         if getattr(self, "_engine", None) is None:
             if compute_dtype is None:
                 frozen = [p for p in self.llma.parameters() if not p.requires_grad]

@@ -342,6 +342,67 @@ def gemm_skinny_nf4(a, q, scales, out, workspace, *, residual=None, epilogue: in
     return _gemm_skinny("a3v_gemm_skinny_nf4", a, q, scales, out, workspace, residual, epilogue)
 
 
+def quantize_mxfp4(w, q=None, scales=None):
+    """MXFP4 image of a bf16 weight w [N, K] (unit column stride, K % 128 == 0; a3v_quantize_mxfp4, the format of
+    include/a3vlm_hip.h "MXFP4 weights"): returns (codes [N, K/2] uint8, e8m0 block scales [N, K/32] uint8)."""
+    N, K = w.shape
+    if w.dtype != torch.bfloat16 or w.stride(1) != 1:
+        raise ValueError("quantize_mxfp4 needs a bf16 weight with unit column stride")
+    q = torch.empty(N, K // 2, dtype=torch.uint8, device=w.device) if q is None else q
+    scales = torch.empty(N, K // 32, dtype=torch.uint8, device=w.device) if scales is None else scales
+    _dev(w, q, scales)
+    assert q.dtype == torch.uint8 and q.shape == (N, K // 2) and q.stride(1) == 1
+    assert scales.dtype == torch.uint8 and scales.is_contiguous() and scales.numel() == N * (K // 32)
+    rc = _l.load().a3v_quantize_mxfp4(_p(w), w.stride(0), _p(q), q.stride(0), _p(scales), N, K, _stream())
+    _l.check(rc, f"a3v_quantize_mxfp4(N={N},K={K})")
+    return q, scales
+
+
+def dequantize_mxfp4(q, scales, out):
+    """out [N, K] bf16 = e2m1(q) * 2^(scales - 127), exact (a3v_dequantize_mxfp4)."""
+    _dev(q, scales, out)
+    N, K = out.shape
+    assert q.dtype == torch.uint8 and q.shape == (N, K // 2) and q.stride(1) == 1 and out.dtype == torch.bfloat16 and out.stride(1) == 1
+    assert scales.dtype == torch.uint8 and scales.is_contiguous() and scales.numel() == N * (K // 32)
+    rc = _l.load().a3v_dequantize_mxfp4(_p(q), q.stride(0), _p(scales), _p(out), out.stride(0), N, K, _stream())
+    _l.check(rc, f"a3v_dequantize_mxfp4(N={N},K={K})")
+    return out
+
+
+def gemm_skinny_mxfp4_ws_bytes(M: int, N: int, K: int) -> int:
+    return int(_l.load().a3v_gemm_skinny_mxfp4_ws_bytes(M, N, K))
+
+
+def mx4_gemv_plan(M: int, N: int, K: int, epilogue: int = 0, cus: int = 256):
+    """(rc, plan ints) of a3v_mx4_gemv_plan: grid, block, K slices, rows per block, LDS bytes, 512-k units, row groups, units per slice."""
+    import ctypes
+    plan = (ctypes.c_int32 * 8)()
+    rc = _l.load().a3v_mx4_gemv_plan(M, N, K, epilogue, cus, plan)
+    return rc, list(plan)
+
+
+def gemm_skinny_mxfp4(a, q, scales, out, workspace, *, residual=None, epilogue: int = 0):
+    """out = epilogue(sum_blocks 2^(ea + ew) * sum_32 a_q * w_q): MXFP4 weights x MXFP8 activations decode GEMV on the scaled MFMA
+    (M <= 16, N % 16 == 0, K % 128 == 0); workspace: zero-filled once, gemm_skinny_mxfp4_ws_bytes (may be gemm_skinny's)."""
+    _dev(a, q, scales, out, workspace, residual)
+    M, K = a.shape
+    N = q.shape[0]
+    assert a.dtype == torch.bfloat16 and a.stride(1) == 1, "activations are bf16 rows"
+    assert q.dtype == torch.uint8 and q.shape[1] * 2 == K and q.stride(1) == 1
+    assert scales.dtype == torch.uint8 and scales.is_contiguous() and scales.numel() == N * (K // 32)
+    ncol = N // 2 if epilogue & EPI_SWIGLU else N
+    assert out.dtype == (torch.float32 if epilogue & EPI_OUT_F32 else torch.bfloat16) and out.stride(1) == 1 and tuple(out.shape) == (M, ncol)
+    assert residual is None or (residual.dtype == torch.bfloat16 and residual.stride(1) == 1 and tuple(residual.shape) == (M, N))
+    need = gemm_skinny_mxfp4_ws_bytes(M, N, K)
+    if need and workspace.numel() * workspace.element_size() < need:
+        raise ValueError("gemm_skinny_mxfp4 workspace too small (a3v_gemm_skinny_mxfp4_ws_bytes)")
+    ep = epilogue | (EPI_RESIDUAL if residual is not None else 0)
+    rc = _l.load().a3v_gemm_skinny_mxfp4(_p(a), a.stride(0), _p(q), q.stride(0), _p(scales), _p(out), out.stride(0), M, N, K,
+                                         _p(residual), residual.stride(0) if residual is not None else 0, ep, _p(workspace), _stream())
+    _l.check(rc, f"a3v_gemm_skinny_mxfp4(M={M},N={N},K={K},epi={ep})")
+    return out
+
+
 def rmsnorm(x, w, out, eps: float, row_idx=None):
     """out = rmsnorm(x) * w; ``row_idx`` (int32 [n]): out row i from x row row_idx[i]."""
     _dev(x, w, out, row_idx)

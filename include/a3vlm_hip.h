@@ -289,6 +289,41 @@ int a3v_gemm_skinny(const void* A, int64_t lda, const void* W, int64_t ldw, void
                     int M, int N, int K, const void* residual, int64_t ldr, int epilogue,
                     void* partial, void* stream);
 
+/* ---- MXFP4 weights (OCP Microscaling v1.0: the 4-bit format CDNA4's scaled MFMA decodes in hardware; opt-in beside NF4) ----
+ * Weights W [N, K] bf16, K % 128 == 0, in blocks of 32 consecutive k of one row:
+ *   codes  q [N, K/2] bytes, row stride ldq BYTES (% 16 == 0), element 2j in the LOW nibble of byte j;
+ *   scales s [N, K/32] uint8 (contiguous rows), e8m0, value 2^(s - 127).
+ *   Block: E = floor(log2(max|w|)) - 2 clamped to [-127, 127], s = E + 127; an all-zero block gets s = 127 and codes 0; 0xFF is never
+ *   written.  Element: w / 2^E (exact) rounded to the nearest e2m1 value, ties to the even code, saturating at +-6.  e2m1 grid: codes
+ *   0..7 = 0, 0.5, 1, 1.5, 2, 3, 4, 6, bit 3 the sign; -0 is written as +0.  4.25 bits per weight.
+ *   Dequantised weight Wd = e2m1(q) * 2^(s - 127), exact in bf16.
+ * Activations (inside the GEMV only): MXFP8 by the same rule with OCP e4m3fn elements: E = floor(log2(max|a|)) - 8 over 32 consecutive
+ *   k of one row, a / 2^E rounded to nearest even, saturating at +-448; zero block: byte 127, codes 0.  Block-local: no row reduction,
+ *   so a K slice of a split plan quantises exactly as the whole row would.
+ * a3v_quantize_mxfp4: one launch, one pass over W (row stride ldw elements, % 8 == 0).  a3v_dequantize_mxfp4: out [N, K] bf16 (row
+ * stride ldo elements, % 8 == 0) = Wd.  w, q, out 16-B aligned.  A3V_ERR_ARG (NULL pointer) / A3V_ERR_SHAPE before any launch. */
+int a3v_quantize_mxfp4(const void* w, int64_t ldw, void* q, int64_t ldq, void* s, int N, int K, void* stream);
+int a3v_dequantize_mxfp4(const void* q, int64_t ldq, const void* s, void* out, int64_t ldo, int N, int K, void* stream);
+/* MXFP4 decode GEMV, M <= 16, N % 16 == 0 (<= 65536), K % 128 == 0 (<= 16384), A bf16 [M, K] (row stride lda elements, % 8 == 0):
+ *   C = epilogue( sum_blocks 2^(ea + ew) * sum_32 a_q * w_q )
+ * a_q / ea: the MXFP8 codes and block exponents of A as stated above, computed by the kernel as it stages A; w_q / ew: the image.  Both
+ * block scales are handed to v_mfma_scale_f32_16x16x128_f8f6f4 as its scale operands; accumulation is fp32 (within a slice in MFMA
+ * order, the K slices of a split plan summed in slice order: bit-identical from run to run).  Epilogues as a3v_gemm_skinny with its
+ * rounding sequence: NONE bf16(acc); RESIDUAL bf16(bf16(acc) + residual); SWIGLU (N counts the 16-row-interleaved w1|w3 rows, N % 32
+ * == 0, C has N/2 columns) bf16(bf16(silu(bf16(gate))) * bf16(up)); OUT_F32 stores float(bf16(acc)) (the LM head; with RESIDUAL the
+ * fp32 sum).  workspace: a3v_gemm_skinny_mxfp4_ws_bytes(M, N, K) bytes laid out as a3v_gemm_skinny's (the first 16384 bytes are arrival
+ * counters zero-filled ONCE by the caller and left zero; the two entry points may share one workspace).  A, q, C, workspace 16-B
+ * aligned, s 4-B, residual 8-B; ldc, ldr % 4 == 0.
+ * a3v_mx4_gemv_plan: the plan the entry point executes, from values alone (no device, no pointer; cus: compute units, 256 on
+ * MI355X).  Writes A3V_MX4_PLAN_INTS values -- grid x, block size, K slices across blocks, W rows per block, dynamic LDS bytes, 512-k
+ * units of K, 64-row groups of W, units of A staged per block -- and returns A3V_OK, or A3V_ERR_SHAPE for what cannot run (the entry
+ * point answers the same before any launch), or A3V_ERR_ARG (NULL plan). */
+enum { A3V_MX4_PLAN_INTS = 8 };
+int a3v_mx4_gemv_plan(int M, int N, int K, int epilogue, int cus, int32_t* plan);
+int64_t a3v_gemm_skinny_mxfp4_ws_bytes(int M, int N, int K);
+int a3v_gemm_skinny_mxfp4(const void* A, int64_t lda, const void* q, int64_t ldq, const void* s, void* C, int64_t ldc, int M, int N,
+                          int K, const void* residual, int64_t ldr, int epilogue, void* workspace, void* stream);
+
 /* y = rmsnorm(x) * w  with the reference's rounding order (model/components.py:39,52-53):
  * fp32 normalise -> cast to x's dtype -> multiply by weight.  x_dtype may be A3V_F32 with
  * y bf16 (training under autocast: fp32 residual stream feeding bf16 GEMMs). */
