@@ -308,10 +308,7 @@ __device__ __forceinline__ void decode_combine_tail(void* out, int64_t o_sb, int
 constexpr int A3V_WS_ATTN_COUNTERS = 16384;
 constexpr int A3V_WS_SSQ = 32768;
 constexpr int A3V_WS_PARTIALS = 65536;
-int a3v_gemv_fused(const void* A, int64_t lda, const void* W, int64_t ldw, const float* wscale, int n4, void* C, int64_t ldc, int M, int N,
-                   int K, const void* residual, int64_t ldr, int epilogue, const void* norm_w, const float* ssq_in, float eps,
-                   float* ssq_out, int rope, const float* cos_sin, void* k_cache, void* vt_cache, int H, int Hkv, int hd,
-                   int Smax, int pos, void* ws, void* stream);
+// (a3v_gemv_fused, the decode step's GEMV building block, is declared with its contract in include/a3vlm_hip.h)
 bool a3v_gemv_supported(int M, int N, int K, int epilogue, int w8);
 // compute units of the current device rounded down to whole XCD rounds (a3v_gemm.hip; 256 without a device): the GEMM and GEMV planners' `cus`
 int a3v_cu_count();

@@ -961,11 +961,11 @@ extern "C" int a3v_gemm_skinny(const void* A, int64_t lda, const void* W, int64_
   return gemv_run(A3V_GEMV_BF16, A, lda, W, ldw, nullptr, C, ldc, M, N, K, residual, ldr, epilogue, nullptr, partial, stream);
 }
 
-// Decode-step forms of the GEMV (internal to the library, used by a3v_llama_decode_step):
+// Decode-step forms of the GEMV (the building block of a3v_llama_decode_step; contract in include/a3vlm_hip.h):
 //   norm_w != NULL : A is the un-normalised residual rows h; RMSNorm(h) is applied while the A slice is staged (ssq_in)
 //   rope != 0      : [q|k|v] rows get RoPE and go to C (q) / the KV cache at `pos` (no separate rope kernel)
 //   ssq_out != NULL: with a residual epilogue, also emit the per-tile sums of squares of the new rows
-int a3v_gemv_fused(const void* A, int64_t lda, const void* W, int64_t ldw, const float* wscale, int n4, void* C, int64_t ldc, int M, int N,
+extern "C" int a3v_gemv_fused(const void* A, int64_t lda, const void* W, int64_t ldw, const float* wscale, int n4, void* C, int64_t ldc, int M, int N,
                    int K, const void* residual, int64_t ldr, int epilogue, const void* norm_w, const float* ssq_in, float eps,
                    float* ssq_out, int rope, const float* cos_sin, void* k_cache, void* vt_cache, int H, int Hkv, int hd,
                    int Smax, int pos, void* ws, void* stream) {

@@ -71,7 +71,8 @@ SIGNATURES = {
     "a3v_lora_merge": (I, [P, L, P, P, P, L, P, L, P, L, I, I, I, I, P]),
     "a3v_gemm_skinny_nf4": (I, [P, L, P, L, P, P, L, I, I, I, P, L, I, P, P]),
     "a3v_gemm_skinny": (I, [P, L, P, L, P, L, I, I, I, P, L, I, P, P]),
-    "a3v_quantize_mxfp4": (I, [P, L, P, L, P, I, I, P]),
+    "a3v_gemv_fused": (I, [P, L, P, L, P, I, P, L, I, I, I, P, L, I, P, P, F, P, I, P, P, P, I, I, I, I, I, P, P]),
+    "a3v_quantize_mxfp4":(I, [P, L, P, L, P, I, I, P]),
     "a3v_dequantize_mxfp4": (I, [P, L, P, P, L, I, I, P]),
     "a3v_mx4_gemv_plan": (I, [I, I, I, I, I, P]),
     "a3v_gemm_skinny_mxfp4_ws_bytes": (L, [I, I, I]),

@@ -199,6 +199,29 @@ def gemm_skinny(a, w, out, partial, *, residual=None, epilogue: int = 0):
     return _gemm_skinny("a3v_gemm_skinny", a, w, None, out, partial, residual, epilogue)
 
 
+def gemv_fused(a, w, out, workspace, *, wscale=None, n4: bool = False, residual=None, epilogue: int = 0, norm_w=None, ssq_in=None,
+               eps: float = 0.0, ssq_out=None, rope=None, check: bool = True) -> int:
+    """One call of a3v_gemv_fused, the decode step's GEMV building block (include/a3vlm_hip.h): gemm_skinny / _fp8 (``wscale`` [N]) / _nf4
+    (``wscale`` = block scales, ``n4``) with the RMSNorm prologue (``norm_w``, ``ssq_in`` [K/16, 16], ``eps``), the sum-of-squares side
+    output (``ssq_out`` [N/16, 16]) and / or the RoPE + KV-cache epilogue, ``rope`` = (cos_sin, k_cache [M, Hkv, Smax, hd],
+    vt_cache [M, Hkv, hd, Smax], H, Hkv, hd, pos).  N is the row count of ``w``.  Returns the entry point's return code; ``check``
+    raises on a non-zero one.  The entry point checks neither strides nor epilogue bits (see the header)."""
+    cos_sin, k_cache, vt_cache, H, Hkv, hd, pos = rope if rope is not None else (None, None, None, 0, 0, 0, 0)
+    _dev(a, w, wscale, out, workspace, residual, norm_w, ssq_in, ssq_out, cos_sin, k_cache, vt_cache)
+    M, K = a.shape
+    N = w.shape[0]
+    if workspace.numel() * workspace.element_size() < gemm_skinny_ws_bytes(M, N, K):
+        raise ValueError("gemv_fused workspace too small (a3v_gemm_skinny_ws_bytes)")
+    Smax = k_cache.shape[2] if k_cache is not None else 0
+    rc = _l.load().a3v_gemv_fused(_p(a), a.stride(0), _p(w), w.stride(0), _p(wscale), int(n4), _p(out), out.stride(0), M, N, K,
+                                  _p(residual), residual.stride(0) if residual is not None else 0, epilogue, _p(norm_w), _p(ssq_in), eps,
+                                  _p(ssq_out), int(rope is not None), _p(cos_sin), _p(k_cache), _p(vt_cache), H, Hkv, hd, Smax, pos,
+                                  _p(workspace), _stream())
+    if check:
+        _l.check(rc, f"a3v_gemv_fused(M={M},N={N},K={K},epi={epilogue})")
+    return rc
+
+
 def quantize_rows_fp8(x, q, scales, norm_w=None, eps: float = 0.0):
     """q[r] = fp8(y[r] / scales[r]), scales[r] = max|y[r]| / 448; y = x, or the bf16 RMSNorm of x when norm_w is given."""
     _dev(x, q, scales, norm_w)

@@ -288,6 +288,28 @@ int a3v_gemm_skinny_nf4(const void* A, int64_t lda, const void* Wq, int64_t ldw,
 int a3v_gemm_skinny(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc,
                     int M, int N, int K, const void* residual, int64_t ldr, int epilogue,
                     void* partial, void* stream);
+/* The decode step's building block: the GEMV a3v_llama_decode_step calls four times per layer, i.e. a3v_gemm_skinny (wscale NULL),
+ * a3v_gemm_skinny_fp8 (wscale [N], n4 == 0) or a3v_gemm_skinny_nf4 (wscale = block scales [N, K/64], n4 != 0) with up to three fused forms:
+ *   norm_w != NULL  RMSNorm prologue.  A holds the un-normalised rows x; ssq_in [K/16][16] fp32 holds, for every 16-column tile t and row
+ *                   m, a partial sum of squares (a producer's ssq_out; all 16 columns are read).  rinv[m] = rsqrtf(sum_t ssq_in[t][m] / K
+ *                   + eps) and the GEMV runs on a' = bf16(bf16(x * rinv) * norm_w): the rounding of a3v_rmsnorm on bf16 rows.
+ *   rope != 0       RoPE + KV-cache epilogue.  Rows n of W are [H q heads | Hkv k heads | Hkv v heads] x hd.  With v = bf16(acc), every
+ *                   pair (v0, v1) = (v[2i], v[2i+1]) of a q or k head becomes bf16(v0 c - v1 s), bf16(v0 s + v1 c), (c, s) =
+ *                   cos_sin[pos][i] (fp32 [positions][hd/2][2]); q goes to C[m, n] (only the first H hd columns of C are written), k to
+ *                   k_cache[m, h, pos, :] of a bf16 [M, Hkv, Smax, hd] cache, v unrotated to vt_cache[m, h, :, pos] of [M, Hkv, hd, Smax].
+ *                   `residual` and `epilogue` are ignored by this form.
+ *   ssq_out != NULL sum-of-squares side output (with the plain bf16 or the RESIDUAL epilogue): ssq_out[n/16][m] = the sum over the 16
+ *                   columns of the tile of the squares of the bf16 values stored to C, for all 16 m (0 for m >= M): the next GEMV's ssq_in.
+ * C may alias `residual` (each element is read, then written by the same lane).  ws: as a3v_gemm_skinny's `partial`.
+ * Needs M <= 16, K % 128 == 0 (fp8 / NF4: % 256), N % 16 == 0, N <= 65536 and a non-NULL ws (A3V_ERR_SHAPE otherwise; also where only the
+ * direct-to-VGPR kernel could run the problem: more than 150 KiB of LDS, SWIGLU without a K split -- the fused forms have no fallback);
+ * NF4 without scales or with K % 256, and rope with hd % 16 != 0 or without cos_sin / k_cache / vt_cache: A3V_ERR_ARG.  Beyond that
+ * it checks neither strides nor epilogue bits: lda % 8, ldw % 8 (fp8 / NF4: bytes, % 16), ldc % 4, ldr % 4, 16-byte aligned A, W,
+ * scales and norm_w, and an epilogue of RESIDUAL, SWIGLU (N % 32 == 0) or OUT_F32 alone are the caller's to guarantee. */
+int a3v_gemv_fused(const void* A, int64_t lda, const void* W, int64_t ldw, const float* wscale, int n4, void* C, int64_t ldc, int M, int N,
+                   int K, const void* residual, int64_t ldr, int epilogue, const void* norm_w, const float* ssq_in, float eps,
+                   float* ssq_out, int rope, const float* cos_sin, void* k_cache, void* vt_cache, int H, int Hkv, int hd,
+                   int Smax, int pos, void* ws, void* stream);
 
 /* ---- MXFP4 weights (OCP Microscaling v1.0: the 4-bit format CDNA4's scaled MFMA decodes in hardware; opt-in beside NF4) ----
  * Weights W [N, K] bf16, K % 128 == 0, in blocks of 32 consecutive k of one row:

@@ -4,7 +4,8 @@ a3v_gemm_nt_splitk, a3v_gemm_tn_splitk, a3v_gemm_tn_strip and a3v_splitk_reduce.
 tests/rowops_fwd_ref.py (whose ``within``, HALF_ULP_BF16, EVAL_F32 and TINY are used here).
 
 Out of scope: the fp8 GEMMs (tests/fp8_base_ref.py states their parity), a3v_gemm_qkv_rope (pinned value for value to a3v_gemm_nt
-followed by a3v_rope_kvcache, and the RoPE has fp64 parity in tests/rowops_fwd_ref.py) and the skinny GEMV file a3v_gemv.hip.
+followed by a3v_rope_kvcache, and the RoPE has fp64 parity in tests/rowops_fwd_ref.py) and the skinny GEMV file a3v_gemv.hip
+(tests/gemv_ref.py states its parity in the same scheme).
 
 The rounding sequence (a3vlm_hip.h; gemm_epilogue, splitk_epilogue_kernel and splitk_reduce_kernel perform it in this order; rbf = round
 to nearest even to bf16, every other operation one fp32 operation):
