@@ -166,7 +166,7 @@ def main(args):
     if getattr(args, "merge_lora", False):
         model.merge_lora()
     if getattr(args, "quant", False):     # eval_affordance_with_quant.py --quant: 4-bit decoder linears + LM head, NF4 or --quant_format mxfp4 (bf16 weights freed)
-        model.llma.quantize_decode_weights(getattr(args, "quant_format", "nf4"))
+        model.llma.quantize_decode_weights(getattr(args, "quant_format", "nf4"), prefill=getattr(args, "quant_prefill", False))
     if getattr(args, "kv_quant", None):
         model.llma.quantize_kv_cache(args.kv_quant)
     model.eval()

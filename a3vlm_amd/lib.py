@@ -77,6 +77,9 @@ SIGNATURES = {
     "a3v_mx4_gemv_plan": (I, [I, I, I, I, I, P]),
     "a3v_gemm_skinny_mxfp4_ws_bytes": (L, [I, I, I]),
     "a3v_gemm_skinny_mxfp4": (I, [P, L, P, L, P, P, L, I, I, I, P, L, I, P, P]),
+    "a3v_quantize_rows_mxfp8": (I, [P, L, P, F, P, L, P, I, I, P]),
+    "a3v_mx4_gemm_plan": (I, [I, I, I, I, I, P]),
+    "a3v_gemm_nt_mxfp4": (I, [P, L, P, P, L, P, P, L, I, I, I, P, L, I, P]),
     "a3v_rmsnorm": (I, [P, L, P, P, L, I, I, F, I, I, I, P]),
     "a3v_layernorm": (I, [P, L, P, P, P, L, P, I, I, F, I, I, I, P]),
     "a3v_rope_kvcache": (I, [P, L, P, L, P, P, P, I, I, I, I, I, I, I, I, I, P]),

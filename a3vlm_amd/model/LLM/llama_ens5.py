@@ -412,6 +412,15 @@ class Transformer(nn.Module):
             self._ws["skinny_ws"] = ws
         return ws
 
+    def _mx4_gemm(self, x, img, out, norm_w=None, **kw):
+        """W4A8 product on an MXFP4 image for any row count (quantize_decode_weights("mxfp4", prefill=True)): the rows of x -- of its
+        bf16 RMSNorm when ``norm_w`` is given, which is then never written -- quantised once to MXFP8, then a3v_gemm_nt_mxfp4."""
+        rows, K = x.shape
+        xq = self._buf("mx8_q", (rows, max(self.args.dim, self.n_heads * self.head_dim, self.ffn)), torch.uint8)[:, :K]
+        xe = self._buf(f"mx8_e{K}", (rows, K // 32), torch.uint8)
+        ops.quantize_rows_mxfp8(x, xq, xe, norm_w, self.args.norm_eps if norm_w is not None else 0.0)
+        return ops.gemm_nt_mxfp4(xq, xe, img.q, img.s, out, residual=kw.get("residual"), epilogue=kw.get("epilogue", 0))
+
     def _linear(self, x, w, out, **kw):
         if isinstance(w, Mx4Image):        # MXFP4 image (codes, e8m0 block scales): the scaled-MFMA GEMV, <= 16 rows per call
             if x.shape[0] > 32:
@@ -453,6 +462,7 @@ class Transformer(nn.Module):
                 and hd in (64, 128))
         n4 = getattr(self, "_n4", None)
         mx4 = getattr(self, "_mx4", None)
+        w4a8 = mx4 is not None and getattr(self, "_mx4_prefill", False) and not (S == 1 and rows <= 32)
         # fp8 KV cache (quantize_kv_cache): k_caches / vt_caches then hold the ONE shared bf16 pair.  S > 1: the layer runs unchanged on
         # the pair (a continuation dequantises the layer's prefix into it first) and its new positions are quantised afterwards;
         # S == 1: the new position goes through the staging pair into the fp8 cache and the attention reads the fp8 cache.
@@ -500,6 +510,16 @@ class Transformer(nn.Module):
                 ops.quantize_rows_fp8(act, aq, sx)
                 ops.gemm_nt_fp8(aq, sx, w2_q, w2_s, h, residual=h)
                 continue
+            if w4a8:
+                # W4A8 (opt-in): every product on the image -- rows quantised to MXFP8 once per product (the two RMSNorm outputs never
+                # exist in bf16), both block scales in the scaled MFMA; qkv stored plainly, then the rope kernel as the GEMV path
+                self._mx4_gemm(h, mx4[f"wqkv.{i}"], qkv, lyr.attention_norm.weight)
+                ops.rope_kvcache(qkv, qkv, kc, vc, cs, B, S, H, Hkv, hd, cpos, rope_pos0)
+                attend(i, kc, vc, strides)
+                self._mx4_gemm(att, mx4[f"wo.{i}"], h, residual=h)
+                self._mx4_gemm(h, mx4[f"w13.{i}"], act, lyr.ffn_norm.weight, epilogue=ops.EPI_SWIGLU)
+                self._mx4_gemm(act, mx4[f"w2.{i}"], h, residual=h)
+                continue
             if mx4 is not None:            # decode rows on the images; every multi-token forward on the layer's Wd (weight-only)
                 wqkv, wo, w13, w2 = (mx4[f"{k}.{i}"] for k in ("wqkv", "wo", "w13", "w2")) if S == 1 and rows <= 32 else self._mx4_dequant_layer(i)
             elif n4 is None:
@@ -538,8 +558,13 @@ class Transformer(nn.Module):
         a3v_quantize_mxfp4; decode rows (<= 32) run a3v_gemm_skinny_mxfp4 kernel by kernel (MXFP8 activations inside the GEMV),
         every multi-token forward dequantises one layer (a3v_dequantize_mxfp4) and is weight-only.  Needs a bf16 model on the GPU
         and dim, ffn, n_heads*head_dim multiples of 128, vocab_size % 16 == 0.  Decode batches above 32 rows have no GEMV form (as
-        for bf16 / fp8) and take the multi-token path: every generated token then dequantises every layer again (~400 MB
-        written per layer at 7B), far slower than decoding the same batch in bf16."""
+        for bf16 / fp8) and by default take the multi-token path: every generated token then dequantises every layer again
+        (~400 MB written per layer at 7B), far slower than decoding the same batch in bf16.  ``prefill=True`` (opt-in, DESIGN.md
+        7e "W4A8 GEMM") runs every product that is not such a GEMV -- every multi-token forward, decode and ragged steps of more
+        than 32 rows, and their LM head -- W4A8 on the images instead: a3v_quantize_rows_mxfp8 once per product (the two norm'd
+        inputs through its RMSNorm prologue), then a3v_gemm_nt_mxfp4; the dequantisation scratch is never allocated and logits
+        are no longer those of the bf16 model on Wd.  Decode steps of at most 32 rows keep the GEMV either way.  Measured at 7B:
+        the 64-row decode step 1.4x faster, products of 128 rows and more slower (a 1100-token prefill 3.8x): hence opt-in."""
         if getattr(self, "_n4", None) is not None:
             raise RuntimeError("this model holds NF4 weights: quantize_decode_weights('nf4') freed its bf16 decoder weights and "
                                "cannot be undone or combined with another mode; reload the checkpoint instead")
@@ -551,6 +576,7 @@ class Transformer(nn.Module):
             return
         if mode == "mxfp4":
             self._quantize_mx4()
+            self._mx4_prefill = bool(prefill)
             return
         self._q8 = None
         self._fp8_prefill = bool(prefill) and mode is not None
@@ -710,6 +736,9 @@ class Transformer(nn.Module):
         on decode steps of at most 32 rows (``decode``): after a multi-token forward, or a decode step of more rows, the rows take
         the dequantised head, so such a forward is weight-only from end to end."""
         if getattr(self, "_mx4", None) is not None and not decode:
+            if getattr(self, "_mx4_prefill", False):       # W4A8: the head on its image too, no dequantisation scratch
+                self._mx4_gemm(xn, self._mx4["output"], logits, epilogue=ops.EPI_OUT_F32)
+                return
             self._linear(xn, self._head_weight(), logits, epilogue=ops.EPI_OUT_F32)
         else:
             self._lm_head_f32(xn, logits)
@@ -989,6 +1018,10 @@ class Transformer(nn.Module):
         o0 = W if out_from is None else out_from       # h[:, image_words:] (llama_ens5.py:486)
         out = torch.empty(B, S - o0, a.vocab_size, dtype=self._dtype, device=self._device)
         xv = xn.view(B, S, a.dim)
+        if getattr(self, "_mx4", None) is not None and getattr(self, "_mx4_prefill", False):
+            for b in range(B):             # W4A8: the head on its image (bf16 logits: the NONE epilogue)
+                self._mx4_gemm(xv[b, o0:], self._mx4["output"], out[b])
+            return out
         wout = self._head_weight()
         for b in range(B):
             ops.gemm_nt(xv[b, o0:], wout, out[b])
@@ -1142,6 +1175,14 @@ class Transformer(nn.Module):
             kc, vc = self._k_cache[i], self._vt_cache[i]
             smax = kc.shape[2]
             strides = (ldq, ldq, hd, Hkv * smax * hd, smax * hd, hd, Hkv * hd * smax, hd * smax, smax, H * hd, H * hd, hd)
+            if mx4 is not None and B > 32 and getattr(self, "_mx4_prefill", False):      # W4A8 on the images, as _decoder_layers
+                self._mx4_gemm(h, mx4[f"wqkv.{i}"], qkv, lyr.attention_norm.weight)
+                ops.rope_kvcache_rows(qkv, qkv, kc, vc, cs, pos, B, H, Hkv, hd)
+                ops.attention_decode_rows(qkv, kc, vc, att, sk, pos_max + 1, B, H, Hkv, hd, strides, scratch, counters)
+                self._mx4_gemm(att, mx4[f"wo.{i}"], h, residual=h)
+                self._mx4_gemm(h, mx4[f"w13.{i}"], act, lyr.ffn_norm.weight, epilogue=ops.EPI_SWIGLU)
+                self._mx4_gemm(act, mx4[f"w2.{i}"], h, residual=h)
+                continue
             if mx4 is not None:
                 wqkv, wo, w13, w2 = (mx4[f"{k}.{i}"] for k in ("wqkv", "wo", "w13", "w2")) if B <= 32 else self._mx4_dequant_layer(i)
             elif n4 is None:

@@ -72,7 +72,8 @@ class MetaModel(nn.Module):
     @classmethod
     def from_pretrained(cls, pretrained_path, llama_type: Optional[str] = None, llama_config=None,
                         tokenizer_path: Optional[str] = None, with_visual: bool = False, max_seq_len: int = 4096,
-                        mp_group=None, dtype=torch.bfloat16, device="cuda", quant=False, kv_quant: Optional[str] = None) -> "MetaModel":
+                        mp_group=None, dtype=torch.bfloat16, device="cuda", quant=False, kv_quant: Optional[str] = None,
+                        quant_prefill: bool = False) -> "MetaModel":
         """Build the model a checkpoint folder describes and load it (reference: model/meta.py:88-222).
 
         What is not given is looked up in the LAST folder of ``pretrained_path``: ``llama_type`` in ``meta.json``,
@@ -85,7 +86,9 @@ class MetaModel(nn.Module):
         then every decoder linear and the LM head is quantised to NF4 layer by layer and its bf16 weight freed
         (``Transformer.quantize_decode_weights("nf4")``; inference only, irreversible).
         ``quant="mxfp4"`` is the same flow in the chip's own 4-bit format (OCP MXFP4 on the scaled MFMA,
-        ``Transformer.quantize_decode_weights("mxfp4")``; no reference counterpart).
+        ``Transformer.quantize_decode_weights("mxfp4")``; no reference counterpart).  ``quant_prefill=True`` with it runs prefill and
+        decode steps of more than 32 rows W4A8 on the images (``prefill=True`` there); with fp8 it is that mode's W8A8 prefill; with
+        ``quant="nf4"`` it is refused.
         ``kv_quant="fp8"`` (no reference counterpart) keeps the KV cache of ``generate`` in fp8 e4m3 with per-position scales
         (``Transformer.quantize_kv_cache``); independent of ``quant``."""
         import os
@@ -94,6 +97,11 @@ class MetaModel(nn.Module):
         paths = [pretrained_path] if isinstance(pretrained_path, str) else list(pretrained_path or [])
         if not paths:
             raise ValueError("pretrained_path should be specified")
+        if quant_prefill and quant == "nf4":
+            raise ValueError("quant_prefill is an MXFP4 option (quant='mxfp4': the W4A8 GEMM on the images; with fp8 it selects the W8A8 "
+                             "prefill): NF4 has no quantised-activation form")
+        if quant_prefill and not quant:
+            raise ValueError("quant_prefill needs quant='mxfp4' (or fp8)")
         for path in paths:
             if path.startswith("hf://"):
                 raise NotImplementedError(f"{path}: downloading from the hub is not available here; pass a local folder")
@@ -128,10 +136,12 @@ class MetaModel(nn.Module):
             warnings.warn(f"checkpoint and model mismatch: \n{load_result}")
         else:
             print("all params match perfectly!")
-        if quant in ("nf4", "mxfp4"):
+        if quant == "mxfp4":
+            model.llma.quantize_decode_weights(quant, prefill=bool(quant_prefill))
+        elif quant == "nf4":
             model.llma.quantize_decode_weights(quant)
         elif quant:
-            model.llma.quantize_decode_weights("fp8")
+            model.llma.quantize_decode_weights("fp8", prefill=bool(quant_prefill))
         if kv_quant is not None:
             model.llma.quantize_kv_cache(kv_quant)
         model.eval()

@@ -426,6 +426,50 @@ def gemm_skinny_mxfp4(a, q, scales, out, workspace, *, residual=None, epilogue: 
     return out
 
 
+def quantize_rows_mxfp8(x, q=None, e=None, norm_w=None, eps: float = 0.0):
+    """MXFP8 rows of bf16 x [rows, K] (K % 128 == 0; a3v_quantize_rows_mxfp8, the "Activations" rule of include/a3vlm_hip.h): returns
+    (e4m3fn codes [rows, K] uint8, e8m0 block exponents [rows, K/32] uint8); with norm_w the rows are the bf16 RMSNorm of x."""
+    rows, K = x.shape
+    if x.dtype != torch.bfloat16 or x.stride(1) != 1:
+        raise ValueError("quantize_rows_mxfp8 needs bf16 rows with unit column stride")
+    q = torch.empty(rows, K, dtype=torch.uint8, device=x.device) if q is None else q
+    e = torch.empty(rows, K // 32, dtype=torch.uint8, device=x.device) if e is None else e
+    _dev(x, q, e, norm_w)
+    assert q.dtype == torch.uint8 and tuple(q.shape) == (rows, K) and q.stride(1) == 1
+    assert e.dtype == torch.uint8 and e.is_contiguous() and e.numel() == rows * (K // 32)
+    assert norm_w is None or (norm_w.dtype == torch.bfloat16 and norm_w.is_contiguous() and norm_w.numel() == K)
+    rc = _l.load().a3v_quantize_rows_mxfp8(_p(x), x.stride(0), _p(norm_w), eps, _p(q), q.stride(0), _p(e), rows, K, _stream())
+    _l.check(rc, f"a3v_quantize_rows_mxfp8(rows={rows},K={K})")
+    return q, e
+
+
+def mx4_gemm_plan(M: int, N: int, K: int, epilogue: int = 0, cus: int = 256):
+    """(rc, plan ints) of a3v_mx4_gemm_plan: tile rows, tile columns, K stage in k, grid, block, LDS bytes, K slices, K stages per slice."""
+    import ctypes
+    plan = (ctypes.c_int32 * 8)()
+    rc = _l.load().a3v_mx4_gemm_plan(M, N, K, epilogue, cus, plan)
+    return rc, list(plan)
+
+
+def gemm_nt_mxfp4(aq, ea, q, scales, out, *, residual=None, epilogue: int = 0):
+    """out = epilogue(sum_blocks 2^(ea + ew) * sum_32 a_q * w_q): the W4A8 GEMM on an MXFP4 image for any M (a3v_gemm_nt_mxfp4); aq / ea
+    from quantize_rows_mxfp8."""
+    _dev(aq, ea, q, scales, out, residual)
+    M, K = aq.shape
+    N = q.shape[0]
+    assert aq.dtype == torch.uint8 and aq.stride(1) == 1 and ea.dtype == torch.uint8 and ea.is_contiguous() and ea.numel() == M * (K // 32)
+    assert q.dtype == torch.uint8 and q.shape[1] * 2 == K and q.stride(1) == 1
+    assert scales.dtype == torch.uint8 and scales.is_contiguous() and scales.numel() == N * (K // 32)
+    ncol = N // 2 if epilogue & EPI_SWIGLU else N
+    assert out.dtype == (torch.float32 if epilogue & EPI_OUT_F32 else torch.bfloat16) and out.stride(1) == 1 and tuple(out.shape) == (M, ncol)
+    assert residual is None or (residual.dtype == torch.bfloat16 and residual.stride(1) == 1 and tuple(residual.shape) == (M, N))
+    ep = epilogue | (EPI_RESIDUAL if residual is not None else 0)
+    rc = _l.load().a3v_gemm_nt_mxfp4(_p(aq), aq.stride(0), _p(ea), _p(q), q.stride(0), _p(scales), _p(out), out.stride(0), M, N, K,
+                                     _p(residual), residual.stride(0) if residual is not None else 0, ep, _stream())
+    _l.check(rc, f"a3v_gemm_nt_mxfp4(M={M},N={N},K={K},epi={ep})")
+    return out
+
+
 def rmsnorm(x, w, out, eps: float, row_idx=None):
     """out = rmsnorm(x) * w; ``row_idx`` (int32 [n]): out row i from x row row_idx[i]."""
     _dev(x, w, out, row_idx)

@@ -345,6 +345,34 @@ int a3v_mx4_gemv_plan(int M, int N, int K, int epilogue, int cus, int32_t* plan)
 int64_t a3v_gemm_skinny_mxfp4_ws_bytes(int M, int N, int K);
 int a3v_gemm_skinny_mxfp4(const void* A, int64_t lda, const void* q, int64_t ldq, const void* s, void* C, int64_t ldc, int M, int N,
                           int K, const void* residual, int64_t ldr, int epilogue, void* workspace, void* stream);
+/* W4A8 GEMM on the same images, for any M (prefill, and decode steps of more than 32 rows): the activation rows are quantised ONCE per
+ * product by a3v_quantize_rows_mxfp8 and a3v_gemm_nt_mxfp4 hands the e8m0 block scales of both operands to the scaled MFMA.
+ * a3v_quantize_rows_mxfp8: x [rows, K] bf16 (row stride ldx elements, % 8 == 0, >= K; x and norm_w 16-B aligned) -> codes q [rows, K]
+ *   e4m3fn bytes (row stride ldq BYTES, % 8 == 0, >= K; q 8-B aligned) and block exponents e [rows, K/32] e8m0 bytes (contiguous rows),
+ *   exactly the "Activations" rule above: E = floor(log2(max|a|)) - 8 per 32 k clamped to [-127, 127], byte E + 127, a / 2^E rounded to
+ *   nearest even, saturating at +-448; zero block: byte 127, codes 0.  norm_w != NULL: the rows quantised are the bf16 RMSNorm of x
+ *   (weight norm_w [K] bf16, eps) without writing it: bit-equal to a3v_rmsnorm (bf16 in, weight and out; K <= 8192 there) followed by the
+ *   plain form.
+ *   K % 128 == 0, K <= 16384; one launch, one block per row.
+ * a3v_gemm_nt_mxfp4: C = epilogue( sum_blocks 2^(ea + ew) * sum_32 a_q * w_q ), Aq [M, K] / ea [M, K/32] as written by the quantiser
+ *   (lda BYTES, % 16 == 0; Aq 16-B aligned), q / s an image as above, the 16-row interleaved w1|w3 rows of SWIGLU included (no second copy
+ *   of an image).  Any M >= 1, N % 16 == 0 (SWIGLU: % 32) and <= 65536, K % 128 == 0 and <= 16384.  Epilogues NONE / RESIDUAL / SWIGLU /
+ *   OUT_F32 with the rounding sequences stated for a3v_gemm_skinny_mxfp4 (residual may be C); no RoPE form: qkv is stored plainly and
+ *   a3v_rope_kvcache follows.  Accumulation is fp32, every accumulator sums its 128-k MFMA steps in k order: the summation order depends
+ *   on (M, N, K, epilogue) alone, a call is bit-identical from run to run; there is no split-K form and no workspace.  C 8-B aligned
+ *   (OUT_F32: 16-B), residual 8-B; ldc, ldr % 4 == 0.
+ * a3v_mx4_gemm_plan: the plan the entry point executes, from values alone (no device, no pointer; cus: compute units, 256 on MI355X --
+ *   today's plan does not depend on it).  Writes A3V_MX4_GEMM_PLAN_INTS values -- tile rows (16, 32, 64 or 128: the smallest that holds M,
+ *   so up to 128 rows the image is streamed once), tile columns (rows of W per block: 64, SWIGLU 128), K stage in k (512), grid x (row
+ *   tiles x column tiles, the row tiles of a column tile adjacent), block size, LDS bytes (0: operands go from global memory / L2 to
+ *   registers), K slices (1), K stages per slice (ceil(K / 512); the K % 512 remainder runs in steps of 128 k).
+ * All three: A3V_ERR_ARG (NULL pointer; RESIDUAL without residual) / A3V_ERR_SHAPE (anything the entry cannot run) before any launch. */
+enum { A3V_MX4_GEMM_PLAN_INTS = 8 };
+int a3v_quantize_rows_mxfp8(const void* x, int64_t ldx, const void* norm_w, float eps, void* q, int64_t ldq, void* e, int rows, int K,
+                            void* stream);
+int a3v_mx4_gemm_plan(int M, int N, int K, int epilogue, int cus, int32_t* plan);
+int a3v_gemm_nt_mxfp4(const void* Aq, int64_t lda, const void* ea, const void* q, int64_t ldq, const void* s, void* C, int64_t ldc, int M,
+                      int N, int K, const void* residual, int64_t ldr, int epilogue, void* stream);
 
 /* y = rmsnorm(x) * w  with the reference's rounding order (model/components.py:39,52-53):
  * fp32 normalise -> cast to x's dtype -> multiply by weight.  x_dtype may be A3V_F32 with
