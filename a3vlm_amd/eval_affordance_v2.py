@@ -140,6 +140,12 @@ def get_args_parser():
                    help="N > 0: answers come from MetaModel.generate_many on N KV-cache rows (every row at its own position, a finished "
                         "row is refilled with the next prompt); the loader then hands over 4 N samples at a time and --batch_size is "
                         "not used.  0 (default): generate() per batch.  Not with --kv_quant or an unmerged LoRA model")
+    p.add_argument("--repetition_penalty", type=float, default=1.0,
+                   help="HF repetition penalty over the prompt text and everything generated so far, applied on the device before "
+                        "temperature / top-p (1.0 = off, the default; > 1 discourages loops in long answers)")
+    p.add_argument("--save_scores", action="store_true", default=False,
+                   help="every record gains \"logprob_sum\" and \"logprobs\": the model's own log-probability of the answer's tokens "
+                        "(raw logits, temperature 1), a confidence for AP-style evaluation")
     return p
 
 
@@ -190,20 +196,26 @@ def main(args):
     # generate(): seeded here, per rank, so that a run with the same --seed reproduces its answers (the reference seeds only the
     # dataset shuffle, :304; its sampling stream is whatever the process left in the generator)
     torch.manual_seed(args.seed + rank)
+    save_scores = getattr(args, "save_scores", False)
+    controls = dict(repetition_penalty=getattr(args, "repetition_penalty", 1.0), return_logprobs=save_scores)
     with torch.no_grad():
         for image, qids, prompts, annotations, paths in loader:
             image = pre.batch(image) if isinstance(image, list) else image.to(dev)
             if rows > 0:           # a chunk of a few batches at a time: the loader's workers stay ahead of the decode
                 answers = model.generate_many(prompts, image, batch_rows=rows, max_gen_len=args.max_gen_len, temperature=args.temperature,
-                                              top_p=args.top_p)
+                                              top_p=args.top_p, **controls)
             else:
-                answers = model.generate(prompts, image, max_gen_len=args.max_gen_len, temperature=args.temperature, top_p=args.top_p)
-            for answer, annotation, question, path in zip(answers, annotations, prompts, paths):
+                answers = model.generate(prompts, image, max_gen_len=args.max_gen_len, temperature=args.temperature, top_p=args.top_p,
+                                         **controls)
+            answers, scores = answers if save_scores else (answers, [None] * len(prompts))
+            for answer, annotation, question, path, sc in zip(answers, annotations, prompts, paths, scores):
                 answer = postprocess_answer(answer)
                 box = format_bounding_box(answer)
                 fail = len(box) != 4 or box[0] > box[2] or box[1] > box[3]
                 outputs.append({"answer": answer, "format_answer": box, "annotation": annotation, "question": question,
                                 "image": path, "fail": fail})
+                if sc is not None:     # the scores of the generated tokens (the text above may be cut further by postprocess_answer)
+                    outputs[-1].update(logprob_sum=sc["sum"], logprobs=sc["logprobs"])
     if distributed:
         gathered = [None] * world
         dist.all_gather_object(gathered, outputs)

@@ -23,6 +23,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
+from . import genctl
 from .tokenizer import Tokenizer, probe_tokenizer_path_from_pretrained  # noqa: F401
 
 # llama_type -> module; extend to plug further model files (same contract as accessory.model.LLM.*)
@@ -307,7 +308,8 @@ class MetaModel(nn.Module):
                  depth_images: Optional[torch.Tensor] = None, max_gen_len: int = 512,
                  temperature: float = 0.0, top_p: float = 0.95,
                  additional_stop_symbols: Iterable[str] = (), return_ids: bool = False, poll_every: int = 4,
-                 sample_uniforms: Optional[torch.Tensor] = None) -> List[str]:
+                 sample_uniforms: Optional[torch.Tensor] = None, repetition_penalty: float = 1.0,
+                 return_logprobs: bool = False) -> List[str]:
         """meta.py:379-485.  ``return_ids`` additionally returns the generated id lists (the
         arguments of tokenizer.decode at :482-484) for bit-exact parity checks.
         ``temperature > 0`` (the eval script's default recipe, T 0.1 / top-p 0.75): the nucleus draw of :456-459 / :568-583 runs on
@@ -316,9 +318,14 @@ class MetaModel(nn.Module):
         handed in as ``sample_uniforms`` [steps, bsz] (parity tests replay the oracle with the same numbers).
         ``poll_every``: the all-rows-stopped flag lives on the device and is read back (a host sync) only every
         ``poll_every`` steps instead of every step (:478-479); steps taken after every row has stopped write past
-        ``stop_pos`` and are discarded, so the outputs are identical for any value (1 = the reference's cadence)."""
+        ``stop_pos`` and are discarded, so the outputs are identical for any value (1 = the reference's cadence).
+        ``repetition_penalty`` (HF's rule over the prompt text and everything generated so far, applied before temperature and
+        top-p; 1.0 = off) and ``return_logprobs`` (the return gains ``scores``: per answer ``{"logprobs": [...], "sum": ...}``, the
+        model's own log-probability of every kept token, from the raw logits at temperature 1) are opt-in and run on the device
+        inside the step (model/genctl.py); with the defaults nothing of them is allocated or launched."""
         if isinstance(prompts, str):
             raise ValueError(f"{self.__class__}.generate expects a batched LIST of prompts, but str is given")
+        controls = genctl.wanted(repetition_penalty, return_logprobs)      # ValueError before any device use
         dev = self._device
         if images is not None:
             images = images.to(dev)
@@ -364,6 +371,11 @@ class MetaModel(nn.Module):
                    else sample_uniforms.to(device=dev, dtype=torch.float32).contiguous())
             assert uni.shape[0] >= total_len - start_pos and uni.shape[1] == bsz, tuple(uni.shape)
             sampled = torch.empty(bsz, dtype=torch.long, device=dev)
+        gc = None
+        if controls:       # teacher-forced prompt positions are marked here, up front, and never scored (generated index < 0)
+            gc = genctl.GenControls(bsz, args.vocab_size, total_len - start_pos, repetition_penalty, return_logprobs, dev)
+            gc.prompt_len.copy_(torch.tensor([len(t) for t in prompt_tokens], dtype=torch.int32))
+            gc.mark_prompts(tokens)
 
         # One iteration = the model step (one C call for a decode step) + ONE launch of a3v_generate_step, which does everything
         # meta.py:456-477 does with a dozen small torch ops: argmax, teacher forcing of longer prompts, the tokens[:, cur_pos]
@@ -377,9 +389,12 @@ class MetaModel(nn.Module):
             else:
                 logits = self.llma.forward_inference(tokens[:, prev_pos:cur_pos], prev_pos,
                                                      images if prev_pos == 0 else None)
+            z = gc.prepare(logits) if gc is not None else logits       # the choice reads the penalised row, the score the raw one
             if temperature > 0:
-                self._sample_into(logits, temperature, top_p, uni[cur_pos - start_pos], sampled)
-            ops.generate_step(logits, sampled, tokens, text_mask, cur_pos, stop_seq, stop_off, len(l_stop), stopped, stop_pos, live)
+                self._sample_into(z, temperature, top_p, uni[cur_pos - start_pos], sampled)
+            ops.generate_step(z, sampled, tokens, text_mask, cur_pos, stop_seq, stop_off, len(l_stop), stopped, stop_pos, live)
+            if gc is not None:         # a stopped row keeps writing past its stop_pos, as its tokens do: cut below
+                gc.record(logits, tokens, col=cur_pos)
             if ((cur_pos - start_pos) % poll_every == poll_every - 1 or cur_pos == total_len - 1) and int(live.item()) == 0:
                 break
             prev_pos = cur_pos
@@ -390,13 +405,18 @@ class MetaModel(nn.Module):
             t = t[len(prompt_tokens[i]):sp[i]]
             ids.append(t)
             decoded.append(self.tokenizer.decode(t))
-        return (decoded, ids) if return_ids else decoded
+        ret = (decoded, ids) if return_ids else decoded
+        if return_logprobs:            # the device array, read back once
+            scores = [genctl.score(row[:len(t)]) for row, t in zip(gc.lp.tolist(), ids)]
+            ret = ret + (scores,) if return_ids else (decoded, scores)
+        return ret
 
     @torch.no_grad()
     def generate_many(self, prompts: List[str], images: Optional[torch.Tensor] = None, *, batch_rows: int,
                       max_gen_len=512, temperature: float = 0.0, top_p: float = 0.95,
                       additional_stop_symbols: Iterable[str] = (), return_ids: bool = False, poll_every: int = 4,
-                      sample_uniforms: Optional[torch.Tensor] = None):
+                      sample_uniforms: Optional[torch.Tensor] = None, repetition_penalty: float = 1.0,
+                      return_logprobs: bool = False):
         """Any number of prompts through ``batch_rows`` KV-cache rows (no reference counterpart; opt-in): every row decodes at its
         own position, and a row whose answer is finished is prefilled with the next prompt while the others keep decoding, so a
         short answer does not hold its row until the longest answer of a batch is done.  Answers come back in input order.
@@ -407,10 +427,13 @@ class MetaModel(nn.Module):
         ``images`` [N, ...]: one image per prompt, or None.  ``temperature > 0``: uniforms are indexed [prompt, generated index]
         (drawn up front, or ``sample_uniforms`` [N, >= max steps]), so an answer does not depend on ``batch_rows`` or on the row it
         ran in.  ``stopped`` is read back every ``poll_every`` steps; a stopped row is not touched by later steps.
+        ``repetition_penalty`` / ``return_logprobs``: as in ``generate``; the seen set belongs to the cache row and is cleared and
+        re-marked when the row is refilled, a finished row's log-probs are read back with its ids.
         Not for the fp8 KV cache, LoRA models before ``merge_lora()`` or the two-image plugin (each raises, naming the way out)."""
         from .ragged import RowScheduler
         if isinstance(prompts, str):
             raise ValueError(f"{self.__class__}.generate_many expects a LIST of prompts, but str is given")
+        controls = genctl.wanted(repetition_penalty, return_logprobs)      # ValueError before any device use
         llma = self.llma
         llma._ragged_check()                                  # before anything is allocated or launched
         dev = self._device
@@ -432,7 +455,8 @@ class MetaModel(nn.Module):
             prompt_tokens.append(t[-(max_seq_len - mg):])
         lens = [len(t) for t in prompt_tokens]
         if N == 0:
-            return ([], []) if return_ids else []
+            ret = ([], []) if return_ids else []
+            return (ret + ([],) if return_ids else ([], [])) if return_logprobs else ret
 
         l_stop = [[self.tokenizer.eos_id]]
         l_stop += [self.tokenizer.encode_segment(s) for s in additional_stop_symbols]
@@ -463,8 +487,13 @@ class MetaModel(nn.Module):
             sampled = torch.zeros(R, dtype=torch.long, device=dev)
             ubase = torch.zeros(R, dtype=torch.long, device=dev)         # index of the row's uniform at scheduler step 0
 
+        gc = None
+        if controls:
+            gc = genctl.GenControls(R, args.vocab_size, max(lim - ln for lim, ln in zip(limits, lens)), repetition_penalty,
+                                    return_logprobs, dev)
         sched = RowScheduler(lens, limits, R, W)
         ids: List[Optional[List[int]]] = [None] * N
+        lps: List[List[float]] = [[] for _ in range(N)]
         llma.allocate_rows(R)
         while True:
             for row, i in sched.refill():
@@ -473,6 +502,9 @@ class MetaModel(nn.Module):
                 tokens[row].zero_()
                 tokens[row, :lens[i]] = t
                 cur[row], limit[row], stopped[row], stop_pos[row] = lens[i], limits[i], False, lens[i] + 1
+                if gc is not None:         # the row's seen set is its new prompt alone; the first id (prefill logits) is recorded below
+                    gc.prompt_len[row] = lens[i]
+                    gc.mark_prompts(tokens, row)
                 if ubase is not None:
                     ubase[row] = i * n_uni - sched.steps
             for i in sched.finished_at_once:
@@ -480,11 +512,17 @@ class MetaModel(nn.Module):
             sched.finished_at_once.clear()
             if not sched.occupied():
                 break
+            z = logits
+            if gc is not None:
+                z = gc.prepare(logits)
+                gc.snapshot(stopped)       # a row that is stopped on entry is not touched by the step, nor by the record
             if temperature > 0:
                 u = uni[(ubase + sched.steps).clamp_(0, uni.numel() - 1)]
-                self._sample_into(logits, temperature, top_p, u, sampled)
-            ops.generate_step_rows(logits, sampled, tokens, cur, limit, W, stop_seq, stop_off, len(l_stop), stopped, stop_pos, None,
+                self._sample_into(z, temperature, top_p, u, sampled)
+            ops.generate_step_rows(z, sampled, tokens, cur, limit, W, stop_seq, stop_off, len(l_stop), stopped, stop_pos, None,
                                    next_tok, pos)
+            if gc is not None:
+                gc.record(logits, tokens, cur=cur, stopped_before=gc.stopped_before)
             pos_max = sched.advance()
             if sched.steps % poll_every == 0 or all(sched.generated[r] >= limits[i] - lens[i] for r, i in sched.occupied()):
                 st = stopped.tolist()
@@ -493,18 +531,28 @@ class MetaModel(nn.Module):
                     sp = stop_pos.tolist()
                     for r, i in fin:
                         ids[i] = tokens[r, lens[i]:sp[r]].tolist()
+                        if return_logprobs:
+                            lps[i] = gc.lp[r, :len(ids[i])].tolist()
                         sched.release(r)
                     if not sched.occupied():
                         continue                                         # refill (or leave) before another step
             llma.forward_inference_rows(next_tok, pos, pos_max, out=logits)
         decoded = [self.tokenizer.decode(t) for t in ids]
-        return (decoded, ids) if return_ids else decoded
+        ret = (decoded, ids) if return_ids else decoded
+        if return_logprobs:
+            scores = [genctl.score(x) for x in lps]
+            ret = ret + (scores,) if return_ids else (decoded, scores)
+        return ret
 
     @torch.no_grad()
     def stream_generate(self, prompt: str, image: Optional[torch.Tensor] = None, max_gen_len: int = 512,
                         temperature: float = 0.0, top_p: float = 0.95,
-                        additional_stop_symbols: Iterable[str] = ()):
-        """meta.py:487-566."""
+                        additional_stop_symbols: Iterable[str] = (), repetition_penalty: float = 1.0,
+                        return_logprobs: bool = False):
+        """meta.py:487-566.  ``repetition_penalty`` / ``return_logprobs`` as in ``generate``; with ``return_logprobs`` every yielded
+        dict also carries ``"logprobs"``: one value per token generated so far (the text may be cut inside the last ones by a stop
+        string)."""
+        controls = genctl.wanted(repetition_penalty, return_logprobs)      # ValueError before any device use
         args = self.llma.args
         dev = self._device
         prompt_tokens = self.tokenizer.encode(prompt, bos=True, eos=False)
@@ -524,28 +572,43 @@ class MetaModel(nn.Module):
         tokens[:prompt_size] = torch.tensor(prompt_tokens, dtype=torch.long)
         start_pos, prev_pos, generate_until = prompt_size, 0, prompt_size
         nt_buf = torch.empty(1, dtype=torch.long, device=dev)
+        gc = None
+        if controls:
+            gc = genctl.GenControls(1, args.vocab_size, total_len - start_pos, repetition_penalty, return_logprobs, dev)
+            gc.prompt_len.fill_(prompt_size)
+            gc.mark_prompts(tokens[None])
+
+        def out(text, end):
+            d = {"text": text, "end_of_content": end}
+            if return_logprobs:
+                d["logprobs"] = gc.lp[0, :generate_until - start_pos].tolist()
+            return d
+
         for cur_pos in range(start_pos, total_len):
             logits = self.llma.forward_inference(tokens[None, prev_pos:cur_pos], prev_pos,
                                                  image if prev_pos == 0 else None)
+            z = gc.prepare(logits) if gc is not None else logits
             if temperature > 0:
-                nt = self._sample_into(logits, temperature, top_p, torch.rand(1, device=dev), nt_buf)
+                nt = self._sample_into(z, temperature, top_p, torch.rand(1, device=dev), nt_buf)
             else:
-                nt = ops.argmax(logits, nt_buf)
+                nt = ops.argmax(z, nt_buf)
             nt = int(nt.reshape(-1)[0].item())
             if nt == self.tokenizer.eos_id:
                 break
             tokens[cur_pos] = nt
+            if gc is not None:
+                gc.record(logits, tokens[None], col=cur_pos)
             prev_pos = cur_pos
             generate_until = cur_pos + 1
             generated = self.tokenizer.decode(tokens[start_pos:generate_until].tolist())
             for s in additional_stop_symbols:
                 sp = generated.find(s)
                 if sp != -1:
-                    yield {"text": generated[:sp], "end_of_content": True}
+                    yield out(generated[:sp], True)
                     return
-            yield {"text": generated, "end_of_content": False}
+            yield out(generated, False)
         generated = self.tokenizer.decode(tokens[start_pos:generate_until].tolist())
-        yield {"text": generated, "end_of_content": True}
+        yield out(generated, True)
 
     def _sample_into(self, logits: torch.Tensor, temperature: float, top_p: float, uniforms: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
         """One top-p draw per row into ``out``: the device kernel where it applies (V <= 65536, 0 < top_p), otherwise the reference's

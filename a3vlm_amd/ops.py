@@ -707,6 +707,78 @@ def argmax(logits, out):
     return out
 
 
+def _seen_ok(seen, rows: int, V: int):
+    assert seen.dtype == torch.int32 and seen.dim() == 2 and seen.stride(1) == 1 and seen.shape[0] >= rows
+    assert seen.stride(0) >= (V + 31) // 32, (seen.stride(0), V)
+
+
+def seen_mark(tokens, lens, seen, V: int):
+    """seen[b] |= bits of tokens[b, :lens[b]] (a3v_seen_mark; seen: int32 storage of the uint32 bitmap [B, >= ceil(V / 32)], the row
+    stride is its words_per_row).  Ids outside [0, V) are ignored; lens[b] <= 0 leaves the row alone."""
+    _dev(tokens, lens, seen)
+    B = tokens.shape[0]
+    assert tokens.dtype == torch.int64 and tokens.dim() == 2 and tokens.stride(1) == 1
+    assert lens.dtype == torch.int32 and lens.is_contiguous() and lens.numel() >= B
+    _seen_ok(seen, B, V)
+    rc = _l.load().a3v_seen_mark(_p(tokens), tokens.stride(0), _p(lens), _p(seen), seen.stride(0), B, int(V), _stream())
+    _l.check(rc, "a3v_seen_mark")
+    return seen
+
+
+def seen_clear_rows(seen, rows):
+    """Zero the bitmap rows listed in ``rows`` (device int32; a3v_seen_clear_rows): seen.shape[1] words of each."""
+    _dev(seen, rows)
+    assert seen.dtype == torch.int32 and seen.dim() == 2 and seen.stride(1) == 1
+    assert rows.dtype == torch.int32 and rows.is_contiguous() and rows.numel() > 0
+    rc = _l.load().a3v_seen_clear_rows(_p(seen), _p(rows), rows.numel(), seen.stride(0), seen.shape[1], seen.shape[0], _stream())
+    _l.check(rc, "a3v_seen_clear_rows")
+    return seen
+
+
+def logits_prepare(logits, seen, penalty: float, out, lse):
+    """One launch, one pass over every row of the raw fp32 logits (a3v_logits_prepare): ``out`` = the rows under the repetition
+    penalty of the ``seen`` bitmap (seen None: out is not touched), ``lse[b]`` = logsumexp of the RAW row (lse None: not computed).
+    The logits are never written."""
+    _dev(logits, seen, out, lse)
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
+    B, V = logits.shape
+    assert seen is not None or lse is not None
+    if seen is not None:
+        _seen_ok(seen, B, V)
+        assert out.dtype == torch.float32 and out.shape == logits.shape and out.stride(1) == 1 and out.data_ptr() != logits.data_ptr()
+        assert penalty > 0, penalty
+    assert lse is None or (lse.dtype == torch.float32 and lse.is_contiguous() and lse.numel() >= B)
+    rc = _l.load().a3v_logits_prepare(_p(logits), logits.stride(0), _p(seen), seen.stride(0) if seen is not None else 0, float(penalty),
+                                      _p(out), out.stride(0) if out is not None else 0, _p(lse), B, V, _stream())
+    _l.check(rc, "a3v_logits_prepare")
+
+
+def generate_record(logits, lse, tokens, seen, logprob, *, col: int = 0, cur=None, stopped_before=None, idx: int = 0, prompt_len=None):
+    """After generate_step / generate_step_rows wrote the chosen ids (a3v_generate_record): per row the id of column ``col`` (uniform
+    step) or ``cur[b] - 1`` (ragged), logprob[b, g] = logits[b, id] - lse[b] at the generated index g = column - prompt_len[b] (or
+    ``idx``), and the id's bit in ``seen``.  Rows with ``stopped_before[b]`` set, idle rows and teacher-forced positions (g < 0)
+    write nothing.  ``seen`` / ``logprob`` may be None (not both)."""
+    _dev(logits, lse, tokens, seen, logprob, cur, stopped_before, prompt_len)
+    B = tokens.shape[0]
+    assert tokens.dtype == torch.int64 and tokens.dim() == 2 and tokens.stride(1) == 1
+    assert seen is not None or logprob is not None
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1 and logits.shape[0] == B     # also names V
+    V = logits.shape[1]
+    if logprob is not None:
+        assert lse.dtype == torch.float32 and lse.is_contiguous() and lse.numel() >= B
+        assert logprob.dtype == torch.float32 and logprob.dim() == 2 and logprob.stride(1) == 1 and logprob.shape[0] >= B
+    if seen is not None:
+        _seen_ok(seen, B, V)
+    for t, d in ((cur, torch.int32), (stopped_before, torch.bool), (prompt_len, torch.int32)):
+        assert t is None or (t.dtype == d and t.is_contiguous() and t.numel() >= B)
+    rc = _l.load().a3v_generate_record(_p(logits), logits.stride(0), _p(lse), _p(tokens), tokens.stride(0),
+                                       int(col), _p(cur), _p(stopped_before), _p(seen), seen.stride(0) if seen is not None else 0,
+                                       _p(logprob), logprob.stride(0) if logprob is not None else 0,
+                                       logprob.shape[1] if logprob is not None else 0, int(idx), _p(prompt_len), B, int(V),
+                                       _stream())
+    _l.check(rc, "a3v_generate_record")
+
+
 def count_valid(labels, n_valid):
     _dev(labels, n_valid)
     rc = _l.load().a3v_count_valid(_p(labels), labels.numel(), _p(n_valid), _stream())

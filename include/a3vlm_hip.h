@@ -632,6 +632,58 @@ int a3v_llama_decode_step_rows(const a3v_llama_layer* layers, int n_layers, void
 int a3v_llama_decode_step_rows_form(int B, int dim, int H, int Hkv, int hd, int ffn, int w8);
 
 /* ---------------------------------------------------------------------------------------
+ * Generation controls (opt-in; a3v_genctl.hip): a log-probability per generated token and the HF repetition penalty, on the
+ * device inside the step.  No existing entry changes; with the options off none of these is launched.
+ *
+ * Seen set: one bitmap per cache row, uint32 [R, words_per_row], words_per_row >= ceil(V / 32) (the row stride in words).  Token
+ *   t is bit t & 31 of word t >> 5.  It holds the row's prompt TEXT tokens and every token generated so far (the scope of HF's
+ *   RepetitionPenaltyLogitsProcessor: the whole input_ids); image words are not tokens and are never in it.  Ids outside [0, V)
+ *   are ignored, never written.
+ * Penalty p > 0 over the raw fp32 logits z of a row:  z'[t] = z[t] / p if t is seen and z[t] > 0;  z[t] * p if t is seen and
+ *   z[t] <= 0;  z[t] otherwise.  The division is a true fp32 division (not a reciprocal multiply): the bits are torch's.  It is
+ *   applied BEFORE temperature and top-p (HF order: processors, then warpers): the sampler / the step kernel read z'.  Greedy is
+ *   the first-index argmax of z'.  NaN and +-inf pass through the same two expressions.
+ * Log-prob: lp = z[tok] - logsumexp(z) on the RAW logits at temperature 1 -- the model's own probability, whatever penalty,
+ *   temperature and nucleus chose the token.  fp32, max-subtracted.  One value per generated token.  The sequence score is the
+ *   sum of lp over the kept tokens of an answer (up to, not including, the stop position, as the text is cut), taken on the
+ *   host in fp64 from the device array, read back once.
+ *   Reduction order of logsumexp (one 1024-thread block per row, ONE pass): thread t owns the 4-element vectors t, t + 1024, ...
+ *   of the row in ascending order, then element 4 (V / 4) + t of the tail (a row whose address -- or whose out row's -- is not
+ *   16-byte aligned: single elements t, t + 1024, ...).  Per vector, with the running pair (m, s) of the thread:
+ *   M = max(m, x0..x3); s = s * exp(m - M) + (((e0 + e1) + e2) + e3), e_j = exp(x_j - M); m = M.  Per wave: M_w = max of m;
+ *   s *= exp(m - M_w); S_w = butterfly sum of s (lanes ^32, ^16, ^8, ^4, ^2, ^1).  Block: M = max of the 16 M_w;
+ *   S = sum over w = 0..15 in order of S_w * exp(M_w - M); lse = M + log(S).  exp / log are expf / logf (<= 1 ulp), an infinite
+ *   maximum is replaced by 0 as the exponent offset (no inf - inf), an empty partial sum stays 0.  The bound that follows from
+ *   this shape is written out in tests/genctl_ref.py (lse_bound).
+ *
+ * a3v_seen_mark: seen[b] |= bits of tokens[b, 0 .. min(lens[b], ld_tok)) for every row in one launch (vector atomicOr);
+ *   lens[b] <= 0 leaves the row alone.  The prompt marking.
+ * a3v_seen_clear_rows: zero the first n_words (<= words_per_row) words of the bitmap rows rows[0 .. n_rows) (device int32; an entry
+ *   outside [0, R) is skipped).
+ * a3v_logits_prepare: logits fp32 [B, V] (row stride ld), never written.  seen != NULL: out [B, V] (row stride ld_out, must not
+ *   alias logits) = the penalised rows; seen == NULL: out is not touched.  lse != NULL: lse[b] = logsumexp of the RAW row; NULL:
+ *   not computed.  One of the two must be asked for.  Any V.
+ * a3v_generate_record: runs AFTER a3v_generate_step / a3v_generate_step_rows has written the chosen id.  Per row b:
+ *   column c = col (cur == NULL: the uniform step, col = the cur_pos of a3v_generate_step), or c = cur[b] - 1 (ragged:
+ *   generate_step_rows_kernel writes tokens[b, cur[b]] and THEN advances cur[b], so after it the id sits one column back).
+ *   generated index g = c - prompt_len[b] (prompt_len != NULL), else idx.  id = tokens[b, c];
+ *   logprob[b, g] = logits[b, id] - lse[b] (one fp32 subtraction; logprob [B, n_lp], row stride ld_lp, may be NULL; g >= n_lp is not written);
+ *   bit id of seen[b] is set (seen may be NULL).  Nothing is written and nothing is marked for a row with stopped_before[b] set
+ *   (the snapshot of `stopped` taken before the step; NULL: no row is skipped for it), with c outside [0, ld_tok) (an idle
+ *   ragged row), with g < 0 (a teacher-forced prompt position of a3v_generate_step: marked up front, never scored) or with an
+ *   id outside [0, V).  The ragged step kernel can also stop a row WITHOUT a write (cur[b] outside its range); such a row must be
+ *   passed as stopped_before by the caller -- generate_many never makes one (a prompt with nothing to write gets no row).
+ * ------------------------------------------------------------------------------------- */
+int a3v_seen_mark(const int64_t* tokens, int64_t ld_tok, const int32_t* lens, uint32_t* seen, int64_t words_per_row, int B, int V,
+                  void* stream);
+int a3v_seen_clear_rows(uint32_t* seen, const int32_t* rows, int n_rows, int64_t words_per_row, int64_t n_words, int R, void* stream);
+int a3v_logits_prepare(const float* logits, int64_t ld, const uint32_t* seen, int64_t words_per_row, float penalty, float* out,
+                       int64_t ld_out, float* lse, int B, int V, void* stream);
+int a3v_generate_record(const float* logits, int64_t ld, const float* lse, const int64_t* tokens, int64_t ld_tok, int col,
+                        const int32_t* cur, const uint8_t* stopped_before, uint32_t* seen, int64_t words_per_row, float* logprob,
+                        int64_t ld_lp, int n_lp, int idx, const int32_t* prompt_len, int B, int V, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Training (backward) entry points. Reference: autograd through the same modules under
  * autocast(bf16) with fp32 master weights (engine_finetune.py:44-68, main_finetune.py:212-217).
  * Convention: activations and their grads use `act_dtype` (bf16 / f32 parity); the residual
