@@ -22,7 +22,6 @@ Differences from the reference that are deliberate and documented in DESIGN.md:
 """
 from __future__ import annotations
 
-import collections
 import math
 from dataclasses import dataclass
 from typing import Callable, Dict, List, Optional
@@ -32,9 +31,7 @@ from torch import nn
 
 from ... import lib as _lib
 from ... import ops
-
-# one MXFP4 weight image: codes [N, K/2] uint8 and e8m0 block scales [N, K/32] uint8 (ops.quantize_mxfp4)
-Mx4Image = collections.namedtuple("Mx4Image", "q s")
+from .weight_formats import FORMATS, LAYER_KEYS, DecodeWeights, WeightImage, head_path, layer_path
 
 
 @dataclass
@@ -228,6 +225,8 @@ class Transformer(nn.Module):
 
         self._packed: Dict[str, torch.Tensor] = {}
         self._packed_version = None
+        self._weights: Optional[DecodeWeights] = None     # quantize_decode_weights: None = the bf16 parameters alone
+        self._layer_tab_key = None
         self._k_cache: List[torch.Tensor] = []
         self._vt_cache: List[torch.Tensor] = []
         self._cache_shape = None
@@ -254,6 +253,11 @@ class Transformer(nn.Module):
     @property
     def _device(self) -> torch.device:
         return self.norm.weight.device
+
+    @property
+    def weight_format(self) -> str:
+        """How the decoder weights are held: "bf16", or "fp8" / "nf4" / "mxfp4" after quantize_decode_weights (weight_formats.FORMATS)."""
+        return "bf16" if self._weights is None else self._weights.fmt
 
     def _buf(self, name: str, shape, dtype=None) -> torch.Tensor:
         """Workspace cache: one allocation per (name, shape, dtype); re-used across calls so the
@@ -289,8 +293,8 @@ class Transformer(nn.Module):
         pk: Dict[str, torch.Tensor] = {}
         with torch.no_grad():
             for i, lyr in enumerate(self.layers):
-                if getattr(self, "_n4", None) is not None or getattr(self, "_mx4", None) is not None:
-                    break                  # NF4 / MXFP4 model: the decoder weights live only as images (self._n4 / self._mx4)
+                if FORMATS[self.weight_format].frees_weights:
+                    break                  # NF4 / MXFP4 model: the decoder weights live only as images (self._weights.images)
                 a, f = lyr.attention, lyr.feed_forward
                 pk[f"wqkv.{i}"] = torch.cat([a.wq.weight, a.wk.weight, a.wv.weight], dim=0).to(dtp).contiguous()
                 w1, w3 = f.w1.weight, f.w3.weight
@@ -394,18 +398,10 @@ class Transformer(nn.Module):
         self._layer_tab_key = None
 
     # ------------------------------------------------------------------ linear dispatch
-    def _skinny_ws(self, M: int, N: int, K: int) -> torch.Tensor:
-        """One zero-initialised GEMV workspace (grown on demand; the kernels leave its counters zero)."""
-        need = ops.gemm_skinny_ws_bytes(M, N, K)
-        ws = self._ws.get("skinny_ws")
-        if ws is None or ws.numel() * 4 < need:
-            ws = torch.zeros((need + 3) // 4, dtype=torch.float32, device=self._device)
-            self._ws["skinny_ws"] = ws
-        return ws
-
-    def _mx4_ws(self, M: int, N: int, K: int) -> torch.Tensor:
-        """The GEMV workspace, large enough for the MXFP4 GEMV of this shape (same layout, same buffer as _skinny_ws)."""
-        need = ops.gemm_skinny_mxfp4_ws_bytes(M, N, K)
+    def _skinny_ws(self, M: int, N: int, K: int, ws_bytes=ops.gemm_skinny_ws_bytes) -> torch.Tensor:
+        """The one zero-initialised GEMV workspace, grown on demand to ``ws_bytes(M, N, K)`` (every GEMV family has the same layout;
+        the kernels leave its counters zero)."""
+        need = ws_bytes(M, N, K)
         ws = self._ws.get("skinny_ws")
         if ws is None or ws.numel() * 4 < need:
             ws = torch.zeros((need + 3) // 4, dtype=torch.float32, device=self._device)
@@ -422,47 +418,91 @@ class Transformer(nn.Module):
         return ops.gemm_nt_mxfp4(xq, xe, img.q, img.s, out, residual=kw.get("residual"), epilogue=kw.get("epilogue", 0))
 
     def _linear(self, x, w, out, **kw):
-        if isinstance(w, Mx4Image):        # MXFP4 image (codes, e8m0 block scales): the scaled-MFMA GEMV, <= 16 rows per call
-            if x.shape[0] > 32:
-                raise RuntimeError("an MXFP4 image takes at most 32 rows: larger products run on the dequantised layer")
-            for r0 in range(0, x.shape[0], 16):
-                res = kw.get("residual")
-                ops.gemm_skinny_mxfp4(x[r0:r0 + 16], w.q, w.s, out[r0:r0 + 16], self._mx4_ws(min(16, x.shape[0] - r0), w.q.shape[0], x.shape[1]),
-                                      residual=None if res is None else res[r0:r0 + 16], epilogue=kw.get("epilogue", 0))
+        if isinstance(w, WeightImage):     # an image of this model's 4-bit format: its GEMV, gemv_rows rows per call
+            f = FORMATS[self._weights.fmt]
+            rows, res = x.shape[0], kw.get("residual")
+            if rows > f.gemv_max_rows:
+                raise RuntimeError(f"an {f.name} image takes at most {f.gemv_max_rows} rows: larger products run on the dequantised layer")
+            for r0 in range(0, rows, f.gemv_rows):
+                r1 = r0 + f.gemv_rows
+                f.gemv(x[r0:r1], w.q, w.s, out[r0:r1], self._skinny_ws(min(f.gemv_rows, rows - r0), w.q.shape[0], x.shape[1], f.gemv_ws_bytes),
+                       residual=None if res is None else res[r0:r1], epilogue=kw.get("epilogue", 0))
             return out
-        if isinstance(w, tuple):           # NF4 image (nibbles, block scales): weight-only NF4 GEMV, <= 16 rows
-            q, sc = w
-            return ops.gemm_skinny_nf4(x, q, sc, out, self._skinny_ws(x.shape[0], q.shape[0], x.shape[1]), residual=kw.get("residual"),
-                                       epilogue=kw.get("epilogue", 0))
         if x.shape[0] <= 16 and x.dtype == torch.bfloat16 and "bias" not in kw and w.shape[1] % 32 == 0:
             ep = kw.get("epilogue", 0)
             return ops.gemm_skinny(x, w, out, self._skinny_ws(x.shape[0], w.shape[0], w.shape[1]), residual=kw.get("residual"), epilogue=ep)
         return ops.gemm_nt(x, w, out, **kw)
 
     # ------------------------------------------------------------------ decoder stack
+    def _row_buffers(self, rows: int, scratch: bool):
+        """xn, qkv, att, act of a pass over ``rows`` rows and, if ``scratch``, the split-KV scratch of a decode attention of as many
+        rows (else None)."""
+        a = self.args
+        H, Hkv, hd = self.n_heads, self.n_kv_heads, self.head_dim
+        xn = self._buf("xn", (rows, a.dim))
+        qkv = self._buf("qkv", (rows, (H + 2 * Hkv) * hd))
+        att = self._buf("att", (rows, H * hd))
+        act = self._buf("act", (rows, self.ffn))
+        sc = self._buf("attn_scratch", (2 * ops.attention_scratch_floats(rows, H, hd, a.max_seq_len + 64),), torch.float32) if scratch else None
+        return xn, qkv, att, act, sc
+
+    def _layer_path(self, h: torch.Tensor, rows: int, decode: bool, ragged: bool = False) -> str:
+        """weight_formats.layer_path of this model for a pass over ``rows`` rows of the stream h."""
+        w = self._weights
+        return layer_path(self.weight_format, w is not None and w.prefill, rows, decode, self.args.dim, self.head_dim,
+                          h.dtype == torch.bfloat16, ragged)
+
+    def _layer_operands(self, i: int, path: str):
+        """(wqkv, wo, w13, w2) of layer i for ``path``: the bf16 weights, the layer's Wd in the scratch, or the images."""
+        if path == "bf16":
+            pk, lyr = self._pack(), self.layers[i]
+            return pk[f"wqkv.{i}"], lyr.attention.wo.weight, pk[f"w13.{i}"], lyr.feed_forward.w2.weight
+        if path == "dequant":              # the layer's Wd in a reused bf16 scratch, then the bf16 GEMMs unchanged (weight-only)
+            return self._dequant_layer(i)
+        return [self._weights.images[f"{k}.{i}"] for k in LAYER_KEYS]
+
+    def _layer(self, i: int, path: str, h, bufs, rope, attend, qkv_rope=None) -> None:
+        """Decoder block i on h in place.  The callers' own steps: ``rope()`` rotates q and k in the qkv buffer and writes the cache,
+        ``attend()`` fills att, and ``qkv_rope(wqkv)``, if given, stands for the qkv product and rope() together."""
+        a, lyr = self.args, self.layers[i]
+        xn, qkv, att, act = bufs
+        wqkv, wo, w13, w2 = self._layer_operands(i, path)
+        if path == "w4a8":
+            # W4A8 (opt-in): every product on the image -- rows quantised to MXFP8 once per product (the two RMSNorm outputs never
+            # exist in bf16), both block scales in the scaled MFMA; qkv stored plainly, then the rope kernel as the GEMV path
+            self._mx4_gemm(h, wqkv, qkv, lyr.attention_norm.weight)
+            rope()
+            attend()
+            self._mx4_gemm(att, wo, h, residual=h)
+            self._mx4_gemm(h, w13, act, lyr.ffn_norm.weight, epilogue=ops.EPI_SWIGLU)
+            self._mx4_gemm(act, w2, h, residual=h)
+            return
+        ops.rmsnorm(h, lyr.attention_norm.weight, xn, a.norm_eps)
+        if qkv_rope is not None:
+            qkv_rope(wqkv)
+        else:
+            self._linear(xn, wqkv, qkv)
+            rope()
+        attend()
+        self._linear(att, wo, h, residual=h)
+        ops.rmsnorm(h, lyr.ffn_norm.weight, xn, a.norm_eps)
+        self._linear(xn, w13, act, epilogue=ops.EPI_SWIGLU)
+        self._linear(act, w2, h, residual=h)
+
     def _decoder_layers(self, h: torch.Tensor, B: int, S: int, start_pos: int, rope_pos0: int,
                         k_caches, vt_caches, causal: bool) -> None:
         """h [B*S, dim] updated in place through all blocks (llama_ens5.py:237-249)."""
         a = self.args
         H, Hkv, hd, dim = self.n_heads, self.n_kv_heads, self.head_dim, a.dim
         rows = B * S
-        pk = self._pack()
+        self._pack()
         cs = self._cos_sin_dev()
-        xn = self._buf("xn", (rows, dim))
-        qkv = self._buf("qkv", (rows, (H + 2 * Hkv) * hd))
-        att = self._buf("att", (rows, H * hd))
-        act = self._buf("act", (rows, self.ffn))
+        xn, qkv, att, act, scratch = self._row_buffers(rows, S == 1 and h.dtype == torch.bfloat16)
         Sk = start_pos + S
-        scratch = None
-        if S == 1 and h.dtype == torch.bfloat16:
-            scratch = self._buf("attn_scratch", (2 * ops.attention_scratch_floats(B, H, hd, a.max_seq_len + 64),), torch.float32)
         ldq = qkv.stride(0)
-        q8 = getattr(self, "_q8", None)
-        w8a8 = (q8 is not None and getattr(self, "_fp8_prefill", False) and rows > 16 and h.dtype == torch.bfloat16
-                and hd in (64, 128))
-        n4 = getattr(self, "_n4", None)
-        mx4 = getattr(self, "_mx4", None)
-        w4a8 = mx4 is not None and getattr(self, "_mx4_prefill", False) and not (S == 1 and rows <= 32)
+        path = self._layer_path(h, rows, S == 1)
+        # rotary embedding + cache write in the qkv GEMM epilogue (qkv never makes a second trip through HBM): not on the GEMV images
+        fuse = path != "gemv" and rows > 16 and h.dtype == torch.bfloat16 and hd in (64, 128) and self._fuse_qkv_rope
         # fp8 KV cache (quantize_kv_cache): k_caches / vt_caches then hold the ONE shared bf16 pair.  S > 1: the layer runs unchanged on
         # the pair (a continuation dequantises the layer's prefix into it first) and its new positions are quantised afterwards;
         # S == 1: the new position goes through the staging pair into the fp8 cache and the attention reads the fp8 cache.
@@ -479,8 +519,8 @@ class Transformer(nn.Module):
                 return ops.attention_decode_fp8kv(qkv, *fp8c, att, B, Sk, H, Hkv, hd, scratch)
             ops.attention(qkv, kc, vc, att, B, S, Sk, H, Hkv, hd, strides, causal and S > 1, scratch)
             ops.kv_quantize_fp8(kc, vc, start_pos, *fp8c, S, start_pos)
-        if w8a8:
-            if q8[0] != self._packed_version:
+        if path == "w8a8":
+            if self._weights.version != self._packed_version:
                 raise RuntimeError("parameters changed after quantize_decode_weights(): call it again (or with mode=None)")
             xq = self._buf("fp8_x", (rows, max(dim, H * hd)), torch.uint8)
             aq = self._buf("fp8_act", (rows, self.ffn), torch.uint8)
@@ -496,10 +536,10 @@ class Transformer(nn.Module):
                        Hkv * smax * hd, smax * hd, hd,         # k cache
                        Hkv * hd * smax, hd * smax, smax,       # v^T cache
                        S * H * hd, H * hd, hd)                 # out
-            if w8a8:
+            if path == "w8a8":
                 # W8A8 prefill (opt-in, BASELINE config 5): every decoder GEMM on fp8 operands -- activations quantised per
                 # token on the fly (the RMSNorm output never exists in bf16), weights per output row, MX-scaled MFMA
-                (wqkv_q, wqkv_s), (wo_q, wo_s), (w13_q, w13_s), (w2_q, w2_s) = q8[1][i]
+                (wqkv_q, wqkv_s), (wo_q, wo_s), (w13_q, w13_s), (w2_q, w2_s) = self._layer_operands(i, path)
                 ops.quantize_rows_fp8(h, xq[:, :dim], sx, lyr.attention_norm.weight, a.norm_eps)
                 ops.gemm_qkv_rope_fp8(xq[:, :dim], sx, wqkv_q, wqkv_s, qkv, kc, vc, cs, B, S, H, Hkv, hd, cpos, rope_pos0)
                 attend(i, kc, vc, strides)
@@ -510,190 +550,82 @@ class Transformer(nn.Module):
                 ops.quantize_rows_fp8(act, aq, sx)
                 ops.gemm_nt_fp8(aq, sx, w2_q, w2_s, h, residual=h)
                 continue
-            if w4a8:
-                # W4A8 (opt-in): every product on the image -- rows quantised to MXFP8 once per product (the two RMSNorm outputs never
-                # exist in bf16), both block scales in the scaled MFMA; qkv stored plainly, then the rope kernel as the GEMV path
-                self._mx4_gemm(h, mx4[f"wqkv.{i}"], qkv, lyr.attention_norm.weight)
-                ops.rope_kvcache(qkv, qkv, kc, vc, cs, B, S, H, Hkv, hd, cpos, rope_pos0)
-                attend(i, kc, vc, strides)
-                self._mx4_gemm(att, mx4[f"wo.{i}"], h, residual=h)
-                self._mx4_gemm(h, mx4[f"w13.{i}"], act, lyr.ffn_norm.weight, epilogue=ops.EPI_SWIGLU)
-                self._mx4_gemm(act, mx4[f"w2.{i}"], h, residual=h)
-                continue
-            if mx4 is not None:            # decode rows on the images; every multi-token forward on the layer's Wd (weight-only)
-                wqkv, wo, w13, w2 = (mx4[f"{k}.{i}"] for k in ("wqkv", "wo", "w13", "w2")) if S == 1 and rows <= 32 else self._mx4_dequant_layer(i)
-            elif n4 is None:
-                wqkv, wo, w13, w2 = pk[f"wqkv.{i}"], lyr.attention.wo.weight, pk[f"w13.{i}"], lyr.feed_forward.w2.weight
-            elif rows <= 16 and a.dim >= 512:   # NF4 decode GEMV on the images (its SwiGLU form needs K = dim >= 512: two K slices)
-                wqkv, wo, w13, w2 = (n4[f"{k}.{i}"] for k in ("wqkv", "wo", "w13", "w2"))
-            else:                          # multi-token: the layer's Wd in a reused bf16 scratch, then the bf16 GEMMs unchanged
-                wqkv, wo, w13, w2 = self._nf4_dequant_layer(i)
-            ops.rmsnorm(h, lyr.attention_norm.weight, xn, a.norm_eps)
-            if rows > 16 and h.dtype == torch.bfloat16 and hd in (64, 128) and self._fuse_qkv_rope and not isinstance(wqkv, Mx4Image):
-                # rotary embedding + cache write in the GEMM epilogue: qkv never makes a second trip through HBM
-                ops.gemm_qkv_rope(xn, wqkv, qkv, kc, vc, cs, B, S, H, Hkv, hd, cpos, rope_pos0)
-            else:
-                self._linear(xn, wqkv, qkv)
-                ops.rope_kvcache(qkv, qkv, kc, vc, cs, B, S, H, Hkv, hd, cpos, rope_pos0)
-            attend(i, kc, vc, strides)
-            self._linear(att, wo, h, residual=h)
-            ops.rmsnorm(h, lyr.ffn_norm.weight, xn, a.norm_eps)
-            self._linear(xn, w13, act, epilogue=ops.EPI_SWIGLU)
-            self._linear(act, w2, h, residual=h)
+            self._layer(i, path, h, (xn, qkv, att, act),
+                        lambda: ops.rope_kvcache(qkv, qkv, kc, vc, cs, B, S, H, Hkv, hd, cpos, rope_pos0),
+                        lambda: attend(i, kc, vc, strides),
+                        (lambda wqkv: ops.gemm_qkv_rope(xn, wqkv, qkv, kc, vc, cs, B, S, H, Hkv, hd, cpos, rope_pos0)) if fuse else None)
 
     def quantize_decode_weights(self, mode: str = "fp8", prefill: bool = False) -> None:
-        """Opt-in fp8 images of the four decoder matrices of every layer (BASELINE config 5; quantiser = a3v_quantize_rows_fp8).
-        The single-call decode step streams them weight-only (half the bytes, bf16 activations).  ``prefill=True`` also runs
-        the multi-token forward W8A8 (a3v_gemm_nt_fp8: activations quantised per token on the fly); otherwise prefill keeps
-        the bf16 weights.  ``mode=None`` drops the images.  Re-run after the weights change.
+        """Opt-in weight images for inference: ``"fp8"`` (per-row e4m3 images beside the bf16 weights; ``mode=None`` drops them; re-run
+        after the weights change), ``"nf4"`` (the reference's bitsandbytes Linear4bit mode, util/quant.py:95-163) or ``"mxfp4"`` (OCP
+        MXFP4).  The 4-bit formats also take the LM head and FREE every bf16 weight they quantise (as the reference's ``del
+        module.weight``): irreversible, and gone from ``state_dict()``.  What a format needs, frees and runs on is its row of
+        weight_formats.FORMATS; the path a product of a given shape takes is weight_formats.layer_path / head_path.  Quantise after
+        ``.to(device)``: the images are not module buffers and do not move with the model.
 
-        ``mode="nf4"``: the reference's 4-bit mode (bitsandbytes Linear4bit nf4, util/quant.py:95-163).  Every decoder linear
-        (wq wk wv wo w1 w2 w3) and the LM head ``output`` is quantised module by module by a3v_quantize_nf4 and its bf16
-        weight is FREED (as the reference's ``del module.weight``): irreversible, and gone from ``state_dict()``.  Decode
-        streams the NF4 images (a3v_gemm_skinny_nf4 / the fused step); the multi-token forward dequantises one layer at a time
-        into a reused bf16 scratch (a3v_dequantize_nf4) and runs the bf16 GEMMs on it.  Quantise after ``.to(device)``:
-        the images are not module buffers and do not move with the model.
-
-        ``mode="mxfp4"``: the chip's own 4-bit format (OCP MXFP4, include/a3vlm_hip.h "MXFP4 weights"): the NF4 flow with
-        a3v_quantize_mxfp4; decode rows (<= 32) run a3v_gemm_skinny_mxfp4 kernel by kernel (MXFP8 activations inside the GEMV),
-        every multi-token forward dequantises one layer (a3v_dequantize_mxfp4) and is weight-only.  Needs a bf16 model on the GPU
-        and dim, ffn, n_heads*head_dim multiples of 128, vocab_size % 16 == 0.  Decode batches above 32 rows have no GEMV form (as
-        for bf16 / fp8) and by default take the multi-token path: every generated token then dequantises every layer again
-        (~400 MB written per layer at 7B), far slower than decoding the same batch in bf16.  ``prefill=True`` (opt-in, DESIGN.md
-        7e "W4A8 GEMM") runs every product that is not such a GEMV -- every multi-token forward, decode and ragged steps of more
-        than 32 rows, and their LM head -- W4A8 on the images instead: a3v_quantize_rows_mxfp8 once per product (the two norm'd
-        inputs through its RMSNorm prologue), then a3v_gemm_nt_mxfp4; the dequantisation scratch is never allocated and logits
-        are no longer those of the bf16 model on Wd.  Decode steps of at most 32 rows keep the GEMV either way.  Measured at 7B:
-        the 64-row decode step 1.4x faster, products of 128 rows and more slower (a 1100-token prefill 3.8x): hence opt-in."""
-        if getattr(self, "_n4", None) is not None:
-            raise RuntimeError("this model holds NF4 weights: quantize_decode_weights('nf4') freed its bf16 decoder weights and "
-                               "cannot be undone or combined with another mode; reload the checkpoint instead")
-        if getattr(self, "_mx4", None) is not None:
-            raise RuntimeError("this model holds MXFP4 weights: quantize_decode_weights('mxfp4') freed its bf16 decoder weights and "
-                               "cannot be undone or combined with another mode; reload the checkpoint instead")
-        if mode == "nf4":
-            self._quantize_nf4()
+        ``prefill=True``, fp8: the multi-token forward W8A8 (a3v_gemm_nt_fp8) instead of on the bf16 weights.  MXFP4 (DESIGN.md 7e
+        "W4A8 GEMM"): every product that is not a GEMV of at most 32 decode rows W4A8 on the images, instead of dequantising every
+        layer for it (~400 MB written per layer at 7B, for every token of a decode batch above 32 rows); logits are then no longer
+        those of the bf16 model on Wd.  Measured at 7B: the 64-row decode step 1.4x faster, products of 128 rows and more slower (a
+        1100-token prefill 3.8x): hence opt-in."""
+        held = FORMATS[self.weight_format]
+        if held.frees_weights:
+            raise RuntimeError(f"this model holds {held.name} weights: quantize_decode_weights('{self.weight_format}') freed its bf16 decoder "
+                               "weights and cannot be undone or combined with another mode; reload the checkpoint instead")
+        if mode in ("nf4", "mxfp4"):
+            self._quantize_4bit(mode, bool(prefill) and mode == "mxfp4")     # (NF4 has no prefill form)
             return
-        if mode == "mxfp4":
-            self._quantize_mx4()
-            self._mx4_prefill = bool(prefill)
-            return
-        self._q8 = None
-        self._fp8_prefill = bool(prefill) and mode is not None
-        self._layer_tab_key = None
+        self._weights, self._layer_tab_key = None, None
         if mode is None:
             return
         if mode != "fp8":
             raise ValueError("only weight-only 'fp8' (OCP e4m3fn) is implemented")
-        a = self.args
-        if a.dim % 256 or self.ffn % 256 or (self.n_heads * self.head_dim) % 256 or self._dtype != torch.bfloat16:
-            raise ValueError("fp8 decode weights need bf16 parameters and dim, ffn, n_heads*head_dim multiples of 256")
-        pk = self._pack(check=True)
-        q8 = []
-
-        def quant(w):                      # per-row e4m3 image + fp32 scales by the HIP quantiser (a3v_quantize_rows_fp8)
-            q = torch.empty(w.shape, dtype=torch.uint8, device=w.device)
-            sc = torch.empty(w.shape[0], dtype=torch.float32, device=w.device)
-            ops.quantize_rows_fp8(w, q, sc)
-            return q, sc
+        f = FORMATS["fp8"]
+        f.check(self)
+        self._pack(check=True)
+        images: Dict[str, WeightImage] = {}
         with torch.no_grad():
-            for i, lyr in enumerate(self.layers):
-                q8.append(tuple(quant(w) for w in (pk[f"wqkv.{i}"], lyr.attention.wo.weight, pk[f"w13.{i}"],
-                                                   lyr.feed_forward.w2.weight)))
-        self._q8 = (self._packed_version, q8)
+            for i in range(self.n_layers):
+                for key, w in zip(LAYER_KEYS, self._layer_operands(i, "bf16")):
+                    images[f"{key}.{i}"] = WeightImage(*f.quantize(w, None))
+        self._weights = DecodeWeights("fp8", bool(prefill), images, self._packed_version)
 
-    def _quantize_nf4(self) -> None:
-        a = self.args
-        H, Hkv, hd = self.n_heads, self.n_kv_heads, self.head_dim
-        if self._dtype != torch.bfloat16 or self._device.type != "cuda":
-            raise ValueError("NF4 weights need a bf16 model on the GPU (quantise after .to(device))")
-        if a.dim % 256 or self.ffn % 256 or (H * hd) % 256 or a.vocab_size % 4 or a.vocab_size > 65536 or 2 * self.ffn > 65536:
-            # the NF4 GEMV (LDS-DMA form only) takes N <= 65536 rows: the LM head and the packed w1|w3 image
-            raise ValueError("NF4 weights need dim, ffn, n_heads*head_dim multiples of 256, vocab_size % 4 == 0 and vocab_size, 2*ffn <= 65536")
-        self._q8, self._fp8_prefill, self._layer_tab_key = None, False, None
-        n4: Dict[str, tuple] = {}
-        ws = torch.empty((int(_lib.load().a3v_quantize_nf4_ws_bytes(max(a.vocab_size, self.ffn * 2), max(a.dim, self.ffn))) + 3) // 4,
-                         dtype=torch.float32, device=self._device)
+    def _quantize_4bit(self, fmt: str, prefill: bool) -> None:
+        """Every decoder linear and the LM head as ``fmt`` images, one original module at a time, its bf16 weight dropped at once."""
+        a, f = self.args, FORMATS[fmt]
+        f.check(self)
+        self._weights, self._layer_tab_key = None, None
+        ws = None if f.quantize_ws_bytes is None else torch.empty(
+            (f.quantize_ws_bytes(max(a.vocab_size, self.ffn * 2), max(a.dim, self.ffn)) + 3) // 4, dtype=torch.float32, device=self._device)
 
-        def quant(mod):                    # one original module -> (nibbles, scales); its bf16 weight is dropped
-            q, sc, _ = ops.quantize_nf4(mod.weight.data.contiguous(), ws=ws)
+        def quant(mod):
+            img = WeightImage(*f.quantize(mod.weight.data.contiguous(), ws))
             del mod.weight
-            return q, sc
+            return img
 
         def rows16(x, y):                  # w1 / w3 interleaved in 16-row blocks (the SwiGLU GEMV row order, as _pack)
             nb = x.shape[0] // 16
             return torch.stack([x.view(nb, 16, -1), y.view(nb, 16, -1)], dim=1).reshape(2 * x.shape[0], -1).contiguous()
+        images: Dict[str, WeightImage] = {}
         with torch.no_grad():
             for i, lyr in enumerate(self.layers):
-                at, f = lyr.attention, lyr.feed_forward
-                (qq, sq), (qk, sk), (qv, sv) = quant(at.wq), quant(at.wk), quant(at.wv)
-                n4[f"wqkv.{i}"] = (torch.cat([qq, qk, qv]), torch.cat([sq, sk, sv]))
-                n4[f"wo.{i}"] = quant(at.wo)
-                (q1, s1), (q3, s3) = quant(f.w1), quant(f.w3)
-                n4[f"w13.{i}"] = (rows16(q1, q3), rows16(s1, s3))
-                n4[f"w2.{i}"] = quant(f.w2)
-                del qq, qk, qv, sq, sk, sv, q1, q3, s1, s3
+                at, ff = lyr.attention, lyr.feed_forward
+                wq, wk, wv = quant(at.wq), quant(at.wk), quant(at.wv)
+                images[f"wqkv.{i}"] = WeightImage(torch.cat([wq.q, wk.q, wv.q]), torch.cat([wq.s, wk.s, wv.s]))
+                images[f"wo.{i}"] = quant(at.wo)
+                w1, w3 = quant(ff.w1), quant(ff.w3)
+                images[f"w13.{i}"] = WeightImage(rows16(w1.q, w3.q), rows16(w1.s, w3.s))
+                images[f"w2.{i}"] = quant(ff.w2)
+                del wq, wk, wv, w1, w3
                 self._packed.pop(f"wqkv.{i}", None)
                 self._packed.pop(f"w13.{i}", None)
-            n4["output"] = quant(self.output)
-        self._n4 = n4
+            images["output"] = quant(self.output)
+        self._weights = DecodeWeights(fmt, prefill, images)
         self._packed_version = None
         self._ws.pop("nf4_scratch", None)
 
-    def _quantize_mx4(self) -> None:
-        a = self.args
-        H, Hkv, hd = self.n_heads, self.n_kv_heads, self.head_dim
-        if self._dtype != torch.bfloat16:
-            raise ValueError(f"MXFP4 weights need a bf16 model, this one is {self._dtype} (fp32 models are refused)")
-        if self._device.type != "cuda":
-            raise ValueError("MXFP4 weights need the model on the GPU (quantise after .to(device))")
-        if a.dim % 128 or self.ffn % 128 or (H * hd) % 128:
-            raise ValueError(f"MXFP4 weights need dim, ffn and n_heads*head_dim multiples of 128 (got {a.dim}, {self.ffn}, {H * hd})")
-        if a.vocab_size % 16 or (Hkv * hd) % 16 or a.vocab_size > 65536 or 2 * self.ffn > 65536 or max(a.dim, self.ffn) > 16384:
-            raise ValueError("MXFP4 weights need vocab_size and n_kv_heads*head_dim multiples of 16, vocab_size, 2*ffn <= 65536 and dim, ffn <= 16384")
-        self._q8, self._fp8_prefill, self._layer_tab_key = None, False, None
-        mx: Dict[str, Mx4Image] = {}
-
-        def quant(mod):                    # one original module -> (codes, scales); its bf16 weight is dropped
-            q, sc = ops.quantize_mxfp4(mod.weight.data.contiguous())
-            del mod.weight
-            return q, sc
-
-        def rows16(x, y):                  # w1 / w3 interleaved in 16-row blocks (the SwiGLU GEMV row order, as _pack)
-            nb = x.shape[0] // 16
-            return torch.stack([x.view(nb, 16, -1), y.view(nb, 16, -1)], dim=1).reshape(2 * x.shape[0], -1).contiguous()
-        with torch.no_grad():
-            for i, lyr in enumerate(self.layers):
-                at, f = lyr.attention, lyr.feed_forward
-                (qq, sq), (qk, sk), (qv, sv) = quant(at.wq), quant(at.wk), quant(at.wv)
-                mx[f"wqkv.{i}"] = Mx4Image(torch.cat([qq, qk, qv]), torch.cat([sq, sk, sv]))
-                mx[f"wo.{i}"] = Mx4Image(*quant(at.wo))
-                (q1, s1), (q3, s3) = quant(f.w1), quant(f.w3)
-                mx[f"w13.{i}"] = Mx4Image(rows16(q1, q3), rows16(s1, s3))
-                mx[f"w2.{i}"] = Mx4Image(*quant(f.w2))
-                del qq, qk, qv, sq, sk, sv, q1, q3, s1, s3
-                self._packed.pop(f"wqkv.{i}", None)
-                self._packed.pop(f"w13.{i}", None)
-            mx["output"] = Mx4Image(*quant(self.output))
-        self._mx4 = mx
-        self._packed_version = None
-        self._ws.pop("nf4_scratch", None)
-
-    def _mx4_dequant_layer(self, i: int):
-        """Wd of layer i's four (packed) matrices in the reused scratch: views (wqkv, wo, w13, w2)."""
-        a = self.args
-        shapes = (((self.n_heads + 2 * self.n_kv_heads) * self.head_dim, a.dim), (a.dim, self.n_heads * self.head_dim),
-                  (2 * self.ffn, a.dim), (a.dim, self.ffn))
-        buf = self._nf4_scratch(sum(n * k for n, k in shapes))
-        out, o = [], 0
-        for key, (n, k) in zip(("wqkv", "wo", "w13", "w2"), shapes):
-            w = buf[o:o + n * k].view(n, k)
-            ops.dequantize_mxfp4(*self._mx4[f"{key}.{i}"], w)
-            out.append(w)
-            o += n * k
-        return out
-
-    def _nf4_scratch(self, n: int) -> torch.Tensor:
+    def _dequant_scratch(self, n: int) -> torch.Tensor:
+        """The one bf16 scratch a 4-bit model dequantises into: a whole layer or the LM head, whichever is larger."""
         buf = self._ws.get("nf4_scratch")
         if buf is None or buf.numel() < n:
             self._ws.pop("nf4_scratch", None)
@@ -704,91 +636,82 @@ class Transformer(nn.Module):
             self._ws["nf4_scratch"] = buf
         return buf
 
-    def _nf4_dequant_layer(self, i: int):
+    def _dequant_layer(self, i: int):
         """Wd of layer i's four (packed) matrices in the reused scratch: views (wqkv, wo, w13, w2)."""
-        a = self.args
+        a, w = self.args, self._weights
         shapes = (((self.n_heads + 2 * self.n_kv_heads) * self.head_dim, a.dim), (a.dim, self.n_heads * self.head_dim),
                   (2 * self.ffn, a.dim), (a.dim, self.ffn))
-        buf = self._nf4_scratch(sum(n * k for n, k in shapes))
+        buf = self._dequant_scratch(sum(n * k for n, k in shapes))
         out, o = [], 0
-        for key, (n, k) in zip(("wqkv", "wo", "w13", "w2"), shapes):
-            w = buf[o:o + n * k].view(n, k)
-            ops.dequantize_nf4(*self._n4[f"{key}.{i}"], w)
-            out.append(w)
+        for key, (n, k) in zip(LAYER_KEYS, shapes):
+            wd = buf[o:o + n * k].view(n, k)
+            FORMATS[w.fmt].dequantize(*w.images[f"{key}.{i}"], wd)
+            out.append(wd)
             o += n * k
         return out
 
-    def _nf4_output_weight(self) -> torch.Tensor:
-        a = self.args
-        w = self._nf4_scratch(a.vocab_size * a.dim)[:a.vocab_size * a.dim].view(a.vocab_size, a.dim)
-        return ops.dequantize_nf4(*self._n4["output"], w)
-
     def _head_weight(self) -> torch.Tensor:
-        """The LM head as a bf16 GEMM operand (an NF4 model: dequantised into the reused scratch)."""
-        mx4 = getattr(self, "_mx4", None)
-        if mx4 is not None:
-            a = self.args
-            return ops.dequantize_mxfp4(*mx4["output"], self._nf4_scratch(a.vocab_size * a.dim)[:a.vocab_size * a.dim].view(a.vocab_size, a.dim))
-        return self.output.weight if getattr(self, "_n4", None) is None else self._nf4_output_weight()
+        """The LM head as a bf16 GEMM operand (a 4-bit model: dequantised into the reused scratch)."""
+        w, a = self._weights, self.args
+        if not FORMATS[self.weight_format].frees_weights:
+            return self.output.weight
+        wd = self._dequant_scratch(a.vocab_size * a.dim)[:a.vocab_size * a.dim].view(a.vocab_size, a.dim)
+        return FORMATS[w.fmt].dequantize(*w.images["output"], wd)
 
     def _lm_head_last(self, xn: torch.Tensor, logits: torch.Tensor, decode: bool) -> None:
-        """_lm_head_f32 for the last rows of a forward.  An MXFP4 model runs its GEMV (MXFP8 activations) where its decoder layers do,
-        on decode steps of at most 32 rows (``decode``): after a multi-token forward, or a decode step of more rows, the rows take
-        the dequantised head, so such a forward is weight-only from end to end."""
-        if getattr(self, "_mx4", None) is not None and not decode:
-            if getattr(self, "_mx4_prefill", False):       # W4A8: the head on its image too, no dequantisation scratch
-                self._mx4_gemm(xn, self._mx4["output"], logits, epilogue=ops.EPI_OUT_F32)
-                return
+        """fp32 logits of the last rows of a forward, on weight_formats.head_path (``decode``: a decode step of at most 32 rows)."""
+        w = self._weights
+        path = head_path(self.weight_format, w is not None and w.prefill, decode, self._dtype == torch.float32)
+        if path == "gemm_nt":
+            ops.gemm_nt(xn, self.output.weight, logits)
+        elif path == "w4a8":               # the head on its image too, no dequantisation scratch
+            self._mx4_gemm(xn, w.images["output"], logits, epilogue=ops.EPI_OUT_F32)
+        elif path == "dequant":
             self._linear(xn, self._head_weight(), logits, epilogue=ops.EPI_OUT_F32)
         else:
             self._lm_head_f32(xn, logits)
 
     def _lm_head_f32(self, xn: torch.Tensor, logits: torch.Tensor) -> None:
         """fp32 logits of bf16 rows xn: the NF4 / MXFP4 GEMV in chunks of 16 rows on such a model, the bf16 path otherwise."""
-        n4 = getattr(self, "_n4", None) or getattr(self, "_mx4", None)
-        if n4 is None:
+        f = FORMATS[self.weight_format]
+        if not f.frees_weights:
             self._linear(xn, self.output.weight, logits, epilogue=ops.EPI_OUT_F32)
             return
-        for r0 in range(0, xn.shape[0], 16):
-            self._linear(xn[r0:r0 + 16], n4["output"], logits[r0:r0 + 16], epilogue=ops.EPI_OUT_F32)
+        for r0 in range(0, xn.shape[0], f.gemv_rows):
+            self._linear(xn[r0:r0 + f.gemv_rows], self._weights.images["output"], logits[r0:r0 + f.gemv_rows], epilogue=ops.EPI_OUT_F32)
+
+
+    def _step_format_code(self) -> Optional[int]:
+        """The weight-format argument of the C step entries (a3v_llama_decode_step_form); None: this format has no C step."""
+        return FORMATS[self.weight_format].step_code
 
     def _llama_layer_table(self):
         """The a3v_llama_layer table of the C step entries (and the a3v_kv8_layer table of an fp8 KV cache), rebuilt when weights,
         caches or weight images change."""
-        from ... import lib as _l
-        pk = self._pack()
-        q8 = getattr(self, "_q8", None)
-        if q8 is not None and q8[0] != self._packed_version:
+        self._pack()
+        w, fmt = self._weights, FORMATS[self.weight_format]
+        if w is not None and w.version is not None and w.version != self._packed_version:
             raise RuntimeError("parameters changed after quantize_decode_weights(): call it again (or with mode=None)")
-        n4 = getattr(self, "_n4", None)
         kv8 = self._kv8
-        key = (self._packed_version, self._cache_shape, q8 is not None, n4 is not None)
-        if getattr(self, "_layer_tab_key", None) != key:
-            tab = (_l.LlamaLayer * self.n_layers)()
+        key = (self._packed_version, self._cache_shape, self.weight_format)
+        if self._layer_tab_key != key:
+            tab = (_lib.LlamaLayer * self.n_layers)()
             self._kv8_tab = None
             if kv8 is not None:            # fp8 KV cache: the k_cache / vt_cache fields below (the shared bf16 pair) are not read by the step
-                self._kv8_tab = (_l.Kv8Layer * self.n_layers)()
+                self._kv8_tab = (_lib.Kv8Layer * self.n_layers)()
                 for i in range(self.n_layers):
                     for f in ("k_q", "vt_q", "k_scale", "v_scale"):
                         setattr(self._kv8_tab[i], f, kv8[f][i].data_ptr())
             for i, lyr in enumerate(self.layers):
-                if n4 is not None:         # NF4 images only: the bf16 fields stay NULL
-                    (tab[i].wqkv_n4, tab[i].wqkv_n4s), (tab[i].wo_n4, tab[i].wo_n4s), (tab[i].w13_n4, tab[i].w13_n4s), (tab[i].w2_n4, tab[i].w2_n4s) = \
-                        [(q.data_ptr(), sc.data_ptr()) for q, sc in (n4[f"{k}.{i}"] for k in ("wqkv", "wo", "w13", "w2"))]
-                    tab[i].attn_norm_w = lyr.attention_norm.weight.data_ptr()
-                    tab[i].ffn_norm_w = lyr.ffn_norm.weight.data_ptr()
-                    tab[i].k_cache = self._k_cache[i].data_ptr()
-                    tab[i].vt_cache = self._vt_cache[i].data_ptr()
-                    continue
-                if q8 is not None:
-                    (tab[i].wqkv_q, tab[i].wqkv_s), (tab[i].wo_q, tab[i].wo_s), (tab[i].w13_q, tab[i].w13_s), (tab[i].w2_q, tab[i].w2_s) = \
-                        [(q.data_ptr(), sc.data_ptr()) for q, sc in q8[1][i]]
+                if fmt.step_fields is not None:        # the images: <key>_q / <key>_s (fp8) or <key>_n4 / <key>_n4s
+                    for k in LAYER_KEYS:
+                        img = w.images[f"{k}.{i}"]
+                        setattr(tab[i], k + fmt.step_fields[0], img.q.data_ptr())
+                        setattr(tab[i], k + fmt.step_fields[1], img.s.data_ptr())
+                if not fmt.frees_weights:              # (NF4 images only: the bf16 fields stay NULL)
+                    tab[i].wqkv, tab[i].wo, tab[i].w13, tab[i].w2 = (t.data_ptr() for t in self._layer_operands(i, "bf16"))
                 tab[i].attn_norm_w = lyr.attention_norm.weight.data_ptr()
-                tab[i].wqkv = pk[f"wqkv.{i}"].data_ptr()
-                tab[i].wo = lyr.attention.wo.weight.data_ptr()
                 tab[i].ffn_norm_w = lyr.ffn_norm.weight.data_ptr()
-                tab[i].w13 = pk[f"w13.{i}"].data_ptr()
-                tab[i].w2 = lyr.feed_forward.w2.weight.data_ptr()
                 tab[i].k_cache = self._k_cache[i].data_ptr()
                 tab[i].vt_cache = self._vt_cache[i].data_ptr()
             self._layer_tab, self._layer_tab_key = tab, key
@@ -798,20 +721,16 @@ class Transformer(nn.Module):
         """xn, qkv, att, act, attention scratch and GEMV workspace of a C step call at B rows."""
         a = self.args
         H, Hkv, hd = self.n_heads, self.n_kv_heads, self.head_dim
-        xn = self._buf("xn", (B, a.dim))
-        qkv = self._buf("qkv", (B, (H + 2 * Hkv) * hd))
-        att = self._buf("att", (B, H * hd))
-        act = self._buf("act", (B, self.ffn))
-        scratch = self._buf("attn_scratch", (2 * ops.attention_scratch_floats(B, H, hd, a.max_seq_len + 64),), torch.float32)
+        xn, qkv, att, act, scratch = self._row_buffers(B, True)
         Bc = B if B <= 16 else (B + 1) // 2          # 17..32 rows run as two row chunks inside the C call
         sws = self._skinny_ws(Bc, max((H + 2 * Hkv) * hd, 2 * self.ffn, a.dim), max(a.dim, self.ffn))
         for (n_, k_) in (((H + 2 * Hkv) * hd, a.dim), (a.dim, H * hd), (2 * self.ffn, a.dim), (a.dim, self.ffn)):
             sws = self._skinny_ws(Bc, n_, k_)
         return xn, qkv, att, act, scratch, sws
 
+
     def _decode_step(self, h: torch.Tensor, B: int, pos: int) -> None:
         """seqlen == 1, bf16: the whole layer stack from one C call (a3v_llama_decode_step)."""
-        from ... import lib as _l
         a = self.args
         self._llama_layer_table()
         kv8 = self._kv8
@@ -819,18 +738,18 @@ class Transformer(nn.Module):
         smax = self._k_cache[0].shape[2]
         xn, qkv, att, act, scratch, sws = self._decode_step_buffers(B)
         if kv8 is not None:
-            rc = _l.load().a3v_llama_decode_step_kv8(self._layer_tab, self._kv8_tab, self.n_layers, h.data_ptr(), xn.data_ptr(), qkv.data_ptr(),
+            rc = _lib.load().a3v_llama_decode_step_kv8(self._layer_tab, self._kv8_tab, self.n_layers, h.data_ptr(), xn.data_ptr(), qkv.data_ptr(),
                                                      att.data_ptr(), act.data_ptr(), scratch.data_ptr(), sws.data_ptr(),
                                                      self._cos_sin_dev().data_ptr(), kv8["stage_k"].data_ptr(), kv8["stage_vt"].data_ptr(),
                                                      B, a.dim, H, Hkv, hd, self.ffn, smax, pos, a.norm_eps,
                                                      torch.cuda.current_stream().cuda_stream)
-            _l.check(rc, "a3v_llama_decode_step_kv8")
+            _lib.check(rc, "a3v_llama_decode_step_kv8")
             return
-        rc = _l.load().a3v_llama_decode_step(self._layer_tab, self.n_layers, h.data_ptr(), xn.data_ptr(), qkv.data_ptr(),
+        rc = _lib.load().a3v_llama_decode_step(self._layer_tab, self.n_layers, h.data_ptr(), xn.data_ptr(), qkv.data_ptr(),
                                              att.data_ptr(), act.data_ptr(), scratch.data_ptr(), sws.data_ptr(), self._cos_sin_dev().data_ptr(),
                                              B, a.dim, H, Hkv, hd, self.ffn, smax, pos, a.norm_eps,
                                              torch.cuda.current_stream().cuda_stream)
-        _l.check(rc, "a3v_llama_decode_step")
+        _lib.check(rc, "a3v_llama_decode_step")
 
     # ------------------------------------------------------------------ vision
     def _vit_geometry(self):
@@ -1018,13 +937,10 @@ class Transformer(nn.Module):
         o0 = W if out_from is None else out_from       # h[:, image_words:] (llama_ens5.py:486)
         out = torch.empty(B, S - o0, a.vocab_size, dtype=self._dtype, device=self._device)
         xv = xn.view(B, S, a.dim)
-        if getattr(self, "_mx4", None) is not None and getattr(self, "_mx4_prefill", False):
-            for b in range(B):             # W4A8: the head on its image (bf16 logits: the NONE epilogue)
-                self._mx4_gemm(xv[b, o0:], self._mx4["output"], out[b])
-            return out
-        wout = self._head_weight()
+        w4a8 = self.weight_format == "mxfp4" and self._weights.prefill     # the head on its image (bf16 logits: the NONE epilogue)
+        wout = self._weights.images["output"] if w4a8 else self._head_weight()
         for b in range(B):
-            ops.gemm_nt(xv[b, o0:], wout, out[b])
+            (self._mx4_gemm if w4a8 else ops.gemm_nt)(xv[b, o0:], wout, out[b])
         return out
 
     # ------------------------------------------------------------------ forward_inference (KV cached)
@@ -1061,14 +977,14 @@ class Transformer(nn.Module):
         ops.embed_assemble(tokens.contiguous(), self.tok_embeddings.weight, h, B, T, W, a.dim)
         if image is not None:
             self.encode_image_into(h, image, B, S, qformer_feats, extra_feats, slots)
+        w8 = self._step_format_code()
         if (S == 1 and (B <= 16 or (B <= 32 and a.dim % 128 == 0 and self.ffn % 128 == 0)) and self._dtype == torch.bfloat16
                 and self.head_dim in (64, 128) and a.dim % 32 == 0 and self.ffn % 32 == 0
-                and getattr(self, "_mx4", None) is None                  # MXFP4 images: the kernel-by-kernel form only
+                and w8 is not None                                       # MXFP4 images: the kernel-by-kernel form only
                 and not getattr(self, "_per_kernel_decode", False)):     # test hook: run the step kernel by kernel
             # the C entry says up front which form it takes (a3v_llama_decode_step_form): 17..32 rows need the fused GEMV forms (two row
             # chunks); a geometry they do not take goes through the general kernels -- decided BEFORE h or the KV cache are touched, an
             # error from inside the step is never papered over
-            w8 = 2 if getattr(self, "_n4", None) is not None else 1 if getattr(self, "_q8", None) is not None else 0
             form = _lib.load().a3v_llama_decode_step_form(B, a.dim, a.n_heads, self.n_kv_heads, self.head_dim, self.ffn, w8)
             # (an fp8 KV cache has the fused form only: elsewhere the per-kernel sequence of _decoder_layers)
             if form == 2 or (self._kv8 is None and (form or (B <= 16 and w8 != 2))):
@@ -1081,10 +997,7 @@ class Transformer(nn.Module):
         xn = self._buf("xn_last", (B, a.dim))
         ops.rmsnorm(last, self.norm.weight, xn, a.norm_eps)
         logits = self._buf("logits", (B, a.vocab_size), torch.float32)
-        if self._dtype == torch.float32:
-            ops.gemm_nt(xn, self.output.weight, logits)
-        else:
-            self._lm_head_last(xn, logits, S == 1 and B <= 32)     # (an MXFP4 model: the head as the layers, GEMV up to 32 rows)
+        self._lm_head_last(xn, logits, S == 1 and B <= 32)     # (an MXFP4 model: the head as the layers, GEMV up to 32 rows)
         # the reference returns a fresh tensor (output(h[:, -1, :]).float(), llama_ens5.py:530-531); `logits` is a cached workspace
         # that the next call overwrites, so hand out a copy (B x V fp32 = 1 MB at bs 8: microseconds next to a 4 ms step)
         return logits.clone()
@@ -1131,74 +1044,44 @@ class Transformer(nn.Module):
         xn = self._buf("xn_last", (1, a.dim))
         ops.rmsnorm(h[S - 1:S], self.norm.weight, xn, a.norm_eps)
         logits = torch.empty(1, a.vocab_size, dtype=torch.float32, device=self._device)
-        if self._dtype == torch.float32:
-            ops.gemm_nt(xn, self.output.weight, logits)
-        else:
-            self._lm_head_last(xn, logits, False)
+        self._lm_head_last(xn, logits, False)
         return logits
 
     def _decode_step_rows(self, h: torch.Tensor, B: int, pos: torch.Tensor, pos_max: int) -> None:
         """One bf16 decode step with row b at cache position pos[b] from one C call (a3v_llama_decode_step_rows)."""
-        from ... import lib as _l
         a = self.args
         tab = self._llama_layer_table()
         H, Hkv, hd = self.n_heads, self.n_kv_heads, self.head_dim
         xn, qkv, att, act, scratch, sws = self._decode_step_buffers(B)
-        rc = _l.load().a3v_llama_decode_step_rows(tab, self.n_layers, h.data_ptr(), xn.data_ptr(), qkv.data_ptr(), att.data_ptr(),
+        rc = _lib.load().a3v_llama_decode_step_rows(tab, self.n_layers, h.data_ptr(), xn.data_ptr(), qkv.data_ptr(), att.data_ptr(),
                                                   act.data_ptr(), scratch.data_ptr(), sws.data_ptr(), self._cos_sin_dev().data_ptr(),
                                                   pos.data_ptr(), pos_max, B, a.dim, H, Hkv, hd, self.ffn, self._k_cache[0].shape[2],
                                                   a.norm_eps, torch.cuda.current_stream().cuda_stream)
-        _l.check(rc, "a3v_llama_decode_step_rows")
+        _lib.check(rc, "a3v_llama_decode_step_rows")
 
     def _decoder_layers_rows(self, h: torch.Tensor, B: int, pos: torch.Tensor, pos_max: int) -> None:
         """The ragged step kernel by kernel: _decoder_layers at S = 1 with a3v_rope_kvcache_rows / a3v_attention_decode_rows."""
         a = self.args
-        H, Hkv, hd, dim = self.n_heads, self.n_kv_heads, self.head_dim, a.dim
-        pk = self._pack()
+        H, Hkv, hd = self.n_heads, self.n_kv_heads, self.head_dim
+        self._pack()
         cs = self._cos_sin_dev()
-        xn = self._buf("xn", (B, dim))
-        qkv = self._buf("qkv", (B, (H + 2 * Hkv) * hd))
-        att = self._buf("att", (B, H * hd))
-        act = self._buf("act", (B, self.ffn))
-        scratch = counters = None
-        if h.dtype == torch.bfloat16 and hd in (64, 128):
-            scratch = self._buf("attn_scratch", (2 * ops.attention_scratch_floats(B, H, hd, a.max_seq_len + 64),), torch.float32)
+        xn, qkv, att, act, scratch = self._row_buffers(B, h.dtype == torch.bfloat16 and hd in (64, 128))
+        counters = None
+        if scratch is not None:
             counters = self._ws.get("rows_counters")
             if counters is None or counters.numel() < B * H:
                 counters = self._ws["rows_counters"] = torch.zeros(B * H, dtype=torch.int32, device=self._device)
         sk = self._buf("rows_sk", (B,), torch.int32)
         torch.add(pos, 1, out=sk)                      # keys of row b (idle rows: <= 0)
         ldq = qkv.stride(0)
-        n4 = getattr(self, "_n4", None)
-        mx4 = getattr(self, "_mx4", None)
-        for i, lyr in enumerate(self.layers):
+        path = self._layer_path(h, B, True, ragged=True)
+        for i in range(self.n_layers):
             kc, vc = self._k_cache[i], self._vt_cache[i]
             smax = kc.shape[2]
             strides = (ldq, ldq, hd, Hkv * smax * hd, smax * hd, hd, Hkv * hd * smax, hd * smax, smax, H * hd, H * hd, hd)
-            if mx4 is not None and B > 32 and getattr(self, "_mx4_prefill", False):      # W4A8 on the images, as _decoder_layers
-                self._mx4_gemm(h, mx4[f"wqkv.{i}"], qkv, lyr.attention_norm.weight)
-                ops.rope_kvcache_rows(qkv, qkv, kc, vc, cs, pos, B, H, Hkv, hd)
-                ops.attention_decode_rows(qkv, kc, vc, att, sk, pos_max + 1, B, H, Hkv, hd, strides, scratch, counters)
-                self._mx4_gemm(att, mx4[f"wo.{i}"], h, residual=h)
-                self._mx4_gemm(h, mx4[f"w13.{i}"], act, lyr.ffn_norm.weight, epilogue=ops.EPI_SWIGLU)
-                self._mx4_gemm(act, mx4[f"w2.{i}"], h, residual=h)
-                continue
-            if mx4 is not None:
-                wqkv, wo, w13, w2 = (mx4[f"{k}.{i}"] for k in ("wqkv", "wo", "w13", "w2")) if B <= 32 else self._mx4_dequant_layer(i)
-            elif n4 is None:
-                wqkv, wo, w13, w2 = pk[f"wqkv.{i}"], lyr.attention.wo.weight, pk[f"w13.{i}"], lyr.feed_forward.w2.weight
-            elif B <= 16 and a.dim >= 512:
-                wqkv, wo, w13, w2 = (n4[f"{k}.{i}"] for k in ("wqkv", "wo", "w13", "w2"))
-            else:
-                wqkv, wo, w13, w2 = self._nf4_dequant_layer(i)
-            ops.rmsnorm(h, lyr.attention_norm.weight, xn, a.norm_eps)
-            self._linear(xn, wqkv, qkv)
-            ops.rope_kvcache_rows(qkv, qkv, kc, vc, cs, pos, B, H, Hkv, hd)
-            ops.attention_decode_rows(qkv, kc, vc, att, sk, pos_max + 1, B, H, Hkv, hd, strides, scratch, counters)
-            self._linear(att, wo, h, residual=h)
-            ops.rmsnorm(h, lyr.ffn_norm.weight, xn, a.norm_eps)
-            self._linear(xn, w13, act, epilogue=ops.EPI_SWIGLU)
-            self._linear(act, w2, h, residual=h)
+            self._layer(i, path, h, (xn, qkv, att, act),
+                        lambda: ops.rope_kvcache_rows(qkv, qkv, kc, vc, cs, pos, B, H, Hkv, hd),
+                        lambda: ops.attention_decode_rows(qkv, kc, vc, att, sk, pos_max + 1, B, H, Hkv, hd, strides, scratch, counters))
 
     @torch.no_grad()
     def forward_inference_rows(self, next_tok: torch.Tensor, pos: torch.Tensor, pos_max: int,
@@ -1215,8 +1098,8 @@ class Transformer(nn.Module):
         assert 0 <= pos_max < min(self._k_cache[0].shape[2], self._cos_sin_cpu.shape[0]), pos_max
         h = self._buf("h", (B, a.dim))
         ops.embed_assemble(next_tok.view(B, 1).contiguous(), self.tok_embeddings.weight, h, B, 1, 0, a.dim)
-        w8 = 2 if getattr(self, "_n4", None) is not None else 1 if getattr(self, "_q8", None) is not None else 0
-        fused = (self._dtype == torch.bfloat16 and not getattr(self, "_per_kernel_decode", False) and getattr(self, "_mx4", None) is None
+        w8 = self._step_format_code()
+        fused = (self._dtype == torch.bfloat16 and not getattr(self, "_per_kernel_decode", False) and w8 is not None
                  and _lib.load().a3v_llama_decode_step_rows_form(B, a.dim, a.n_heads, self.n_kv_heads, self.head_dim, self.ffn, w8) == 2)
         if fused:
             self._decode_step_rows(h, B, pos, pos_max)
@@ -1225,8 +1108,5 @@ class Transformer(nn.Module):
         xn = self._buf("xn_last", (B, a.dim))
         ops.rmsnorm(h, self.norm.weight, xn, a.norm_eps)
         logits = out if out is not None else torch.empty(B, a.vocab_size, dtype=torch.float32, device=self._device)
-        if self._dtype == torch.float32:
-            ops.gemm_nt(xn, self.output.weight, logits)
-        else:
-            self._lm_head_last(xn, logits, B <= 32)
+        self._lm_head_last(xn, logits, B <= 32)
         return logits

@@ -24,6 +24,7 @@ import torch.nn as nn
 
 from .. import ops
 from . import genctl
+from .LLM.weight_formats import FORMATS
 from .tokenizer import Tokenizer, probe_tokenizer_path_from_pretrained  # noqa: F401
 
 # llama_type -> module; extend to plug further model files (same contract as accessory.model.LLM.*)
@@ -193,10 +194,9 @@ class MetaModel(nn.Module):
         """The HIP forward/backward engine of the plugin (a3vlm_amd/train.py).  compute dtype: bf16
         ("autocast") unless the model is all-fp32 (parity path)."""
         from ..train import TrainEngine
-        if getattr(self.llma, "_n4", None) is not None:
-            raise RuntimeError("this model holds NF4 weights (inference only): training needs the bf16 checkpoint")
-        if getattr(self.llma, "_mx4", None) is not None:
-            raise RuntimeError("this model holds MXFP4 weights (inference only): training needs the bf16 checkpoint")
+        fmt = FORMATS[self.llma.weight_format]
+        if fmt.frees_weights:
+            raise RuntimeError(f"this model holds {fmt.name} weights (inference only): training needs the bf16 checkpoint")
         if getattr(self, "_engine", None) is None:
             if compute_dtype is None:
                 frozen = [p for p in self.llma.parameters() if not p.requires_grad]

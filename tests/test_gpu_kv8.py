@@ -221,15 +221,16 @@ def _per_kernel_step(m, tok, pos):
     xn, qkv = torch.empty_like(h), torch.empty(B, (H + 2 * Hkv) * hd, dtype=BF, device=DEV)
     att, act = torch.empty(B, H * hd, dtype=BF, device=DEV), torch.empty(B, m.ffn, dtype=BF, device=DEV)
     scratch = torch.empty(ops.attention_scratch_floats(B, H, hd, pos + 1), dtype=torch.float32, device=DEV)
-    pk, q8, n4 = m._pack(), getattr(m, "_q8", None), getattr(m, "_n4", None)
+    pk, fmt, images = m._pack(), m.weight_format, None if m._weights is None else m._weights.images
 
     def lin(x, i, key, out, **kw):
         idx = ("wqkv", "wo", "w13", "w2").index(key)
         ws = m._skinny_ws(B, out.shape[1] * (2 if kw.get("epilogue") == ops.EPI_SWIGLU else 1), x.shape[1])
-        if n4 is not None:
-            return ops.gemm_skinny_nf4(x, *n4[f"{key}.{i}"], out, ws, **kw)
-        if q8 is not None:
-            return ops.gemm_skinny_fp8(x, *q8[1][i][idx], out, ws, **kw)
+        if fmt == "nf4":
+            return ops.gemm_skinny_nf4(x, *images[f"{key}.{i}"], out, ws, **kw)
+        if fmt == "fp8":
+            return ops.gemm_skinny_fp8(x, *images[f"{key}.{i}"], out, ws, **kw)
+        assert fmt == "bf16"
         lyr = m.layers[i]
         w = (pk[f"wqkv.{i}"], lyr.attention.wo.weight, pk[f"w13.{i}"], lyr.feed_forward.w2.weight)[idx]
         return ops.gemm_skinny(x, w, out, ws, **kw)
@@ -443,7 +444,7 @@ def test_from_pretrained_kv_quant_generate(ckpt, quant):
     mm = MetaModel.from_pretrained(ckdir, llama_type="llama_ens5", llama_config=[str(cfgp)], tokenizer_path=os.path.join(GD, "tokenizer.model"),
                                    with_visual=True, max_seq_len=512, quant=quant or False, kv_quant="fp8")
     assert mm.llma._kv_quant == "fp8"
-    assert (getattr(mm.llma, "_n4", None) is not None) == (quant == "nf4") and (getattr(mm.llma, "_q8", None) is not None) == (quant is True)
+    assert mm.llma.weight_format == {None: "bf16", True: "fp8", "nf4": "nf4"}[quant]
     prompt, n = "Detect all manipulable object parts.", 10
     _, ids = mm.generate([prompt], None, max_gen_len=n, temperature=0, return_ids=True)
     assert mm.llma._kv8 is not None and mm.llma._kv8["k_q"][0].dtype == torch.uint8

@@ -273,7 +273,7 @@ def test_quantising_a_merged_model(mode):
     mb.llma.load_state_dict(merged, strict=True)
     mp.llma.quantize_decode_weights(mode)
     mb.llma.quantize_decode_weights(mode)
-    assert (getattr(mp.llma, "_n4", None) is not None) == (mode == "nf4") and (getattr(mp.llma, "_q8", None) is not None) == (mode == "fp8")
+    assert mp.llma.weight_format == mode and mb.llma.weight_format == mode
     prompts = ["Detect all manipulable object parts.", "the quick brown fox"]
     _, ids_p = mp.generate(prompts, None, max_gen_len=12, temperature=0, return_ids=True)
     _, ids_b = mb.generate(prompts, None, max_gen_len=12, temperature=0, return_ids=True)

@@ -281,7 +281,7 @@ def _tokens(B, T, seed):
 def test_prefill_equals_the_bf16_model_holding_wd(hd):
     sd = _weights(hd)
     mq, md = _model(hd, sd, "mxfp4"), _model(hd, _wd_state(sd, 2))
-    assert mq._mx4 is not None and not hasattr(mq.layers[0].attention.wq, "weight") and "output.weight" not in mq.state_dict()
+    assert mq.weight_format == "mxfp4" and mq._weights.images and not hasattr(mq.layers[0].attention.wq, "weight") and "output.weight" not in mq.state_dict()
     ex = _tokens(2, 21, seed=5)
     assert torch.equal(mq.forward_inference(ex, 0), md.forward_inference(ex, 0)), "prefill is weight-only: bit-equal logits"
     for i in range(2):
@@ -311,7 +311,7 @@ def test_decode_step_equals_the_sequence_of_public_ops(B):
     kc1 = [t.clone() for t in m._k_cache]
     for t, src in zip(m._k_cache + m._vt_cache, kc0 + vc0):
         t.copy_(src)
-    a, mx = m.args, m._mx4
+    a, mx = m.args, m._weights.images
     H, Hkv, dim, pos = m.n_heads, m.n_kv_heads, a.dim, T - 1
     h = torch.empty(B, dim, dtype=BF, device=DEV)
     ops.embed_assemble(ex[:, T - 1:].contiguous(), m.tok_embeddings.weight, h, B, 1, 0, dim)
@@ -455,7 +455,7 @@ def test_from_pretrained_mxfp4_generates(ckpt, kv):
     cfgp, ckdir = ckpt
     mm = MetaModel.from_pretrained(ckdir, llama_type="llama_ens5", llama_config=[str(cfgp)], tokenizer_path=os.path.join(GD, "tokenizer.model"),
                                    with_visual=True, max_seq_len=512, quant="mxfp4", kv_quant=kv)
-    assert mm.llma._mx4 is not None and mm.llma._kv_quant == kv
+    assert mm.llma.weight_format == "mxfp4" and mm.llma._weights.images and mm.llma._kv_quant == kv
     prompts, n = ["Detect all manipulable object parts.", "Lid?"], 8
     ids = [mm.generate([p], None, max_gen_len=n, temperature=0, return_ids=True)[1][0] for p in prompts]
     tok = mm.tokenizer.encode(prompts[0], bos=True, eos=False)

@@ -317,7 +317,7 @@ def _tokens(B, T, seed):
 
 def _public_ops_forward(m, tok, pos):
     """forward_inference(tok [B, S], pos) of a prefill=True model as the sequence of public ops on the model's caches: fp32 logits [B, V]."""
-    a, mx, hd = m.args, m._mx4, m.head_dim
+    a, mx, hd = m.args, m._weights.images, m.head_dim
     H, Hkv, dim = m.n_heads, m.n_kv_heads, a.dim
     B, S = tok.shape
     rows = B * S
@@ -367,7 +367,7 @@ def _against_public_ops(m, tok, pos):
 @pytest.mark.parametrize("hd", [64, 128])
 def test_prefill_and_33_row_step_equal_the_sequence_of_public_ops(hd):
     m = _model(hd, _weights(hd), True)
-    assert m._mx4 is not None and m._mx4_prefill
+    assert m.weight_format == "mxfp4" and m._weights.images and m._weights.prefill is True
     _against_public_ops(m, _tokens(2, 21, seed=5), 0)               # 42 rows at S = 21
     B, T = 33, 6
     ex = _tokens(B, T, seed=9)
@@ -401,7 +401,7 @@ def test_prefill_false_beside_it_is_still_weight_only(hd):
     lp, lq, ld = mp.forward_inference(ex, 0), mq.forward_inference(ex, 0), md.forward_inference(ex, 0)
     assert torch.equal(lq, ld), "prefill=False: weight-only, the logits of the bf16 model on Wd"
     assert "nf4_scratch" in mq._ws and "nf4_scratch" not in mp._ws
-    assert not mq._mx4_prefill and not torch.equal(lp, ld), "prefill=True quantises the activations: other logits"
+    assert mq._weights.prefill is False and not torch.equal(lp, ld), "prefill=True quantises the activations: other logits"
 
 
 class _FakeQuantOracle(ref_cpu.OracleDecoder):
@@ -527,7 +527,7 @@ def test_from_pretrained_quant_prefill_generates(ckpt):
     with pytest.raises(ValueError, match="MXFP4 option"):
         MetaModel.from_pretrained(ckdir, quant="nf4", quant_prefill=True, **kw)
     mm = MetaModel.from_pretrained(ckdir, quant="mxfp4", quant_prefill=True, **kw)
-    assert mm.llma._mx4 is not None and mm.llma._mx4_prefill
+    assert mm.llma.weight_format == "mxfp4" and mm.llma._weights.images and mm.llma._weights.prefill is True
     prompts, n = ["Detect all manipulable object parts.", "Lid?"], 8
     ids = [mm.generate([p], None, max_gen_len=n, temperature=0, return_ids=True)[1][0] for p in prompts]
     assert all(len(i) > 0 for i in ids)

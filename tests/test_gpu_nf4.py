@@ -179,7 +179,7 @@ def test_nf4_memory_and_state_dict():
     m.quantize_decode_weights("nf4")
     torch.cuda.synchronize()
     after = torch.cuda.memory_allocated()
-    n4_bytes = sum(q.numel() + s.numel() * 4 for q, s in m._n4.values())
+    n4_bytes = sum(q.numel() + s.numel() * 4 for q, s in m._weights.images.values())
     assert n4_bytes == bf16_bytes * 4.5 / 16
     assert before - after >= 0.7 * bf16_bytes, (before, after, bf16_bytes)
     sd = m.state_dict()

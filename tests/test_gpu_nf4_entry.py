@@ -64,7 +64,7 @@ def test_from_pretrained_nf4_greedy_ids_match_the_bf16_model_on_wd(ckpt):
     cfgp, ckdir, sd, _ = ckpt
     mq = MetaModel.from_pretrained(ckdir, llama_type="llama_ens5", llama_config=[str(cfgp)], tokenizer_path=os.path.join(GD, "tokenizer.model"),
                                    with_visual=True, max_seq_len=512, quant="nf4")
-    assert mq.llma._n4 is not None
+    assert mq.llma.weight_format == "nf4" and mq.llma._weights.images
     names = mq.state_dict()
     assert "llma.layers.0.attention.wq.weight" not in names and "llma.output.weight" not in names
     assert "llma.layers.0.attention_norm.weight" in names

@@ -223,7 +223,7 @@ def _per_kernel_step_rows(m, tok, pos, pos_max):
     H, Hkv, hd, dim = m.n_heads, m.n_kv_heads, m.head_dim, a.dim
     hh = torch.empty(B, dim, dtype=BF, device=DEV)
     ops.embed_assemble(tok.view(B, 1).contiguous(), m.tok_embeddings.weight, hh, B, 1, 0, dim)
-    pk, q8, n4 = m._pack(), getattr(m, "_q8", None), getattr(m, "_n4", None)
+    pk, fmt, images = m._pack(), m.weight_format, None if m._weights is None else m._weights.images
     Bc = B if B <= 16 else (B + 1) // 2
     for b0 in range(0, B, Bc):
         nb = min(Bc, B - b0)
@@ -237,10 +237,11 @@ def _per_kernel_step_rows(m, tok, pos, pos_max):
         def lin(x, i, key, out, **kw):
             idx = ("wqkv", "wo", "w13", "w2").index(key)
             ws = m._skinny_ws(nb, out.shape[1] * (2 if kw.get("epilogue") == ops.EPI_SWIGLU else 1), x.shape[1])
-            if n4 is not None:
-                return ops.gemm_skinny_nf4(x, *n4[f"{key}.{i}"], out, ws, **kw)
-            if q8 is not None:
-                return ops.gemm_skinny_fp8(x, *q8[1][i][idx], out, ws, **kw)
+            if fmt == "nf4":
+                return ops.gemm_skinny_nf4(x, *images[f"{key}.{i}"], out, ws, **kw)
+            if fmt == "fp8":
+                return ops.gemm_skinny_fp8(x, *images[f"{key}.{i}"], out, ws, **kw)
+            assert fmt == "bf16"
             lyr = m.layers[i]
             w = (pk[f"wqkv.{i}"], lyr.attention.wo.weight, pk[f"w13.{i}"], lyr.feed_forward.w2.weight)[idx]
             return ops.gemm_skinny(x, w, out, ws, **kw)

@@ -95,7 +95,7 @@ def test_plan_slices_and_refusals():
 def test_parsers_and_signatures():
     from a3vlm_amd import eval_affordance_with_quant as ev
     from a3vlm_amd.model.meta import MetaModel
-    from a3vlm_amd.model.LLM import llama_ens5, llama_ens5_peft
+    from a3vlm_amd.model.LLM import llama_ens5, llama_ens5_peft, weight_formats
     p = ev.get_parser()
     base = ["--llama_config", "c.json", "--tokenizer_path", "t.model"]
     req = [a for a in p._actions if a.required]
@@ -109,7 +109,8 @@ def test_parsers_and_signatures():
     assert "quant" in inspect.signature(MetaModel.from_pretrained).parameters
     assert "mxfp4" in inspect.getsource(MetaModel.from_pretrained)
     assert "mxfp4" in inspect.getsource(llama_ens5_peft.Transformer.quantize_decode_weights)
-    assert hasattr(llama_ens5.Transformer, "_quantize_mx4") and llama_ens5.Mx4Image._fields == ("q", "s")
+    assert hasattr(llama_ens5.Transformer, "_quantize_4bit") and weight_formats.WeightImage._fields == ("q", "s")
+    assert weight_formats.FORMATS["mxfp4"].quantize is not None and weight_formats.FORMATS["mxfp4"].frees_weights
     for name in ("quantize_mxfp4", "dequantize_mxfp4", "gemm_skinny_mxfp4"):
         assert callable(getattr(ops, name))
 

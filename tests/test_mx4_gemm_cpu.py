@@ -196,7 +196,8 @@ def test_row_quantiser_refusals_come_before_any_launch():
 def test_quant_prefill_parser_rules():
     from a3vlm_amd import eval_affordance_with_quant as ev
     from a3vlm_amd.model.meta import MetaModel
-    from a3vlm_amd.model.LLM import llama_ens5
+    import dataclasses
+    from a3vlm_amd.model.LLM import llama_ens5, weight_formats
     p = ev.get_parser()
     argv = []
     for a in (a for a in p._actions if a.required):
@@ -215,5 +216,6 @@ def test_quant_prefill_parser_rules():
     with pytest.raises(ValueError, match="MXFP4 option"):
         MetaModel.from_pretrained("/nonexistent", quant="nf4", quant_prefill=True)
     assert "prefill" in inspect.signature(llama_ens5.Transformer.quantize_decode_weights).parameters
-    assert "_mx4_prefill" in inspect.getsource(llama_ens5.Transformer.quantize_decode_weights)
+    assert "prefill" in inspect.getsource(llama_ens5.Transformer._quantize_4bit)
+    assert "prefill" in [f.name for f in dataclasses.fields(weight_formats.DecodeWeights)]
     assert isinstance(p, argparse.ArgumentParser)
