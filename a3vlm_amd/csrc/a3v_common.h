@@ -317,3 +317,167 @@ int a3v_attention_decode_fused(const void* q, const void* k, const void* vt, voi
 // internal (a3v_train.hip): bf16 transposes of n_out x n_in matrices [R, C] -> [C, Rpad] in one launch
 int a3v_transpose_2level(const bf16_t* src, int64_t ld_src, int64_t bs_in, int64_t bs_out, bf16_t* dst, int64_t ld_dst, int64_t bsd_in,
                          int64_t bsd_out, int R, int C, int Rpad, int n_in, int n_out, void* stream);
+
+// ---------------------------------------------------------------- mass selection of the device samplers
+// (a3v_rowops.hip: a3v_sample_top_p, where the algorithm is described; a3v_sampler.hip: a3v_sample_top_k_p.  One block = one row.)
+struct TopPSel { unsigned key; float above; int rank; int id; };
+
+// CACHE 1 (true): e_i is read from the LDS copy ec[V]; 0 (false): recomputed from the row.  2 (a3v_sampler.hip above the cache's
+// size): recomputed where the token's bit in the keep bitmap (`ec` reinterpreted, bit i of 32-bit word i / 32) is set, else the
+// negative value every pass skips.  The first two forms are a3v_sample_top_p's, unchanged.
+template <int CACHE>
+__device__ __forceinline__ float topp_e(const float* __restrict__ r, const float* __restrict__ ec, int i, float T, float xm) {
+  if constexpr (CACHE == 1) return ec[i];
+  else if constexpr (CACHE == 2) return ((reinterpret_cast<const unsigned*>(ec)[i >> 5] >> (i & 31)) & 1u) ? expf(r[i] / T - xm) : -1.f;
+  else return expf(r[i] / T - xm);
+}
+
+// shared scratch of the selection (one block = one row)
+struct TopPShared {
+  float hist[16][256];        // per-wave mass histograms of the current digit
+  float bin[256];
+  float bin_top[256];         // the first digit's merged histogram: the same for both selections of a row (taken once)
+  unsigned long long ball[64][16];   // tie ballots per (iteration, wave) of the last pass
+  int wcnt[64][16];
+  float red[16];
+  unsigned ured[2][16];
+  unsigned sel_key; float sel_above; int sel_bin; int found;
+  int tie_n;
+};
+
+// target in units of Z.  want_id: also locate the token (selection 2); else only (key, above, rank) are needed (selection 1).
+// kmin / levels / lsh: keys are ranked as (bits(e) - kmin) << lsh -- the left shift puts the range's top bit on the top bit of the
+// first of `levels` 8-bit digits (0 levels: every element has the same value), so the first histogram already spreads over 128+ bins.
+template <int CACHE>
+__device__ void topp_select(const float* __restrict__ r, const float* __restrict__ ec, int V, float T, float xm, unsigned kmin, int levels, int lsh,
+                            float target, bool want_id, bool reuse_top, TopPShared& sh, TopPSel& out) {
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  unsigned prefix = 0;
+  float above = 0.f;
+  bool all_kept = false;
+  for (int level = levels - 1; level >= 0; --level) {
+    const int shift = level * 8;
+    if (level == levels - 1 && reuse_top) {               // selection 2: the first digit's histogram of selection 1
+      if (tid < 256) sh.bin[tid] = sh.bin_top[tid];
+      if (tid == 0) sh.found = -1;
+      __syncthreads();
+    } else {
+    for (int b = tid; b < 16 * 256; b += 1024) (&sh.hist[0][0])[b] = 0.f;
+    __syncthreads();
+    // four elements per trip: the reads (LDS or expf) of a trip are in flight together; the adds keep the element order of the plain loop
+    for (int i0 = tid; i0 < V; i0 += 4096) {
+      float e4[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int i = i0 + q * 1024;
+        e4[q] = i < V ? topp_e<CACHE>(r, ec, i, T, xm) : -1.f;
+      }
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const unsigned k = (__float_as_uint(e4[q]) - kmin) << lsh;
+        if (e4[q] >= 0.f && (level == levels - 1 || (k >> (shift + 8)) == (prefix >> (shift + 8)))) atomicAdd(&sh.hist[wave][(k >> shift) & 255], e4[q]);
+      }
+    }
+    __syncthreads();
+    if (tid < 256) {
+      float m = 0.f;
+#pragma unroll
+      for (int w = 0; w < 16; ++w) m += sh.hist[w][tid];
+      sh.bin[tid] = m;
+      if (level == levels - 1) sh.bin_top[tid] = m;
+    }
+    if (tid == 0) sh.found = -1;
+    __syncthreads();
+    }
+    if (wave == 0) {
+      // lane l owns bins 4 l .. 4 l + 3; suffix sums from bin 255 down
+      float b4[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) b4[q] = sh.bin[lane * 4 + q];
+      const float own = (b4[0] + b4[1]) + (b4[2] + b4[3]);
+      float suf = own;                                   // inclusive suffix over lanes >= l
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const float v = __shfl_down(suf, o, 64);
+        if (lane + o < 64) suf += v;
+      }
+      const float nxt = __shfl_down(suf, 1, 64);
+      float excl = above + (lane < 63 ? nxt : 0.f);      // mass of everything ranked before bin 4 l + 3
+      int hi = -1, lo = 0x7fffffff;                      // highest bin whose inclusive mass passes the target / lowest non-empty bin
+      float hi_excl = 0.f, lo_excl = 0.f;
+#pragma unroll
+      for (int q = 3; q >= 0; --q) {
+        const float incl = excl + b4[q];
+        if (b4[q] > 0.f) {
+          if (hi < 0 && incl > target) { hi = lane * 4 + q; hi_excl = excl; }
+          lo = lane * 4 + q; lo_excl = excl;
+        }
+        excl = incl;
+      }
+      int best_hi = hi, best_lo = lo;
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        best_hi = max(best_hi, __shfl_xor(best_hi, o, 64));
+        best_lo = min(best_lo, __shfl_xor(best_lo, o, 64));
+      }
+      // no bin passes: at the top level the target is beyond the total mass (cut: nothing is cut; draw: clamp onto the last
+      // token); below it, the sub-bins' sum fell an ulp short of their parent's -- take the last non-empty one
+      const bool clamp_lo = best_hi < 0 && (level < levels - 1 || want_id) && best_lo != 0x7fffffff;
+      if (best_hi >= 0 && best_hi == hi) { sh.found = hi; sh.sel_above = hi_excl; }
+      if (clamp_lo && best_lo == lo) { sh.found = lo; sh.sel_above = lo_excl; }
+    }
+    __syncthreads();
+    if (sh.found < 0) { all_kept = true; break; }        // target >= total mass: nothing is cut (top_p >= 1)
+    prefix |= (unsigned)sh.found << shift;
+    above = sh.sel_above;
+    __syncthreads();
+  }
+  if (all_kept) { out.key = 0u; out.above = -1.f; out.rank = 0; out.id = -1; return; }
+  const unsigned key = (prefix >> lsh) + kmin;           // (levels == 0: every element equals the smallest key)
+  const float ek = __uint_as_float(key);
+  // ties on the selected value: rank inside them by token index
+  int rank = ek > 0.f ? (int)floorf((target - above) / ek) : 0;
+  if (rank < 0) rank = 0;
+  out.key = key; out.above = above; out.rank = rank; out.id = -1;
+  const int iters = (V + 1023) / 1024;
+  for (int k = 0; k < iters; ++k) {
+    const int i = k * 1024 + tid;
+    const bool tie = i < V && __float_as_uint(topp_e<CACHE>(r, ec, i, T, xm)) == key;
+    const unsigned long long bl = __ballot(tie);
+    if (lane == 0) { sh.ball[k][wave] = bl; sh.wcnt[k][wave] = __popcll(bl); }
+  }
+  __syncthreads();
+  // (k, w) slots in token order = flat index t = k * 16 + w; thread t holds slot t's count: total and the slot the rank falls into by a
+  // block-wide scan over the <= 1024 slots (was: one thread walking 512 LDS words twice, ~10 us per selection)
+  {
+    const int c = tid < iters * 16 ? (&sh.wcnt[0][0])[tid] : 0;
+    int incl = c;                                        // inclusive scan inside the wave
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int v = __shfl_up(incl, o, 64);
+      if (lane >= o) incl += v;
+    }
+    if (lane == 63) sh.ured[0][wave] = (unsigned)incl;
+    __syncthreads();
+    int base = 0, n = 0;
+#pragma unroll
+    for (int w = 0; w < 16; ++w) {
+      const int t = (int)sh.ured[0][w];
+      if (w < wave) base += t;
+      n += t;
+    }
+    if (rank >= n) rank = n - 1;                         // float division landed past the last tied element
+    if (tid == 0) { sh.tie_n = rank; sh.sel_bin = -1; }
+    __syncthreads();
+    const int before = base + incl - c;                  // ties in earlier slots
+    if (want_id && c > 0 && rank >= before && rank < before + c) {
+      unsigned long long bl = (&sh.ball[0][0])[tid];
+      for (int q = 0; q < rank - before; ++q) bl &= bl - 1;   // drop the lowest set bits
+      sh.sel_bin = (tid >> 4) * 1024 + (tid & 15) * 64 + __ffsll((long long)bl) - 1;
+    }
+  }
+  __syncthreads();
+  out.rank = sh.tie_n;
+  out.id = sh.sel_bin;
+  __syncthreads();
+}

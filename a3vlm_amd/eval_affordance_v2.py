@@ -143,6 +143,12 @@ def get_args_parser():
     p.add_argument("--repetition_penalty", type=float, default=1.0,
                    help="HF repetition penalty over the prompt text and everything generated so far, applied on the device before "
                         "temperature / top-p (1.0 = off, the default; > 1 discourages loops in long answers)")
+    p.add_argument("--top_k", type=int, default=0,
+                   help="sample among the k largest logits only (ties at the k-th kept; 0 = off, the default); applied on the device "
+                        "after temperature and before top-p, as HF generate does")
+    p.add_argument("--min_p", type=float, default=0.0,
+                   help="drop tokens whose probability is below min_p times the most likely token's (0 = off, the default); applied on "
+                        "the device after top-p")
     p.add_argument("--save_scores", action="store_true", default=False,
                    help="every record gains \"logprob_sum\" and \"logprobs\": the model's own log-probability of the answer's tokens "
                         "(raw logits, temperature 1), a confidence for AP-style evaluation")
@@ -198,6 +204,8 @@ def main(args):
     torch.manual_seed(args.seed + rank)
     save_scores = getattr(args, "save_scores", False)
     controls = dict(repetition_penalty=getattr(args, "repetition_penalty", 1.0), return_logprobs=save_scores)
+    if getattr(args, "top_k", 0) or getattr(args, "min_p", 0.0):      # opt-in: with the defaults the calls below are what they were
+        controls.update(top_k=args.top_k, min_p=args.min_p)
     with torch.no_grad():
         for image, qids, prompts, annotations, paths in loader:
             image = pre.batch(image) if isinstance(image, list) else image.to(dev)

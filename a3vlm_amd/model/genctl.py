@@ -19,6 +19,16 @@ def check_penalty(repetition_penalty: float) -> float:
     return p
 
 
+def check_filters(top_k: int, min_p: float):
+    """The sampler's two opt-in filters: ``top_k`` an integer >= 0 (0 = off), ``min_p`` in [0, 1] (0 = off)."""
+    if isinstance(top_k, bool) or int(top_k) != top_k or top_k < 0:
+        raise ValueError(f"top_k must be an integer >= 0 (0 = off), got {top_k}")
+    m = float(min_p)
+    if not 0.0 <= m <= 1.0:
+        raise ValueError(f"min_p must be in [0, 1] (0 = off), got {min_p}")
+    return int(top_k), m
+
+
 def wanted(repetition_penalty: float, return_logprobs: bool) -> bool:
     return check_penalty(repetition_penalty) != 1.0 or bool(return_logprobs)
 

@@ -309,7 +309,7 @@ class MetaModel(nn.Module):
                  temperature: float = 0.0, top_p: float = 0.95,
                  additional_stop_symbols: Iterable[str] = (), return_ids: bool = False, poll_every: int = 4,
                  sample_uniforms: Optional[torch.Tensor] = None, repetition_penalty: float = 1.0,
-                 return_logprobs: bool = False) -> List[str]:
+                 return_logprobs: bool = False, top_k: int = 0, min_p: float = 0.0) -> List[str]:
         """meta.py:379-485.  ``return_ids`` additionally returns the generated id lists (the
         arguments of tokenizer.decode at :482-484) for bit-exact parity checks.
         ``temperature > 0`` (the eval script's default recipe, T 0.1 / top-p 0.75): the nucleus draw of :456-459 / :568-583 runs on
@@ -322,10 +322,14 @@ class MetaModel(nn.Module):
         ``repetition_penalty`` (HF's rule over the prompt text and everything generated so far, applied before temperature and
         top-p; 1.0 = off) and ``return_logprobs`` (the return gains ``scores``: per answer ``{"logprobs": [...], "sum": ...}``, the
         model's own log-probability of every kept token, from the raw logits at temperature 1) are opt-in and run on the device
-        inside the step (model/genctl.py); with the defaults nothing of them is allocated or launched."""
+        inside the step (model/genctl.py); with the defaults nothing of them is allocated or launched.
+        ``top_k`` / ``min_p`` (opt-in, ``temperature > 0`` only; 0 = off): HF's two other filters on the device, in HF's order
+        temperature, top-k, top-p, min-p (``a3v_sample_top_k_p``); they see the penalised row.  With the defaults the sampler is
+        ``a3v_sample_top_p`` as before."""
         if isinstance(prompts, str):
             raise ValueError(f"{self.__class__}.generate expects a batched LIST of prompts, but str is given")
         controls = genctl.wanted(repetition_penalty, return_logprobs)      # ValueError before any device use
+        top_k, min_p = genctl.check_filters(top_k, min_p)
         dev = self._device
         if images is not None:
             images = images.to(dev)
@@ -391,7 +395,7 @@ class MetaModel(nn.Module):
                                                      images if prev_pos == 0 else None)
             z = gc.prepare(logits) if gc is not None else logits       # the choice reads the penalised row, the score the raw one
             if temperature > 0:
-                self._sample_into(z, temperature, top_p, uni[cur_pos - start_pos], sampled)
+                self._sample_into(z, temperature, top_p, uni[cur_pos - start_pos], sampled, top_k, min_p)
             ops.generate_step(z, sampled, tokens, text_mask, cur_pos, stop_seq, stop_off, len(l_stop), stopped, stop_pos, live)
             if gc is not None:         # a stopped row keeps writing past its stop_pos, as its tokens do: cut below
                 gc.record(logits, tokens, col=cur_pos)
@@ -416,7 +420,7 @@ class MetaModel(nn.Module):
                       max_gen_len=512, temperature: float = 0.0, top_p: float = 0.95,
                       additional_stop_symbols: Iterable[str] = (), return_ids: bool = False, poll_every: int = 4,
                       sample_uniforms: Optional[torch.Tensor] = None, repetition_penalty: float = 1.0,
-                      return_logprobs: bool = False):
+                      return_logprobs: bool = False, top_k: int = 0, min_p: float = 0.0):
         """Any number of prompts through ``batch_rows`` KV-cache rows (no reference counterpart; opt-in): every row decodes at its
         own position, and a row whose answer is finished is prefilled with the next prompt while the others keep decoding, so a
         short answer does not hold its row until the longest answer of a batch is done.  Answers come back in input order.
@@ -428,12 +432,14 @@ class MetaModel(nn.Module):
         (drawn up front, or ``sample_uniforms`` [N, >= max steps]), so an answer does not depend on ``batch_rows`` or on the row it
         ran in.  ``stopped`` is read back every ``poll_every`` steps; a stopped row is not touched by later steps.
         ``repetition_penalty`` / ``return_logprobs``: as in ``generate``; the seen set belongs to the cache row and is cleared and
-        re-marked when the row is refilled, a finished row's log-probs are read back with its ids.
+        re-marked when the row is refilled, a finished row's log-probs are read back with its ids.  ``top_k`` / ``min_p``: as in
+        ``generate``.
         Not for the fp8 KV cache, LoRA models before ``merge_lora()`` or the two-image plugin (each raises, naming the way out)."""
         from .ragged import RowScheduler
         if isinstance(prompts, str):
             raise ValueError(f"{self.__class__}.generate_many expects a LIST of prompts, but str is given")
         controls = genctl.wanted(repetition_penalty, return_logprobs)      # ValueError before any device use
+        top_k, min_p = genctl.check_filters(top_k, min_p)
         llma = self.llma
         llma._ragged_check()                                  # before anything is allocated or launched
         dev = self._device
@@ -518,7 +524,7 @@ class MetaModel(nn.Module):
                 gc.snapshot(stopped)       # a row that is stopped on entry is not touched by the step, nor by the record
             if temperature > 0:
                 u = uni[(ubase + sched.steps).clamp_(0, uni.numel() - 1)]
-                self._sample_into(z, temperature, top_p, u, sampled)
+                self._sample_into(z, temperature, top_p, u, sampled, top_k, min_p)
             ops.generate_step_rows(z, sampled, tokens, cur, limit, W, stop_seq, stop_off, len(l_stop), stopped, stop_pos, None,
                                    next_tok, pos)
             if gc is not None:
@@ -548,11 +554,12 @@ class MetaModel(nn.Module):
     def stream_generate(self, prompt: str, image: Optional[torch.Tensor] = None, max_gen_len: int = 512,
                         temperature: float = 0.0, top_p: float = 0.95,
                         additional_stop_symbols: Iterable[str] = (), repetition_penalty: float = 1.0,
-                        return_logprobs: bool = False):
+                        return_logprobs: bool = False, top_k: int = 0, min_p: float = 0.0):
         """meta.py:487-566.  ``repetition_penalty`` / ``return_logprobs`` as in ``generate``; with ``return_logprobs`` every yielded
         dict also carries ``"logprobs"``: one value per token generated so far (the text may be cut inside the last ones by a stop
-        string)."""
+        string).  ``top_k`` / ``min_p`` as in ``generate``."""
         controls = genctl.wanted(repetition_penalty, return_logprobs)      # ValueError before any device use
+        top_k, min_p = genctl.check_filters(top_k, min_p)
         args = self.llma.args
         dev = self._device
         prompt_tokens = self.tokenizer.encode(prompt, bos=True, eos=False)
@@ -589,7 +596,7 @@ class MetaModel(nn.Module):
                                                  image if prev_pos == 0 else None)
             z = gc.prepare(logits) if gc is not None else logits
             if temperature > 0:
-                nt = self._sample_into(z, temperature, top_p, torch.rand(1, device=dev), nt_buf)
+                nt = self._sample_into(z, temperature, top_p, torch.rand(1, device=dev), nt_buf, top_k, min_p)
             else:
                 nt = ops.argmax(z, nt_buf)
             nt = int(nt.reshape(-1)[0].item())
@@ -610,21 +617,31 @@ class MetaModel(nn.Module):
         generated = self.tokenizer.decode(tokens[start_pos:generate_until].tolist())
         yield out(generated, True)
 
-    def _sample_into(self, logits: torch.Tensor, temperature: float, top_p: float, uniforms: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    def _sample_into(self, logits: torch.Tensor, temperature: float, top_p: float, uniforms: torch.Tensor, out: torch.Tensor,
+                     top_k: int = 0, min_p: float = 0.0) -> torch.Tensor:
         """One top-p draw per row into ``out``: the device kernel where it applies (V <= 65536, 0 < top_p), otherwise the reference's
-        sort / cumsum / multinomial recipe (meta.py:456-458, 568-583) -- larger vocabularies must keep working as they do there."""
+        sort / cumsum / multinomial recipe (meta.py:456-458, 568-583) -- larger vocabularies must keep working as they do there.
+        ``top_k`` / ``min_p`` set: ``a3v_sample_top_k_p`` under the same condition, otherwise the same three rules in torch."""
+        filters = top_k > 0 or min_p > 0
         if logits.shape[-1] <= 65536 and top_p > 0:
+            if filters:
+                return ops.sample_top_k_p(logits, temperature, top_k, top_p, min_p, uniforms, out)
             return ops.sample_top_p(logits, temperature, top_p, uniforms, out)
-        probs = torch.softmax(logits.float() / temperature, dim=-1)
-        out.copy_(self.sample_top_p(probs, top_p).reshape(-1))
+        z = logits.float()
+        if 0 < top_k < z.shape[-1]:                       # on the logits' own values: ties at the k-th one are kept
+            z = z.masked_fill(z < z.topk(top_k, dim=-1).values[..., -1:], float("-inf"))
+        probs = torch.softmax(z / temperature, dim=-1)
+        out.copy_(self.sample_top_p(probs, top_p, min_p).reshape(-1))
         return out
 
-    def sample_top_p(self, probs: torch.Tensor, p: float) -> torch.Tensor:
+    def sample_top_p(self, probs: torch.Tensor, p: float, min_p: float = 0.0) -> torch.Tensor:
         """meta.py:568-583, kept for callers of the reference's method (torch ops; ``generate`` itself draws on the device with
         ``a3v_sample_top_p``, same nucleus, explicit uniforms)."""
         ranked, order = probs.sort(dim=-1, descending=True)
         before = ranked.cumsum(dim=-1) - ranked                 # mass ranked ahead of each token
         kept = ranked.masked_fill(before > p, 0.0)
+        if min_p > 0:                                     # p_i >= min_p * p_max (ranked[..., 0] is the maximum)
+            kept = kept.masked_fill(ranked < min_p * ranked[..., :1], 0.0)
         draw = torch.multinomial(kept / kept.sum(dim=-1, keepdim=True), num_samples=1)
         return order.gather(-1, draw)
 

@@ -698,6 +698,19 @@ def sample_top_p(logits, temperature: float, top_p: float, u, out):
     return out
 
 
+def sample_top_k_p(logits, temperature: float, top_k: int, top_p: float, min_p: float, u, out):
+    """sample_top_p with HF's two other filters, in HF's order (a3v_sample_top_k_p): top-k on the logits' own bits (0 or >= V: off,
+    ties at the k-th value kept), then top-p over what is left, then min-p (p_i >= min_p * p_max; 0: off), one draw at u[b]."""
+    _dev(logits, u, out)
+    assert logits.dtype == torch.float32 and logits.stride(1) == 1 and u.dtype == torch.float32 and out.dtype == torch.int64
+    B, V = logits.shape
+    assert u.numel() >= B and out.numel() >= B and u.is_contiguous() and out.is_contiguous()
+    rc = _l.load().a3v_sample_top_k_p(_p(logits), logits.stride(0), B, V, float(temperature), int(top_k), float(top_p), float(min_p),
+                                      _p(u), _p(out), _stream())
+    _l.check(rc, "a3v_sample_top_k_p")
+    return out
+
+
 def argmax(logits, out):
     _dev(logits, out)
     assert logits.dtype == torch.float32 and out.dtype == torch.int64

@@ -494,6 +494,23 @@ int a3v_generate_step(const float* logits, int64_t ld, const int64_t* sampled, i
 int a3v_sample_top_p(const float* logits, int64_t ld, int B, int V, float temperature, float top_p, const float* u,
                      int64_t* out, void* stream);
 
+/* a3v_sample_top_p with two more filters, in HF's order: temperature, top-k, top-p, min-p.  No reference counterpart (opt-in).
+ * z = one row of fp32 logits (with a repetition penalty: the row a3v_logits_prepare wrote), T = temperature > 0,
+ * x_i = z_i / T, xm = max x, e_i = expf(x_i - xm) -- the expressions of a3v_sample_top_p.
+ *   1. top-k   top_k = 0 or >= V: off.  t = the top_k-th largest value of z counting duplicates; K = {i : z_i >= t}, decided on the
+ *              logits' own bits (nothing rounds; every token tied at t is kept, as HF's TopKLogitsWarper does).  Outside K: mass 0.
+ *   2. top-p   a3v_sample_top_p's rule on K: rank K by e descending, token index ascending; kept iff the mass ranked before the
+ *              token is <= top_p * Z_K, Z_K = sum of e over K.
+ *   3. min-p   0 <= min_p <= 1, 0: off.  kept iff e_i >= min_p; e_max is exactly 1, so this is p_i >= min_p * p_max under either
+ *              renormalisation above, and the arg-max always survives.
+ *   4. draw    the inverse CDF over the kept tokens in ranked order at u * M, M = the kept mass, u clamped into [0, 1).
+ * Inside K the top-p set and the min-p set are prefixes of one ranking: the final set is the shorter one.  A row without a finite
+ * logit gives id 0.  With top_k = 0 and min_p = 0 the ids are a3v_sample_top_p's, bit for bit.
+ * Returns A3V_ERR_ARG for top_k < 0 or min_p outside [0, 1] (and a3v_sample_top_p's argument errors), A3V_ERR_SHAPE as
+ * a3v_sample_top_p; nothing is launched on an error. */
+int a3v_sample_top_k_p(const float* logits, int64_t ld, int B, int V, float temperature, int top_k, float top_p, float min_p,
+                       const float* u, int64_t* out, void* stream);
+
 /* torch.argmax(logits, -1) with first-index tie break (model/meta.py:460).  fp32 [B,V]. */
 int a3v_argmax(const float* logits, int64_t ld, int64_t* out, int B, int V, void* stream);
 
