@@ -13,6 +13,13 @@
 //  * attn_rows_generic_kernel<T>   : attn_generic_kernel at Sq = 1 with the row's key count (fp32 parity path, odd head dims).
 //  * generate_step_rows_kernel     : generate_step_kernel with per-row cur / limit, no text_mask; emits the next id and its position.
 //  * a3v_llama_decode_step_rows    : the fused form of a3v_llama_decode_step with those kernels, six launches per layer.
+//  * shared prompt keys (the SH = true instantiations of the two attention kernels, a3v_attention_decode_rows_shared): a row's
+//    64-key tiles below its shared length are read from another cache row.  Only the base pointer of a tile differs -- a
+//    wave-uniform select of one 64-bit offset -- so the walk, the masks and the merges are the expressions above in their order.
+//    Every tile starts at a multiple of 64 in absolute position (chunk is a multiple of 64) and the shared length is one too, so
+//    a tile, its clamped K re-reads and its 16-byte V^T vectors lie in one row.  The SH = false instantiations take RowsAttnArgs
+//    as before: their code does not change.
+//  * kv_copy_span_kernel<T>        : positions [lo, hi) of one cache row into other rows, every layer in one launch.
 #include "a3v_common.h"
 
 namespace {
@@ -59,6 +66,23 @@ struct RowsAttnArgs {
   int sk_add, sk_max, H, Hkv;        // keys of row b = min(sk[b] + sk_add, sk_max)
   float scale;
 };
+// + the shared-prefix arrays.  k / vt are the caches of ALL Btot rows; batch index b of the launch is cache row row0 + b, and
+// src_row[b] is a cache row (absolute), read as the own row when outside [0, Btot).
+struct RowsSharedArgs : RowsAttnArgs {
+  const int32_t* src_row; const int32_t* shared;
+  int row0, Btot;
+};
+template <bool SH> struct RowsArgsOf { using type = RowsAttnArgs; };
+template <> struct RowsArgsOf<true> { using type = RowsSharedArgs; };
+
+// effective shared length of a row with skb keys: min(shared, skb) rounded down to a multiple of 64; 0 for the own row
+__device__ __forceinline__ int shared_len(const RowsSharedArgs& p, int b, int skb, int* src) {
+  const int own = p.row0 + b;
+  int s = p.src_row[b];
+  if (s < 0 || s >= p.Btot) s = own;
+  *src = s;
+  return s == own ? 0 : max(min(p.shared[b], skb), 0) & ~63;
+}
 
 // sums / maxima over the 8 (16) lanes of a DPP half row (row): quad_perm [1,0,3,2], [2,3,0,1], row_half_mirror, row_mirror
 __device__ __forceinline__ float r8_sum(float v) {
@@ -75,8 +99,9 @@ __device__ __forceinline__ float r8_max(float v) {
   return v;
 }
 
-template <int HD>
-__global__ __launch_bounds__(512) void attn_decode_rows_kernel(RowsAttnArgs p, float* part, int nsplit, int chunk, int* counters) {
+template <int HD, bool SH>
+__global__ __launch_bounds__(512) void attn_decode_rows_kernel(typename RowsArgsOf<SH>::type p, float* part, int nsplit, int chunk,
+                                                               int* counters) {
   constexpr int LPR = HD / 8;        // lanes per K row (16 B each)
   constexpr int RPW = 64 / LPR;      // K rows per wave-wide load
   constexpr int NKL = 64 / RPW;      // K loads per 64-key tile
@@ -96,8 +121,17 @@ __global__ __launch_bounds__(512) void attn_decode_rows_kernel(RowsAttnArgs p, f
   const int n = min(skb, kv_lo + chunk) - kv_lo;
   float* po = part + ((int64_t)(b * p.H + h) * nsplit + sp) * (HD + 2);
   const bf16_t* Q = (const bf16_t*)p.q + b * p.q_sb + h * p.q_sh;
-  const bf16_t* K = (const bf16_t*)p.k + b * p.k_sb + hk * p.k_sh + (int64_t)kv_lo * p.k_ss;
-  const bf16_t* VT = (const bf16_t*)p.vt + b * p.v_sb + hk * p.v_sh + kv_lo;
+  int64_t row = b, dk = 0, dv = 0;                        // the own cache row; element offsets from it to the source row
+  int sh_rel = 0;                                          // tiles of the range that start below it come from the source row
+  if constexpr (SH) {
+    int src;
+    sh_rel = shared_len(p, b, skb, &src) - kv_lo;
+    row = p.row0 + b;
+    dk = (src - row) * p.k_sb;
+    dv = (src - row) * p.v_sb;
+  }
+  const bf16_t* K = (const bf16_t*)p.k + row * p.k_sb + hk * p.k_sh + (int64_t)kv_lo * p.k_ss;
+  const bf16_t* VT = (const bf16_t*)p.vt + row * p.v_sb + hk * p.v_sh + kv_lo;
   const int lo = wave * 64, hi = max(n, 0);
   float m = -INFINITY, l = 0.f, acc[NVL];
 #pragma unroll
@@ -110,10 +144,12 @@ __global__ __launch_bounds__(512) void attn_decode_rows_kernel(RowsAttnArgs p, f
     const int last_vec = (hi - 1) & ~7;
     bf16x8 kk[NKL];
     auto load_k = [&](int t0) {
+      const bf16_t* Kt = K;
+      if constexpr (SH) Kt = K + (t0 < sh_rel ? dk : 0);    // wave-uniform: t0 is a multiple of 64, the clamped rows stay in the tile
 #pragma unroll
       for (int u = 0; u < NKL; ++u) {
         const int r = min(t0 + u * RPW + lr, hi - 1);
-        const bf16x8* kp = reinterpret_cast<const bf16x8*>(K + (int64_t)r * p.k_ss + lc);
+        const bf16x8* kp = reinterpret_cast<const bf16x8*>(Kt + (int64_t)r * p.k_ss + lc);
         kk[u] = __builtin_nontemporal_load(kp);            // the K / V^T stream is read once per step by one block
       }
     };
@@ -121,9 +157,11 @@ __global__ __launch_bounds__(512) void attn_decode_rows_kernel(RowsAttnArgs p, f
     for (int t0 = lo; t0 < hi; t0 += 512) {
       bf16x8 vv[NVL];
       const int kvc = min(t0 + c8, last_vec);              // vectors past the wave's range re-read its last one (masked below)
+      const bf16_t* Vt = VT;
+      if constexpr (SH) Vt = VT + (t0 < sh_rel ? dv : 0);   // last_vec >= t0: the re-read vector lies in the tile too
 #pragma unroll
       for (int j = 0; j < NVL; ++j) {
-        const bf16x8* vp = reinterpret_cast<const bf16x8*>(VT + (int64_t)(j * 8 + dr) * p.v_sd + kvc);
+        const bf16x8* vp = reinterpret_cast<const bf16x8*>(Vt + (int64_t)(j * 8 + dr) * p.v_sd + kvc);
         vv[j] = __builtin_nontemporal_load(vp);
       }
 #pragma unroll
@@ -197,8 +235,8 @@ __global__ __launch_bounds__(512) void attn_decode_rows_kernel(RowsAttnArgs p, f
 }
 
 // one wave per (head, batch): attn_generic_kernel (a3v_attn.hip) at Sq = 1 over the row's own keys; any hd <= 256
-template <typename T>
-__global__ __launch_bounds__(64) void attn_rows_generic_kernel(RowsAttnArgs p, int hd) {
+template <typename T, bool SH>
+__global__ __launch_bounds__(64) void attn_rows_generic_kernel(typename RowsArgsOf<SH>::type p, int hd) {
   __shared__ float pbuf[64];
   __shared__ float qs[256];
   const int lane = threadIdx.x;
@@ -212,8 +250,17 @@ __global__ __launch_bounds__(64) void attn_rows_generic_kernel(RowsAttnArgs p, i
     return;
   }
   const T* Q = (const T*)p.q + b * p.q_sb + h * p.q_sh;
-  const T* K = (const T*)p.k + b * p.k_sb + hk * p.k_sh;
-  const T* VT = (const T*)p.vt + b * p.v_sb + hk * p.v_sh;
+  int64_t row = b, dk = 0, dv = 0;
+  int sh = 0;
+  if constexpr (SH) {
+    int src;
+    sh = shared_len(p, b, kv_end, &src);
+    row = p.row0 + b;
+    dk = (src - row) * p.k_sb;
+    dv = (src - row) * p.v_sb;
+  }
+  const T* K = (const T*)p.k + row * p.k_sb + hk * p.k_sh;
+  const T* VT = (const T*)p.vt + row * p.v_sb + hk * p.v_sh;
   for (int d = lane; d < hd; d += 64) qs[d] = Cvt<T>::ld(Q + d);
   __syncthreads();
   float m = -INFINITY, l = 0.f;
@@ -222,7 +269,7 @@ __global__ __launch_bounds__(64) void attn_rows_generic_kernel(RowsAttnArgs p, i
     const int kv = kv0 + lane;
     float s = -INFINITY;
     if (kv < kv_end) {
-      const T* kr = K + (int64_t)kv * p.k_ss;
+      const T* kr = K + (SH && kv0 < sh ? dk : 0) + (int64_t)kv * p.k_ss;
       float a = 0.f;
       for (int d = 0; d < hd; ++d) a = fmaf(qs[d], Cvt<T>::ld(kr + d), a);
       s = a * p.scale;
@@ -241,7 +288,7 @@ __global__ __launch_bounds__(64) void attn_rows_generic_kernel(RowsAttnArgs p, i
     for (int i = 0; i < 4; ++i) {
       const int d = lane + 64 * i;
       if (d < hd) {
-        const T* vr = VT + (int64_t)d * p.v_sd + kv0;
+        const T* vr = VT + (SH && kv0 < sh ? dv : 0) + (int64_t)d * p.v_sd + kv0;
         float a = o[i] * alpha;
         for (int j = 0; j < cnt; ++j) a = fmaf(pbuf[j], Cvt<T>::ld(vr + j), a);
         o[i] = a;
@@ -353,6 +400,35 @@ __global__ __launch_bounds__(256) void rows_ssq_rows_kernel(const bf16_t* __rest
   ssq[t] = s;
 }
 
+// Positions [lo, hi) (0 < hi - lo < 64) of cache row src into the rows dst[0..n_dst): grid (n_dst, Hkv, layers).  K: one contiguous
+// run of (hi - lo) * hd elements per (row, head), 16-byte vectors (hd is a multiple of 8).  V^T: hi - lo elements per d row, one
+// thread per d row: elements up to the first 16-byte boundary, vectors, then the elements behind the last whole vector (source
+// and destination sit at the same offset of 16-byte aligned rows, so they share the alignment).  Nothing outside the span is written.
+template <typename T>
+__global__ __launch_bounds__(256) void kv_copy_span_kernel(const void* const* __restrict__ k_ptrs, const void* const* __restrict__ vt_ptrs,
+                                                           int src, const int32_t* __restrict__ dst, int B, int lo, int hi, int Hkv, int hd,
+                                                           int Smax) {
+  constexpr int VEC = 16 / (int)sizeof(T);
+  const int r = dst[blockIdx.x];
+  if (r < 0 || r >= B || r == src) return;             // block-uniform
+  const int hk = blockIdx.y, layer = blockIdx.z, tid = threadIdx.x;
+  T* kb = (T*)k_ptrs[layer];
+  T* vb = (T*)vt_ptrs[layer];
+  const int64_t head = (int64_t)Smax * hd;
+  const T* ks = kb + ((int64_t)src * Hkv + hk) * head + (int64_t)lo * hd;
+  T* kd = kb + ((int64_t)r * Hkv + hk) * head + (int64_t)lo * hd;
+  const int nvec = (hi - lo) * hd / VEC;
+  for (int i = tid; i < nvec; i += 256) reinterpret_cast<f32x4*>(kd)[i] = reinterpret_cast<const f32x4*>(ks)[i];
+  const int a0 = min(hi, (lo + VEC - 1) / VEC * VEC), a1 = a0 + (hi - a0) / VEC * VEC;
+  for (int d = tid; d < hd; d += 256) {
+    const T* vs = vb + (((int64_t)src * Hkv + hk) * hd + d) * Smax;
+    T* vd = vb + (((int64_t)r * Hkv + hk) * hd + d) * Smax;
+    for (int e = lo; e < a0; ++e) vd[e] = vs[e];
+    for (int e = a0; e < a1; e += VEC) *reinterpret_cast<f32x4*>(vd + e) = *reinterpret_cast<const f32x4*>(vs + e);
+    for (int e = a1; e < hi; ++e) vd[e] = vs[e];
+  }
+}
+
 // the split rule of a3v_attention_decode_fused at Sk = sk_max (never more splits than a3v_attention_scratch_floats is sized for)
 void rows_decode_plan(int B, int H, int sk_max, int* nsplit, int* chunk) {
   const int ns = (int)(a3v_attention_scratch_floats(B, H, 64, sk_max) / ((int64_t)B * H * 66));
@@ -365,14 +441,19 @@ void rows_decode_plan(int B, int H, int sk_max, int* nsplit, int* chunk) {
   *chunk = ch2;
 }
 
+// src_row == NULL: the plain kernels on k / vt = the caches of the B rows of the call.  Otherwise the shared-prefix forms: k / vt
+// are the caches of all Btot rows and row b of the call is cache row row0 + b.
 int attention_rows_impl(const void* q, const void* k, const void* vt, void* out, const int32_t* sk, int sk_add, int sk_max, int B, int H,
-                        int Hkv, int hd, const int64_t* strides, float* scratch, int* counters, int dtype, void* stream) {
+                        int Hkv, int hd, const int64_t* strides, float* scratch, int* counters, int dtype, void* stream,
+                        const int32_t* src_row = nullptr, const int32_t* shared = nullptr, int row0 = 0, int Btot = 0) {
   if (!q || !k || !vt || !out || !sk || !strides || B <= 0 || H <= 0 || Hkv <= 0 || sk_max <= 0) return A3V_ERR_ARG;
+  if (src_row && (!shared || row0 < 0 || Btot < row0 + B)) return A3V_ERR_ARG;
   if (H % Hkv || hd <= 0 || hd > 256) return A3V_ERR_SHAPE;
   if (dtype != A3V_BF16 && dtype != A3V_F32) return A3V_ERR_DTYPE;
   // the caches are [B,Hkv,Smax,hd] / [B,Hkv,hd,Smax] in whatever strides: a V^T row (strides[8]) and a K head (strides[4]) bound sk_max
   if (sk_max > strides[8] || (int64_t)sk_max * strides[5] > strides[4]) return A3V_ERR_SHAPE;
-  RowsAttnArgs p;
+  RowsSharedArgs p;
+  p.src_row = src_row; p.shared = shared; p.row0 = row0; p.Btot = Btot;
   p.q = q; p.k = k; p.vt = vt; p.out = out; p.sk = sk;
   p.q_sb = strides[0]; p.q_sh = strides[2];
   p.k_sb = strides[3]; p.k_sh = strides[4]; p.k_ss = strides[5];
@@ -382,8 +463,12 @@ int attention_rows_impl(const void* q, const void* k, const void* vt, void* out,
   p.scale = 1.0f / sqrtf((float)hd);
   hipStream_t st = (hipStream_t)stream;
   if (dtype == A3V_F32 || (hd != 64 && hd != 128)) {
-    if (dtype == A3V_F32) hipLaunchKernelGGL(attn_rows_generic_kernel<float>, dim3(H, B), dim3(64), 0, st, p, hd);
-    else hipLaunchKernelGGL(attn_rows_generic_kernel<bf16_t>, dim3(H, B), dim3(64), 0, st, p, hd);
+    const RowsAttnArgs& pp = p;
+    if (src_row) {
+      if (dtype == A3V_F32) hipLaunchKernelGGL((attn_rows_generic_kernel<float, true>), dim3(H, B), dim3(64), 0, st, p, hd);
+      else hipLaunchKernelGGL((attn_rows_generic_kernel<bf16_t, true>), dim3(H, B), dim3(64), 0, st, p, hd);
+    } else if (dtype == A3V_F32) hipLaunchKernelGGL((attn_rows_generic_kernel<float, false>), dim3(H, B), dim3(64), 0, st, pp, hd);
+    else hipLaunchKernelGGL((attn_rows_generic_kernel<bf16_t, false>), dim3(H, B), dim3(64), 0, st, pp, hd);
     A3V_LAUNCH_CHECK();
     return A3V_OK;
   }
@@ -394,8 +479,12 @@ int attention_rows_impl(const void* q, const void* k, const void* vt, void* out,
   int ns, ch;
   rows_decode_plan(B, H, sk_max, &ns, &ch);
   const dim3 grid(ns, H, B);
-  if (hd == 128) hipLaunchKernelGGL(attn_decode_rows_kernel<128>, grid, dim3(512), 0, st, p, scratch, ns, ch, counters);
-  else hipLaunchKernelGGL(attn_decode_rows_kernel<64>, grid, dim3(512), 0, st, p, scratch, ns, ch, counters);
+  const RowsAttnArgs& pp = p;
+  if (src_row) {
+    if (hd == 128) hipLaunchKernelGGL((attn_decode_rows_kernel<128, true>), grid, dim3(512), 0, st, p, scratch, ns, ch, counters);
+    else hipLaunchKernelGGL((attn_decode_rows_kernel<64, true>), grid, dim3(512), 0, st, p, scratch, ns, ch, counters);
+  } else if (hd == 128) hipLaunchKernelGGL((attn_decode_rows_kernel<128, false>), grid, dim3(512), 0, st, pp, scratch, ns, ch, counters);
+  else hipLaunchKernelGGL((attn_decode_rows_kernel<64, false>), grid, dim3(512), 0, st, pp, scratch, ns, ch, counters);
   A3V_LAUNCH_CHECK();
   return A3V_OK;
 }
@@ -434,6 +523,29 @@ extern "C" int a3v_attention_decode_rows(const void* q, const void* k, const voi
   return attention_rows_impl(q, k, vt, out, sk, 0, sk_max, B, H, Hkv, hd, strides, scratch, counters, dtype, stream);
 }
 
+extern "C" int a3v_attention_decode_rows_shared(const void* q, const void* k, const void* vt, void* out, const int32_t* sk,
+                                                const int32_t* src_row, const int32_t* shared, int sk_max, int B, int H, int Hkv, int hd,
+                                                const int64_t* strides, float* scratch, int* counters, int dtype, void* stream) {
+  if (!src_row) return attention_rows_impl(q, k, vt, out, sk, 0, sk_max, B, H, Hkv, hd, strides, scratch, counters, dtype, stream);
+  return attention_rows_impl(q, k, vt, out, sk, 0, sk_max, B, H, Hkv, hd, strides, scratch, counters, dtype, stream, src_row, shared, 0, B);
+}
+
+extern "C" int a3v_kv_copy_span(const void* const* k_ptrs, const void* const* vt_ptrs, int n_layers, int src_row, const int32_t* dst_rows,
+                                int n_dst, int B, int lo, int hi, int Hkv, int hd, int Smax, int dtype, void* stream) {
+  if (!k_ptrs || !vt_ptrs || n_layers <= 0 || n_dst < 0 || (n_dst > 0 && !dst_rows) || B <= 0 || src_row < 0 || src_row >= B) return A3V_ERR_ARG;
+  if (dtype != A3V_BF16 && dtype != A3V_F32) return A3V_ERR_DTYPE;
+  if (Hkv <= 0 || hd <= 0 || hd % 8 || Smax <= 0 || Smax % 8 || lo < 0 || hi < lo || hi - lo >= 64 || hi > Smax) return A3V_ERR_SHAPE;
+  if (n_layers > 65535 || Hkv > 65535) return A3V_ERR_SHAPE;
+  if (hi == lo || n_dst == 0) return A3V_OK;             // nothing to copy: nothing launched
+  const dim3 g(n_dst, Hkv, n_layers);
+  if (dtype == A3V_BF16)
+    hipLaunchKernelGGL(kv_copy_span_kernel<bf16_t>, g, dim3(256), 0, (hipStream_t)stream, k_ptrs, vt_ptrs, src_row, dst_rows, B, lo, hi, Hkv, hd, Smax);
+  else
+    hipLaunchKernelGGL(kv_copy_span_kernel<float>, g, dim3(256), 0, (hipStream_t)stream, k_ptrs, vt_ptrs, src_row, dst_rows, B, lo, hi, Hkv, hd, Smax);
+  A3V_LAUNCH_CHECK();
+  return A3V_OK;
+}
+
 extern "C" int a3v_generate_step_rows(const float* logits, int64_t ld, const int64_t* sampled, int B, int V, int64_t* tokens,
                                       int64_t ld_tok, int32_t* cur, const int32_t* limit, int pos_base, const int64_t* stop_seq,
                                       const int32_t* stop_off, int n_stop, uint8_t* stopped, int64_t* stop_pos, int32_t* live,
@@ -450,9 +562,11 @@ extern "C" int a3v_llama_decode_step_rows_form(int B, int dim, int H, int Hkv, i
   return a3v_llama_decode_step_form(B, dim, H, Hkv, hd, ffn, w8) == 2 ? 2 : 0;
 }
 
-extern "C" int a3v_llama_decode_step_rows(const a3v_llama_layer* layers, int n_layers, void* h, void* xn, void* qkv, void* att, void* act,
-                                          float* attn_scratch, void* skinny_ws, const float* cos_sin, const int32_t* pos, int pos_max,
-                                          int B, int dim, int H, int Hkv, int hd, int ffn, int Smax, float eps, void* stream) {
+namespace {
+int decode_step_rows_impl(const a3v_llama_layer* layers, int n_layers, void* h, void* xn, void* qkv, void* att, void* act,
+                          float* attn_scratch, void* skinny_ws, const float* cos_sin, const int32_t* pos, const int32_t* src_row,
+                          const int32_t* shared, int pos_max, int B, int dim, int H, int Hkv, int hd, int ffn, int Smax, float eps,
+                          void* stream) {
   if (!layers || n_layers <= 0 || !h || !xn || !qkv || !att || !act || !attn_scratch || !skinny_ws || !cos_sin || !pos) return A3V_ERR_ARG;
   if (B <= 0 || B > 32 || pos_max < 0 || pos_max >= Smax || Smax % 8) return A3V_ERR_SHAPE;
   const int w8 = layers[0].wqkv_q != nullptr ? 1 : layers[0].wqkv_n4 != nullptr ? 2 : 0;
@@ -502,7 +616,12 @@ extern "C" int a3v_llama_decode_step_rows(const a3v_llama_layer* layers, int n_l
       if ((rc = a3v_gemv_fused(hc, dim, wqkv, dim / dv, sqkv, q4, qc, ldq, nb, (int)ldq, dim, nullptr, 0, 0, L.attn_norm_w, ssq, eps, nullptr,
                                0, nullptr, nullptr, nullptr, H, Hkv, hd, Smax, 0, skinny_ws, stream))) return rc;    // plain store: no RoPE epilogue
       if ((rc = a3v_rope_kvcache_rows(qc, ldq, qc, ldq, kc, vc, cos_sin, pc, nb, H, Hkv, hd, Smax, A3V_BF16, stream))) return rc;
-      if ((rc = attention_rows_impl(qc, kc, vc, ac, pc, 1, pos_max + 1, nb, H, Hkv, hd, strides, attn_scratch, actr, A3V_BF16, stream))) return rc;
+      if (!src_row)
+        rc = attention_rows_impl(qc, kc, vc, ac, pc, 1, pos_max + 1, nb, H, Hkv, hd, strides, attn_scratch, actr, A3V_BF16, stream);
+      else                                             // src_row[] names rows of the whole cache: its base, and the chunk's first row
+        rc = attention_rows_impl(qc, L.k_cache, L.vt_cache, ac, pc, 1, pos_max + 1, nb, H, Hkv, hd, strides, attn_scratch, actr, A3V_BF16,
+                                 stream, src_row + b0, shared + b0, b0, B);
+      if (rc) return rc;
       if ((rc = a3v_gemv_fused(ac, (int64_t)H * hd, wo, (int64_t)H * hd / dv, so, q4, hc, dim, nb, dim, H * hd, hc, dim, A3V_EPI_RESIDUAL,
                                nullptr, nullptr, eps, ssq, 0, nullptr, nullptr, nullptr, H, Hkv, hd, Smax, 0, skinny_ws, stream))) return rc;
       if ((rc = a3v_gemv_fused(hc, dim, w13, dim / dv, s13, q4, fc, ffn, nb, 2 * ffn, dim, nullptr, 0, A3V_EPI_SWIGLU, L.ffn_norm_w, ssq, eps,
@@ -512,4 +631,21 @@ extern "C" int a3v_llama_decode_step_rows(const a3v_llama_layer* layers, int n_l
     }
   }
   return A3V_OK;
+}
+}  // namespace
+
+extern "C" int a3v_llama_decode_step_rows(const a3v_llama_layer* layers, int n_layers, void* h, void* xn, void* qkv, void* att, void* act,
+                                          float* attn_scratch, void* skinny_ws, const float* cos_sin, const int32_t* pos, int pos_max,
+                                          int B, int dim, int H, int Hkv, int hd, int ffn, int Smax, float eps, void* stream) {
+  return decode_step_rows_impl(layers, n_layers, h, xn, qkv, att, act, attn_scratch, skinny_ws, cos_sin, pos, nullptr, nullptr, pos_max, B,
+                               dim, H, Hkv, hd, ffn, Smax, eps, stream);
+}
+
+extern "C" int a3v_llama_decode_step_rows_shared(const a3v_llama_layer* layers, int n_layers, void* h, void* xn, void* qkv, void* att,
+                                                 void* act, float* attn_scratch, void* skinny_ws, const float* cos_sin, const int32_t* pos,
+                                                 const int32_t* src_row, const int32_t* shared, int pos_max, int B, int dim, int H, int Hkv,
+                                                 int hd, int ffn, int Smax, float eps, void* stream) {
+  if (!src_row != !shared) return A3V_ERR_ARG;
+  return decode_step_rows_impl(layers, n_layers, h, xn, qkv, att, act, attn_scratch, skinny_ws, cos_sin, pos, src_row, shared, pos_max, B,
+                               dim, H, Hkv, hd, ffn, Smax, eps, stream);
 }

@@ -152,10 +152,44 @@ def get_args_parser():
     p.add_argument("--save_scores", action="store_true", default=False,
                    help="every record gains \"logprob_sum\" and \"logprobs\": the model's own log-probability of the answer's tokens "
                         "(raw logits, temperature 1), a confidence for AP-style evaluation")
+    p.add_argument("--num_samples", type=int, default=1,
+                   help="N > 1: draw N answers per (image, question) from ONE prefill (MetaModel.generate_many(n=N): the image is "
+                        "encoded once and the prompt's keys are stored once) and keep the most confident well-formed box; every record "
+                        "gains \"samples\".  Needs --continuous_rows >= N and --temperature > 0")
     return p
 
 
+def make_record(answer: str, score=None) -> dict:
+    """answer / format_answer / fail of one generated text, with its logprob_sum if a score is given"""
+    answer = postprocess_answer(answer)
+    box = format_bounding_box(answer)
+    rec = {"answer": answer, "format_answer": box, "fail": len(box) != 4 or box[0] > box[2] or box[1] > box[3]}
+    if score is not None:
+        rec["logprob_sum"] = score["sum"]
+    return rec
+
+
+def select_sample(samples) -> int:
+    """Best-of-n: the index of the sample with the largest ``logprob_sum`` among those with ``fail == False``; if every sample
+    failed, the largest ``logprob_sum`` overall.  Ties go to the first."""
+    pool = [k for k, s in enumerate(samples) if not s["fail"]] or list(range(len(samples)))
+    return max(pool, key=lambda k: (samples[k]["logprob_sum"], -k))
+
+
+def check_num_samples(args) -> int:
+    n = int(getattr(args, "num_samples", 1))
+    if n < 1:
+        raise SystemExit(f"--num_samples {n}: at least 1")
+    if n > 1 and getattr(args, "continuous_rows", 0) < n:
+        raise SystemExit(f"--num_samples {n} decodes the {n} answers of a prompt in {n} KV-cache rows at once: add --continuous_rows R with R >= {n}")
+    if n > 1 and not args.temperature > 0:
+        raise SystemExit(f"--num_samples {n} with --temperature 0 would draw the same greedy answer {n} times: set --temperature > 0 "
+                         "(the recipe's 0.1), or --num_samples 1")
+    return n
+
+
 def main(args):
+    num_samples = check_num_samples(args)      # before the model is built
     distributed = "RANK" in os.environ and "WORLD_SIZE" in os.environ
     rank, world, local = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("LOCAL_RANK", 0))
     if args.model_parallel_size != 1:
@@ -203,12 +237,24 @@ def main(args):
     # dataset shuffle, :304; its sampling stream is whatever the process left in the generator)
     torch.manual_seed(args.seed + rank)
     save_scores = getattr(args, "save_scores", False)
-    controls = dict(repetition_penalty=getattr(args, "repetition_penalty", 1.0), return_logprobs=save_scores)
+    controls = dict(repetition_penalty=getattr(args, "repetition_penalty", 1.0), return_logprobs=save_scores or num_samples > 1)
     if getattr(args, "top_k", 0) or getattr(args, "min_p", 0.0):      # opt-in: with the defaults the calls below are what they were
         controls.update(top_k=args.top_k, min_p=args.min_p)
     with torch.no_grad():
         for image, qids, prompts, annotations, paths in loader:
             image = pre.batch(image) if isinstance(image, list) else image.to(dev)
+            if num_samples > 1:    # best-of-n: n answers per prompt from one prefill, the most confident well-formed one is the record's
+                answers, scores = model.generate_many(prompts, image, batch_rows=rows, max_gen_len=args.max_gen_len,
+                                                      temperature=args.temperature, top_p=args.top_p, n=num_samples, **controls)
+                for texts, scs, annotation, question, path in zip(answers, scores, annotations, prompts, paths):
+                    samples = [make_record(t, sc) for t, sc in zip(texts, scs)]
+                    best = select_sample(samples)
+                    b = samples[best]
+                    outputs.append({"answer": b["answer"], "format_answer": b["format_answer"], "annotation": annotation,
+                                    "question": question, "image": path, "fail": b["fail"], "samples": samples})
+                    if save_scores:
+                        outputs[-1].update(logprob_sum=scs[best]["sum"], logprobs=scs[best]["logprobs"])
+                continue
             if rows > 0:           # a chunk of a few batches at a time: the loader's workers stay ahead of the decode
                 answers = model.generate_many(prompts, image, batch_rows=rows, max_gen_len=args.max_gen_len, temperature=args.temperature,
                                               top_p=args.top_p, **controls)

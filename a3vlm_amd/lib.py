@@ -130,6 +130,8 @@ SIGNATURES = {
     "a3v_rope_kvcache_rows": (I, [P, L, P, L, P, P, P, P, I, I, I, I, I, I, P]),
     "a3v_attention_decode_rows": (I, [P, P, P, P, P, I, I, I, I, I, ctypes.POINTER(c_int64), P, P, I, P]),
     "a3v_attention_decode_rows_splits": (I, [I, I, I]),
+    "a3v_attention_decode_rows_shared": (I, [P, P, P, P, P, P, P, I, I, I, I, I, ctypes.POINTER(c_int64), P, P, I, P]),
+    "a3v_kv_copy_span": (I, [P, P, I, I, P, I, I, I, I, I, I, I, I, P]),
     "a3v_generate_step_rows": (I, [P, L, P, I, I, P, L, P, P, I, P, P, I, P, P, P, P, P, P]),
     "a3v_llama_decode_step_rows_form": (I, [I, I, I, I, I, I, I]),
     "a3v_seen_mark": (I, [P, L, P, P, L, I, I, P]),
@@ -164,6 +166,8 @@ SIGNATURES["a3v_llama_decode_step_kv8"] = (I, [ctypes.POINTER(LlamaLayer), ctype
                                                I, I, I, I, I, I, I, I, F, P])
 SIGNATURES["a3v_llama_decode_step_form"] = (I, [I, I, I, I, I, I, I])
 SIGNATURES["a3v_llama_decode_step_rows"] = (I, [ctypes.POINTER(LlamaLayer), I, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, F, P])
+SIGNATURES["a3v_llama_decode_step_rows_shared"] = (I, [ctypes.POINTER(LlamaLayer), I, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I,
+                                                       F, P])
 
 _lib = None
 

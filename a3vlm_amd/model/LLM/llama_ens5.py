@@ -1047,20 +1047,30 @@ class Transformer(nn.Module):
         self._lm_head_last(xn, logits, False)
         return logits
 
-    def _decode_step_rows(self, h: torch.Tensor, B: int, pos: torch.Tensor, pos_max: int) -> None:
-        """One bf16 decode step with row b at cache position pos[b] from one C call (a3v_llama_decode_step_rows)."""
+    def _decode_step_rows(self, h: torch.Tensor, B: int, pos: torch.Tensor, pos_max: int, src_row=None, shared=None) -> None:
+        """One bf16 decode step with row b at cache position pos[b] from one C call (a3v_llama_decode_step_rows; with shared prompt
+        keys a3v_llama_decode_step_rows_shared)."""
         a = self.args
         tab = self._llama_layer_table()
         H, Hkv, hd = self.n_heads, self.n_kv_heads, self.head_dim
         xn, qkv, att, act, scratch, sws = self._decode_step_buffers(B)
+        if src_row is not None:
+            rc = _lib.load().a3v_llama_decode_step_rows_shared(tab, self.n_layers, h.data_ptr(), xn.data_ptr(), qkv.data_ptr(), att.data_ptr(),
+                                                             act.data_ptr(), scratch.data_ptr(), sws.data_ptr(), self._cos_sin_dev().data_ptr(),
+                                                             pos.data_ptr(), src_row.data_ptr(), shared.data_ptr(), pos_max, B, a.dim, H, Hkv,
+                                                             hd, self.ffn, self._k_cache[0].shape[2], a.norm_eps,
+                                                             torch.cuda.current_stream().cuda_stream)
+            _lib.check(rc, "a3v_llama_decode_step_rows_shared")
+            return
         rc = _lib.load().a3v_llama_decode_step_rows(tab, self.n_layers, h.data_ptr(), xn.data_ptr(), qkv.data_ptr(), att.data_ptr(),
                                                   act.data_ptr(), scratch.data_ptr(), sws.data_ptr(), self._cos_sin_dev().data_ptr(),
                                                   pos.data_ptr(), pos_max, B, a.dim, H, Hkv, hd, self.ffn, self._k_cache[0].shape[2],
                                                   a.norm_eps, torch.cuda.current_stream().cuda_stream)
         _lib.check(rc, "a3v_llama_decode_step_rows")
 
-    def _decoder_layers_rows(self, h: torch.Tensor, B: int, pos: torch.Tensor, pos_max: int) -> None:
-        """The ragged step kernel by kernel: _decoder_layers at S = 1 with a3v_rope_kvcache_rows / a3v_attention_decode_rows."""
+    def _decoder_layers_rows(self, h: torch.Tensor, B: int, pos: torch.Tensor, pos_max: int, src_row=None, shared=None) -> None:
+        """The ragged step kernel by kernel: _decoder_layers at S = 1 with a3v_rope_kvcache_rows / a3v_attention_decode_rows (with
+        shared prompt keys: a3v_attention_decode_rows_shared)."""
         a = self.args
         H, Hkv, hd = self.n_heads, self.n_kv_heads, self.head_dim
         self._pack()
@@ -1079,20 +1089,31 @@ class Transformer(nn.Module):
             kc, vc = self._k_cache[i], self._vt_cache[i]
             smax = kc.shape[2]
             strides = (ldq, ldq, hd, Hkv * smax * hd, smax * hd, hd, Hkv * hd * smax, hd * smax, smax, H * hd, H * hd, hd)
-            self._layer(i, path, h, (xn, qkv, att, act),
-                        lambda: ops.rope_kvcache_rows(qkv, qkv, kc, vc, cs, pos, B, H, Hkv, hd),
-                        lambda: ops.attention_decode_rows(qkv, kc, vc, att, sk, pos_max + 1, B, H, Hkv, hd, strides, scratch, counters))
+            if src_row is None:
+                attend = lambda: ops.attention_decode_rows(qkv, kc, vc, att, sk, pos_max + 1, B, H, Hkv, hd, strides, scratch, counters)
+            else:
+                attend = lambda: ops.attention_decode_rows_shared(qkv, kc, vc, att, sk, src_row, shared, pos_max + 1, B, H, Hkv, hd, strides,
+                                                                  scratch, counters)
+            self._layer(i, path, h, (xn, qkv, att, act), lambda: ops.rope_kvcache_rows(qkv, qkv, kc, vc, cs, pos, B, H, Hkv, hd), attend)
 
     @torch.no_grad()
     def forward_inference_rows(self, next_tok: torch.Tensor, pos: torch.Tensor, pos_max: int,
-                               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                               out: Optional[torch.Tensor] = None, *, src_row: Optional[torch.Tensor] = None,
+                               shared: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One decode step with every cache row at its own position: next_tok [B] (int64, device) is embedded, row b is written at
         cache position pos[b] (int32, device, image words included; negative = idle row: nothing written, its logits are not
         meaningful) and attends to pos[b] + 1 keys.  ``pos_max`` = the largest position (host value).  fp32 logits [B, V] (into
-        ``out`` if given).  bf16 and fp32 streams."""
+        ``out`` if given).  bf16 and fp32 streams.
+        ``src_row`` / ``shared`` (both or neither; int32 [B], device): shared prompt keys -- row b reads its keys below shared[b]
+        (a multiple of 64, see ``share_prefix``) from cache row src_row[b] (include/a3vlm_hip.h, "Shared prompt keys").  Without
+        them the call is the one it was."""
         self._ragged_check()
         a = self.args
         B = next_tok.shape[0]
+        if (src_row is None) != (shared is None):
+            raise ValueError("forward_inference_rows: src_row and shared are given together, or neither")
+        if src_row is not None:
+            assert all(t.dtype == torch.int32 and t.numel() == B and t.is_contiguous() and t.is_cuda for t in (src_row, shared))
         assert self._k_cache and self._k_cache[0].shape[0] == B, "allocate_rows(batch_rows) first; one token per cache row"
         assert next_tok.dtype == torch.int64 and pos.dtype == torch.int32 and pos.numel() == B and pos.is_contiguous()
         assert 0 <= pos_max < min(self._k_cache[0].shape[2], self._cos_sin_cpu.shape[0]), pos_max
@@ -1102,11 +1123,30 @@ class Transformer(nn.Module):
         fused = (self._dtype == torch.bfloat16 and not getattr(self, "_per_kernel_decode", False) and w8 is not None
                  and _lib.load().a3v_llama_decode_step_rows_form(B, a.dim, a.n_heads, self.n_kv_heads, self.head_dim, self.ffn, w8) == 2)
         if fused:
-            self._decode_step_rows(h, B, pos, pos_max)
+            self._decode_step_rows(h, B, pos, pos_max, src_row, shared)
         else:
-            self._decoder_layers_rows(h, B, pos, pos_max)
+            self._decoder_layers_rows(h, B, pos, pos_max, src_row, shared)
         xn = self._buf("xn_last", (B, a.dim))
         ops.rmsnorm(h, self.norm.weight, xn, a.norm_eps)
         logits = out if out is not None else torch.empty(B, a.vocab_size, dtype=torch.float32, device=self._device)
         self._lm_head_last(xn, logits, B <= 32)
         return logits
+
+    def share_prefix(self, src_row: int, dst_rows, P: int) -> int:
+        """Makes the rows ``dst_rows`` siblings of cache row ``src_row``, whose prompt fills positions [0, P) (image words
+        included): the keys below the last 64 boundary, P & ~63, stay in the source row alone and are read from there
+        (``forward_inference_rows(..., src_row=, shared=)``); the rest of the prompt, [P & ~63, P), is copied into every sibling's
+        own row by one launch over all layers (a3v_kv_copy_span).  Returns P & ~63, the value to put in ``shared[]``."""
+        self._ragged_check()
+        assert self._k_cache and 0 <= src_row < self._k_cache[0].shape[0], "allocate_rows(batch_rows) first"
+        assert 0 <= P <= self._k_cache[0].shape[2], (P, self._k_cache[0].shape[2])
+        lo = P & ~63
+        dst = dst_rows if isinstance(dst_rows, torch.Tensor) else torch.tensor(list(dst_rows), dtype=torch.int32, device=self._device)
+        if dst.numel() and P > lo:
+            key = tuple(t.data_ptr() for t in self._k_cache) + tuple(t.data_ptr() for t in self._vt_cache)
+            ptrs = self._ws.get("kv_ptrs")
+            if ptrs is None or ptrs[0] != key:             # the device table of base pointers follows the cache allocation
+                ptrs = self._ws["kv_ptrs"] = (key, None)
+            tab = ops.kv_copy_span(self._k_cache, self._vt_cache, src_row, dst, lo, P, ptrs[1])
+            self._ws["kv_ptrs"] = (key, tab)
+        return lo

@@ -420,7 +420,7 @@ class MetaModel(nn.Module):
                       max_gen_len=512, temperature: float = 0.0, top_p: float = 0.95,
                       additional_stop_symbols: Iterable[str] = (), return_ids: bool = False, poll_every: int = 4,
                       sample_uniforms: Optional[torch.Tensor] = None, repetition_penalty: float = 1.0,
-                      return_logprobs: bool = False, top_k: int = 0, min_p: float = 0.0):
+                      return_logprobs: bool = False, top_k: int = 0, min_p: float = 0.0, n: int = 1):
         """Any number of prompts through ``batch_rows`` KV-cache rows (no reference counterpart; opt-in): every row decodes at its
         own position, and a row whose answer is finished is prefilled with the next prompt while the others keep decoding, so a
         short answer does not hold its row until the longest answer of a batch is done.  Answers come back in input order.
@@ -434,12 +434,27 @@ class MetaModel(nn.Module):
         ``repetition_penalty`` / ``return_logprobs``: as in ``generate``; the seen set belongs to the cache row and is cleared and
         re-marked when the row is refilled, a finished row's log-probs are read back with its ids.  ``top_k`` / ``min_p``: as in
         ``generate``.
+        ``n > 1`` (parallel sampling; needs ``temperature > 0`` and ``n <= batch_rows``): n answers per prompt from ONE prefill.  A
+        prompt is admitted when n rows are free (``GroupScheduler``); the lowest is the leader: it is prefilled and runs sample 0,
+        its logits start every sample, and the siblings read the prompt's keys below the last 64 boundary from the leader's row
+        (``share_prefix``: the image is encoded once and most of the prompt is stored once).  Uniforms are indexed [prompt, sample,
+        generated index] (``sample_uniforms`` [N, n, >= max steps]; [N, >= max steps] is still taken when n == 1), so sample s of a
+        prompt is the answer of that prompt alone with that row of uniforms.  Every per-prompt element of the return (text, ids,
+        scores) becomes a list of n, in sample order.  With ``n == 1`` the call is the one it was.
         Not for the fp8 KV cache, LoRA models before ``merge_lora()`` or the two-image plugin (each raises, naming the way out)."""
-        from .ragged import RowScheduler
+        from .ragged import GroupScheduler, RowScheduler
         if isinstance(prompts, str):
             raise ValueError(f"{self.__class__}.generate_many expects a LIST of prompts, but str is given")
         controls = genctl.wanted(repetition_penalty, return_logprobs)      # ValueError before any device use
         top_k, min_p = genctl.check_filters(top_k, min_p)
+        n = int(n)
+        if n < 1:
+            raise ValueError(f"generate_many: n = {n} samples per prompt; n >= 1")
+        if n > 1 and not temperature > 0:
+            raise ValueError(f"generate_many: n = {n} samples per prompt need temperature > 0 (at temperature 0 all {n} are the same "
+                             "greedy answer); use n=1")
+        if n > int(batch_rows):
+            raise ValueError(f"generate_many: n = {n} samples per prompt need n cache rows at once: batch_rows = {batch_rows} < n")
         llma = self.llma
         llma._ragged_check()                                  # before anything is allocated or launched
         dev = self._device
@@ -485,10 +500,12 @@ class MetaModel(nn.Module):
         uni = sampled = ubase = None
         if temperature > 0:
             n_steps = max(max(lim - ln for lim, ln in zip(limits, lens)), 1)
-            uni = (torch.rand(N, n_steps, device=dev, dtype=torch.float32) if sample_uniforms is None
+            uni = (torch.rand(N, n, n_steps, device=dev, dtype=torch.float32) if sample_uniforms is None
                    else sample_uniforms.to(device=dev, dtype=torch.float32).contiguous())
-            assert uni.shape[0] == N and uni.shape[1] >= n_steps, (tuple(uni.shape), N, n_steps)
-            n_uni = uni.shape[1]
+            if n == 1 and uni.dim() == 2:
+                uni = uni[:, None]
+            assert uni.dim() == 3 and tuple(uni.shape[:2]) == (N, n) and uni.shape[2] >= n_steps, (tuple(uni.shape), N, n, n_steps)
+            n_uni = uni.shape[2]
             uni = uni.reshape(-1)
             sampled = torch.zeros(R, dtype=torch.long, device=dev)
             ubase = torch.zeros(R, dtype=torch.long, device=dev)         # index of the row's uniform at scheduler step 0
@@ -497,24 +514,41 @@ class MetaModel(nn.Module):
         if controls:
             gc = genctl.GenControls(R, args.vocab_size, max(lim - ln for lim, ln in zip(limits, lens)), repetition_penalty,
                                     return_logprobs, dev)
-        sched = RowScheduler(lens, limits, R, W)
-        ids: List[Optional[List[int]]] = [None] * N
-        lps: List[List[float]] = [[] for _ in range(N)]
+        # answers are kept per (prompt, sample) at index i * n + s
+        sched = RowScheduler(lens, limits, R, W) if n == 1 else GroupScheduler(lens, limits, R, W, n)
+        ids: List[Optional[List[int]]] = [None] * (N * n)
+        lps: List[List[float]] = [[] for _ in range(N * n)]
         llma.allocate_rows(R)
+        src_row = shared = None
+        if n > 1:                          # shared prompt keys: row r reads its keys below shared[r] from cache row src_row[r]
+            src_row = torch.arange(R, dtype=torch.int32, device=dev)
+            shared = torch.zeros(R, dtype=torch.int32, device=dev)
+        sample_of = [0] * R
         while True:
-            for row, i in sched.refill():
+            for i, rows in ([(i, [row]) for row, i in sched.refill()] if n == 1 else sched.refill()):
+                lead = rows[0]
                 t = torch.tensor(prompt_tokens[i], dtype=torch.long, device=dev)
-                logits[row].copy_(llma.prefill_row(row, t[None], None if images is None else images[i:i + 1])[0])
-                tokens[row].zero_()
-                tokens[row, :lens[i]] = t
-                cur[row], limit[row], stopped[row], stop_pos[row] = lens[i], limits[i], False, lens[i] + 1
-                if gc is not None:         # the row's seen set is its new prompt alone; the first id (prefill logits) is recorded below
-                    gc.prompt_len[row] = lens[i]
-                    gc.mark_prompts(tokens, row)
-                if ubase is not None:
-                    ubase[row] = i * n_uni - sched.steps
+                logits[lead].copy_(llma.prefill_row(lead, t[None], None if images is None else images[i:i + 1])[0])
+                if n > 1:                  # one prefill per group: the siblings start from the leader's logits and read its prefix
+                    src_row[lead], shared[lead] = lead, 0
+                    sib = torch.tensor(rows[1:], dtype=torch.long, device=dev)
+                    for r in rows[1:]:
+                        logits[r].copy_(logits[lead])
+                    src_row[sib] = lead
+                    shared[sib] = llma.share_prefix(lead, sib.to(torch.int32), W + lens[i])
+                for s, row in enumerate(rows):
+                    sample_of[row] = s
+                    tokens[row].zero_()
+                    tokens[row, :lens[i]] = t
+                    cur[row], limit[row], stopped[row], stop_pos[row] = lens[i], limits[i], False, lens[i] + 1
+                    if gc is not None:     # the row's seen set is its new prompt alone; the first id (prefill logits) is recorded below
+                        gc.prompt_len[row] = lens[i]
+                        gc.mark_prompts(tokens, row)
+                    if ubase is not None:
+                        ubase[row] = (i * n + s) * n_uni - sched.steps
             for i in sched.finished_at_once:
-                ids[i] = []
+                for s in range(n):
+                    ids[i * n + s] = []
             sched.finished_at_once.clear()
             if not sched.occupied():
                 break
@@ -536,17 +570,25 @@ class MetaModel(nn.Module):
                 if fin:
                     sp = stop_pos.tolist()
                     for r, i in fin:
-                        ids[i] = tokens[r, lens[i]:sp[r]].tolist()
+                        j = i * n + sample_of[r]
+                        ids[j] = tokens[r, lens[i]:sp[r]].tolist()
                         if return_logprobs:
-                            lps[i] = gc.lp[r, :len(ids[i])].tolist()
+                            lps[j] = gc.lp[r, :len(ids[j])].tolist()
                         sched.release(r)
                     if not sched.occupied():
                         continue                                         # refill (or leave) before another step
-            llma.forward_inference_rows(next_tok, pos, pos_max, out=logits)
+            if n == 1:
+                llma.forward_inference_rows(next_tok, pos, pos_max, out=logits)
+            else:
+                llma.forward_inference_rows(next_tok, pos, pos_max, out=logits, src_row=src_row, shared=shared)
         decoded = [self.tokenizer.decode(t) for t in ids]
+        scores = [genctl.score(x) for x in lps] if return_logprobs else None
+        if n > 1:                          # per prompt: a list of n, sample order
+            decoded, ids = ([x[i * n:(i + 1) * n] for i in range(N)] for x in (decoded, ids))
+            if scores is not None:
+                scores = [scores[i * n:(i + 1) * n] for i in range(N)]
         ret = (decoded, ids) if return_ids else decoded
         if return_logprobs:
-            scores = [genctl.score(x) for x in lps]
             ret = ret + (scores,) if return_ids else (decoded, scores)
         return ret
 

@@ -72,3 +72,89 @@ class RowScheduler:
         self.rows[row] = None
         self.next_pos[row] = -1
         return i
+
+
+class GroupScheduler:
+    """Parallel sampling (``generate_many(..., n=...)``): every prompt runs ``n`` samples that share the prompt's keys, which are
+    stored once, in the row of the group's leader.
+
+    * Prompts are admitted in input order, and only when ``n`` rows are free: a prompt takes the n lowest free rows.  The lowest
+      is the leader (it is prefilled and runs sample 0), the others run samples 1..n-1 in row order.
+    * ``refill()`` returns the admitted groups as ``(prompt, [rows])``; ``sample[row]`` is the sample a row runs.
+    * ``release(row)`` ends the row's sample.  A sibling's row is free at once.  The leader's row is free only when the last
+      sample of its group has been released, because its prefix is read until then: a leader that stopped earlier sits idle
+      meanwhile (it is no longer occupied: ``advance()`` does not count it).
+    * ``advance()`` / ``occupied()`` / ``pending()`` / ``done()`` / ``finished_at_once`` / ``steps`` as in ``RowScheduler``; with
+      ``n == 1`` the assignments, the ``pos_max`` values and ``steps`` are that class's on any script of finishes."""
+
+    def __init__(self, prompt_lens: Sequence[int], limits: Sequence[int], batch_rows: int, pos_base: int = 0, n: int = 1):
+        assert len(prompt_lens) == len(limits) and batch_rows > 0 and pos_base >= 0
+        assert 1 <= n <= batch_rows, (n, batch_rows)
+        self.prompt_lens, self.limits, self.pos_base, self.n = list(prompt_lens), list(limits), pos_base, n
+        self.rows: List[Optional[int]] = [None] * batch_rows      # prompt index per row that runs a sample
+        self.sample: List[int] = [0] * batch_rows                 # which of the prompt's n samples
+        self.leader: List[int] = [-1] * batch_rows                # the leader row of the row's group
+        self.left: List[int] = [0] * batch_rows                   # per leader row: samples of its group not yet released
+        self.next_pos: List[int] = [-1] * batch_rows
+        self.generated: List[int] = [0] * batch_rows
+        self.next_prompt = 0
+        self.finished_at_once: List[int] = []
+        self.steps = 0
+
+    def occupied(self) -> List[Tuple[int, int]]:
+        return [(r, i) for r, i in enumerate(self.rows) if i is not None]
+
+    def free_rows(self) -> List[int]:
+        """rows that run nothing and whose prefix nobody reads"""
+        return [r for r, i in enumerate(self.rows) if i is None and self.left[r] == 0]
+
+    def held(self) -> List[int]:
+        """leader rows that have finished their own sample and wait for their group"""
+        return [r for r, i in enumerate(self.rows) if i is None and self.left[r] > 0]
+
+    def pending(self) -> int:
+        return len(self.prompt_lens) - self.next_prompt
+
+    def done(self) -> bool:
+        return self.pending() == 0 and not self.occupied()
+
+    def refill(self) -> List[Tuple[int, List[int]]]:
+        out = []
+        while True:
+            free = self.free_rows()
+            if len(free) < self.n:
+                break
+            while self.next_prompt < len(self.prompt_lens) and self.limits[self.next_prompt] <= self.prompt_lens[self.next_prompt]:
+                self.finished_at_once.append(self.next_prompt)
+                self.next_prompt += 1
+            if self.next_prompt == len(self.prompt_lens):
+                break
+            i = self.next_prompt
+            self.next_prompt += 1
+            rows = free[:self.n]
+            self.left[rows[0]] = self.n
+            for s, r in enumerate(rows):
+                self.rows[r], self.sample[r], self.leader[r] = i, s, rows[0]
+                self.next_pos[r] = self.pos_base + self.prompt_lens[i]
+                self.generated[r] = 0
+            out.append((i, rows))
+        return out
+
+    def advance(self) -> int:
+        occ = self.occupied()
+        assert occ, "advance() without an occupied row"
+        pos_max = 0
+        for r, i in occ:
+            pos_max = max(pos_max, min(self.next_pos[r], self.pos_base + self.limits[i] - 1))
+            self.next_pos[r] += 1
+            self.generated[r] += 1
+        self.steps += 1
+        return pos_max
+
+    def release(self, row: int) -> int:
+        i = self.rows[row]
+        assert i is not None, row
+        self.rows[row] = None
+        self.next_pos[row] = -1
+        self.left[self.leader[row]] -= 1
+        return i

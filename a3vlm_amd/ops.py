@@ -609,6 +609,42 @@ def attention_decode_rows(q, k, vt, out, sk, sk_max: int, B, H, Hkv, hd, strides
     return out
 
 
+def attention_decode_rows_shared(q, k, vt, out, sk, src_row, shared, sk_max: int, B, H, Hkv, hd, strides, scratch=None, counters=None):
+    """``attention_decode_rows`` with shared prompt keys: row b reads its keys below min(shared[b], sk[b]) rounded down to a
+    multiple of 64 from cache row src_row[b] (device int32 [B] each; a src_row outside [0, B) or equal to b, or shared <= 0: the
+    plain row).  k / vt hold all B rows.  Bit-equal to ``attention_decode_rows`` on caches with that prefix copied."""
+    _dev(q, k, vt, out, sk, src_row, shared, scratch, counters)
+    assert all(t.dtype == torch.int32 and t.is_contiguous() and t.numel() >= B for t in (sk, src_row, shared))
+    assert k.shape[0] >= B and vt.shape[0] >= B
+    assert scratch is None or (scratch.dtype == torch.float32 and scratch.numel() >= attention_scratch_floats(B, H, hd, sk_max))
+    assert counters is None or (counters.dtype == torch.int32 and counters.numel() >= B * H)
+    rc = _l.load().a3v_attention_decode_rows_shared(_p(q), _p(k), _p(vt), _p(out), _p(sk), _p(src_row), _p(shared), int(sk_max), B, H, Hkv,
+                                                    hd, _Strides(*strides), _p(scratch), _p(counters), dt(q), _stream())
+    _l.check(rc, f"a3v_attention_decode_rows_shared(B={B},sk_max={sk_max},H={H},hd={hd})")
+    return out
+
+
+def kv_copy_span(k_caches, vt_caches, src_row: int, dst_rows, lo: int, hi: int, ptrs=None):
+    """Positions [lo, hi) (0 <= hi - lo < 64) of cache row ``src_row`` into the rows ``dst_rows`` (device int32; entries outside the
+    cache are skipped) of every layer, one launch: k_caches / vt_caches are the per-layer [B,Hkv,Smax,hd] / [B,Hkv,hd,Smax] tensors.
+    ``ptrs``: the device int64 [2, layers] table of their base pointers if the caller keeps one (returned either way)."""
+    k0 = k_caches[0]
+    B, Hkv, Smax, hd = k0.shape
+    for k, v in zip(k_caches, vt_caches):
+        _dev(k, v)
+        assert k.is_contiguous() and v.is_contiguous() and k.dtype == v.dtype == k0.dtype
+        assert tuple(k.shape) == (B, Hkv, Smax, hd) and tuple(v.shape) == (B, Hkv, hd, Smax)
+    _dev(dst_rows)
+    assert dst_rows.dtype == torch.int32 and dst_rows.is_contiguous() and len(k_caches) == len(vt_caches)
+    if ptrs is None:
+        ptrs = torch.tensor([[t.data_ptr() for t in k_caches], [t.data_ptr() for t in vt_caches]], dtype=torch.int64, device=k0.device)
+    assert ptrs.dtype == torch.int64 and tuple(ptrs.shape) == (2, len(k_caches)) and ptrs.is_contiguous()
+    rc = _l.load().a3v_kv_copy_span(_p(ptrs[0]), _p(ptrs[1]), len(k_caches), int(src_row), _p(dst_rows), dst_rows.numel(), B, int(lo),
+                                    int(hi), Hkv, hd, Smax, dt(k0), _stream())
+    _l.check(rc, f"a3v_kv_copy_span(src={src_row},lo={lo},hi={hi},hd={hd})")
+    return ptrs
+
+
 def generate_step_rows(logits, sampled, tokens, cur, limit, pos_base: int, stop_seq, stop_off, n_stop: int, stopped, stop_pos, live,
                        next_tok, pos):
     """One launch = one step of generate_many's bookkeeping (a3v_generate_step_rows): per row argmax (or the sampled id), the

@@ -648,6 +648,46 @@ int a3v_llama_decode_step_rows(const a3v_llama_layer* layers, int n_layers, void
                                int dim, int H, int Hkv, int hd, int ffn, int Smax, float eps, void* stream);
 int a3v_llama_decode_step_rows_form(int B, int dim, int H, int Hkv, int hd, int ffn, int w8);
 
+/* Shared prompt keys (opt-in; parallel sampling: n answers of one prompt decode over ONE stored copy of its keys).  Two more
+ * DEVICE int32[B] arrays sit beside sk / pos:
+ *   src_row[b]  the cache row that holds row b's shared keys.  A value outside [0, B) is read as b (bounded by the kernel: the
+ *               host cannot see a device array).  One level only: the source row's own src_row is never followed.
+ *   shared[b]   row b's keys at positions < S_b are read from row src_row[b] of the same K / V^T caches, every other key from its
+ *               own row, where S_b = min(shared[b], sk[b]) rounded DOWN to a multiple of 64 (a shared[b] that is no multiple of
+ *               64 acts as the multiple below it; one above the row's key count is clamped first, so the keys between the last
+ *               64 boundary below sk[b] and sk[b] are the row's own).  shared[b] <= 0 or src_row[b] == b: exactly the plain row.
+ * Why 64: the split plan rounds a key range to 64 keys, so every 64-key tile of the walk starts at a multiple of 64 in absolute
+ * position and lies wholly in one row; the 16-byte V^T vectors and the clamped re-reads at a range's end never straddle two rows.
+ * Positions below S_b of row b's own cache are never read (they may hold anything).  Idle rows (sk[b] <= 0): zeros, as before.
+ *
+ * a3v_attention_decode_rows_shared: a3v_attention_decode_rows plus the two arrays: the same three forms (bf16 wave-streaming at hd
+ * 64 / 128; one wave per (batch, head) for fp32 and for bf16 at other head dims), the same split plan at sk_max, walk, masks,
+ * (m, l) merges and combine -- only the base pointer of a tile differs.  BIT-EQUALITY CONTRACT: the output equals
+ * a3v_attention_decode_rows on caches in which positions [0, S_b) of row src_row[b] were copied into row b, bit for bit; counters
+ * are left zero.  k / vt must hold all B rows (src_row indexes them).  src_row == NULL: the call IS a3v_attention_decode_rows.
+ * a3v_kv_copy_span: positions [lo, hi), 0 <= hi - lo < 64, of cache row src_row into the rows dst_rows[0..n_dst) (DEVICE int32;
+ * entries outside [0, B) or equal to src_row are skipped) of EVERY layer in one launch: k_ptrs / vt_ptrs are DEVICE arrays of
+ * n_layers base pointers of [B,Hkv,Smax,hd] / [B,Hkv,hd,Smax] caches (16-byte aligned, contiguous; hd and Smax multiples of 8),
+ * bf16 or fp32.  K rows by 16-byte vectors; V^T runs of hi - lo elements per d row, vector stores where aligned and element by
+ * element at the edges.  Nothing outside the span is written.  hi == lo or n_dst == 0 launches nothing.  (A sibling needs
+ * [P & ~63, P) of its leader's prompt of P positions in its own row: the part of the prompt behind the last 64 boundary.)
+ * a3v_llama_decode_step_rows_shared: a3v_llama_decode_step_rows with the two arrays handed to the attention launch: six launches
+ * per layer, the same form query and the same two-chunk rule for 17..32 rows.  src_row[] holds absolute rows of the whole cache:
+ * the attention of the chunk that starts at row b0 gets the un-offset cache base, the slices src_row + b0 / shared + b0 / pos + b0
+ * and the row offset b0 (batch index b of the launch is cache row b0 + b; src_row is bounded by [0, B) of the whole call), so a
+ * sibling in the second chunk may read a leader in the first.  The step writes the new key of row b at pos[b] of its OWN row, so
+ * shared[b] <= pos[b] is the caller's to keep (share_prefix hands out P & ~63 <= P <= pos[b]).  Both arrays NULL: a3v_llama_decode_step_rows; one NULL: an error.
+ * a3v_llama_decode_step_rows keeps its signature and its bits. */
+int a3v_attention_decode_rows_shared(const void* q, const void* k, const void* vt, void* out, const int32_t* sk,
+                                     const int32_t* src_row, const int32_t* shared, int sk_max, int B, int H, int Hkv, int hd,
+                                     const int64_t* strides, float* scratch, int* counters, int dtype, void* stream);
+int a3v_kv_copy_span(const void* const* k_ptrs, const void* const* vt_ptrs, int n_layers, int src_row, const int32_t* dst_rows,
+                     int n_dst, int B, int lo, int hi, int Hkv, int hd, int Smax, int dtype, void* stream);
+int a3v_llama_decode_step_rows_shared(const a3v_llama_layer* layers, int n_layers, void* h, void* xn, void* qkv, void* att, void* act,
+                                      float* attn_scratch, void* skinny_ws, const float* cos_sin, const int32_t* pos,
+                                      const int32_t* src_row, const int32_t* shared, int pos_max, int B, int dim, int H, int Hkv,
+                                      int hd, int ffn, int Smax, float eps, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * Generation controls (opt-in; a3v_genctl.hip): a log-probability per generated token and the HF repetition penalty, on the
  * device inside the step.  No existing entry changes; with the options off none of these is launched.
