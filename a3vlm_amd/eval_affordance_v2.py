@@ -156,7 +156,27 @@ def get_args_parser():
                    help="N > 1: draw N answers per (image, question) from ONE prefill (MetaModel.generate_many(n=N): the image is "
                         "encoded once and the prompt's keys are stored once) and keep the most confident well-formed box; every record "
                         "gains \"samples\".  Needs --continuous_rows >= N and --temperature > 0")
+    p.add_argument("--lookup_decoding", type=int, default=0,
+                   help="D > 0: lookup decoding (MetaModel.generate_many(lookup=D)): every decode step verifies up to D tokens drafted "
+                        "from the row's own earlier tokens; the answers are the greedy ones, every record gains \"accepted_per_step\" "
+                        "(accepted drafts per row step of the generate_many call that produced it).  Needs --continuous_rows R with "
+                        "R * (D + 1) <= 32 and --temperature 0")
     return p
+
+
+def check_lookup(args) -> int:
+    d = int(getattr(args, "lookup_decoding", 0) or 0)
+    if d < 0 or d > 7:
+        raise SystemExit(f"--lookup_decoding {d}: 0 (off) .. 7 drafted tokens per step")
+    if d and getattr(args, "continuous_rows", 0) <= 0:
+        raise SystemExit(f"--lookup_decoding {d} runs on the per-row decode path: add --continuous_rows R")
+    if d and args.temperature > 0:
+        raise SystemExit(f"--lookup_decoding {d} verifies drafts against the greedy choice: set --temperature 0")
+    if d and int(getattr(args, "num_samples", 1)) > 1:
+        raise SystemExit(f"--lookup_decoding {d} is greedy: use --num_samples 1")
+    if d and getattr(args, "continuous_rows", 0) * (d + 1) > 32:
+        raise SystemExit(f"--lookup_decoding {d} with --continuous_rows {args.continuous_rows}: rows * (D + 1) must be <= 32")
+    return d
 
 
 def make_record(answer: str, score=None) -> dict:
@@ -190,6 +210,7 @@ def check_num_samples(args) -> int:
 
 def main(args):
     num_samples = check_num_samples(args)      # before the model is built
+    lookup = check_lookup(args)
     distributed = "RANK" in os.environ and "WORLD_SIZE" in os.environ
     rank, world, local = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("LOCAL_RANK", 0))
     if args.model_parallel_size != 1:
@@ -257,7 +278,7 @@ def main(args):
                 continue
             if rows > 0:           # a chunk of a few batches at a time: the loader's workers stay ahead of the decode
                 answers = model.generate_many(prompts, image, batch_rows=rows, max_gen_len=args.max_gen_len, temperature=args.temperature,
-                                              top_p=args.top_p, **controls)
+                                              top_p=args.top_p, **controls, **({"lookup": lookup} if lookup else {}))
             else:
                 answers = model.generate(prompts, image, max_gen_len=args.max_gen_len, temperature=args.temperature, top_p=args.top_p,
                                          **controls)
@@ -268,6 +289,9 @@ def main(args):
                 fail = len(box) != 4 or box[0] > box[2] or box[1] > box[3]
                 outputs.append({"answer": answer, "format_answer": box, "annotation": annotation, "question": question,
                                 "image": path, "fail": fail})
+                if lookup:
+                    st = model.last_lookup_stats
+                    outputs[-1]["accepted_per_step"] = st["accepted"] / max(st["steps"], 1)
                 if sc is not None:     # the scores of the generated tokens (the text above may be cut further by postprocess_answer)
                     outputs[-1].update(logprob_sum=sc["sum"], logprobs=sc["logprobs"])
     if distributed:

@@ -134,6 +134,13 @@ SIGNATURES = {
     "a3v_kv_copy_span": (I, [P, P, I, I, P, I, I, I, I, I, I, I, I, P]),
     "a3v_generate_step_rows": (I, [P, L, P, I, I, P, L, P, P, I, P, P, I, P, P, P, P, P, P]),
     "a3v_llama_decode_step_rows_form": (I, [I, I, I, I, I, I, I]),
+    "a3v_rope_kvcache_spans": (I, [P, L, P, L, P, P, P, P, P, I, I, I, I, I, I, I, P]),
+    "a3v_attention_verify_rows": (I, [P, P, P, P, P, P, I, I, I, I, I, I, ctypes.POINTER(c_int64), P, P, I, P]),
+    "a3v_attention_verify_rows_splits": (I, [I, I, I]),
+    "a3v_attention_verify_rows_scratch_floats": (L, [I, I, I, I, I]),
+    "a3v_lookup_draft_rows": (I, [P, L, P, P, P, P, P, I, I, I, I, P, P, P]),
+    "a3v_accept_rows": (I, [P, L, I, I, I, P, P, P, L, P, P, I, P, P, I, P, P, P, P, P, P]),
+    "a3v_llama_decode_step_verify_form": (I, [I, I, I, I, I, I, I, I]),
     "a3v_seen_mark": (I, [P, L, P, P, L, I, I, P]),
     "a3v_seen_clear_rows": (I, [P, P, I, L, L, I, P]),
     "a3v_logits_prepare": (I, [P, L, P, L, F, P, L, P, I, I, P]),
@@ -166,6 +173,7 @@ SIGNATURES["a3v_llama_decode_step_kv8"] = (I, [ctypes.POINTER(LlamaLayer), ctype
                                                I, I, I, I, I, I, I, I, F, P])
 SIGNATURES["a3v_llama_decode_step_form"] = (I, [I, I, I, I, I, I, I])
 SIGNATURES["a3v_llama_decode_step_rows"] = (I, [ctypes.POINTER(LlamaLayer), I, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, F, P])
+SIGNATURES["a3v_llama_decode_step_verify"] = (I, [ctypes.POINTER(LlamaLayer), I, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, F, P])
 SIGNATURES["a3v_llama_decode_step_rows_shared"] = (I, [ctypes.POINTER(LlamaLayer), I, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I,
                                                        F, P])
 

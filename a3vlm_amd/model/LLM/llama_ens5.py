@@ -1132,6 +1132,74 @@ class Transformer(nn.Module):
         self._lm_head_last(xn, logits, B <= 32)
         return logits
 
+    def _verify_buffers(self, B: int, Q: int):
+        """The split-KV scratch and the arrival counters of a3v_attention_verify_rows at B cache rows of Q queries (any sk_max)."""
+        H, hd = self.n_heads, self.head_dim
+        want = -(-768 // (B * H))                      # the decode plan never takes more key ranges than this
+        scratch = self._buf("verify_scratch", (B * Q * H * want * (hd + 2),), torch.float32)
+        counters = self._ws.get("verify_counters")
+        if counters is None or counters.numel() < 2 * B * H:
+            counters = self._ws["verify_counters"] = torch.zeros(2 * B * H, dtype=torch.int32, device=self._device)
+        return scratch, counters
+
+    @torch.no_grad()
+    def forward_verify_rows(self, x: torch.Tensor, pos: torch.Tensor, nq: torch.Tensor, pos_max: int,
+                            out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """One lookup-decoding step: x [B, Q] (int64, device) holds per cache row its last emitted token and up to Q - 1 drafted
+        ones; query j of row b is embedded, written at cache position pos[b] + j (pos: int32 [B], device; negative = idle row)
+        and attends to pos[b] + j + 1 keys; only the first nq[b] (int32 [B], 1 <= nq[b] <= Q) queries of a row are live.
+        ``pos_max`` >= the largest pos[b] (host value).  fp32 logits [B * Q, V], row b * Q + j for query j of row b (into ``out``
+        if given); the rows of idle queries are not meaningful.  bf16 and fp32 streams.
+        INVARIANT: the step leaves keys at pos[b] .. pos[b] + nq[b] - 1.  Those of rejected drafts lie behind the position the row
+        continues from: no later query reads them (each masks at its own key count) and the next step overwrites them."""
+        self._ragged_check()
+        a = self.args
+        B, Q = x.shape
+        M = B * Q
+        assert 1 <= Q <= 8 and M <= 32, (B, Q)
+        assert self._k_cache and self._k_cache[0].shape[0] == B, "allocate_rows(batch_rows) first; Q tokens per cache row"
+        assert x.dtype == torch.int64 and x.is_contiguous()
+        assert all(t.dtype == torch.int32 and t.numel() == B and t.is_contiguous() for t in (pos, nq))
+        smax = self._k_cache[0].shape[2]
+        assert 0 <= pos_max < min(smax, self._cos_sin_cpu.shape[0]), pos_max
+        H, Hkv, hd = self.n_heads, self.n_kv_heads, self.head_dim
+        h = self._buf("h", (M, a.dim))
+        ops.embed_assemble(x.view(M, 1), self.tok_embeddings.weight, h, M, 1, 0, a.dim)
+        w8 = self._step_format_code()
+        fused = (self._dtype == torch.bfloat16 and not getattr(self, "_per_kernel_decode", False) and w8 is not None
+                 and _lib.load().a3v_llama_decode_step_verify_form(B, Q, a.dim, H, Hkv, hd, self.ffn, w8) == 2)
+        sk_max = min(pos_max + Q, smax)
+        if fused:
+            tab = self._llama_layer_table()
+            xn, qkv, att, act, _, sws = self._decode_step_buffers(min(M, 16))
+            xn, qkv, att, act, _ = self._row_buffers(M, False)
+            scratch, _ = self._verify_buffers(B, Q)
+            rc = _lib.load().a3v_llama_decode_step_verify(tab, self.n_layers, h.data_ptr(), xn.data_ptr(), qkv.data_ptr(), att.data_ptr(),
+                                                        act.data_ptr(), scratch.data_ptr(), sws.data_ptr(), self._cos_sin_dev().data_ptr(),
+                                                        pos.data_ptr(), nq.data_ptr(), pos_max, B, Q, a.dim, H, Hkv, hd, self.ffn, smax,
+                                                        a.norm_eps, torch.cuda.current_stream().cuda_stream)
+            _lib.check(rc, "a3v_llama_decode_step_verify")
+        else:
+            self._pack()
+            cs = self._cos_sin_dev()
+            xn, qkv, att, act, _ = self._row_buffers(M, False)
+            scratch = counters = None
+            if h.dtype == torch.bfloat16 and hd in (64, 128):
+                scratch, counters = self._verify_buffers(B, Q)
+            ldq = qkv.stride(0)
+            path = self._layer_path(h, M, True, ragged=True)
+            for i in range(self.n_layers):
+                kc, vc = self._k_cache[i], self._vt_cache[i]
+                strides = (ldq, ldq, hd, Hkv * smax * hd, smax * hd, hd, Hkv * hd * smax, hd * smax, smax, H * hd, H * hd, hd)
+                self._layer(i, path, h, (xn, qkv, att, act),
+                            lambda: ops.rope_kvcache_spans(qkv, qkv, kc, vc, cs, pos, nq, B, Q, H, Hkv, hd),
+                            lambda: ops.attention_verify_rows(qkv, kc, vc, att, pos, nq, sk_max, B, Q, H, Hkv, hd, strides, scratch, counters))
+        xn = self._buf("xn_last", (M, a.dim))
+        ops.rmsnorm(h, self.norm.weight, xn, a.norm_eps)
+        logits = out if out is not None else torch.empty(M, a.vocab_size, dtype=torch.float32, device=self._device)
+        self._lm_head_last(xn, logits, True)
+        return logits
+
     def share_prefix(self, src_row: int, dst_rows, P: int) -> int:
         """Makes the rows ``dst_rows`` siblings of cache row ``src_row``, whose prompt fills positions [0, P) (image words
         included): the keys below the last 64 boundary, P & ~63, stay in the source row alone and are read from there

@@ -420,7 +420,8 @@ class MetaModel(nn.Module):
                       max_gen_len=512, temperature: float = 0.0, top_p: float = 0.95,
                       additional_stop_symbols: Iterable[str] = (), return_ids: bool = False, poll_every: int = 4,
                       sample_uniforms: Optional[torch.Tensor] = None, repetition_penalty: float = 1.0,
-                      return_logprobs: bool = False, top_k: int = 0, min_p: float = 0.0, n: int = 1):
+                      return_logprobs: bool = False, top_k: int = 0, min_p: float = 0.0, n: int = 1,
+                      lookup: Optional[int] = None, lookup_ngram: int = 3, lookup_drafter=None):
         """Any number of prompts through ``batch_rows`` KV-cache rows (no reference counterpart; opt-in): every row decodes at its
         own position, and a row whose answer is finished is prefilled with the next prompt while the others keep decoding, so a
         short answer does not hold its row until the longest answer of a batch is done.  Answers come back in input order.
@@ -441,8 +442,15 @@ class MetaModel(nn.Module):
         generated index] (``sample_uniforms`` [N, n, >= max steps]; [N, >= max steps] is still taken when n == 1), so sample s of a
         prompt is the answer of that prompt alone with that row of uniforms.  Every per-prompt element of the return (text, ids,
         scores) becomes a list of n, in sample order.  With ``n == 1`` the call is the one it was.
+        ``lookup=D`` (1..7; greedy only; 0 / None: the loop as it was): lookup decoding.  Every step drafts up to D tokens per row
+        by prompt lookup -- the continuation of the latest earlier occurrence of the row's last ``lookup_ngram``-gram (then shorter
+        ones) in its own tokens -- feeds the last token and the drafts through ONE decode step (``forward_verify_rows``) and keeps
+        the longest prefix the model itself produces: the answers are the plain loop's.  draft -> verify -> accept run without a
+        host read; ``batch_rows * (D + 1) <= 32``.  Afterwards ``self.last_lookup_stats`` holds ``steps`` (row steps), ``tokens``,
+        ``drafted`` and ``accepted``.  ``lookup_drafter`` (tests): a callable ``(tokens, cur, limit, pos, stopped, next_tok, x, nq)``
+        that fills x / nq in place of the lookup kernel.
         Not for the fp8 KV cache, LoRA models before ``merge_lora()`` or the two-image plugin (each raises, naming the way out)."""
-        from .ragged import GroupScheduler, RowScheduler
+        from .ragged import GroupScheduler, LookupBound, RowScheduler
         if isinstance(prompts, str):
             raise ValueError(f"{self.__class__}.generate_many expects a LIST of prompts, but str is given")
         controls = genctl.wanted(repetition_penalty, return_logprobs)      # ValueError before any device use
@@ -455,6 +463,22 @@ class MetaModel(nn.Module):
                              "greedy answer); use n=1")
         if n > int(batch_rows):
             raise ValueError(f"generate_many: n = {n} samples per prompt need n cache rows at once: batch_rows = {batch_rows} < n")
+        D = int(lookup or 0)
+        if D:                              # refusals of lookup decoding, before any device use
+            if D < 0 or D > 7:
+                raise ValueError(f"generate_many: lookup = {D} drafted tokens per step; 1 .. 7 (a step has at most 8 query positions per row)")
+            if temperature > 0:
+                raise ValueError("generate_many: lookup decoding verifies drafts against the greedy choice: use temperature=0, or lookup=0")
+            if n > 1:
+                raise ValueError(f"generate_many: lookup decoding is greedy, n = {n} samples need temperature > 0: use n=1, or lookup=0")
+            if controls:
+                raise ValueError("generate_many: lookup decoding has no repetition-penalty / log-prob form (several tokens per step): "
+                                 "use repetition_penalty=1.0 and return_logprobs=False, or lookup=0")
+            if int(batch_rows) * (D + 1) > 32:
+                raise ValueError(f"generate_many: batch_rows * (lookup + 1) = {int(batch_rows) * (D + 1)} > 32 rows of one decode step: "
+                                 f"use batch_rows <= {32 // (D + 1)} or lookup <= {max(32 // int(batch_rows) - 1, 0)}")
+            if int(lookup_ngram) < 1:
+                raise ValueError(f"generate_many: lookup_ngram = {lookup_ngram}; >= 1")
         llma = self.llma
         llma._ragged_check()                                  # before anything is allocated or launched
         dev = self._device
@@ -524,6 +548,52 @@ class MetaModel(nn.Module):
             src_row = torch.arange(R, dtype=torch.int32, device=dev)
             shared = torch.zeros(R, dtype=torch.int32, device=dev)
         sample_of = [0] * R
+        if D:
+            Q = D + 1
+            xq = torch.zeros((R, Q), dtype=torch.long, device=dev)
+            nq = torch.ones(R, dtype=torch.int32, device=dev)
+            vlogits = torch.zeros((R * Q, args.vocab_size), dtype=torch.float32, device=dev)
+            stats = torch.zeros(2, dtype=torch.int64, device=dev)
+            bound = LookupBound(R, Q)
+            smax = llma._k_cache[0].shape[2]
+            emitted = it = 0
+            while True:
+                for row, i in sched.refill():
+                    t = torch.tensor(prompt_tokens[i], dtype=torch.long, device=dev)
+                    vlogits[row * Q].copy_(llma.prefill_row(row, t[None], None if images is None else images[i:i + 1])[0])
+                    tokens[row].zero_()
+                    tokens[row, :lens[i]] = t
+                    cur[row], limit[row], stopped[row], stop_pos[row], nq[row] = lens[i], limits[i], False, lens[i] + 1, 1
+                    bound.start(row, W + lens[i], W + limits[i] - 1)      # the first generated id lands behind the prompt
+                for i in sched.finished_at_once:
+                    ids[i] = []
+                sched.finished_at_once.clear()
+                if not sched.occupied():
+                    break
+                # a refilled row has nq = 1 and its prefill logits in query 0: the plain token step
+                ops.accept_rows(vlogits, xq, nq, tokens, cur, limit, W, stop_seq, stop_off, len(l_stop), stopped, stop_pos, next_tok, pos, stats)
+                it += 1
+                if it % poll_every == 0:                     # the one host read: stopped, and cur to re-synchronise the position bound
+                    st, cu, sp = stopped.tolist(), cur.tolist(), stop_pos.tolist()
+                    for r, i in sched.occupied():
+                        if st[r]:
+                            ids[i] = tokens[r, lens[i]:sp[r]].tolist()
+                            emitted += cu[r] - lens[i]
+                            sched.release(r)
+                            bound.release(r)
+                        else:
+                            bound.resync(r, W + cu[r] - 1)
+                    if not sched.occupied():
+                        continue                                         # refill (or leave) before another step
+                if lookup_drafter is not None:
+                    lookup_drafter(tokens, cur, limit, pos, stopped, next_tok, xq, nq)
+                else:
+                    ops.lookup_draft_rows(tokens, cur, limit, pos, stopped, next_tok, D, int(lookup_ngram), smax, xq, nq)
+                llma.forward_verify_rows(xq, pos, nq, bound.step(), out=vlogits)
+            drafted, accepted = (int(v) for v in stats.tolist())
+            self.last_lookup_stats = {"steps": emitted - accepted, "tokens": emitted, "drafted": drafted, "accepted": accepted}
+            decoded = [self.tokenizer.decode(t) for t in ids]
+            return (decoded, ids) if return_ids else decoded
         while True:
             for i, rows in ([(i, [row]) for row, i in sched.refill()] if n == 1 else sched.refill()):
                 lead = rows[0]

@@ -158,3 +158,43 @@ class GroupScheduler:
         self.next_pos[row] = -1
         self.left[self.leader[row]] -= 1
         return i
+
+
+class LookupBound:
+    """Lookup decoding (``generate_many(..., lookup=D)``): a row advances by 1 .. Q = D + 1 positions per step and only the device
+    knows by how many, so the host keeps an UPPER BOUND of every running row's cache position instead of the exact count.
+
+    * ``start(row, pos, last)``: the row's next step runs at cache position ``pos`` exactly (a refill); ``last`` is the largest
+      position it can ever decode at (prompt positions + max_gen_len - 1, below the cache length).
+    * ``step()`` returns the bound of the largest position of this step, then lets every running row grow by Q, clamped by its
+      ``last``.
+    * ``resync(row, pos)``: the exact position read back from the device (the read that already fetches ``stopped``).
+    * ``release(row)``: the row no longer runs.
+
+    The bound never falls below a running row's true position (a row gains at most Q per step and never passes ``last``), and it
+    never reaches the cache length because no ``last`` does."""
+
+    def __init__(self, batch_rows: int, Q: int):
+        assert batch_rows > 0 and Q >= 1
+        self.Q = Q
+        self.bound: List[Optional[int]] = [None] * batch_rows
+        self.last: List[int] = [0] * batch_rows
+
+    def start(self, row: int, pos: int, last: int) -> None:
+        assert 0 <= pos <= last, (pos, last)
+        self.bound[row], self.last[row] = pos, last
+
+    def resync(self, row: int, pos: int) -> None:
+        if self.bound[row] is not None:
+            self.bound[row] = min(max(pos, 0), self.last[row])
+
+    def release(self, row: int) -> None:
+        self.bound[row] = None
+
+    def step(self) -> int:
+        run = [r for r, b in enumerate(self.bound) if b is not None]
+        assert run, "step() without a running row"
+        pos_max = max(self.bound[r] for r in run)
+        for r in run:
+            self.bound[r] = min(self.bound[r] + self.Q, self.last[r])
+        return pos_max

@@ -666,6 +666,74 @@ def generate_step_rows(logits, sampled, tokens, cur, limit, pos_base: int, stop_
     _l.check(rc, "a3v_generate_step_rows")
 
 
+def rope_kvcache_spans(qkv, q_out, k_cache, vt_cache, cos_sin, pos, nq, B, Q, H, Hkv, hd):
+    """Lookup decoding: rope_kvcache_rows over Q query positions per cache row -- virtual row b * Q + j of qkv [B*Q, .] is rotated
+    at position pos[b] + j and written there into cache row b (pos, nq: device int32 [B]; an idle query -- pos[b] < 0, j >= nq[b] or
+    a position outside the cache -- writes nothing and gets a zero q row)."""
+    _dev(qkv, q_out, k_cache, vt_cache, cos_sin, pos, nq)
+    assert all(t.dtype == torch.int32 and t.is_contiguous() and t.numel() >= B for t in (pos, nq))
+    assert qkv.shape[0] >= B * Q and q_out.shape[0] >= B * Q
+    assert k_cache.is_contiguous() and vt_cache.is_contiguous() and k_cache.shape[0] >= B and k_cache.dtype == vt_cache.dtype == qkv.dtype
+    rc = _l.load().a3v_rope_kvcache_spans(_p(qkv), qkv.stride(0), _p(q_out), q_out.stride(0), _p(k_cache), _p(vt_cache), _p(cos_sin),
+                                          _p(pos), _p(nq), B, Q, H, Hkv, hd, k_cache.shape[2], dt(qkv), _stream())
+    _l.check(rc, f"a3v_rope_kvcache_spans(B={B},Q={Q},H={H},Hkv={Hkv},hd={hd})")
+
+
+def attention_verify_rows_splits(B: int, H: int, sk_max: int) -> int:
+    return _l.load().a3v_attention_verify_rows_splits(B, H, sk_max)
+
+
+def attention_verify_rows_scratch_floats(B: int, Q: int, H: int, hd: int, sk_max: int) -> int:
+    return _l.load().a3v_attention_verify_rows_scratch_floats(B, Q, H, hd, sk_max)
+
+
+def attention_verify_rows(q, k, vt, out, pos, nq, sk_max: int, B, Q, H, Hkv, hd, strides, scratch=None, counters=None):
+    """Lookup decoding: query j of cache row b (virtual row b * Q + j of q / out) attends to keys [0, pos[b] + j + 1) of cache row
+    b; pos, nq device int32 [B]; strides as ``attention`` at Sq = 1 with the q / out batch strides per virtual row.  bf16 at hd
+    64 / 128 needs scratch (attention_verify_rows_scratch_floats) and counters (int32 [>= 2*B*H], zero; left zero)."""
+    _dev(q, k, vt, out, pos, nq, scratch, counters)
+    assert all(t.dtype == torch.int32 and t.is_contiguous() and t.numel() >= B for t in (pos, nq))
+    assert k.shape[0] >= B and vt.shape[0] >= B and q.shape[0] >= B * Q and out.shape[0] >= B * Q
+    assert scratch is None or (scratch.dtype == torch.float32 and scratch.numel() >= attention_verify_rows_scratch_floats(B, Q, H, hd, sk_max))
+    assert counters is None or (counters.dtype == torch.int32 and counters.numel() >= 2 * B * H)
+    rc = _l.load().a3v_attention_verify_rows(_p(q), _p(k), _p(vt), _p(out), _p(pos), _p(nq), int(sk_max), B, Q, H, Hkv, hd,
+                                             _Strides(*strides), _p(scratch), _p(counters), dt(q), _stream())
+    _l.check(rc, f"a3v_attention_verify_rows(B={B},Q={Q},sk_max={sk_max},H={H},hd={hd})")
+    return out
+
+
+def lookup_draft_rows(tokens, cur, limit, pos, stopped, next_tok, D: int, max_ngram: int, Smax: int, x, nq):
+    """Prompt-lookup drafts (a3v_lookup_draft_rows): x [B, D+1] int64 = the row's next id and up to D drafts copied from behind the
+    latest earlier occurrence of its last n-gram (n = max_ngram .. 1), nq [B] int32 = 1 + the number of drafts."""
+    _dev(tokens, cur, limit, pos, stopped, next_tok, x, nq)
+    B = tokens.shape[0]
+    assert tokens.dtype == torch.int64 and tokens.stride(1) == 1 and stopped.dtype == torch.bool and next_tok.dtype == x.dtype == torch.int64
+    assert cur.dtype == limit.dtype == pos.dtype == nq.dtype == torch.int32
+    assert all(t.is_contiguous() and t.numel() >= B for t in (cur, limit, pos, stopped, next_tok, nq))
+    assert x.is_contiguous() and tuple(x.shape) == (B, D + 1)
+    rc = _l.load().a3v_lookup_draft_rows(_p(tokens), tokens.stride(0), _p(cur), _p(limit), _p(pos), _p(stopped), _p(next_tok), B, int(D),
+                                         int(max_ngram), int(Smax), _p(x), _p(nq), _stream())
+    _l.check(rc, f"a3v_lookup_draft_rows(B={B},D={D},max_ngram={max_ngram})")
+
+
+def accept_rows(logits, x, nq, tokens, cur, limit, pos_base: int, stop_seq, stop_off, n_stop: int, stopped, stop_pos, next_tok, pos,
+                stats=None):
+    """One launch = the bookkeeping of a lookup-decoding step (a3v_accept_rows): the argmax of every query's logits row, then per
+    cache row as many ``generate_step_rows`` token steps as the drafts x[b, 1..] agree with.  stats: int64 [2] (drafted, accepted)."""
+    _dev(logits, x, nq, tokens, cur, limit, stopped, stop_pos, next_tok, pos, stats)
+    B, Q = x.shape
+    assert logits.dtype == torch.float32 and logits.stride(1) == 1 and logits.shape[0] == B * Q
+    assert tokens.dtype == x.dtype == torch.int64 and tokens.stride(1) == 1 and tokens.shape[0] == B and x.is_contiguous()
+    assert stopped.dtype == torch.bool and stop_pos.dtype == torch.int64 and next_tok.dtype == torch.int64
+    assert cur.dtype == limit.dtype == pos.dtype == nq.dtype == torch.int32
+    assert all(t.is_contiguous() and t.numel() >= B for t in (cur, limit, pos, nq, next_tok, stopped, stop_pos))
+    assert stats is None or (stats.dtype == torch.int64 and stats.is_contiguous() and stats.numel() >= 2)
+    rc = _l.load().a3v_accept_rows(_p(logits), logits.stride(0), B, Q, logits.shape[1], _p(x), _p(nq), _p(tokens), tokens.stride(0),
+                                   _p(cur), _p(limit), int(pos_base), _p(stop_seq), _p(stop_off), int(n_stop), _p(stopped), _p(stop_pos),
+                                   _p(next_tok), _p(pos), _p(stats), _stream())
+    _l.check(rc, f"a3v_accept_rows(B={B},Q={Q})")
+
+
 def embed_assemble(tokens, table, h, B, T, W, dim):
     _dev(tokens, table, h)
     assert tokens.dtype == torch.int64 and tokens.stride(1) == 1

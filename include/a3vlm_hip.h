@@ -689,6 +689,72 @@ int a3v_llama_decode_step_rows_shared(const a3v_llama_layer* layers, int n_layer
                                       int hd, int ffn, int Smax, float eps, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Lookup decoding (opt-in; a3v_spec.hip; no reference counterpart).  One decode step feeds Q = D + 1 query positions per cache row,
+ * 1 <= Q <= 8: the row's last emitted token and up to D drafted ones, and keeps the longest prefix of the drafts that the model
+ * itself produces (greedy: the answer is the plain loop's).  B cache rows, B * Q <= 32 GEMV rows.  VIRTUAL ROW m = b * Q + j is
+ * query j of cache row b: activations (qkv, att, logits) are [B * Q, ...], caches are [B, ...].  pos[b] (the cache position of
+ * query 0; negative: idle row) and nq[b] (live queries of the row, 1 <= nq[b] <= Q: one for the last emitted token plus its
+ * drafts) are DEVICE int32[B].  Query j of row b is LIVE when pos[b] >= 0, j < nq[b] and pos[b] + j < Smax (attention: < sk_max);
+ * any other query is idle: it writes nothing into a cache and its outputs are zeros, never NaN.  bf16 KV cache only.
+ * INVARIANT: a step writes the keys of positions pos[b] .. pos[b] + nq[b] - 1.  When only e of them are kept (a3v_accept_rows), the
+ * next step starts at pos[b] + e: the keys behind it are never read (every query masks at its own count) and are overwritten.
+ *
+ * a3v_rope_kvcache_spans: qkv [B*Q, ldqkv]; virtual row m is rotated with the angle of position pos[b] + j, and its K row / V^T
+ * column are written at that position of cache row b; an idle query writes nothing and gets a zero q row (bounded by the kernel).
+ * bf16 and fp32.  Per live virtual row bit-equal to a3v_rope_kvcache_rows at that position.
+ * a3v_attention_verify_rows: query j of row b attends to keys [0, pos[b] + j + 1) of cache row b (the causal mask among the drafts
+ * is the key count).  strides as a3v_attention with Sq = 1, where the batch strides of q and out ([0], [9]) step VIRTUAL rows and
+ * those of k and vt ([3], [6]) cache rows.  sk_max >= the largest key count (host value, pos_max + Q clamped to Smax); a query whose
+ * position is >= sk_max is idle.  bf16 at hd 64 / 128: one block per (cache row, group of queries, head, key range); the group is
+ * the power of two >= Q, at most 8 (hd 64) or 4 (hd 128: Q = 5..8 run as two groups of 4); every 32-key K tile and V^T tile of the
+ * range is loaded once (non-temporal) and applied to all queries of the group, each with its own key-count mask by select, its own
+ * (m, l) and its own output; split plan of a3v_attention_decode_rows at (B, H, sk_max); partials merged by the last-arriving block.
+ * A key at or beyond a query's count (NaN, a rejected draft of an earlier step, the key of a later draft) never reaches its sums;
+ * a query's output bits do not depend on whether later queries of its row are live.  scratch:
+ * a3v_attention_verify_rows_scratch_floats(B, Q, H, hd, sk_max) floats; counters: 2 * B * H zero-initialised ints, left zero.
+ * fp32, and bf16 at other head dims <= 256: one wave per (virtual row, head), bit-equal per live query to
+ * a3v_attention_decode_rows in its one-wave form with sk = pos[b] + j + 1; scratch / counters unused.
+ * a3v_attention_verify_rows_splits: the number of key ranges of the plan.
+ * a3v_lookup_draft_rows (integer work, bit-identical to tests/spec_ref.py): prompt lookup.  For a running row (stopped[b] == 0,
+ * pos[b] >= 0, 1 <= cur[b] <= ld_tok) with c = tokens[b, 0 .. cur[b]): for n = min(max_ngram, cur - 1) down to 1, the LARGEST i
+ * with i + n <= cur - 1 and c[i .. i+n) == c[cur-n .. cur); the first n with a match wins, the drafts are c[i+n ..] and
+ * nd = max(0, min(D, cur - (i+n), limit[b] - 1 - cur[b], Smax - 1 - pos[b])).  No match, or a row that is not running: nd = 0.
+ * x [B, Q] int64 (Q = D + 1): x[b, 0] = next_tok[b], x[b, 1 .. nd] = the drafts, the rest 0; nq[b] = 1 + nd.  0 <= D <= 7.
+ * a3v_accept_rows (integer work on the argmax, bit-identical to tests/spec_ref.py; greedy only): logits fp32 [B*Q, V] (row stride
+ * ld).  A row with stopped[b] set is not touched (next_tok 0, pos -1).  Otherwise nd = clamp(nq[b], 1, Q) - 1, t_j = argmax of
+ * virtual row (b, j), first index on ties (as a3v_generate_step_rows); the row emits t_0, then t_j while j <= nd and
+ * t_{j-1} == x[b, j].  Every emission is exactly one token step of a3v_generate_step_rows at cur[b] with sampled = t_j (the token
+ * write, stop sequences, cur += 1, the limit); a stop ends the row's emissions.  Outputs as that entry's: next_tok[b] = the last
+ * emitted id and pos[b] = pos_base + cur[b] - 1 for a row that still runs, 0 and -1 for one that stopped.  stats (may be NULL):
+ * DEVICE int64[2]; every row that emits adds nd to stats[0] (drafted) and emissions - 1 to stats[1] (accepted).
+ * a3v_llama_decode_step_verify: a3v_llama_decode_step_rows over the B * Q virtual rows with a3v_rope_kvcache_spans and
+ * a3v_attention_verify_rows (sk_max = min(pos_max + Q, Smax)) in place of the rows kernels: six launches per layer.  Up to 16
+ * virtual rows run as one chunk; above that the step runs in chunks of floor(16 / Q) whole cache rows, so the rope and attention
+ * launches of a chunk see whole cache rows (two chunks for B * Q = 32 at Q = 2, 4, 8).  attn_scratch:
+ * a3v_attention_verify_rows_scratch_floats of the largest chunk.  Fused form only (a3v_llama_decode_step_verify_form == 2: the GEMV
+ * forms of a3v_llama_decode_step_rows_form at a chunk's row count -- bf16, fp8 or NF4 images; else the query says 0, the call
+ * returns A3V_ERR_SHAPE with nothing touched and the host runs kernel by kernel).  Bit-equal to the per-kernel sequence of public
+ * entries over the same chunks. */
+int a3v_rope_kvcache_spans(const void* qkv, int64_t ldqkv, void* q_out, int64_t ldq, void* k_cache, void* vt_cache,
+                           const float* cos_sin, const int32_t* pos, const int32_t* nq, int B, int Q, int H, int Hkv, int hd, int Smax,
+                           int dtype, void* stream);
+int a3v_attention_verify_rows(const void* q, const void* k, const void* vt, void* out, const int32_t* pos, const int32_t* nq,
+                              int sk_max, int B, int Q, int H, int Hkv, int hd, const int64_t* strides, float* scratch, int* counters,
+                              int dtype, void* stream);
+int a3v_attention_verify_rows_splits(int B, int H, int sk_max);
+int64_t a3v_attention_verify_rows_scratch_floats(int B, int Q, int H, int hd, int sk_max);
+int a3v_lookup_draft_rows(const int64_t* tokens, int64_t ld_tok, const int32_t* cur, const int32_t* limit, const int32_t* pos,
+                          const uint8_t* stopped, const int64_t* next_tok, int B, int D, int max_ngram, int Smax, int64_t* x,
+                          int32_t* nq, void* stream);
+int a3v_accept_rows(const float* logits, int64_t ld, int B, int Q, int V, const int64_t* x, const int32_t* nq, int64_t* tokens,
+                    int64_t ld_tok, int32_t* cur, const int32_t* limit, int pos_base, const int64_t* stop_seq, const int32_t* stop_off,
+                    int n_stop, uint8_t* stopped, int64_t* stop_pos, int64_t* next_tok, int32_t* pos, int64_t* stats, void* stream);
+int a3v_llama_decode_step_verify_form(int B, int Q, int dim, int H, int Hkv, int hd, int ffn, int w8);
+int a3v_llama_decode_step_verify(const a3v_llama_layer* layers, int n_layers, void* h, void* xn, void* qkv, void* att, void* act,
+                                 float* attn_scratch, void* skinny_ws, const float* cos_sin, const int32_t* pos, const int32_t* nq,
+                                 int pos_max, int B, int Q, int dim, int H, int Hkv, int hd, int ffn, int Smax, float eps, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Generation controls (opt-in; a3v_genctl.hip): a log-probability per generated token and the HF repetition penalty, on the
  * device inside the step.  No existing entry changes; with the options off none of these is launched.
  *
