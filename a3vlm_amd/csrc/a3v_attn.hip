@@ -788,6 +788,21 @@ inline void decode_plan(int B, int H, int Sk, int* nsplit, int* chunk) {
 
 }  // namespace
 
+// The split plan of every wave-streaming decode attention (attn_decode_wave_kernel here, the fp8-KV, per-row and verify kernels of
+// a3v_kv8 / a3v_ragged / a3v_spec.hip): one block per (batch, head) when that alone covers the CUs, else the fewest splits that do --
+// never more than the two-phase plan, which a3v_attention_scratch_floats sizes the scratch for -- on chunks of whole 64-key tiles.
+// (decode_plan returns ns >= 1 for Sk >= 1, so ns2 >= 1 without a clamp of its own.)
+void a3v_decode_wave_plan(int B, int H, int Sk, int* nsplit, int* chunk) {
+  int ns, ch;
+  decode_plan(B, H, Sk, &ns, &ch);
+  int ns2 = (256 + B * H - 1) / (B * H);
+  if (ns2 > ns) ns2 = ns;
+  int ch2 = (Sk + ns2 - 1) / ns2;
+  ch2 = (ch2 + 63) & ~63;
+  *nsplit = (Sk + ch2 - 1) / ch2;
+  *chunk = ch2;
+}
+
 extern "C" int64_t a3v_attention_scratch_floats(int B, int H, int hd, int Sk) {
   int ns, ch;
   decode_plan(B, H, Sk, &ns, &ch);
@@ -838,10 +853,8 @@ static int attention_impl(const void* q, const void* k, const void* vt, void* ou
     const size_t shm = (size_t)(ch + 8) * sizeof(float);
     const bool we = A3V_ENV_INT("A3V_ATTN_DECODE_WAVE_STANDALONE", 0) == 1;     // tuning runs (tools/attn_decode_bench.py): the wave-streaming form here too
     if (we && dtype == A3V_BF16) {
-      int ns2 = (256 + B * H - 1) / (B * H);
-      if (ns2 > ns) ns2 = ns;
-      int ch2 = (((Sk + ns2 - 1) / ns2) + 63) & ~63;
-      ns2 = (Sk + ch2 - 1) / ch2;
+      int ns2, ch2;
+      a3v_decode_wave_plan(B, H, Sk, &ns2, &ch2);
       if (hd == 128) {
         hipLaunchKernelGGL((attn_decode_wave_kernel<128>), dim3(ns2, H, B), dim3(512), 0, st, p, scratch, ns2, ch2, (int*)nullptr);
         hipLaunchKernelGGL(attn_decode_combine_kernel<128>, dim3(H, B), dim3(128), 0, st, scratch, out, p.o_sb, p.o_sh, H, ns2, dtype);
@@ -918,16 +931,9 @@ int a3v_attention_decode_fused(const void* q, const void* k, const void* vt, voi
   p.lse = nullptr;
   p.head_group = 1;
   p.staged_o = 0;
-  int ns, ch;
-  decode_plan(B, H, Sk, &ns, &ch);
+  int ns2, ch2;
+  a3v_decode_wave_plan(B, H, Sk, &ns2, &ch2);
   hipStream_t st = (hipStream_t)stream;
-  // one block per (batch, head) when that alone covers the CUs, else the fewest splits that do (never more than the
-  // two-phase plan: the scratch buffer is sized for that one)
-  int ns2 = (256 + B * H - 1) / (B * H);
-  if (ns2 > ns) ns2 = ns;
-  int ch2 = (Sk + ns2 - 1) / ns2;
-  ch2 = (ch2 + 63) & ~63;
-  ns2 = (Sk + ch2 - 1) / ch2;
   const dim3 grid(ns2, H, B);
   if (hd == 128) hipLaunchKernelGGL(attn_decode_wave_kernel<128>, grid, dim3(512), 0, st, p, scratch, ns2, ch2, counters);
   else hipLaunchKernelGGL(attn_decode_wave_kernel<64>, grid, dim3(512), 0, st, p, scratch, ns2, ch2, counters);

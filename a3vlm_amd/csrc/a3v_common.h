@@ -314,6 +314,36 @@ bool a3v_gemv_supported(int M, int N, int K, int epilogue, int w8);
 int a3v_cu_count();
 int a3v_attention_decode_fused(const void* q, const void* k, const void* vt, void* out, int B, int Sk, int H, int Hkv, int hd,
                                const int64_t* strides, float* scratch, int* counters, void* stream);
+// the split plan of every wave-streaming decode attention (a3v_attn.hip): the launches and the exported *_splits / *_scratch_floats
+void a3v_decode_wave_plan(int B, int H, int Sk, int* nsplit, int* chunk);
+
+// ---- The fused decode step's one layer loop (a3v_decode.hip), shared by a3v_llama_decode_step[_kv8 | _rows | _rows_shared | _verify].
+// An entry checks its own arguments, calls a3v_decode_layer_table, takes its _form decision, and hands a3v_decode_fused_layers a
+// stage: the rows of a chunk, whether the qkv GEMV carries the RoPE + cache epilogue, and the launches between it and the wo GEMV.
+struct a3v_decode_chunk {            // one (row chunk, layer), as the loop hands it to the stage's attend()
+  const a3v_llama_layer* L;
+  int layer, b0, nbr;                // layer index; first cache row of the chunk and its cache rows
+  bf16_t* q; bf16_t* att;            // the chunk's GEMV rows of the qkv buffer (row stride (H + 2 Hkv) hd) and of the attention output
+  int H, Hkv, hd, Smax;
+  int64_t kv_row;                    // elements per cache row of a bf16 K / V^T cache: the chunk's rows start at b0 * kv_row
+  const int64_t* strides;            // [12] of q / caches / att at this geometry, as a3v_attention takes them
+  float* scratch; int* counters; void* stream;
+};
+struct a3v_decode_stage {
+  int Bc, Q;                         // cache rows per chunk and queries per cache row: a chunk is nbr * Q <= 16 GEMV rows
+  // The qkv GEMV's RoPE + cache epilogue (cos_sin == NULL: plain store, the stage rotates and writes the cache itself): the table
+  // row of the position, the cache pair [B, Hkv, Smax, hd] / [B, Hkv, hd, Smax] (NULL: the layer's own), its Smax and the position.
+  const float* cos_sin; void* k; void* vt; int Smax, pos;
+  int (*attend)(const void* ctx, const a3v_decode_chunk& c);   // every launch between the qkv GEMV and the wo GEMV
+  const void* ctx;
+};
+// every layer in one weight format, images with their scales, norm weights, and (need_kv) the bf16 caches: A3V_OK and
+// *w8 = 0 bf16 / 1 fp8 images / 2 NF4 images, else A3V_ERR_ARG
+int a3v_decode_layer_table(const a3v_llama_layer* layers, int n_layers, bool need_kv, int* w8);
+// the loop; the caller has decided the fused form for (stage.Bc * stage.Q rows, w8).  Nothing here refuses before the first launch.
+int a3v_decode_fused_layers(const a3v_llama_layer* layers, int n_layers, int w8, void* h, void* qkv, void* att, void* act, float* attn_scratch,
+                            void* skinny_ws, int B, int dim, int H, int Hkv, int hd, int ffn, int Smax, float eps,
+                            const a3v_decode_stage& stage, void* stream);
 // internal (a3v_train.hip): bf16 transposes of n_out x n_in matrices [R, C] -> [C, Rpad] in one launch
 int a3v_transpose_2level(const bf16_t* src, int64_t ld_src, int64_t bs_in, int64_t bs_out, bf16_t* dst, int64_t ld_dst, int64_t bsd_in,
                          int64_t bsd_out, int R, int C, int Rpad, int n_in, int n_out, void* stream);

@@ -390,19 +390,6 @@ __global__ void attn_decode_fp8kv_combine_kernel(const float* part, bf16_t* out,
   out[b * ldo + h * HD + d] = f2bf(acc / l);
 }
 
-// the split rule of a3v_attention_decode_fused: one block per (batch, head) when that alone covers the CUs, else the fewest splits
-// that do, never more than the plan the scratch is sized for (a3v_attention_scratch_floats)
-void kv8_decode_plan(int B, int H, int Sk, int* nsplit, int* chunk) {
-  const int ns = (int)(a3v_attention_scratch_floats(B, H, 64, Sk) / ((int64_t)B * H * 66));
-  int ns2 = (256 + B * H - 1) / (B * H);
-  if (ns2 > ns) ns2 = ns;
-  if (ns2 < 1) ns2 = 1;
-  int ch2 = (Sk + ns2 - 1) / ns2;
-  ch2 = (ch2 + 63) & ~63;
-  *nsplit = (Sk + ch2 - 1) / ch2;
-  *chunk = ch2;
-}
-
 inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
@@ -439,7 +426,7 @@ extern "C" int a3v_kv_dequantize_fp8(const void* k_q, const void* vt_q, const fl
 extern "C" int a3v_attention_decode_fp8kv_splits(int B, int H, int Sk) {
   if (B <= 0 || H <= 0 || Sk <= 0) return A3V_ERR_ARG;
   int ns, ch;
-  kv8_decode_plan(B, H, Sk, &ns, &ch);
+  a3v_decode_wave_plan(B, H, Sk, &ns, &ch);
   return ns;
 }
 
@@ -453,7 +440,7 @@ extern "C" int a3v_attention_decode_fp8kv(const void* q, int64_t ldq, const void
   Kv8AttnArgs p{(const bf16_t*)q, (const uint8_t*)k_q, (const uint8_t*)vt_q, k_scale, v_scale, (bf16_t*)out, ldq, ldo, Sk, H, Hkv, Smax,
                 1.0f / sqrtf((float)hd)};
   int ns, ch;
-  kv8_decode_plan(B, H, Sk, &ns, &ch);
+  a3v_decode_wave_plan(B, H, Sk, &ns, &ch);
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid(ns, H, B);
   if (hd == 128) hipLaunchKernelGGL(attn_decode_fp8kv_kernel<128>, grid, dim3(512), 0, st, p, scratch, ns, ch, counters);

@@ -12,7 +12,8 @@
 //    leaves before the combine with its counter untouched and split 0 writes the zeros.
 //  * attn_rows_generic_kernel<T>   : attn_generic_kernel at Sq = 1 with the row's key count (fp32 parity path, odd head dims).
 //  * generate_step_rows_kernel     : generate_step_kernel with per-row cur / limit, no text_mask; emits the next id and its position.
-//  * a3v_llama_decode_step_rows    : the fused form of a3v_llama_decode_step with those kernels, six launches per layer.
+//  * a3v_llama_decode_step_rows    : the fused layer loop of a3v_llama_decode_step (a3v_decode.hip: a3v_decode_fused_layers) with those
+//    kernels as its attention stage (attend_rows below), six launches per layer.
 //  * shared prompt keys (the SH = true instantiations of the two attention kernels, a3v_attention_decode_rows_shared): a row's
 //    64-key tiles below its shared length are read from another cache row.  Only the base pointer of a tile differs -- a
 //    wave-uniform select of one 64-bit offset -- so the walk, the masks and the merges are the expressions above in their order.
@@ -386,20 +387,6 @@ __global__ __launch_bounds__(1024) void generate_step_rows_kernel(const float* _
   pos[row] = st ? -1 : pos_base + c - 1;
 }
 
-// sums of squares of the rows of h [B, dim] in the producer layout ([dim/16][16]) for the first layer's prologue (as a3v_decode.hip)
-__global__ __launch_bounds__(256) void rows_ssq_rows_kernel(const bf16_t* __restrict__ h, int64_t ld, int B, int dim, float* __restrict__ ssq) {
-  const int t = blockIdx.x * 256 + threadIdx.x;         // (tile, m)
-  const int tile = t >> 4, m = t & 15;
-  if (tile * 16 >= dim) return;
-  float s = 0.f;
-  if (m < B) {
-    const bf16_t* r = h + (int64_t)m * ld + tile * 16;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) { const float x = (float)r[e]; s = fmaf(x, x, s); }
-  }
-  ssq[t] = s;
-}
-
 // Positions [lo, hi) (0 < hi - lo < 64) of cache row src into the rows dst[0..n_dst): grid (n_dst, Hkv, layers).  K: one contiguous
 // run of (hi - lo) * hd elements per (row, head), 16-byte vectors (hd is a multiple of 8).  V^T: hi - lo elements per d row, one
 // thread per d row: elements up to the first 16-byte boundary, vectors, then the elements behind the last whole vector (source
@@ -427,18 +414,6 @@ __global__ __launch_bounds__(256) void kv_copy_span_kernel(const void* const* __
     for (int e = a0; e < a1; e += VEC) *reinterpret_cast<f32x4*>(vd + e) = *reinterpret_cast<const f32x4*>(vs + e);
     for (int e = a1; e < hi; ++e) vd[e] = vs[e];
   }
-}
-
-// the split rule of a3v_attention_decode_fused at Sk = sk_max (never more splits than a3v_attention_scratch_floats is sized for)
-void rows_decode_plan(int B, int H, int sk_max, int* nsplit, int* chunk) {
-  const int ns = (int)(a3v_attention_scratch_floats(B, H, 64, sk_max) / ((int64_t)B * H * 66));
-  int ns2 = (256 + B * H - 1) / (B * H);
-  if (ns2 > ns) ns2 = ns;
-  if (ns2 < 1) ns2 = 1;
-  int ch2 = (sk_max + ns2 - 1) / ns2;
-  ch2 = (ch2 + 63) & ~63;
-  *nsplit = (sk_max + ch2 - 1) / ch2;
-  *chunk = ch2;
 }
 
 // src_row == NULL: the plain kernels on k / vt = the caches of the B rows of the call.  Otherwise the shared-prefix forms: k / vt
@@ -477,7 +452,7 @@ int attention_rows_impl(const void* q, const void* k, const void* vt, void* out,
     if (i != 1 && i != 10 && (strides[i] % 8)) return A3V_ERR_SHAPE;      // 16-B vector access (the Sq strides are not used)
   if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k) | reinterpret_cast<uintptr_t>(vt)) & 15) return A3V_ERR_SHAPE;
   int ns, ch;
-  rows_decode_plan(B, H, sk_max, &ns, &ch);
+  a3v_decode_wave_plan(B, H, sk_max, &ns, &ch);
   const dim3 grid(ns, H, B);
   const RowsAttnArgs& pp = p;
   if (src_row) {
@@ -513,7 +488,7 @@ extern "C" int a3v_rope_kvcache_rows(const void* qkv, int64_t ldqkv, void* q_out
 extern "C" int a3v_attention_decode_rows_splits(int B, int H, int sk_max) {
   if (B <= 0 || H <= 0 || sk_max <= 0) return A3V_ERR_ARG;
   int ns, ch;
-  rows_decode_plan(B, H, sk_max, &ns, &ch);
+  a3v_decode_wave_plan(B, H, sk_max, &ns, &ch);
   return ns;
 }
 
@@ -563,74 +538,37 @@ extern "C" int a3v_llama_decode_step_rows_form(int B, int dim, int H, int Hkv, i
 }
 
 namespace {
+// what a3v_decode_fused_layers (a3v_decode.hip) runs between the plain-store qkv GEMV and the wo GEMV: RoPE + cache write at the
+// rows' own positions, then the per-row attention -- six launches per layer
+struct RowsStage { const float* cos_sin; const int32_t* pos; const int32_t* src_row; const int32_t* shared; int pos_max, B; };
+int attend_rows(const void* ctx, const a3v_decode_chunk& c) {
+  const RowsStage& s = *(const RowsStage*)ctx;
+  const int64_t ldq = c.strides[0];
+  const int32_t* pc = s.pos + c.b0;
+  bf16_t* kc = (bf16_t*)c.L->k_cache + c.b0 * c.kv_row;
+  bf16_t* vc = (bf16_t*)c.L->vt_cache + c.b0 * c.kv_row;
+  int rc;
+  if ((rc = a3v_rope_kvcache_rows(c.q, ldq, c.q, ldq, kc, vc, s.cos_sin, pc, c.nbr, c.H, c.Hkv, c.hd, c.Smax, A3V_BF16, c.stream))) return rc;
+  if (!s.src_row)
+    return attention_rows_impl(c.q, kc, vc, c.att, pc, 1, s.pos_max + 1, c.nbr, c.H, c.Hkv, c.hd, c.strides, c.scratch, c.counters, A3V_BF16,
+                               c.stream);
+  // src_row[] names rows of the whole cache: its base, and the chunk's first row
+  return attention_rows_impl(c.q, c.L->k_cache, c.L->vt_cache, c.att, pc, 1, s.pos_max + 1, c.nbr, c.H, c.Hkv, c.hd, c.strides, c.scratch,
+                             c.counters, A3V_BF16, c.stream, s.src_row + c.b0, s.shared + c.b0, c.b0, s.B);
+}
+
 int decode_step_rows_impl(const a3v_llama_layer* layers, int n_layers, void* h, void* xn, void* qkv, void* att, void* act,
                           float* attn_scratch, void* skinny_ws, const float* cos_sin, const int32_t* pos, const int32_t* src_row,
                           const int32_t* shared, int pos_max, int B, int dim, int H, int Hkv, int hd, int ffn, int Smax, float eps,
                           void* stream) {
   if (!layers || n_layers <= 0 || !h || !xn || !qkv || !att || !act || !attn_scratch || !skinny_ws || !cos_sin || !pos) return A3V_ERR_ARG;
   if (B <= 0 || B > 32 || pos_max < 0 || pos_max >= Smax || Smax % 8) return A3V_ERR_SHAPE;
-  const int w8 = layers[0].wqkv_q != nullptr ? 1 : layers[0].wqkv_n4 != nullptr ? 2 : 0;
-  for (int i = 0; i < n_layers; ++i) {
-    const a3v_llama_layer& L = layers[i];
-    const int q8 = (L.wqkv_q != nullptr) + (L.wo_q != nullptr) + (L.w13_q != nullptr) + (L.w2_q != nullptr);
-    const int n4 = (L.wqkv_n4 != nullptr) + (L.wo_n4 != nullptr) + (L.w13_n4 != nullptr) + (L.w2_n4 != nullptr);
-    if (q8 != (w8 == 1 ? 4 : 0) || (w8 == 1 && (!L.wqkv_s || !L.wo_s || !L.w13_s || !L.w2_s))) return A3V_ERR_ARG;   // all four or none
-    if (n4 != (w8 == 2 ? 4 : 0) || (w8 == 2 && (!L.wqkv_n4s || !L.wo_n4s || !L.w13_n4s || !L.w2_n4s))) return A3V_ERR_ARG;
-    if (!L.k_cache || !L.vt_cache || !L.attn_norm_w || !L.ffn_norm_w) return A3V_ERR_ARG;
-  }
+  int rc, w8;
+  if ((rc = a3v_decode_layer_table(layers, n_layers, true, &w8))) return rc;
   if (a3v_llama_decode_step_rows_form(B, dim, H, Hkv, hd, ffn, w8) != 2) return A3V_ERR_SHAPE;    // nothing launched
-  const int64_t ldq = (int64_t)(H + 2 * Hkv) * hd;
-  const int64_t strides[12] = {ldq, ldq, hd,
-                               (int64_t)Hkv * Smax * hd, (int64_t)Smax * hd, hd,
-                               (int64_t)Hkv * hd * Smax, (int64_t)hd * Smax, Smax,
-                               (int64_t)H * hd, (int64_t)H * hd, hd};
-  const int Bc = B > 16 ? (B + 1) / 2 : B;           // 17..32 rows: two row chunks, as a3v_llama_decode_step
-  float* ssq = (float*)((char*)skinny_ws + A3V_WS_SSQ);
-  int* actr = (int*)((char*)skinny_ws + A3V_WS_ATTN_COUNTERS);
-  const int64_t kv_b = (int64_t)Hkv * Smax * hd;     // elements per batch row of a K / V^T cache
-  const bool q4 = w8 == 2;
-  const int dv = q4 ? 2 : 1;
-  int rc;
-  for (int b0 = 0; b0 < B; b0 += Bc) {
-    const int nb = B - b0 < Bc ? B - b0 : Bc;
-    bf16_t* hc = (bf16_t*)h + (int64_t)b0 * dim;
-    bf16_t* qc = (bf16_t*)qkv + (int64_t)b0 * ldq;
-    bf16_t* ac = (bf16_t*)att + (int64_t)b0 * H * hd;
-    bf16_t* fc = (bf16_t*)act + (int64_t)b0 * ffn;
-    const int32_t* pc = pos + b0;
-    hipLaunchKernelGGL(rows_ssq_rows_kernel, dim3((dim / 16 * 16 + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)hc, (int64_t)dim, nb, dim, ssq);
-    A3V_LAUNCH_CHECK();
-    for (int i = 0; i < n_layers; ++i) {
-      const a3v_llama_layer& L = layers[i];
-      // per matrix: weight image, its row stride (elements of bf16, bytes of fp8 / NF4) and scales
-      const void* wqkv = q4 ? L.wqkv_n4 : w8 ? L.wqkv_q : L.wqkv;
-      const void* wo = q4 ? L.wo_n4 : w8 ? L.wo_q : L.wo;
-      const void* w13 = q4 ? L.w13_n4 : w8 ? L.w13_q : L.w13;
-      const void* w2 = q4 ? L.w2_n4 : w8 ? L.w2_q : L.w2;
-      const float* sqkv = q4 ? L.wqkv_n4s : L.wqkv_s;
-      const float* so = q4 ? L.wo_n4s : L.wo_s;
-      const float* s13 = q4 ? L.w13_n4s : L.w13_s;
-      const float* s2 = q4 ? L.w2_n4s : L.w2_s;
-      bf16_t* kc = (bf16_t*)L.k_cache + b0 * kv_b;
-      bf16_t* vc = (bf16_t*)L.vt_cache + b0 * kv_b;
-      if ((rc = a3v_gemv_fused(hc, dim, wqkv, dim / dv, sqkv, q4, qc, ldq, nb, (int)ldq, dim, nullptr, 0, 0, L.attn_norm_w, ssq, eps, nullptr,
-                               0, nullptr, nullptr, nullptr, H, Hkv, hd, Smax, 0, skinny_ws, stream))) return rc;    // plain store: no RoPE epilogue
-      if ((rc = a3v_rope_kvcache_rows(qc, ldq, qc, ldq, kc, vc, cos_sin, pc, nb, H, Hkv, hd, Smax, A3V_BF16, stream))) return rc;
-      if (!src_row)
-        rc = attention_rows_impl(qc, kc, vc, ac, pc, 1, pos_max + 1, nb, H, Hkv, hd, strides, attn_scratch, actr, A3V_BF16, stream);
-      else                                             // src_row[] names rows of the whole cache: its base, and the chunk's first row
-        rc = attention_rows_impl(qc, L.k_cache, L.vt_cache, ac, pc, 1, pos_max + 1, nb, H, Hkv, hd, strides, attn_scratch, actr, A3V_BF16,
-                                 stream, src_row + b0, shared + b0, b0, B);
-      if (rc) return rc;
-      if ((rc = a3v_gemv_fused(ac, (int64_t)H * hd, wo, (int64_t)H * hd / dv, so, q4, hc, dim, nb, dim, H * hd, hc, dim, A3V_EPI_RESIDUAL,
-                               nullptr, nullptr, eps, ssq, 0, nullptr, nullptr, nullptr, H, Hkv, hd, Smax, 0, skinny_ws, stream))) return rc;
-      if ((rc = a3v_gemv_fused(hc, dim, w13, dim / dv, s13, q4, fc, ffn, nb, 2 * ffn, dim, nullptr, 0, A3V_EPI_SWIGLU, L.ffn_norm_w, ssq, eps,
-                               nullptr, 0, nullptr, nullptr, nullptr, H, Hkv, hd, Smax, 0, skinny_ws, stream))) return rc;
-      if ((rc = a3v_gemv_fused(fc, ffn, w2, ffn / dv, s2, q4, hc, dim, nb, dim, ffn, hc, dim, A3V_EPI_RESIDUAL, nullptr, nullptr, eps, ssq, 0,
-                               nullptr, nullptr, nullptr, H, Hkv, hd, Smax, 0, skinny_ws, stream))) return rc;
-    }
-  }
-  return A3V_OK;
+  const RowsStage ctx{cos_sin, pos, src_row, shared, pos_max, B};
+  const a3v_decode_stage stage{B > 16 ? (B + 1) / 2 : B, 1, nullptr, nullptr, nullptr, 0, 0, attend_rows, &ctx};   // 17..32 rows: two row chunks
+  return a3v_decode_fused_layers(layers, n_layers, w8, h, qkv, att, act, attn_scratch, skinny_ws, B, dim, H, Hkv, hd, ffn, Smax, eps, stage, stream);
 }
 }  // namespace
 

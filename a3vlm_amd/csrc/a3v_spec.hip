@@ -19,7 +19,8 @@
 //  * lookup_draft_rows_kernel      : prompt-lookup drafts from the row's own tokens (integer work, tests/spec_ref.py).
 //  * accept_rows_kernel            : argmax of the Q logits rows of a cache row, then the emissions -- each one the token step of
 //    generate_step_rows_kernel at cur[b] -- while the drafts agree (tests/spec_ref.py).
-//  * a3v_llama_decode_step_verify  : a3v_llama_decode_step_rows over B * Q GEMV rows with the two kernels above, six launches per layer.
+//  * a3v_llama_decode_step_verify  : the fused layer loop of a3v_llama_decode_step (a3v_decode.hip: a3v_decode_fused_layers) over B * Q
+//    GEMV rows with the two kernels above as its attention stage (attend_verify below), six launches per layer.
 #include "a3v_common.h"
 
 namespace {
@@ -499,32 +500,6 @@ __global__ __launch_bounds__(1024) void accept_rows_kernel(const float* __restri
   }
 }
 
-// sums of squares of the rows of h [M, dim] in the producer layout ([dim/16][16]) for the first layer's prologue (as a3v_ragged.hip)
-__global__ __launch_bounds__(256) void rows_ssq_verify_kernel(const bf16_t* __restrict__ h, int64_t ld, int B, int dim, float* __restrict__ ssq) {
-  const int t = blockIdx.x * 256 + threadIdx.x;         // (tile, m)
-  const int tile = t >> 4, m = t & 15;
-  if (tile * 16 >= dim) return;
-  float s = 0.f;
-  if (m < B) {
-    const bf16_t* r = h + (int64_t)m * ld + tile * 16;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) { const float x = (float)r[e]; s = fmaf(x, x, s); }
-  }
-  ssq[t] = s;
-}
-
-// the split rule of a3v_attention_decode_rows at (B, H, sk_max), restated from its exported parts (a3v_ragged.hip: rows_decode_plan)
-void verify_plan(int B, int H, int sk_max, int* nsplit, int* chunk) {
-  const int ns = (int)(a3v_attention_scratch_floats(B, H, 64, sk_max) / ((int64_t)B * H * 66));
-  int ns2 = (256 + B * H - 1) / (B * H);
-  if (ns2 > ns) ns2 = ns;
-  if (ns2 < 1) ns2 = 1;
-  int ch2 = (sk_max + ns2 - 1) / ns2;
-  ch2 = (ch2 + 63) & ~63;
-  *nsplit = (sk_max + ch2 - 1) / ch2;
-  *chunk = ch2;
-}
-
 // queries per block: the power of two that holds all Q of a row (every tile of a row is then loaded once per head); at hd 128 at
 // most 4 -- 8 sets of accumulators beside the tiles need more than the 256 registers of a wave at two waves per SIMD (the compiler
 // spills 164 bytes per lane) -- so Q = 5..8 run there as two groups of 4 over the grid's z dimension
@@ -566,14 +541,14 @@ extern "C" int a3v_rope_kvcache_spans(const void* qkv, int64_t ldqkv, void* q_ou
 extern "C" int a3v_attention_verify_rows_splits(int B, int H, int sk_max) {
   if (B <= 0 || H <= 0 || sk_max <= 0) return A3V_ERR_ARG;
   int ns, ch;
-  verify_plan(B, H, sk_max, &ns, &ch);
+  a3v_decode_wave_plan(B, H, sk_max, &ns, &ch);
   return ns;
 }
 
 extern "C" int64_t a3v_attention_verify_rows_scratch_floats(int B, int Q, int H, int hd, int sk_max) {
   if (B <= 0 || Q <= 0 || H <= 0 || sk_max <= 0) return 0;
   int ns, ch;
-  verify_plan(B, H, sk_max, &ns, &ch);
+  a3v_decode_wave_plan(B, H, sk_max, &ns, &ch);
   return (int64_t)B * Q * H * ns * (hd + 2);
 }
 
@@ -606,7 +581,7 @@ extern "C" int a3v_attention_verify_rows(const void* q, const void* k, const voi
     if (i != 1 && i != 10 && (strides[i] % 8)) return A3V_ERR_SHAPE;      // 16-B vector access (the Sq strides are not used)
   if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k) | reinterpret_cast<uintptr_t>(vt)) & 15) return A3V_ERR_SHAPE;
   int ns, ch;
-  verify_plan(B, H, sk_max, &ns, &ch);
+  a3v_decode_wave_plan(B, H, sk_max, &ns, &ch);
   const int G = verify_group(hd, Q);
   if (hd == 64) {
     if (G == 1) launch_verify<64, 1>(p, scratch, ns, ch, B, counters, st);
@@ -658,70 +633,35 @@ extern "C" int a3v_llama_decode_step_verify_form(int B, int Q, int dim, int H, i
   return a3v_llama_decode_step_rows_form(Bc * Q, dim, H, Hkv, hd, ffn, w8) == 2 ? 2 : 0;
 }
 
+namespace {
+// what a3v_decode_fused_layers (a3v_decode.hip) runs between the plain-store qkv GEMV and the wo GEMV over the chunk's nbr * Q GEMV
+// rows: RoPE + cache write of the rows' spans, then the verify attention -- six launches per layer
+struct VerifyStage { const float* cos_sin; const int32_t* pos; const int32_t* nq; int Q, sk_max; };
+int attend_verify(const void* ctx, const a3v_decode_chunk& c) {
+  const VerifyStage& s = *(const VerifyStage*)ctx;
+  const int64_t ldq = c.strides[0];
+  const int32_t* pc = s.pos + c.b0;
+  const int32_t* nc = s.nq + c.b0;
+  bf16_t* kc = (bf16_t*)c.L->k_cache + c.b0 * c.kv_row;
+  bf16_t* vc = (bf16_t*)c.L->vt_cache + c.b0 * c.kv_row;
+  int rc;
+  if ((rc = a3v_rope_kvcache_spans(c.q, ldq, c.q, ldq, kc, vc, s.cos_sin, pc, nc, c.nbr, s.Q, c.H, c.Hkv, c.hd, c.Smax, A3V_BF16, c.stream))) return rc;
+  return a3v_attention_verify_rows(c.q, kc, vc, c.att, pc, nc, s.sk_max, c.nbr, s.Q, c.H, c.Hkv, c.hd, c.strides, c.scratch, c.counters, A3V_BF16,
+                                   c.stream);
+}
+}  // namespace
+
 extern "C" int a3v_llama_decode_step_verify(const a3v_llama_layer* layers, int n_layers, void* h, void* xn, void* qkv, void* att, void* act,
                                             float* attn_scratch, void* skinny_ws, const float* cos_sin, const int32_t* pos,
                                             const int32_t* nq, int pos_max, int B, int Q, int dim, int H, int Hkv, int hd, int ffn,
                                             int Smax, float eps, void* stream) {
   if (!layers || n_layers <= 0 || !h || !xn || !qkv || !att || !act || !attn_scratch || !skinny_ws || !cos_sin || !pos || !nq) return A3V_ERR_ARG;
   if (B <= 0 || Q < 1 || Q > 8 || B * Q > 32 || pos_max < 0 || pos_max >= Smax || Smax % 8) return A3V_ERR_SHAPE;
-  const int w8 = layers[0].wqkv_q != nullptr ? 1 : layers[0].wqkv_n4 != nullptr ? 2 : 0;
-  for (int i = 0; i < n_layers; ++i) {
-    const a3v_llama_layer& L = layers[i];
-    const int q8 = (L.wqkv_q != nullptr) + (L.wo_q != nullptr) + (L.w13_q != nullptr) + (L.w2_q != nullptr);
-    const int n4 = (L.wqkv_n4 != nullptr) + (L.wo_n4 != nullptr) + (L.w13_n4 != nullptr) + (L.w2_n4 != nullptr);
-    if (q8 != (w8 == 1 ? 4 : 0) || (w8 == 1 && (!L.wqkv_s || !L.wo_s || !L.w13_s || !L.w2_s))) return A3V_ERR_ARG;   // all four or none
-    if (n4 != (w8 == 2 ? 4 : 0) || (w8 == 2 && (!L.wqkv_n4s || !L.wo_n4s || !L.w13_n4s || !L.w2_n4s))) return A3V_ERR_ARG;
-    if (!L.k_cache || !L.vt_cache || !L.attn_norm_w || !L.ffn_norm_w) return A3V_ERR_ARG;
-  }
+  int rc, w8;
+  if ((rc = a3v_decode_layer_table(layers, n_layers, true, &w8))) return rc;
   if (a3v_llama_decode_step_verify_form(B, Q, dim, H, Hkv, hd, ffn, w8) != 2) return A3V_ERR_SHAPE;    // nothing launched
-  const int64_t ldq = (int64_t)(H + 2 * Hkv) * hd;
-  const int64_t strides[12] = {ldq, ldq, hd,
-                               (int64_t)Hkv * Smax * hd, (int64_t)Smax * hd, hd,
-                               (int64_t)Hkv * hd * Smax, (int64_t)hd * Smax, Smax,
-                               (int64_t)H * hd, (int64_t)H * hd, hd};
-  const int Bc = verify_chunk_rows(B, Q);            // the rope and attention launches of a chunk see whole cache rows
-  const int sk_max = pos_max + Q < Smax ? pos_max + Q : Smax;
-  float* ssq = (float*)((char*)skinny_ws + A3V_WS_SSQ);
-  int* actr = (int*)((char*)skinny_ws + A3V_WS_ATTN_COUNTERS);
-  const int64_t kv_b = (int64_t)Hkv * Smax * hd;     // elements per cache row of a K / V^T cache
-  const bool q4 = w8 == 2;
-  const int dv = q4 ? 2 : 1;
-  int rc;
-  for (int b0 = 0; b0 < B; b0 += Bc) {
-    const int nbr = B - b0 < Bc ? B - b0 : Bc;       // cache rows of the chunk
-    const int nb = nbr * Q;                          // its GEMV rows
-    const int64_t r0 = (int64_t)b0 * Q;
-    bf16_t* hc = (bf16_t*)h + r0 * dim;
-    bf16_t* qc = (bf16_t*)qkv + r0 * ldq;
-    bf16_t* ac = (bf16_t*)att + r0 * H * hd;
-    bf16_t* fc = (bf16_t*)act + r0 * ffn;
-    const int32_t* pc = pos + b0;
-    const int32_t* nc = nq + b0;
-    hipLaunchKernelGGL(rows_ssq_verify_kernel, dim3((dim / 16 * 16 + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)hc, (int64_t)dim, nb, dim, ssq);
-    A3V_LAUNCH_CHECK();
-    for (int i = 0; i < n_layers; ++i) {
-      const a3v_llama_layer& L = layers[i];
-      const void* wqkv = q4 ? L.wqkv_n4 : w8 ? L.wqkv_q : L.wqkv;
-      const void* wo = q4 ? L.wo_n4 : w8 ? L.wo_q : L.wo;
-      const void* w13 = q4 ? L.w13_n4 : w8 ? L.w13_q : L.w13;
-      const void* w2 = q4 ? L.w2_n4 : w8 ? L.w2_q : L.w2;
-      const float* sqkv = q4 ? L.wqkv_n4s : L.wqkv_s;
-      const float* so = q4 ? L.wo_n4s : L.wo_s;
-      const float* s13 = q4 ? L.w13_n4s : L.w13_s;
-      const float* s2 = q4 ? L.w2_n4s : L.w2_s;
-      bf16_t* kc = (bf16_t*)L.k_cache + b0 * kv_b;
-      bf16_t* vc = (bf16_t*)L.vt_cache + b0 * kv_b;
-      if ((rc = a3v_gemv_fused(hc, dim, wqkv, dim / dv, sqkv, q4, qc, ldq, nb, (int)ldq, dim, nullptr, 0, 0, L.attn_norm_w, ssq, eps, nullptr,
-                               0, nullptr, nullptr, nullptr, H, Hkv, hd, Smax, 0, skinny_ws, stream))) return rc;    // plain store: no RoPE epilogue
-      if ((rc = a3v_rope_kvcache_spans(qc, ldq, qc, ldq, kc, vc, cos_sin, pc, nc, nbr, Q, H, Hkv, hd, Smax, A3V_BF16, stream))) return rc;
-      if ((rc = a3v_attention_verify_rows(qc, kc, vc, ac, pc, nc, sk_max, nbr, Q, H, Hkv, hd, strides, attn_scratch, actr, A3V_BF16, stream))) return rc;
-      if ((rc = a3v_gemv_fused(ac, (int64_t)H * hd, wo, (int64_t)H * hd / dv, so, q4, hc, dim, nb, dim, H * hd, hc, dim, A3V_EPI_RESIDUAL,
-                               nullptr, nullptr, eps, ssq, 0, nullptr, nullptr, nullptr, H, Hkv, hd, Smax, 0, skinny_ws, stream))) return rc;
-      if ((rc = a3v_gemv_fused(hc, dim, w13, dim / dv, s13, q4, fc, ffn, nb, 2 * ffn, dim, nullptr, 0, A3V_EPI_SWIGLU, L.ffn_norm_w, ssq, eps,
-                               nullptr, 0, nullptr, nullptr, nullptr, H, Hkv, hd, Smax, 0, skinny_ws, stream))) return rc;
-      if ((rc = a3v_gemv_fused(fc, ffn, w2, ffn / dv, s2, q4, hc, dim, nb, dim, ffn, hc, dim, A3V_EPI_RESIDUAL, nullptr, nullptr, eps, ssq, 0,
-                               nullptr, nullptr, nullptr, H, Hkv, hd, Smax, 0, skinny_ws, stream))) return rc;
-    }
-  }
-  return A3V_OK;
+  const VerifyStage ctx{cos_sin, pos, nq, Q, pos_max + Q < Smax ? pos_max + Q : Smax};
+  // the rope and attention launches of a chunk see whole cache rows
+  const a3v_decode_stage stage{verify_chunk_rows(B, Q), Q, nullptr, nullptr, nullptr, 0, 0, attend_verify, &ctx};
+  return a3v_decode_fused_layers(layers, n_layers, w8, h, qkv, att, act, attn_scratch, skinny_ws, B, dim, H, Hkv, hd, ffn, Smax, eps, stage, stream);
 }

@@ -729,27 +729,25 @@ class Transformer(nn.Module):
         return xn, qkv, att, act, scratch, sws
 
 
-    def _decode_step(self, h: torch.Tensor, B: int, pos: int) -> None:
-        """seqlen == 1, bf16: the whole layer stack from one C call (a3v_llama_decode_step)."""
+    def _call_step(self, entry: str, h: torch.Tensor, bufs, rows, after=(), tables=()) -> None:
+        """One C step entry: (layer table, *tables, n_layers, h, xn, qkv, att, act, scratch, sws, cos_sin, *rows, dim, H, Hkv, hd, ffn,
+        Smax, *after, eps, stream) -- ``rows`` are the entry's position / row-count arguments, ``bufs`` its _decode_step_buffers()."""
         a = self.args
-        self._llama_layer_table()
-        kv8 = self._kv8
-        H, Hkv, hd = self.n_heads, self.n_kv_heads, self.head_dim
-        smax = self._k_cache[0].shape[2]
-        xn, qkv, att, act, scratch, sws = self._decode_step_buffers(B)
+        tab = self._llama_layer_table()
+        rc = getattr(_lib.load(), entry)(tab, *tables, self.n_layers, h.data_ptr(), *(t.data_ptr() for t in bufs),
+                                         self._cos_sin_dev().data_ptr(), *rows, a.dim, self.n_heads, self.n_kv_heads, self.head_dim,
+                                         self.ffn, self._k_cache[0].shape[2], *after, a.norm_eps, torch.cuda.current_stream().cuda_stream)
+        _lib.check(rc, entry)
+
+    def _decode_step(self, h: torch.Tensor, B: int, pos: int) -> None:
+        """seqlen == 1, bf16: the whole layer stack from one C call (a3v_llama_decode_step; with an fp8 KV cache a3v_llama_decode_step_kv8)."""
+        self._llama_layer_table()      # (builds the kv8 table too)
+        bufs, kv8 = self._decode_step_buffers(B), self._kv8
         if kv8 is not None:
-            rc = _lib.load().a3v_llama_decode_step_kv8(self._layer_tab, self._kv8_tab, self.n_layers, h.data_ptr(), xn.data_ptr(), qkv.data_ptr(),
-                                                     att.data_ptr(), act.data_ptr(), scratch.data_ptr(), sws.data_ptr(),
-                                                     self._cos_sin_dev().data_ptr(), kv8["stage_k"].data_ptr(), kv8["stage_vt"].data_ptr(),
-                                                     B, a.dim, H, Hkv, hd, self.ffn, smax, pos, a.norm_eps,
-                                                     torch.cuda.current_stream().cuda_stream)
-            _lib.check(rc, "a3v_llama_decode_step_kv8")
-            return
-        rc = _lib.load().a3v_llama_decode_step(self._layer_tab, self.n_layers, h.data_ptr(), xn.data_ptr(), qkv.data_ptr(),
-                                             att.data_ptr(), act.data_ptr(), scratch.data_ptr(), sws.data_ptr(), self._cos_sin_dev().data_ptr(),
-                                             B, a.dim, H, Hkv, hd, self.ffn, smax, pos, a.norm_eps,
-                                             torch.cuda.current_stream().cuda_stream)
-        _lib.check(rc, "a3v_llama_decode_step")
+            self._call_step("a3v_llama_decode_step_kv8", h, bufs, (kv8["stage_k"].data_ptr(), kv8["stage_vt"].data_ptr(), B), (pos,),
+                            tables=(self._kv8_tab,))
+        else:
+            self._call_step("a3v_llama_decode_step", h, bufs, (B,), (pos,))
 
     # ------------------------------------------------------------------ vision
     def _vit_geometry(self):
@@ -1050,23 +1048,11 @@ class Transformer(nn.Module):
     def _decode_step_rows(self, h: torch.Tensor, B: int, pos: torch.Tensor, pos_max: int, src_row=None, shared=None) -> None:
         """One bf16 decode step with row b at cache position pos[b] from one C call (a3v_llama_decode_step_rows; with shared prompt
         keys a3v_llama_decode_step_rows_shared)."""
-        a = self.args
-        tab = self._llama_layer_table()
-        H, Hkv, hd = self.n_heads, self.n_kv_heads, self.head_dim
-        xn, qkv, att, act, scratch, sws = self._decode_step_buffers(B)
+        bufs = self._decode_step_buffers(B)
         if src_row is not None:
-            rc = _lib.load().a3v_llama_decode_step_rows_shared(tab, self.n_layers, h.data_ptr(), xn.data_ptr(), qkv.data_ptr(), att.data_ptr(),
-                                                             act.data_ptr(), scratch.data_ptr(), sws.data_ptr(), self._cos_sin_dev().data_ptr(),
-                                                             pos.data_ptr(), src_row.data_ptr(), shared.data_ptr(), pos_max, B, a.dim, H, Hkv,
-                                                             hd, self.ffn, self._k_cache[0].shape[2], a.norm_eps,
-                                                             torch.cuda.current_stream().cuda_stream)
-            _lib.check(rc, "a3v_llama_decode_step_rows_shared")
-            return
-        rc = _lib.load().a3v_llama_decode_step_rows(tab, self.n_layers, h.data_ptr(), xn.data_ptr(), qkv.data_ptr(), att.data_ptr(),
-                                                  act.data_ptr(), scratch.data_ptr(), sws.data_ptr(), self._cos_sin_dev().data_ptr(),
-                                                  pos.data_ptr(), pos_max, B, a.dim, H, Hkv, hd, self.ffn, self._k_cache[0].shape[2],
-                                                  a.norm_eps, torch.cuda.current_stream().cuda_stream)
-        _lib.check(rc, "a3v_llama_decode_step_rows")
+            self._call_step("a3v_llama_decode_step_rows_shared", h, bufs, (pos.data_ptr(), src_row.data_ptr(), shared.data_ptr(), pos_max, B))
+        else:
+            self._call_step("a3v_llama_decode_step_rows", h, bufs, (pos.data_ptr(), pos_max, B))
 
     def _decoder_layers_rows(self, h: torch.Tensor, B: int, pos: torch.Tensor, pos_max: int, src_row=None, shared=None) -> None:
         """The ragged step kernel by kernel: _decoder_layers at S = 1 with a3v_rope_kvcache_rows / a3v_attention_decode_rows (with
@@ -1170,15 +1156,10 @@ class Transformer(nn.Module):
                  and _lib.load().a3v_llama_decode_step_verify_form(B, Q, a.dim, H, Hkv, hd, self.ffn, w8) == 2)
         sk_max = min(pos_max + Q, smax)
         if fused:
-            tab = self._llama_layer_table()
-            xn, qkv, att, act, _, sws = self._decode_step_buffers(min(M, 16))
-            xn, qkv, att, act, _ = self._row_buffers(M, False)
+            sws = self._decode_step_buffers(min(M, 16))[5]
             scratch, _ = self._verify_buffers(B, Q)
-            rc = _lib.load().a3v_llama_decode_step_verify(tab, self.n_layers, h.data_ptr(), xn.data_ptr(), qkv.data_ptr(), att.data_ptr(),
-                                                        act.data_ptr(), scratch.data_ptr(), sws.data_ptr(), self._cos_sin_dev().data_ptr(),
-                                                        pos.data_ptr(), nq.data_ptr(), pos_max, B, Q, a.dim, H, Hkv, hd, self.ffn, smax,
-                                                        a.norm_eps, torch.cuda.current_stream().cuda_stream)
-            _lib.check(rc, "a3v_llama_decode_step_verify")
+            self._call_step("a3v_llama_decode_step_verify", h, (*self._row_buffers(M, False)[:4], scratch, sws),
+                            (pos.data_ptr(), nq.data_ptr(), pos_max, B, Q))
         else:
             self._pack()
             cs = self._cos_sin_dev()
