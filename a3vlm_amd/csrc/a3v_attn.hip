@@ -940,3 +940,24 @@ int a3v_attention_decode_fused(const void* q, const void* k, const void* vt, voi
   A3V_LAUNCH_CHECK();
   return A3V_OK;
 }
+
+// The split plan as the library computes it, for callers that place key counts at its edges (tests/decode_attn_ref.py):
+// wave != 0: a3v_decode_wave_plan (every wave-streaming entry); wave == 0: the two-phase plan of a3v_attention at Sq = 1.
+extern "C" int a3v_attention_decode_plan(int B, int H, int Sk, int wave, int* nsplit, int* chunk) {
+  if (!nsplit || !chunk || B <= 0 || H <= 0 || Sk <= 0) return A3V_ERR_ARG;
+  if (wave) a3v_decode_wave_plan(B, H, Sk, nsplit, chunk);
+  else decode_plan(B, H, Sk, nsplit, chunk);
+  return A3V_OK;
+}
+
+// a3v_attention_decode_fused behind the checks of the other bf16 decode entries (16-byte vector access: strides and bases)
+extern "C" int a3v_attention_decode_fused_bf16(const void* q, const void* k, const void* vt, void* out, int B, int Sk, int H, int Hkv,
+                                               int hd, const int64_t* strides, float* scratch, int* counters, void* stream) {
+  if (!q || !k || !vt || !out || !strides || !scratch || !counters || B <= 0 || Sk <= 0 || H <= 0 || Hkv <= 0) return A3V_ERR_ARG;
+  if (H % Hkv || (hd != 64 && hd != 128)) return A3V_ERR_SHAPE;
+  for (int i = 0; i < 12; ++i)
+    if (i != 1 && i != 10 && (strides[i] % 8)) return A3V_ERR_SHAPE;      // the Sq strides are not used
+  if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k) | reinterpret_cast<uintptr_t>(vt)) & 15) return A3V_ERR_SHAPE;
+  if (Sk > strides[8] || (int64_t)Sk * strides[5] > strides[4]) return A3V_ERR_SHAPE;    // a V^T row and a K head bound Sk
+  return a3v_attention_decode_fused(q, k, vt, out, B, Sk, H, Hkv, hd, strides, scratch, counters, stream);
+}

@@ -86,6 +86,8 @@ SIGNATURES = {
     "a3v_vt_pack": (I, [P, L, P, I, I, I, I, I, I, P]),
     "a3v_attention_scratch_floats": (L, [I, I, I, I]),
     "a3v_attention": (I, [P, P, P, P, I, I, I, I, I, I, ctypes.POINTER(c_int64), I, P, I, P]),
+    "a3v_attention_decode_plan": (I, [I, I, I, I, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
+    "a3v_attention_decode_fused_bf16": (I, [P, P, P, P, I, I, I, I, I, ctypes.POINTER(c_int64), P, P, P]),
     "a3v_embed_assemble": (I, [P, L, P, P, I, I, I, I, I, I, I, P]),
     "a3v_fill_rows": (I, [P, P, L, P, I, I, I, I, P]),
     "a3v_patch_im2col": (I, [P, P, I, I, I, I, I, I, I, P]),

@@ -537,6 +537,27 @@ def attention(q, k, vt, out, B, Sq, Sk, H, Hkv, hd, strides, causal: bool, scrat
     return out
 
 
+def attention_decode_plan(B: int, H: int, Sk: int, wave: bool = True):
+    """(nsplit, chunk) of the library's decode split plan: the wave-streaming entries' (default) or the two-phase kernel's."""
+    ns, ch = ctypes.c_int(0), ctypes.c_int(0)
+    rc = _l.load().a3v_attention_decode_plan(B, H, Sk, 1 if wave else 0, ctypes.byref(ns), ctypes.byref(ch))
+    _l.check(rc, f"a3v_attention_decode_plan(B={B},H={H},Sk={Sk})")
+    return ns.value, ch.value
+
+
+def attention_decode_fused(q, k, vt, out, B, Sk, H, Hkv, hd, strides, scratch, counters):
+    """The decode attention of the fused decode step (bf16, hd 64 / 128): strides as ``attention`` at Sq = 1, scratch of
+    attention_scratch_floats(B, H, hd, Sk) floats, counters int32 [>= B*H], zero; left zero."""
+    _dev(q, k, vt, out, scratch, counters)
+    assert q.dtype == k.dtype == vt.dtype == out.dtype == torch.bfloat16
+    assert scratch.dtype == torch.float32 and scratch.numel() >= attention_scratch_floats(B, H, hd, Sk)
+    assert counters.dtype == torch.int32 and counters.numel() >= B * H
+    rc = _l.load().a3v_attention_decode_fused_bf16(_p(q), _p(k), _p(vt), _p(out), B, Sk, H, Hkv, hd, _Strides(*strides), _p(scratch),
+                                                   _p(counters), _stream())
+    _l.check(rc, f"a3v_attention_decode_fused_bf16(B={B},Sk={Sk},H={H},hd={hd})")
+    return out
+
+
 def kv_quantize_fp8(k_src, vt_src, src_pos: int, k_q, vt_q, k_scale, v_scale, S: int, dst_pos: int):
     """Positions src_pos .. src_pos+S-1 of a bf16 K [B,Hkv,Smax_src,hd] / V^T [B,Hkv,hd,Smax_src] pair -> positions dst_pos .. of the fp8
     caches (uint8, same layouts) and their per-(batch, kv-head, position) fp32 scales."""

@@ -421,6 +421,15 @@ int64_t a3v_attention_scratch_floats(int B, int H, int hd, int Sk);
 int a3v_attention(const void* q, const void* k, const void* vt, void* out, int B, int Sq, int Sk,
                   int H, int Hkv, int hd, const int64_t* strides, int causal, float* scratch,
                   int dtype, void* stream);
+/* a3v_attention_decode_plan: the split of Sk keys the decode entries use at (B, H): nsplit key ranges of `chunk` keys (a multiple
+ * of 64; the last range holds the rest).  wave != 0: the plan of every wave-streaming entry (decode_fused, decode_rows,
+ * decode_fp8kv, verify_rows at sk_max); wave == 0: the two-phase plan of a3v_attention at Sq = 1, which also sizes the scratch.
+ * a3v_attention_decode_fused_bf16: the decode attention of a3v_llama_decode_step as an entry of its own: bf16, hd in {64, 128},
+ * strides as a3v_attention at Sq = 1, 16-byte aligned q / k / vt, scratch of a3v_attention_scratch_floats(B, H, hd, Sk) floats,
+ * counters: B*H zero-initialised ints, left zero (the split partials are merged inside the launch). */
+int a3v_attention_decode_plan(int B, int H, int Sk, int wave, int* nsplit, int* chunk);
+int a3v_attention_decode_fused_bf16(const void* q, const void* k, const void* vt, void* out, int B, int Sk, int H, int Hkv, int hd,
+                                    const int64_t* strides, float* scratch, int* counters, void* stream);
 
 /* h[b, s, :] for the sequence [BOS | image words | text]: rows s==0 and s>W come from the
  * embedding table (tok_embeddings, LLM/llama_ens5.py:464,495), rows 1..W are left untouched
