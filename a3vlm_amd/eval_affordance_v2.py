@@ -161,7 +161,26 @@ def get_args_parser():
                         "from the row's own earlier tokens; the answers are the greedy ones, every record gains \"accepted_per_step\" "
                         "(accepted drafts per row step of the generate_many call that produced it).  Needs --continuous_rows R with "
                         "R * (D + 1) <= 32 and --temperature 0")
+    p.add_argument("--answer_regex", type=str, default=None,
+                   help="constrained decoding (MetaModel.generate(constraint=PATTERN)): every step may only choose tokens that can still "
+                        "lead to a full match of PATTERN (literals, escapes, '.', '\\d', [...] classes, groups, '|', '?', '*', '+', "
+                        "'{m}', '{m,n}'), and EOS only where the answer matches; an answer cut by --max_gen_len is a prefix of a match "
+                        "and keeps its \"fail\" flag.  Not with --lookup_decoding")
     return p
+
+
+def check_answer_regex(args):
+    pattern = getattr(args, "answer_regex", None)
+    if pattern is not None and int(getattr(args, "lookup_decoding", 0) or 0):
+        raise SystemExit(f"--answer_regex changes the choice lookup decoding verifies its drafts against: set --lookup_decoding 0 "
+                         f"(or drop --answer_regex)")
+    if pattern is not None:
+        from .model.constrain import parse_regex
+        try:
+            parse_regex(pattern)           # a pattern outside the subset ends the run before the model is built
+        except ValueError as e:
+            raise SystemExit(f"--answer_regex: {e}")
+    return pattern
 
 
 def check_lookup(args) -> int:
@@ -211,6 +230,7 @@ def check_num_samples(args) -> int:
 def main(args):
     num_samples = check_num_samples(args)      # before the model is built
     lookup = check_lookup(args)
+    answer_regex = check_answer_regex(args)
     distributed = "RANK" in os.environ and "WORLD_SIZE" in os.environ
     rank, world, local = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("LOCAL_RANK", 0))
     if args.model_parallel_size != 1:
@@ -261,6 +281,12 @@ def main(args):
     controls = dict(repetition_penalty=getattr(args, "repetition_penalty", 1.0), return_logprobs=save_scores or num_samples > 1)
     if getattr(args, "top_k", 0) or getattr(args, "min_p", 0.0):      # opt-in: with the defaults the calls below are what they were
         controls.update(top_k=args.top_k, min_p=args.min_p)
+    if answer_regex is not None:      # compiled against the model's vocabulary once (MetaModel keeps it by pattern); refusals end the run here
+        try:
+            model.constraint_automaton(answer_regex)
+        except ValueError as e:
+            raise SystemExit(f"--answer_regex: {e}")
+        controls.update(constraint=answer_regex)
     with torch.no_grad():
         for image, qids, prompts, annotations, paths in loader:
             image = pre.batch(image) if isinstance(image, list) else image.to(dev)

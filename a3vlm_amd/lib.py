@@ -147,6 +147,8 @@ SIGNATURES = {
     "a3v_seen_clear_rows": (I, [P, P, I, L, L, I, P]),
     "a3v_logits_prepare": (I, [P, L, P, L, F, P, L, P, I, I, P]),
     "a3v_generate_record": (I, [P, L, P, P, L, I, P, P, P, L, P, L, I, I, P, I, I, P]),
+    "a3v_constrain_logits": (I, [P, L, P, I, I, P, P, L, I, P]),
+    "a3v_constrain_advance": (I, [P, L, I, P, P, P, P, I, I, P, I, P]),
     "a3v_adam8_quantize": (I, [P, P, P, P, P, P, L, P]),
     "a3v_adam8_dequantize": (I, [P, P, P, P, P, P, L, P]),
     "a3v_adamw8_scaled": (I, [P, P, P, P, P, P, L, F, F, F, F, F, L, P, P, P]),

@@ -23,7 +23,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from . import genctl
+from . import constrain, genctl
 from .LLM.weight_formats import FORMATS
 from .tokenizer import Tokenizer, probe_tokenizer_path_from_pretrained  # noqa: F401
 
@@ -69,6 +69,7 @@ class MetaModel(nn.Module):
         self.criterion = torch.nn.CrossEntropyLoss(ignore_index=0)  # kept as an attribute (meta.py:67)
         self._set_default_trainability(pretrain_stage)
         self.is_peft = getattr(model, "is_peft", False)
+        self._constraints: Dict[str, constrain.TokenAutomaton] = {}      # pattern -> automaton over this model's vocabulary
 
     # ------------------------------------------------------------------ construction from a checkpoint folder
     @classmethod
@@ -303,13 +304,29 @@ class MetaModel(nn.Module):
         return res
 
     # ------------------------------------------------------------------ generation
+    def constraint_automaton(self, constraint) -> Optional[constrain.TokenAutomaton]:
+        """The ``constraint`` argument of ``generate`` / ``generate_many`` as a ``TokenAutomaton``: a pattern string is compiled
+        against this model's tokenizer (``model/constrain.py``: regex -> DFA -> int16 table over the vocabulary) and kept by pattern.
+        Host work only; every refusal (unsupported construct, dead end under the vocabulary, too many states) is a ``ValueError``."""
+        constrain.check_constraint(constraint)
+        V = self.llma.args.vocab_size
+        if isinstance(constraint, str):
+            if constraint not in self._constraints:
+                pieces = list(self.tokenizer.pieces())[:V]
+                pieces += [None] * (V - len(pieces))             # ids the tokenizer does not know contribute no text
+                self._constraints[constraint] = constrain.compile_constraint(constraint, pieces, self.tokenizer.eos_id)
+            constraint = self._constraints[constraint]
+        if constraint is not None and constraint.vocab_size != V:
+            raise ValueError(f"constraint: the automaton was compiled for {constraint.vocab_size} tokens, the model has {V}")
+        return constraint
+
     @torch.no_grad()
     def generate(self, prompts: List[str], images: Optional[torch.Tensor] = None,
                  depth_images: Optional[torch.Tensor] = None, max_gen_len: int = 512,
                  temperature: float = 0.0, top_p: float = 0.95,
                  additional_stop_symbols: Iterable[str] = (), return_ids: bool = False, poll_every: int = 4,
                  sample_uniforms: Optional[torch.Tensor] = None, repetition_penalty: float = 1.0,
-                 return_logprobs: bool = False, top_k: int = 0, min_p: float = 0.0) -> List[str]:
+                 return_logprobs: bool = False, top_k: int = 0, min_p: float = 0.0, constraint=None) -> List[str]:
         """meta.py:379-485.  ``return_ids`` additionally returns the generated id lists (the
         arguments of tokenizer.decode at :482-484) for bit-exact parity checks.
         ``temperature > 0`` (the eval script's default recipe, T 0.1 / top-p 0.75): the nucleus draw of :456-459 / :568-583 runs on
@@ -325,11 +342,19 @@ class MetaModel(nn.Module):
         inside the step (model/genctl.py); with the defaults nothing of them is allocated or launched.
         ``top_k`` / ``min_p`` (opt-in, ``temperature > 0`` only; 0 = off): HF's two other filters on the device, in HF's order
         temperature, top-k, top-p, min-p (``a3v_sample_top_k_p``); they see the penalised row.  With the defaults the sampler is
-        ``a3v_sample_top_p`` as before."""
+        ``a3v_sample_top_p`` as before.
+        ``constraint`` (opt-in; a ``TokenAutomaton`` or a regex pattern string, see ``constraint_automaton``): constrained decoding.
+        Every step's choice is restricted to the tokens that can still lead to a full match of the pattern, and EOS to the places
+        where the text so far is one: the row's automaton state lives on the device, ``a3v_constrain_logits`` masks the (penalised)
+        row in front of the sampler / argmax and ``a3v_constrain_advance`` moves the state behind the token write, no host read.
+        An answer that ends on EOS matches the pattern; one that reaches ``max_gen_len`` first is a viable PREFIX of a match, not a
+        match.  Scores (``return_logprobs``) stay the UNCONSTRAINED model's log-probabilities of the chosen tokens (raw logits), and
+        the repetition penalty is applied before the mask.  With ``constraint=None`` nothing of it is allocated or launched."""
         if isinstance(prompts, str):
             raise ValueError(f"{self.__class__}.generate expects a batched LIST of prompts, but str is given")
         controls = genctl.wanted(repetition_penalty, return_logprobs)      # ValueError before any device use
         top_k, min_p = genctl.check_filters(top_k, min_p)
+        automaton = self.constraint_automaton(constraint)
         dev = self._device
         if images is not None:
             images = images.to(dev)
@@ -380,6 +405,10 @@ class MetaModel(nn.Module):
             gc = genctl.GenControls(bsz, args.vocab_size, total_len - start_pos, repetition_penalty, return_logprobs, dev)
             gc.prompt_len.copy_(torch.tensor([len(t) for t in prompt_tokens], dtype=torch.int32))
             gc.mark_prompts(tokens)
+        cs = None
+        if automaton is not None:      # every row starts in the automaton's start state; its first generated id sits behind its prompt
+            cs = constrain.ConstraintState(automaton, bsz, args.vocab_size, dev)
+            cs.first.copy_(torch.tensor([len(t) for t in prompt_tokens], dtype=torch.int32))
 
         # One iteration = the model step (one C call for a decode step) + ONE launch of a3v_generate_step, which does everything
         # meta.py:456-477 does with a dozen small torch ops: argmax, teacher forcing of longer prompts, the tokens[:, cur_pos]
@@ -394,11 +423,15 @@ class MetaModel(nn.Module):
                 logits = self.llma.forward_inference(tokens[:, prev_pos:cur_pos], prev_pos,
                                                      images if prev_pos == 0 else None)
             z = gc.prepare(logits) if gc is not None else logits       # the choice reads the penalised row, the score the raw one
+            if cs is not None:         # ... under the automaton's mask (a teacher-forced step is masked too: its choice is discarded)
+                z = cs.mask(z, logits)
             if temperature > 0:
                 self._sample_into(z, temperature, top_p, uni[cur_pos - start_pos], sampled, top_k, min_p)
             ops.generate_step(z, sampled, tokens, text_mask, cur_pos, stop_seq, stop_off, len(l_stop), stopped, stop_pos, live)
             if gc is not None:         # a stopped row keeps writing past its stop_pos, as its tokens do: cut below
                 gc.record(logits, tokens, col=cur_pos)
+            if cs is not None:         # a stopped row sits in DONE (only EOS allowed) or keeps walking: cut below as well
+                cs.advance(tokens, col=cur_pos)
             if ((cur_pos - start_pos) % poll_every == poll_every - 1 or cur_pos == total_len - 1) and int(live.item()) == 0:
                 break
             prev_pos = cur_pos
@@ -421,7 +454,7 @@ class MetaModel(nn.Module):
                       additional_stop_symbols: Iterable[str] = (), return_ids: bool = False, poll_every: int = 4,
                       sample_uniforms: Optional[torch.Tensor] = None, repetition_penalty: float = 1.0,
                       return_logprobs: bool = False, top_k: int = 0, min_p: float = 0.0, n: int = 1,
-                      lookup: Optional[int] = None, lookup_ngram: int = 3, lookup_drafter=None):
+                      lookup: Optional[int] = None, lookup_ngram: int = 3, lookup_drafter=None, constraint=None):
         """Any number of prompts through ``batch_rows`` KV-cache rows (no reference counterpart; opt-in): every row decodes at its
         own position, and a row whose answer is finished is prefilled with the next prompt while the others keep decoding, so a
         short answer does not hold its row until the longest answer of a batch is done.  Answers come back in input order.
@@ -449,6 +482,9 @@ class MetaModel(nn.Module):
         host read; ``batch_rows * (D + 1) <= 32``.  Afterwards ``self.last_lookup_stats`` holds ``steps`` (row steps), ``tokens``,
         ``drafted`` and ``accepted``.  ``lookup_drafter`` (tests): a callable ``(tokens, cur, limit, pos, stopped, next_tok, x, nq)``
         that fills x / nq in place of the lookup kernel.
+        ``constraint``: as in ``generate`` (a ``TokenAutomaton`` or a pattern string; scores stay the unconstrained model's).  The
+        state belongs to the cache row and is set back to the start at every refill, for every sibling row when ``n > 1``.  Not with
+        ``lookup`` (verification compares against the unconstrained argmax): use ``lookup=0``.
         Not for the fp8 KV cache, LoRA models before ``merge_lora()`` or the two-image plugin (each raises, naming the way out)."""
         from .ragged import GroupScheduler, LookupBound, RowScheduler
         if isinstance(prompts, str):
@@ -464,6 +500,10 @@ class MetaModel(nn.Module):
         if n > int(batch_rows):
             raise ValueError(f"generate_many: n = {n} samples per prompt need n cache rows at once: batch_rows = {batch_rows} < n")
         D = int(lookup or 0)
+        if D and constraint is not None:
+            raise ValueError("generate_many: lookup decoding verifies drafts against the unconstrained argmax, a constraint changes the "
+                             "choice: use lookup=0, or constraint=None")
+        automaton = self.constraint_automaton(constraint)
         if D:                              # refusals of lookup decoding, before any device use
             if D < 0 or D > 7:
                 raise ValueError(f"generate_many: lookup = {D} drafted tokens per step; 1 .. 7 (a step has at most 8 query positions per row)")
@@ -538,6 +578,7 @@ class MetaModel(nn.Module):
         if controls:
             gc = genctl.GenControls(R, args.vocab_size, max(lim - ln for lim, ln in zip(limits, lens)), repetition_penalty,
                                     return_logprobs, dev)
+        cs = constrain.ConstraintState(automaton, R, args.vocab_size, dev) if automaton is not None else None
         # answers are kept per (prompt, sample) at index i * n + s
         sched = RowScheduler(lens, limits, R, W) if n == 1 else GroupScheduler(lens, limits, R, W, n)
         ids: List[Optional[List[int]]] = [None] * (N * n)
@@ -616,6 +657,8 @@ class MetaModel(nn.Module):
                         gc.mark_prompts(tokens, row)
                     if ubase is not None:
                         ubase[row] = (i * n + s) * n_uni - sched.steps
+                    if cs is not None:     # a refilled row (every sibling of a group) starts over
+                        cs.reset(row, lens[i])
             for i in sched.finished_at_once:
                 for s in range(n):
                     ids[i * n + s] = []
@@ -626,6 +669,9 @@ class MetaModel(nn.Module):
             if gc is not None:
                 z = gc.prepare(logits)
                 gc.snapshot(stopped)       # a row that is stopped on entry is not touched by the step, nor by the record
+            if cs is not None:
+                z = cs.mask(z, logits)
+                cs.stopped_before.copy_(stopped)               # as gc.snapshot: a row stopped on entry is not advanced
             if temperature > 0:
                 u = uni[(ubase + sched.steps).clamp_(0, uni.numel() - 1)]
                 self._sample_into(z, temperature, top_p, u, sampled, top_k, min_p)
@@ -633,6 +679,8 @@ class MetaModel(nn.Module):
                                    next_tok, pos)
             if gc is not None:
                 gc.record(logits, tokens, cur=cur, stopped_before=gc.stopped_before)
+            if cs is not None:
+                cs.advance(tokens, cur=cur, stopped_before=cs.stopped_before)
             pos_max = sched.advance()
             if sched.steps % poll_every == 0 or all(sched.generated[r] >= limits[i] - lens[i] for r, i in sched.occupied()):
                 st = stopped.tolist()
@@ -666,10 +714,14 @@ class MetaModel(nn.Module):
     def stream_generate(self, prompt: str, image: Optional[torch.Tensor] = None, max_gen_len: int = 512,
                         temperature: float = 0.0, top_p: float = 0.95,
                         additional_stop_symbols: Iterable[str] = (), repetition_penalty: float = 1.0,
-                        return_logprobs: bool = False, top_k: int = 0, min_p: float = 0.0):
+                        return_logprobs: bool = False, top_k: int = 0, min_p: float = 0.0, constraint=None):
         """meta.py:487-566.  ``repetition_penalty`` / ``return_logprobs`` as in ``generate``; with ``return_logprobs`` every yielded
         dict also carries ``"logprobs"``: one value per token generated so far (the text may be cut inside the last ones by a stop
-        string).  ``top_k`` / ``min_p`` as in ``generate``."""
+        string).  ``top_k`` / ``min_p`` as in ``generate``.  ``constraint`` is refused: constrained decoding has no streaming form
+        (use ``generate`` / ``generate_many``)."""
+        if constraint is not None:
+            raise ValueError("stream_generate: constrained decoding has no streaming form: use generate(constraint=...) or "
+                             "generate_many(constraint=...), or constraint=None")
         controls = genctl.wanted(repetition_penalty, return_logprobs)      # ValueError before any device use
         top_k, min_p = genctl.check_filters(top_k, min_p)
         args = self.llma.args

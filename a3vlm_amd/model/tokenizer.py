@@ -33,6 +33,17 @@ class _SentencePieceVocab:
     def write(self, directory: str) -> None:
         (Path(directory) / "tokenizer.model").write_bytes(self.impl.serialized_model_proto())
 
+    def pieces(self) -> List[Optional[str]]:
+        sp, out = self.impl, []
+        for v in range(self.size):
+            if sp.is_control(v) or sp.is_unknown(v) or sp.is_unused(v):
+                out.append(None)
+            elif sp.is_byte(v):
+                out.append(_byte_piece(sp.id_to_piece(v)))
+            else:
+                out.append(sp.id_to_piece(v).replace("\u2581", " "))
+        return out
+
 
 class _HuggingFaceVocab:
     kind = "transformers"
@@ -50,6 +61,45 @@ class _HuggingFaceVocab:
 
     def write(self, directory: str) -> None:
         self.impl.save_pretrained(directory)
+
+    def pieces(self) -> List[Optional[str]]:
+        special = set(self.impl.all_special_ids)
+        toks = self.impl.convert_ids_to_tokens(list(range(self.size)))
+        # a byte-level BPE vocabulary spells every byte as one printable character (GPT-2's table: "\u0120" is the space)
+        byte_level = any(t is not None and t.startswith("\u0120") for t in toks)
+        table = _gpt2_byte_table() if byte_level else None
+        out: List[Optional[str]] = []
+        for v, t in enumerate(toks):
+            if t is None or v in special:
+                out.append(None)
+            elif byte_level:
+                try:
+                    out.append(bytes(table[c] for c in t).decode("utf-8"))
+                except (KeyError, UnicodeDecodeError):     # an added token, or a piece that ends inside a UTF-8 sequence
+                    out.append(None)
+            elif len(t) == 6 and t.startswith("<0x") and t.endswith(">"):
+                out.append(_byte_piece(t))
+            else:
+                out.append(t.replace("\u2581", " "))
+        return out
+
+
+def _byte_piece(piece: str) -> Optional[str]:
+    """A byte-fallback token ``<0xNN>``: its character when the byte is ASCII, None otherwise (a fragment of a UTF-8 sequence is no
+    text on its own)."""
+    b = int(piece[3:5], 16)
+    return chr(b) if b < 0x80 else None
+
+
+def _gpt2_byte_table() -> dict:
+    """printable character -> byte of byte-level BPE vocabularies (the inverse of GPT-2's bytes_to_unicode)"""
+    keep = list(range(ord("!"), ord("~") + 1)) + list(range(0xA1, 0xAD)) + list(range(0xAE, 0x100))
+    table, n = {chr(b): b for b in keep}, 0
+    for b in range(256):
+        if b not in keep:
+            table[chr(256 + n)] = b
+            n += 1
+    return table
 
 
 def _ends_with(seq: Sequence[int], tail: Sequence[int]) -> bool:
@@ -112,6 +162,12 @@ class Tokenizer:
     @property
     def n_words(self) -> int:
         return self._vocab.size
+
+    def pieces(self) -> List[Optional[str]]:
+        """Per token id the text it contributes to a decoded answer, SentencePiece's word-boundary marker read as a space; ``None``
+        for a token that contributes no text (BOS, EOS, pad, unknown, control, a lone byte of a multi-byte character).  The input
+        of ``model.constrain.compile_constraint``."""
+        return self._vocab.pieces()
 
 
 def probe_tokenizer_path_from_pretrained(pretrained_path: str) -> Optional[str]:

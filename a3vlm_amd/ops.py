@@ -917,6 +917,43 @@ def generate_record(logits, lse, tokens, seen, logprob, *, col: int = 0, cur=Non
     _l.check(rc, "a3v_generate_record")
 
 
+def _trans_ok(trans, V: int):
+    assert trans.dtype == torch.int16 and trans.dim() == 2 and trans.is_contiguous() and trans.shape[1] == V, (tuple(trans.shape), V)
+    assert 1 <= trans.shape[0] <= 32767, trans.shape[0]
+
+
+def constrain_logits(logits, trans, state, out):
+    """One launch (a3v_constrain_logits): out[b, v] = logits[b, v] where the token automaton ``trans`` (int16 [n_states, V]) allows
+    token v in ``state[b]`` (device int32), -inf elsewhere; a row whose state is outside [0, n_states) is copied unchanged.  ``out``
+    may be ``logits`` itself (in place).  Kept values keep their bits."""
+    _dev(logits, trans, state, out)
+    assert logits.dtype == out.dtype == torch.float32 and logits.dim() == out.dim() == 2 and logits.stride(1) == out.stride(1) == 1
+    B, V = logits.shape
+    assert out.shape == logits.shape, (tuple(out.shape), tuple(logits.shape))
+    _trans_ok(trans, V)
+    assert state.dtype == torch.int32 and state.is_contiguous() and state.numel() >= B
+    rc = _l.load().a3v_constrain_logits(_p(logits), logits.stride(0), _p(trans), V, trans.shape[0], _p(state), _p(out), out.stride(0), B,
+                                        _stream())
+    _l.check(rc, "a3v_constrain_logits")
+    return out
+
+
+def constrain_advance(tokens, trans, state, first, *, col: int = 0, cur=None, stopped_before=None):
+    """After generate_step / generate_step_rows wrote the chosen ids (a3v_constrain_advance): state[b] = trans[state[b], id] for the id
+    of column ``col`` (uniform step) or ``cur[b] - 1`` (ragged).  Rows with ``stopped_before[b]`` set, idle rows, columns below
+    ``first[b]`` (teacher-forced prompt tokens), out-of-range states and ids change nothing."""
+    _dev(tokens, trans, state, first, cur, stopped_before)
+    B = tokens.shape[0]
+    assert tokens.dtype == torch.int64 and tokens.dim() == 2 and tokens.stride(1) == 1
+    _trans_ok(trans, trans.shape[1])
+    for t, d in ((state, torch.int32), (first, torch.int32), (cur, torch.int32), (stopped_before, torch.bool)):
+        assert t is None or (t.dtype == d and t.is_contiguous() and t.numel() >= B)
+    rc = _l.load().a3v_constrain_advance(_p(tokens), tokens.stride(0), int(col), _p(cur), _p(first), _p(stopped_before), _p(trans),
+                                         trans.shape[1], trans.shape[0], _p(state), B, _stream())
+    _l.check(rc, "a3v_constrain_advance")
+    return state
+
+
 def count_valid(labels, n_valid):
     _dev(labels, n_valid)
     rc = _l.load().a3v_count_valid(_p(labels), labels.numel(), _p(n_valid), _stream())

@@ -816,6 +816,43 @@ int a3v_generate_record(const float* logits, int64_t ld, const float* lse, const
                         int64_t ld_lp, int n_lp, int idx, const int32_t* prompt_len, int B, int V, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Constrained decoding (opt-in; a3v_constrain.hip): every step's choice is restricted to the tokens that can still lead to a full
+ * match of a regular expression.  No existing entry changes; without a constraint none of these is launched.
+ *
+ * Token automaton (built on the host, model/constrain.py): trans int16 [n_states, V], row-major, 1 <= n_states <= 32767.
+ *   trans[s, v] = the state after token v from state s, or -1 when v is not allowed in s (its text leaves the language, it
+ *   contributes no text, or it is the end-of-sequence id in a state that does not accept).  The end-of-sequence id leads from an
+ *   accepting state to a last state DONE in which only that id is allowed.  The host refuses an automaton with a reachable state
+ *   that allows no token, so a masked row always keeps at least one finite entry.
+ * State: device int32 [B], one per cache row.  A value outside [0, n_states) marks an UNCONSTRAINED row: the mask leaves its logits
+ *   alone and the advance leaves its state alone.  The kernels bound the state themselves (the host never reads it).
+ * Step order: a3v_logits_prepare (repetition penalty) -> a3v_constrain_logits -> sampler / argmax -> the token write of
+ *   a3v_generate_step / a3v_generate_step_rows -> a3v_generate_record on the RAW logits -> a3v_constrain_advance.  The scores stay
+ *   the unconstrained model's log-probabilities.
+ *
+ * a3v_constrain_logits: logits / out fp32 [B, V] (row strides ld >= V, ld_out >= V, any value: rows need not be 16-byte aligned);
+ *   out == logits with ld_out == ld is the in-place form, any other overlap is undefined.  Row b with 0 <= state[b] < n_states:
+ *   out[b, v] = logits[b, v] where trans[state[b], v] >= 0 -- the input's bit pattern, NaN payloads included -- and -inf elsewhere.
+ *   Any other state[b]: the row is copied unchanged.  Columns [V, ld_out) are never written.  Any V >= 1; one launch.
+ *   The -inf entries are safe for every consumer: a3v_argmax and the step kernels start from -inf with a first-index tie break, so a
+ *   finite entry always wins; a3v_sample_top_p / a3v_sample_top_k_p give such a token the mass expf(-inf) = 0 exactly, and their
+ *   selection only ever lands on a bin of positive mass (a3v_common.h, topp_select); top-k ranks -inf below every finite value and
+ *   min-p > 0 removes a zero mass.
+ * a3v_constrain_advance: runs AFTER the step kernel has written the chosen id (and after a3v_generate_record, which it does not
+ *   depend on).  Column c = col (cur == NULL: the uniform step), or cur[b] - 1 (the rows form, after a3v_generate_step_rows has
+ *   advanced cur).  Nothing changes for a row with stopped_before[b] set (may be NULL), with c outside [0, ld_tok), with
+ *   c < first[b] (first: device int32 [B], the index of the row's first generated token: below it the column holds a teacher-forced
+ *   prompt token of generate), with a state outside [0, n_states) or with an id outside [0, V).  Otherwise
+ *   state[b] = trans[state[b], tokens[b, c]].  Integer work: bit-identical to the restatement in tests/constrain_ref.py.
+ * Both return A3V_ERR_ARG for a NULL array, B <= 0, V <= 0, n_states outside [1, 32767], a stride below V, ld_tok <= 0 or (uniform
+ *   form) col outside [0, ld_tok); nothing is launched on an error.
+ * ------------------------------------------------------------------------------------- */
+int a3v_constrain_logits(const float* logits, int64_t ld, const int16_t* trans, int V, int n_states, const int32_t* state, float* out,
+                         int64_t ld_out, int B, void* stream);
+int a3v_constrain_advance(const int64_t* tokens, int64_t ld_tok, int col, const int32_t* cur, const int32_t* first,
+                          const uint8_t* stopped_before, const int16_t* trans, int V, int n_states, int32_t* state, int B, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Training (backward) entry points. Reference: autograd through the same modules under
  * autocast(bf16) with fp32 master weights (engine_finetune.py:44-68, main_finetune.py:212-217).
  * Convention: activations and their grads use `act_dtype` (bf16 / f32 parity); the residual
