@@ -122,7 +122,7 @@ __global__ __launch_bounds__(256) void adamw8_kernel(float* __restrict__ p, cons
                                                      int64_t nblk, float decay, float b1, float b2, float step_size, float inv_bc2_sqrt,
                                                      float eps, bf16_t* __restrict__ img, const float* __restrict__ gscale) {
   const float gs = gscale ? *gscale : 1.f;
-  if (!(gs >= 0.f)) return;                      // negative or NaN: no-op on the parameter, the codes, the scales and the image
+  if (adamw_skip(gs)) return;                      // negative or NaN: no-op on the parameter, the codes, the scales and the image
   const int lane = threadIdx.x & 63;
   const int64_t stride = (int64_t)gridDim.x * 4;
   int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);

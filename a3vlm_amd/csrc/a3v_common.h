@@ -64,6 +64,9 @@ __device__ __forceinline__ void adamw_update(float& p, float g, float& m, float&
   p -= step_size * m / (sqrtf(v) * inv_bc2_sqrt + eps);
 }
 
+// The clip coefficient that makes an AdamW step a no-op: NaN or sign bit set (negative, and -0.0 with them: the sign is the flag)
+__device__ __forceinline__ bool adamw_skip(float gs) { return !(gs >= 0.f) || (__float_as_uint(gs) >> 31); }
+
 template <typename T> struct Cvt;
 template <> struct Cvt<float> {
   static __device__ __forceinline__ float ld(const float* p) { return *p; }

@@ -1113,7 +1113,7 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
                                                     float step_size, float inv_bc2_sqrt, float eps, bf16_t* __restrict__ img,
                                                     const float* __restrict__ gscale) {
   const float gs = gscale ? *gscale : 1.f;       // clip coefficient (device scalar): g * coef rounded to fp32 = the value grad.mul_(coef) stores
-  if (!(gs >= 0.f)) return;                      // negative or NaN: the caller's "this step saw a non-finite loss / gradient norm" flag
+  if (adamw_skip(gs)) return;                      // negative or NaN: the caller's "this step saw a non-finite loss / gradient norm" flag
                                                  // -> the update is a no-op (masters, moments and bf16 images stay as they were)
   const int64_t stride = (int64_t)gridDim.x * 256;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
@@ -1204,7 +1204,7 @@ __global__ __launch_bounds__(256) void adamw_tile_t_kernel(float* __restrict__ p
                                                            float step_size, float inv_bc2_sqrt, float eps, bf16_t* __restrict__ img,
                                                            bf16_t* __restrict__ imgt, int64_t ldt, const float* __restrict__ gscale) {
   const float gs = gscale ? *gscale : 1.f;
-  if (!(gs >= 0.f)) return;
+  if (adamw_skip(gs)) return;
   constexpr int PITCH = TR + 2;                   // bf16 elements per patch row (c-major: patch[c][r]); an odd number of dwords
   __shared__ bf16_t patch2[2][64 * PITCH];        // alternating patches: ONE barrier per tile (a patch is re-written two tiles later, behind the next tile's barrier)
   int flip = 0;
@@ -1316,7 +1316,7 @@ namespace {
 __global__ __launch_bounds__(256) void adamw_multi_kernel(const a3v_adamw_tensor* __restrict__ tab, float decay, float b1, float b2,
                                                           float step_size, float inv_bc2_sqrt, float eps, const float* __restrict__ gscale) {
   const float gs = gscale ? *gscale : 1.f;
-  if (!(gs >= 0.f)) return;
+  if (adamw_skip(gs)) return;
   const a3v_adamw_tensor t = tab[blockIdx.y];
   const int64_t n4 = t.n / 4;
   const int64_t stride = (int64_t)gridDim.x * 256;

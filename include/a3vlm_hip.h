@@ -988,7 +988,7 @@ int a3v_adamw(float* param, const float* grad, float* exp_avg, float* exp_avg_sq
  * NativeScalerWithGradNormCount.__call__ (util/misc.py:302-315) / clip_grad_norm (util/clip_grad.py:187-193: coef =
  * max_norm / (norm + 1e-6) clamped to 1, every gradient multiplied by it) folded into the optimizer pass -- same values as
  * grad.mul_(coef) followed by a3v_adamw, without the extra read + write of every gradient and without a host read of the norm. */
-/* A NEGATIVE or NaN *grad_scale makes the call a no-op: the trainer folds "loss and gradient norm of this step are finite" into
+/* A NEGATIVE (sign bit set: -0.0 included) or NaN *grad_scale makes the call a no-op: the trainer folds "loss and gradient norm of this step are finite" into
  * the coefficient on the device, so a bad step never reaches the fp32 masters, the moments or the bf16 weight images (the
  * reference stops before backward on a non-finite loss, engine_finetune.py:56-58; here the host reads the flag later). */
 int a3v_adamw_scaled(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1, float beta2,
