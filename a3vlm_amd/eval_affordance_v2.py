@@ -165,15 +165,21 @@ def get_args_parser():
                    help="constrained decoding (MetaModel.generate(constraint=PATTERN)): every step may only choose tokens that can still "
                         "lead to a full match of PATTERN (literals, escapes, '.', '\\d', [...] classes, groups, '|', '?', '*', '+', "
                         "'{m}', '{m,n}'), and EOS only where the answer matches; an answer cut by --max_gen_len is a prefix of a match "
-                        "and keeps its \"fail\" flag.  Not with --lookup_decoding")
+                        "and keeps its \"fail\" flag.  Not with --lookup_decoding, unless --lookup_verify choice")
+    p.add_argument("--lookup_verify", type=str, choices=["argmax", "choice"], default="argmax",
+                   help="how --lookup_decoding verifies its drafts.  argmax (default): against the greedy choice.  choice: sample and "
+                        "match (MetaModel.generate_many(lookup_verify='choice')): every query's token is chosen as the plain loop would "
+                        "choose it -- penalty, --answer_regex mask, temperature / top-k / top-p / min-p with the uniform of its generated "
+                        "index -- and a draft is kept when the choice equals it; allows --temperature > 0, --answer_regex, "
+                        "--repetition_penalty and --save_scores beside --lookup_decoding (still --num_samples 1)")
     return p
 
 
 def check_answer_regex(args):
     pattern = getattr(args, "answer_regex", None)
-    if pattern is not None and int(getattr(args, "lookup_decoding", 0) or 0):
+    if pattern is not None and int(getattr(args, "lookup_decoding", 0) or 0) and getattr(args, "lookup_verify", "argmax") != "choice":
         raise SystemExit(f"--answer_regex changes the choice lookup decoding verifies its drafts against: set --lookup_decoding 0 "
-                         f"(or drop --answer_regex)")
+                         f"(or drop --answer_regex), or add --lookup_verify choice")
     if pattern is not None:
         from .model.constrain import parse_regex
         try:
@@ -189,10 +195,11 @@ def check_lookup(args) -> int:
         raise SystemExit(f"--lookup_decoding {d}: 0 (off) .. 7 drafted tokens per step")
     if d and getattr(args, "continuous_rows", 0) <= 0:
         raise SystemExit(f"--lookup_decoding {d} runs on the per-row decode path: add --continuous_rows R")
-    if d and args.temperature > 0:
-        raise SystemExit(f"--lookup_decoding {d} verifies drafts against the greedy choice: set --temperature 0")
+    choice = getattr(args, "lookup_verify", "argmax") == "choice"
+    if d and args.temperature > 0 and not choice:
+        raise SystemExit(f"--lookup_decoding {d} verifies drafts against the greedy choice: set --temperature 0, or add --lookup_verify choice")
     if d and int(getattr(args, "num_samples", 1)) > 1:
-        raise SystemExit(f"--lookup_decoding {d} is greedy: use --num_samples 1")
+        raise SystemExit(f"--lookup_decoding {d} " + ("has no parallel-sampling form" if choice else "is greedy") + ": use --num_samples 1")
     if d and getattr(args, "continuous_rows", 0) * (d + 1) > 32:
         raise SystemExit(f"--lookup_decoding {d} with --continuous_rows {args.continuous_rows}: rows * (D + 1) must be <= 32")
     return d
@@ -304,7 +311,8 @@ def main(args):
                 continue
             if rows > 0:           # a chunk of a few batches at a time: the loader's workers stay ahead of the decode
                 answers = model.generate_many(prompts, image, batch_rows=rows, max_gen_len=args.max_gen_len, temperature=args.temperature,
-                                              top_p=args.top_p, **controls, **({"lookup": lookup} if lookup else {}))
+                                              top_p=args.top_p, **controls, **({"lookup": lookup} if lookup else {}),
+                                              **({"lookup_verify": "choice"} if lookup and getattr(args, "lookup_verify", "argmax") == "choice" else {}))
             else:
                 answers = model.generate(prompts, image, max_gen_len=args.max_gen_len, temperature=args.temperature, top_p=args.top_p,
                                          **controls)

@@ -75,3 +75,42 @@ class GenControls:
     def record(self, logits: torch.Tensor, tokens: torch.Tensor, *, col: int = 0, cur=None, stopped_before=None) -> None:
         ops.generate_record(logits, self.lse, tokens, self.seen, self.lp, col=col, cur=cur, stopped_before=stopped_before,
                             prompt_len=self.prompt_len)
+
+
+class VerifyControls:
+    """Device state of ``generate_many(lookup=D, lookup_verify="choice")`` (include/a3vlm_hip.h, "Lookup decoding: sample and match"):
+    ``rows`` cache rows of ``Q`` queries each.  ``gc`` (a ``GenControls`` or None) lends its seen bitmap, penalty, log-prob array
+    and ``prompt_len``; ``cs`` (a ``constrain.ConstraintState`` or None) its table and states.  Per step ``prepare`` is one
+    ``a3v_verify_prepare`` launch (none when neither is given: the choice reads the raw rows), ``uniforms`` one
+    ``a3v_verify_uniforms`` launch and ``accept`` one ``a3v_accept_rows_chosen`` launch."""
+
+    def __init__(self, rows: int, Q: int, V: int, device, gc: Optional[GenControls] = None, cs=None, sampling: bool = False):
+        self.Q, self.V, self.gc, self.cs = Q, V, gc, cs
+        n = rows * Q
+        self.prompt_len = gc.prompt_len if gc is not None else torch.zeros(rows, dtype=torch.int32, device=device)
+        self.seen = gc.seen if gc is not None else None
+        self.lp = gc.lp if gc is not None else None
+        self.lse = torch.zeros(n, dtype=torch.float32, device=device) if self.lp is not None else None
+        self.active = self.seen is not None or self.lp is not None or cs is not None
+        self.out = torch.empty((n, V), dtype=torch.float32, device=device) if self.active else None
+        self.chosen = torch.zeros(n, dtype=torch.long, device=device)
+        self.u = torch.zeros(n, dtype=torch.float32, device=device) if sampling else None
+        self.row_base = torch.zeros(rows, dtype=torch.long, device=device)      # index of the row's answer in the flat uniforms
+
+    def prepare(self, vlogits: torch.Tensor, x: torch.Tensor, nq: torch.Tensor, pos: torch.Tensor) -> torch.Tensor:
+        """The rows the choice is made from; the raw ``vlogits`` are never written."""
+        if not self.active:
+            return vlogits
+        cs = self.cs
+        return ops.verify_prepare(vlogits, x, nq, pos, self.out, seen=self.seen, penalty=self.gc.penalty if self.seen is not None else 1.0,
+                                  trans=cs.trans if cs is not None else None, state=cs.state if cs is not None else None, lse=self.lse)
+
+    def uniforms(self, uni: torch.Tensor, cur: torch.Tensor) -> torch.Tensor:
+        return ops.verify_uniforms(uni, self.row_base, cur, self.prompt_len, self.Q, self.u)
+
+    def accept(self, vlogits, x, nq, tokens, cur, limit, pos_base, stop_seq, stop_off, n_stop, stopped, stop_pos, next_tok, pos, stats) -> None:
+        cs = self.cs
+        ops.accept_rows_chosen(self.chosen, x, nq, tokens, cur, limit, pos_base, stop_seq, stop_off, n_stop, stopped, stop_pos, next_tok, pos,
+                               stats, V=self.V, logits=vlogits if self.lp is not None else None, lse=self.lse, logprob=self.lp,
+                               prompt_len=self.prompt_len, seen=self.seen, trans=cs.trans if cs is not None else None,
+                               state=cs.state if cs is not None else None)

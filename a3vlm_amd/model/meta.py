@@ -454,7 +454,8 @@ class MetaModel(nn.Module):
                       additional_stop_symbols: Iterable[str] = (), return_ids: bool = False, poll_every: int = 4,
                       sample_uniforms: Optional[torch.Tensor] = None, repetition_penalty: float = 1.0,
                       return_logprobs: bool = False, top_k: int = 0, min_p: float = 0.0, n: int = 1,
-                      lookup: Optional[int] = None, lookup_ngram: int = 3, lookup_drafter=None, constraint=None):
+                      lookup: Optional[int] = None, lookup_ngram: int = 3, lookup_drafter=None, constraint=None,
+                      lookup_verify: str = "argmax"):
         """Any number of prompts through ``batch_rows`` KV-cache rows (no reference counterpart; opt-in): every row decodes at its
         own position, and a row whose answer is finished is prefilled with the next prompt while the others keep decoding, so a
         short answer does not hold its row until the longest answer of a batch is done.  Answers come back in input order.
@@ -485,6 +486,13 @@ class MetaModel(nn.Module):
         ``constraint``: as in ``generate`` (a ``TokenAutomaton`` or a pattern string; scores stay the unconstrained model's).  The
         state belongs to the cache row and is set back to the start at every refill, for every sibling row when ``n > 1``.  Not with
         ``lookup`` (verification compares against the unconstrained argmax): use ``lookup=0``.
+        ``lookup_verify`` (``"argmax"``, the default: everything above; ``"choice"``, opt-in): sample and match.  Every query of a
+        verify step is prepared as the plain loop would prepare it had the drafts in front of it been emitted (penalty over the
+        seen set and those drafts, the constraint's mask in the state behind them: ``a3v_verify_prepare``), its token is drawn with
+        the uniform of its generated index (or is the argmax at temperature 0), and a draft is accepted if and only if the draw
+        equals it (``a3v_accept_rows_chosen``): the answers are the plain loop's for the same ``sample_uniforms``.  It lifts the
+        refusals of ``lookup`` for ``temperature > 0`` (with ``top_p`` / ``top_k`` / ``min_p``), ``repetition_penalty``,
+        ``return_logprobs`` and ``constraint``; ``n > 1`` is still refused (use ``n=1``, or ``lookup=0``).
         Not for the fp8 KV cache, LoRA models before ``merge_lora()`` or the two-image plugin (each raises, naming the way out)."""
         from .ragged import GroupScheduler, LookupBound, RowScheduler
         if isinstance(prompts, str):
@@ -500,20 +508,30 @@ class MetaModel(nn.Module):
         if n > int(batch_rows):
             raise ValueError(f"generate_many: n = {n} samples per prompt need n cache rows at once: batch_rows = {batch_rows} < n")
         D = int(lookup or 0)
+        if lookup_verify not in ("argmax", "choice"):
+            raise ValueError(f"generate_many: lookup_verify = {lookup_verify!r}; 'argmax' (greedy verification, the default) or 'choice' "
+                             "(sample and match)")
+        if D and lookup_verify == "choice":
+            return self._generate_many_choice(prompts, images, batch_rows=batch_rows, max_gen_len=max_gen_len, temperature=temperature,
+                                              top_p=top_p, additional_stop_symbols=additional_stop_symbols, return_ids=return_ids,
+                                              poll_every=poll_every, sample_uniforms=sample_uniforms, repetition_penalty=repetition_penalty,
+                                              return_logprobs=return_logprobs, top_k=top_k, min_p=min_p, n=n, D=D, lookup_ngram=lookup_ngram,
+                                              lookup_drafter=lookup_drafter, constraint=constraint)
         if D and constraint is not None:
             raise ValueError("generate_many: lookup decoding verifies drafts against the unconstrained argmax, a constraint changes the "
-                             "choice: use lookup=0, or constraint=None")
+                             "choice: use lookup=0, or constraint=None, or lookup_verify='choice'")
         automaton = self.constraint_automaton(constraint)
         if D:                              # refusals of lookup decoding, before any device use
             if D < 0 or D > 7:
                 raise ValueError(f"generate_many: lookup = {D} drafted tokens per step; 1 .. 7 (a step has at most 8 query positions per row)")
             if temperature > 0:
-                raise ValueError("generate_many: lookup decoding verifies drafts against the greedy choice: use temperature=0, or lookup=0")
+                raise ValueError("generate_many: lookup decoding verifies drafts against the greedy choice: use temperature=0, or lookup=0, "
+                                 "or lookup_verify='choice'")
             if n > 1:
                 raise ValueError(f"generate_many: lookup decoding is greedy, n = {n} samples need temperature > 0: use n=1, or lookup=0")
             if controls:
                 raise ValueError("generate_many: lookup decoding has no repetition-penalty / log-prob form (several tokens per step): "
-                                 "use repetition_penalty=1.0 and return_logprobs=False, or lookup=0")
+                                 "use repetition_penalty=1.0 and return_logprobs=False, or lookup=0, or lookup_verify='choice'")
             if int(batch_rows) * (D + 1) > 32:
                 raise ValueError(f"generate_many: batch_rows * (lookup + 1) = {int(batch_rows) * (D + 1)} > 32 rows of one decode step: "
                                  f"use batch_rows <= {32 // (D + 1)} or lookup <= {max(32 // int(batch_rows) - 1, 0)}")
@@ -707,6 +725,147 @@ class MetaModel(nn.Module):
                 scores = [scores[i * n:(i + 1) * n] for i in range(N)]
         ret = (decoded, ids) if return_ids else decoded
         if return_logprobs:
+            ret = ret + (scores,) if return_ids else (decoded, scores)
+        return ret
+
+    def _generate_many_choice(self, prompts, images, *, batch_rows, max_gen_len, temperature, top_p, additional_stop_symbols, return_ids,
+                              poll_every, sample_uniforms, repetition_penalty, return_logprobs, top_k, min_p, n, D, lookup_ngram,
+                              lookup_drafter, constraint):
+        """``generate_many(lookup=D, lookup_verify="choice")``: the lookup loop with sample and match in place of the greedy
+        accept.  Per step: draft -> ``forward_verify_rows`` -> ``a3v_verify_prepare`` -> sampler or argmax over the R * Q prepared
+        rows -> ``a3v_accept_rows_chosen``; no host read outside the poll.  Afterwards ``last_lookup_stats`` as in the greedy
+        loop and ``last_lookup_state``: the final seen bitmap and automaton states of the cache rows (None where not used)."""
+        from .ragged import LookupBound, RowScheduler
+        controls = genctl.wanted(repetition_penalty, return_logprobs)      # every refusal: a ValueError before any device use
+        if D < 1 or D > 7:
+            raise ValueError(f"generate_many: lookup = {D} drafted tokens per step; 1 .. 7 (a step has at most 8 query positions per row)")
+        if n > 1:
+            raise ValueError(f"generate_many: lookup decoding has no shared-prefix verify step, n = {n} samples per prompt cannot use it: "
+                             "use n=1, or lookup=0")
+        if int(batch_rows) * (D + 1) > 32:
+            raise ValueError(f"generate_many: batch_rows * (lookup + 1) = {int(batch_rows) * (D + 1)} > 32 rows of one decode step: "
+                             f"use batch_rows <= {32 // (D + 1)} or lookup <= {max(32 // int(batch_rows) - 1, 0)}")
+        if int(lookup_ngram) < 1:
+            raise ValueError(f"generate_many: lookup_ngram = {lookup_ngram}; >= 1")
+        automaton = self.constraint_automaton(constraint)
+        llma = self.llma
+        llma._ragged_check()                                  # before anything is allocated or launched
+        dev = self._device
+        N = len(prompts)
+        args = llma.args
+        R, Q, V = int(batch_rows), D + 1, args.vocab_size
+        assert 0 < R <= args.max_batch_size, (R, args.max_batch_size)
+        mgl = [int(max_gen_len)] * N if isinstance(max_gen_len, int) else [int(x) for x in max_gen_len]
+        assert len(mgl) == N, (len(mgl), N)
+        if images is not None:
+            images = images.to(dev)
+            assert images.shape[0] == N, (tuple(images.shape), N)
+        max_seq_len = args.max_seq_len - (llma.image_words if images is not None else 0)
+        W = llma.image_words if images is not None else 0
+        prompt_tokens, limits = [], []
+        for x, mg in zip(prompts, mgl):
+            t = self.tokenizer.encode(x, bos=True, eos=False)
+            limits.append(min(max_seq_len, mg + len(t)))
+            prompt_tokens.append(t[-(max_seq_len - mg):])
+        lens = [len(t) for t in prompt_tokens]
+        if N == 0:
+            ret = ([], []) if return_ids else []
+            return (ret + ([],) if return_ids else ([], [])) if return_logprobs else ret
+
+        l_stop = [[self.tokenizer.eos_id]]
+        l_stop += [self.tokenizer.encode_segment(s) for s in additional_stop_symbols]
+        l_stop += [self.tokenizer.encode_wo_prefix_space(s) for s in additional_stop_symbols]
+        offs = [0]
+        for st in l_stop:
+            offs.append(offs[-1] + len(st))
+        stop_seq = torch.tensor([t for st in l_stop for t in st], dtype=torch.long, device=dev)
+        stop_off = torch.tensor(offs, dtype=torch.int32, device=dev)
+
+        width = max(max(limits), max(lens), 1)
+        max_new = max(max(lim - ln for lim, ln in zip(limits, lens)), 1)
+        tokens = torch.zeros((R, width), dtype=torch.long, device=dev)
+        cur = torch.zeros(R, dtype=torch.int32, device=dev)
+        limit = torch.zeros(R, dtype=torch.int32, device=dev)
+        stopped = torch.ones(R, dtype=torch.bool, device=dev)            # an empty row is a stopped row: no step touches it
+        stop_pos = torch.zeros(R, dtype=torch.long, device=dev)
+        next_tok = torch.zeros(R, dtype=torch.long, device=dev)
+        pos = torch.full((R,), -1, dtype=torch.int32, device=dev)
+        uni, n_uni = None, 0
+        if temperature > 0:            # indexed [prompt, generated index], as the plain loop's
+            uni = (torch.rand(N, max_new, device=dev, dtype=torch.float32) if sample_uniforms is None
+                   else sample_uniforms.to(device=dev, dtype=torch.float32).contiguous())
+            if uni.dim() == 3 and uni.shape[1] == 1:
+                uni = uni[:, 0]
+            assert uni.dim() == 2 and uni.shape[0] == N and uni.shape[1] >= max_new, (tuple(uni.shape), N, max_new)
+            n_uni = uni.shape[1]
+            uni = uni.reshape(-1)
+        gc = genctl.GenControls(R, V, max_new, repetition_penalty, return_logprobs, dev) if controls else None
+        cs = constrain.ConstraintState(automaton, R, V, dev) if automaton is not None else None
+        vc = genctl.VerifyControls(R, Q, V, dev, gc=gc, cs=cs, sampling=uni is not None)
+        sched = RowScheduler(lens, limits, R, W)
+        ids: List[Optional[List[int]]] = [None] * N
+        lps: List[List[float]] = [[] for _ in range(N)]
+        llma.allocate_rows(R)
+        xq = torch.zeros((R, Q), dtype=torch.long, device=dev)
+        nq = torch.ones(R, dtype=torch.int32, device=dev)
+        vlogits = torch.zeros((R * Q, V), dtype=torch.float32, device=dev)
+        stats = torch.zeros(2, dtype=torch.int64, device=dev)
+        bound = LookupBound(R, Q)
+        smax = llma._k_cache[0].shape[2]
+        emitted = it = 0
+        while True:
+            for row, i in sched.refill():
+                t = torch.tensor(prompt_tokens[i], dtype=torch.long, device=dev)
+                vlogits[row * Q].copy_(llma.prefill_row(row, t[None], None if images is None else images[i:i + 1])[0])
+                tokens[row].zero_()
+                tokens[row, :lens[i]] = t
+                cur[row], limit[row], stopped[row], stop_pos[row], nq[row] = lens[i], limits[i], False, lens[i] + 1, 1
+                pos[row] = W + lens[i] - 1                    # query 0 of a refilled row is live: the prefill logits of its last prompt token
+                vc.prompt_len[row] = lens[i]
+                vc.row_base[row] = i * n_uni
+                if gc is not None:                            # the row's seen set is its new prompt alone
+                    gc.mark_prompts(tokens, row)
+                if cs is not None:
+                    cs.reset(row, lens[i])
+                bound.start(row, W + lens[i], W + limits[i] - 1)
+            for i in sched.finished_at_once:
+                ids[i] = []
+            sched.finished_at_once.clear()
+            if not sched.occupied():
+                break
+            z = vc.prepare(vlogits, xq, nq, pos)              # a refilled row has nq = 1 and its prefill logits in query 0
+            if uni is not None:
+                self._sample_into(z, temperature, top_p, vc.uniforms(uni, cur), vc.chosen, top_k, min_p)
+            else:
+                ops.argmax(z, vc.chosen)
+            vc.accept(vlogits, xq, nq, tokens, cur, limit, W, stop_seq, stop_off, len(l_stop), stopped, stop_pos, next_tok, pos, stats)
+            it += 1
+            if it % poll_every == 0:                          # the one host read: stopped, and cur to re-synchronise the position bound
+                st, cu, sp = stopped.tolist(), cur.tolist(), stop_pos.tolist()
+                for r, i in sched.occupied():
+                    if st[r]:
+                        ids[i] = tokens[r, lens[i]:sp[r]].tolist()
+                        if return_logprobs:
+                            lps[i] = gc.lp[r, :len(ids[i])].tolist()
+                        emitted += cu[r] - lens[i]
+                        sched.release(r)
+                        bound.release(r)
+                    else:
+                        bound.resync(r, W + cu[r] - 1)
+                if not sched.occupied():
+                    continue                                  # refill (or leave) before another step
+            if lookup_drafter is not None:
+                lookup_drafter(tokens, cur, limit, pos, stopped, next_tok, xq, nq)
+            else:
+                ops.lookup_draft_rows(tokens, cur, limit, pos, stopped, next_tok, D, int(lookup_ngram), smax, xq, nq)
+            llma.forward_verify_rows(xq, pos, nq, bound.step(), out=vlogits)
+        drafted, accepted = (int(v) for v in stats.tolist())
+        self.last_lookup_stats = {"steps": emitted - accepted, "tokens": emitted, "drafted": drafted, "accepted": accepted}
+        self.last_lookup_state = {"seen": gc.seen if gc is not None else None, "state": cs.state if cs is not None else None}
+        decoded = [self.tokenizer.decode(t) for t in ids]
+        ret = (decoded, ids) if return_ids else decoded
+        if return_logprobs:
+            scores = [genctl.score(x) for x in lps]
             ret = ret + (scores,) if return_ids else (decoded, scores)
         return ret
 

@@ -954,6 +954,83 @@ def constrain_advance(tokens, trans, state, first, *, col: int = 0, cur=None, st
     return state
 
 
+def verify_prepare(logits, x, nq, pos, out, *, seen=None, penalty: float = 1.0, trans=None, state=None, lse=None):
+    """Lookup decoding, sample and match (a3v_verify_prepare): one pass over the fp32 verify logits [B*Q, V].  ``out`` row b * Q + j =
+    the row as the plain loop would prepare it if drafts x[b, 1..j] had been emitted: the repetition penalty over ``seen[b]`` and
+    those drafts (seen None: none), then the automaton's mask in the state reached from ``state[b]`` over them (trans None: none; a
+    forbidden draft: the row is all -inf); ``lse`` (None: not computed) = logsumexp of the RAW rows.  Idle queries: zeros."""
+    _dev(logits, x, nq, pos, out, seen, trans, state, lse)
+    B, Q = x.shape
+    assert logits.dtype == out.dtype == torch.float32 and logits.dim() == out.dim() == 2 and logits.stride(1) == out.stride(1) == 1
+    assert logits.shape[0] == B * Q and out.shape == logits.shape and out.data_ptr() != logits.data_ptr()
+    V = logits.shape[1]
+    assert x.dtype == torch.int64 and x.is_contiguous()
+    assert all(t.dtype == torch.int32 and t.is_contiguous() and t.numel() >= B for t in (nq, pos))
+    if seen is not None:
+        _seen_ok(seen, B, V)
+        assert penalty > 0, penalty
+    if trans is not None:
+        _trans_ok(trans, V)
+        assert state.dtype == torch.int32 and state.is_contiguous() and state.numel() >= B
+    assert lse is None or (lse.dtype == torch.float32 and lse.is_contiguous() and lse.numel() >= B * Q)
+    rc = _l.load().a3v_verify_prepare(_p(logits), logits.stride(0), B, Q, V, _p(x), _p(nq), _p(pos), _p(seen),
+                                      seen.stride(0) if seen is not None else 0, float(penalty), _p(trans),
+                                      trans.shape[0] if trans is not None else 0, _p(state) if trans is not None else None, _p(lse), _p(out),
+                                      out.stride(0), _stream())
+    _l.check(rc, f"a3v_verify_prepare(B={B},Q={Q},V={V})")
+    return out
+
+
+def accept_rows_chosen(chosen, x, nq, tokens, cur, limit, pos_base: int, stop_seq, stop_off, n_stop: int, stopped, stop_pos, next_tok, pos,
+                       stats=None, *, V: int = 0, logits=None, lse=None, logprob=None, prompt_len=None, seen=None, trans=None, state=None):
+    """``accept_rows`` with the per-query choice handed in (a3v_accept_rows_chosen; chosen int64 [B*Q]), plus per emission the plain
+    loop's bookkeeping: logprob[b, g] = logits[m, id] - lse[m] on the RAW logits of the producing query, the id's bit in ``seen``,
+    ``state[b] = trans[state[b], id]``.  Each of logprob / seen / state may be None; with any of them ``prompt_len`` is needed."""
+    _dev(chosen, x, nq, tokens, cur, limit, stopped, stop_pos, next_tok, pos, stats, logits, lse, logprob, prompt_len, seen, trans, state)
+    B, Q = x.shape
+    assert chosen.dtype == torch.int64 and chosen.is_contiguous() and chosen.numel() >= B * Q
+    assert tokens.dtype == x.dtype == torch.int64 and tokens.stride(1) == 1 and tokens.shape[0] == B and x.is_contiguous()
+    assert stopped.dtype == torch.bool and stop_pos.dtype == torch.int64 and next_tok.dtype == torch.int64
+    assert cur.dtype == limit.dtype == pos.dtype == nq.dtype == torch.int32
+    assert all(t.is_contiguous() and t.numel() >= B for t in (cur, limit, pos, nq, next_tok, stopped, stop_pos))
+    assert stats is None or (stats.dtype == torch.int64 and stats.is_contiguous() and stats.numel() >= 2)
+    book = logprob is not None or seen is not None or state is not None
+    if book:
+        assert V > 0, "the vocabulary size V is needed with logprob / seen / state"
+        assert prompt_len is not None and prompt_len.dtype == torch.int32 and prompt_len.is_contiguous() and prompt_len.numel() >= B
+    if logprob is not None:
+        assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1 and logits.shape[0] == B * Q
+        assert lse.dtype == torch.float32 and lse.is_contiguous() and lse.numel() >= B * Q
+        assert logprob.dtype == torch.float32 and logprob.dim() == 2 and logprob.stride(1) == 1 and logprob.shape[0] >= B
+    if seen is not None:
+        _seen_ok(seen, B, V)
+    if state is not None:
+        _trans_ok(trans, V)
+        assert state.dtype == torch.int32 and state.is_contiguous() and state.numel() >= B
+    rc = _l.load().a3v_accept_rows_chosen(_p(chosen), B, Q, _p(x), _p(nq), _p(tokens), tokens.stride(0), _p(cur), _p(limit), int(pos_base),
+                                          _p(stop_seq), _p(stop_off), int(n_stop), _p(stopped), _p(stop_pos), _p(next_tok), _p(pos), _p(stats),
+                                          _p(logits) if logprob is not None else None, logits.stride(0) if logprob is not None else 0, int(V),
+                                          _p(lse) if logprob is not None else None, _p(logprob),
+                                          logprob.stride(0) if logprob is not None else 0, logprob.shape[1] if logprob is not None else 0,
+                                          _p(prompt_len) if book else None, _p(seen), seen.stride(0) if seen is not None else 0,
+                                          _p(trans) if state is not None else None, trans.shape[0] if state is not None else 0, _p(state),
+                                          _stream())
+    _l.check(rc, f"a3v_accept_rows_chosen(B={B},Q={Q})")
+
+
+def verify_uniforms(uni, row_base, cur, prompt_len, Q: int, u):
+    """u[b * Q + j] = uni[row_base[b] + (cur[b] - prompt_len[b]) + j], clamped into ``uni`` (a3v_verify_uniforms): the uniform number
+    the plain loop draws the token of that generated index with."""
+    _dev(uni, row_base, cur, prompt_len, u)
+    B = row_base.numel()
+    assert uni.dtype == u.dtype == torch.float32 and uni.is_contiguous() and u.is_contiguous() and u.numel() >= B * Q and uni.numel() > 0
+    assert row_base.dtype == torch.int64 and row_base.is_contiguous()
+    assert all(t.dtype == torch.int32 and t.is_contiguous() and t.numel() >= B for t in (cur, prompt_len))
+    rc = _l.load().a3v_verify_uniforms(_p(uni), uni.numel(), _p(row_base), _p(cur), _p(prompt_len), B, int(Q), _p(u), _stream())
+    _l.check(rc, "a3v_verify_uniforms")
+    return u
+
+
 def count_valid(labels, n_valid):
     _dev(labels, n_valid)
     rc = _l.load().a3v_count_valid(_p(labels), labels.numel(), _p(n_valid), _stream())

@@ -853,6 +853,64 @@ int a3v_constrain_advance(const int64_t* tokens, int64_t ld_tok, int col, const 
                           const uint8_t* stopped_before, const int16_t* trans, int V, int n_states, int32_t* state, int B, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Lookup decoding: sample and match (opt-in; a3v_spec_ctl.hip; generate_many(lookup=D, lookup_verify="choice")).  Lookup decoding
+ * under temperature / top-k / top-p / min-p, the repetition penalty, log-probs and a constraint.  No existing entry changes: the
+ * verify step, a3v_accept_rows, the samplers and a3v_argmax are called as they are.
+ *
+ * Rule: the plain loop draws generated token g of an answer with one fixed uniform number, from the row's prepared logits (penalty,
+ *   then the constraint mask, then the sampler's filters).  For query j of a row (virtual row m = b * Q + j) the logits are prepared
+ *   exactly as the plain loop would prepare them if drafts x[b, 1..j] had been emitted, the draw uses the uniform of generated index
+ *   g + j, and draft j + 1 is accepted if and only if the draw equals it.  The emitted tokens are the plain loop's for the same
+ *   uniforms (at temperature 0: the first-index argmax of the prepared row), so no rejection sampling is needed.
+ * Step order: a3v_lookup_draft_rows -> a3v_llama_decode_step_verify -> a3v_verify_prepare -> a3v_sample_top_p / a3v_sample_top_k_p /
+ *   a3v_argmax over the B * Q rows of `out` -> a3v_accept_rows_chosen.
+ *
+ * a3v_verify_prepare: logits fp32 [B*Q, V] (row stride ld >= V), never written; out fp32 [B*Q, V] (row stride ld_out >= V; out ==
+ *   logits is refused, any other overlap is undefined); x int64 [B, Q], nq / pos device int32 [B] as in the verify step.  Query j
+ *   of row b is LIVE when pos[b] >= 0 and j < clamp(nq[b], 1, Q).  For a live query, in this order:
+ *   1. seen set = seen[b] (the bitmap of "Generation controls", uint32 [B, words_per_row], one row per CACHE row) united with
+ *      x[b, 1..j]; x[b, 0] is already in the bitmap (the step that emitted it marked it).  The drafts are compared per element, no
+ *      [B*Q, words] bitmap exists; a draft id outside [0, V) is ignored.  seen == NULL: no penalty.
+ *   2. penalty: a3v_logits_prepare's two expressions on the raw value, a true fp32 division.
+ *   3. constraint state: s_0 = state[b], s_k = trans[s_{k-1}, x[b, k]] for k = 1..j.  s_0 outside [0, n_states): the row is
+ *      unconstrained for every j.  If the walk meets -1 (or a state >= n_states), or a draft id outside [0, V), the query is DEAD:
+ *      its out row is all -inf.  A dead query is never examined by a3v_accept_rows_chosen: from s_{k-1} the token x[b, k] is masked
+ *      in the out row of query k - 1, so it lies below every finite entry for the argmax and has mass expf(-inf) = 0 for the
+ *      samplers, whose selection only lands on a bin of positive mass (see a3v_constrain_logits above); the choice of query k - 1
+ *      therefore differs from x[b, k] and the chain of acceptances breaks before query k.  trans == NULL: no mask.
+ *   4. mask: a3v_constrain_logits's select in state s_j on the penalised value; a kept value keeps its bit pattern.
+ *   5. lse[m] (lse != NULL) = logsumexp of the RAW row in the reduction order fixed above for a3v_logits_prepare (1024-thread
+ *      block, one pass): bit-equal to that entry's lse on the same logits row with an out row on the same 16-byte phase (both rows
+ *      on a 16-byte boundary: the vector walk, and then also its lse-only form; otherwise the element walk).  Dead queries included.
+ *   An idle query gets an out row of zeros and lse 0; its logits row is not read.  Any V >= 1; out rows off the 16-byte boundary
+ *   take the element form.  One launch, B * Q blocks of 1024 threads, 16-byte loads and stores, 8-byte loads of the int16 row.
+ *   A3V_ERR_ARG: a NULL array among logits / x / nq / pos / out, out == logits, B <= 0, V <= 0, a stride below V, seen with
+ *   penalty <= 0 or words_per_row < ceil(V / 32), trans without state or n_states outside [1, 32767].  A3V_ERR_SHAPE: Q outside 1..8.
+ * a3v_accept_rows_chosen: a3v_accept_rows with t_j = chosen[b * Q + j] (int64 [B*Q]: the samplers' or a3v_argmax's output over the
+ *   rows of `out`) -- the emission rule, the token write, stop sequences, cur, limit, next_tok, pos and stats are that entry's.  For
+ *   every emission, the one that stops the row included, with id at column c and generated index g = c - prompt_len[b] >= 0 and
+ *   0 <= id < V (a3v_generate_record's and a3v_constrain_advance's guards; prompt_len is also the `first` of the latter):
+ *   logprob[b, g] = logits[m, id] - lse[m], one fp32 subtraction on the RAW logits of the query m that produced it (g >= n_lp is not
+ *   written); bit id of seen[b] is set; state[b] = trans[state[b], id] when state[b] is in [0, n_states).  logprob, seen and state
+ *   are each optional (NULL); with any of them prompt_len and V are required.  A row with stopped[b] set is not touched.  With all
+ *   three NULL and chosen the argmax of the logits, every output equals a3v_accept_rows's bit for bit.  Integer work apart from the
+ *   one subtraction: bit-identical to tests/spec_ctl_ref.py.
+ * a3v_verify_uniforms: u[b * Q + j] = uni[clamp(row_base[b] + (cur[b] - prompt_len[b]) + j, 0, n_uni - 1)]: the plain loop's uniform
+ *   of the generated index each query would emit at (row_base: device int64 [B], the index of the row's answer in uni).
+ * ------------------------------------------------------------------------------------- */
+int a3v_verify_prepare(const float* logits, int64_t ld, int B, int Q, int V, const int64_t* x, const int32_t* nq, const int32_t* pos,
+                       const uint32_t* seen, int64_t words_per_row, float penalty, const int16_t* trans, int n_states,
+                       const int32_t* state, float* lse, float* out, int64_t ld_out, void* stream);
+int a3v_accept_rows_chosen(const int64_t* chosen, int B, int Q, const int64_t* x, const int32_t* nq, int64_t* tokens, int64_t ld_tok,
+                           int32_t* cur, const int32_t* limit, int pos_base, const int64_t* stop_seq, const int32_t* stop_off,
+                           int n_stop, uint8_t* stopped, int64_t* stop_pos, int64_t* next_tok, int32_t* pos, int64_t* stats,
+                           const float* logits, int64_t ld, int V, const float* lse, float* logprob, int64_t ld_lp, int n_lp,
+                           const int32_t* prompt_len, uint32_t* seen, int64_t words_per_row, const int16_t* trans, int n_states,
+                           int32_t* state, void* stream);
+int a3v_verify_uniforms(const float* uni, int64_t n_uni, const int64_t* row_base, const int32_t* cur, const int32_t* prompt_len, int B,
+                        int Q, float* u, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Training (backward) entry points. Reference: autograd through the same modules under
  * autocast(bf16) with fp32 master weights (engine_finetune.py:44-68, main_finetune.py:212-217).
  * Convention: activations and their grads use `act_dtype` (bf16 / f32 parity); the residual
