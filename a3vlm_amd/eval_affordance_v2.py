@@ -172,7 +172,37 @@ def get_args_parser():
                         "choose it -- penalty, --answer_regex mask, temperature / top-k / top-p / min-p with the uniform of its generated "
                         "index -- and a draft is kept when the choice equals it; allows --temperature > 0, --answer_regex, "
                         "--repetition_penalty and --save_scores beside --lookup_decoding (still --num_samples 1)")
+    p.add_argument("--num_beams", type=int, default=0,
+                   help="K > 0: beam search (MetaModel.beam_search(num_beams=K)): K beams per (image, question) from ONE prefill, the "
+                        "best finished hypothesis is the answer; every record gains \"beam_score\" (sum of log-probs over "
+                        "length ** --length_penalty) and \"logprob_sum\".  0 (default): the path as it was.  Needs --continuous_rows >= K "
+                        "and --temperature 0; combines with --answer_regex; not with --num_samples > 1, --lookup_decoding or "
+                        "--repetition_penalty != 1")
+    p.add_argument("--length_penalty", type=float, default=1.0,
+                   help="--num_beams: a hypothesis of n tokens scores sum / n ** length_penalty (1.0, the default: the mean log-prob)")
+    p.add_argument("--beam_early_stopping", action="store_true", default=False,
+                   help="--num_beams: a prompt ends as soon as K hypotheses are finished (default: when no live beam can still beat "
+                        "the worst of them)")
     return p
+
+
+def check_num_beams(args) -> int:
+    k = int(getattr(args, "num_beams", 0) or 0)
+    if k == 0:
+        return 0
+    if k < 0 or k > 8:
+        raise SystemExit(f"--num_beams {k}: 0 (off) .. 8 beams per prompt")
+    if getattr(args, "continuous_rows", 0) < k:
+        raise SystemExit(f"--num_beams {k} decodes the {k} beams of a prompt in {k} KV-cache rows at once: add --continuous_rows R with R >= {k}")
+    if args.temperature > 0:
+        raise SystemExit(f"--num_beams {k} is deterministic: set --temperature 0, or use --num_samples for best-of-n sampling")
+    if int(getattr(args, "num_samples", 1)) > 1:
+        raise SystemExit(f"--num_beams {k} and --num_samples {args.num_samples} are two ways to the same end: use --num_samples 1, or --num_beams 0")
+    if int(getattr(args, "lookup_decoding", 0) or 0):
+        raise SystemExit(f"--num_beams {k}: lookup decoding verifies drafts against one greedy continuation: set --lookup_decoding 0, or --num_beams 0")
+    if float(getattr(args, "repetition_penalty", 1.0)) != 1.0:
+        raise SystemExit(f"--num_beams {k} scores beams by raw log-probs: set --repetition_penalty 1.0, or --num_beams 0")
+    return k
 
 
 def check_answer_regex(args):
@@ -235,7 +265,8 @@ def check_num_samples(args) -> int:
 
 
 def main(args):
-    num_samples = check_num_samples(args)      # before the model is built
+    num_beams = check_num_beams(args)          # before the model is built
+    num_samples = check_num_samples(args)
     lookup = check_lookup(args)
     answer_regex = check_answer_regex(args)
     distributed = "RANK" in os.environ and "WORLD_SIZE" in os.environ
@@ -297,6 +328,16 @@ def main(args):
     with torch.no_grad():
         for image, qids, prompts, annotations, paths in loader:
             image = pre.batch(image) if isinstance(image, list) else image.to(dev)
+            if num_beams:          # beam search: the best finished hypothesis of every prompt, with its two scores
+                answers, scores = model.beam_search(prompts, image, num_beams=num_beams, batch_rows=rows, max_gen_len=args.max_gen_len,
+                                                    length_penalty=args.length_penalty, early_stopping=args.beam_early_stopping,
+                                                    constraint=answer_regex, return_scores=True)
+                for answer, sc, annotation, question, path in zip(answers, scores, annotations, prompts, paths):
+                    rec = make_record(answer)
+                    outputs.append({"answer": rec["answer"], "format_answer": rec["format_answer"], "annotation": annotation,
+                                    "question": question, "image": path, "fail": rec["fail"], "beam_score": sc["score"],
+                                    "logprob_sum": sc["sum"]})
+                continue
             if num_samples > 1:    # best-of-n: n answers per prompt from one prefill, the most confident well-formed one is the record's
                 answers, scores = model.generate_many(prompts, image, batch_rows=rows, max_gen_len=args.max_gen_len,
                                                       temperature=args.temperature, top_p=args.top_p, n=num_samples, **controls)

@@ -152,6 +152,9 @@ SIGNATURES = {
     "a3v_verify_prepare": (I, [P, L, I, I, I, P, P, P, P, L, F, P, I, P, P, P, L, P]),
     "a3v_accept_rows_chosen": (I, [P, I, I, P, P, P, L, P, P, I, P, P, I, P, P, P, P, P, P, L, I, P, P, L, I, P, P, L, P, I, P, P]),
     "a3v_verify_uniforms": (I, [P, L, P, P, P, I, I, P, P]),
+    "a3v_beam_select": (I, [P, L, P, P, P, P, I, P, I, I, I, P, P, P, P]),
+    "a3v_beam_advance": (I, [P, P, P, I, I, I, I, I, P, I, P, I, P, P, I, P, P, P, P, P, P, P, P, P, P, L, P, P, P, P, P, P, P, P]),
+    "a3v_kv_permute_tails": (I, [P, P, I, P, P, P, I, I, I, I, I, I, I, P]),
     "a3v_adam8_quantize": (I, [P, P, P, P, P, P, L, P]),
     "a3v_adam8_dequantize": (I, [P, P, P, P, P, P, L, P]),
     "a3v_adamw8_scaled": (I, [P, P, P, P, P, P, L, F, F, F, F, F, L, P, P, P]),

@@ -870,6 +870,30 @@ class MetaModel(nn.Module):
         return ret
 
     @torch.no_grad()
+    def beam_search(self, prompts: List[str], images: Optional[torch.Tensor] = None, *, num_beams: int, batch_rows: int,
+                    max_gen_len=512, length_penalty: float = 1.0, early_stopping: bool = True, num_return_sequences: int = 1,
+                    constraint=None, return_ids: bool = False, return_scores: bool = False, poll_every: int = 4,
+                    additional_stop_symbols: Iterable[str] = (), temperature: float = 0.0, repetition_penalty: float = 1.0, lookup=None):
+        """Beam search over ``batch_rows // num_beams`` prompts at a time (no reference counterpart; opt-in; ``model/beam.py``): the
+        most probable answers by the sum of raw log-probs over ``len ** length_penalty``, HF ``num_beams`` semantics
+        (``tests/beam_ref.py`` is the contract).  1 <= ``num_beams`` <= 8 consecutive cache rows per prompt, ONE prefill per prompt
+        (the siblings read the leader's prompt keys, ``share_prefix``); a finished group is refilled with the next prompt, in input
+        order.  Truncation and limits per prompt are ``generate_many``'s.  Only the EOS id ends a hypothesis.  ``early_stopping``:
+        a prompt ends when ``num_beams`` hypotheses are finished; False: when no live beam can still beat the worst of them.
+        ``constraint``: as in ``generate_many`` (scores stay the unconstrained model's).  Returns per prompt the best text (a list of
+        ``num_return_sequences`` when that is > 1); with ``return_ids`` the ids, with ``return_scores``
+        ``{"sum": sum of log-probs, "score": sum / len ** length_penalty}``.  Every step moves the generated keys of re-parented
+        beams, which grows linearly with the answer's length: made for the short structured answers of this task.
+        ``additional_stop_symbols``, ``temperature > 0``, ``repetition_penalty != 1`` and ``lookup`` are refused, as are the fp8 KV
+        cache, LoRA models before ``merge_lora()`` and the two-image plugin (each raises, naming the way out)."""
+        from . import beam
+        return beam.beam_search(self, prompts, images, num_beams=num_beams, batch_rows=batch_rows, max_gen_len=max_gen_len,
+                                length_penalty=length_penalty, early_stopping=early_stopping, num_return_sequences=num_return_sequences,
+                                constraint=constraint, return_ids=return_ids, return_scores=return_scores, poll_every=poll_every,
+                                additional_stop_symbols=additional_stop_symbols, temperature=temperature,
+                                repetition_penalty=repetition_penalty, lookup=lookup)
+
+    @torch.no_grad()
     def stream_generate(self, prompt: str, image: Optional[torch.Tensor] = None, max_gen_len: int = 512,
                         temperature: float = 0.0, top_p: float = 0.95,
                         additional_stop_symbols: Iterable[str] = (), repetition_penalty: float = 1.0,

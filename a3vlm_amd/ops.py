@@ -954,6 +954,89 @@ def constrain_advance(tokens, trans, state, first, *, col: int = 0, cur=None, st
     return state
 
 
+def beam_select(logits, lse, cum, alive, K: int, cand_score, cand_beam, cand_tok, *, trans=None, state=None):
+    """One launch (a3v_beam_select): per group of ``K`` consecutive rows of the raw fp32 ``logits`` [R, V] (any row stride) the best
+    2K candidates (beam, token) of the rows with ``alive`` set, scored cum[b] + (z[b, v] - lse[b]), ordered by score descending,
+    then b * V + v ascending, into cand_* [G, 2K]; unfilled slots (-inf, -1, -1).  ``trans`` / ``state``: only tokens the automaton
+    allows in the row's state (a state outside [0, n_states): every token)."""
+    _dev(logits, lse, cum, alive, cand_score, cand_beam, cand_tok, trans, state)
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
+    R, V = logits.shape
+    K = int(K)
+    assert 1 <= K <= 8 and R % K == 0, (R, K)
+    G = R // K
+    for t, d in ((lse, torch.float32), (cum, torch.float32), (alive, torch.uint8)):
+        assert t.dtype == d and t.is_contiguous() and t.numel() >= R
+    for t, d in ((cand_score, torch.float32), (cand_beam, torch.int32), (cand_tok, torch.int32)):
+        assert t.dtype == d and t.is_contiguous() and tuple(t.shape) == (G, 2 * K), (tuple(t.shape), G, K)
+    if trans is not None:
+        _trans_ok(trans, V)
+        assert state.dtype == torch.int32 and state.is_contiguous() and state.numel() >= R
+    rc = _l.load().a3v_beam_select(_p(logits), logits.stride(0), _p(lse), _p(cum), _p(alive), _p(trans),
+                                   trans.shape[0] if trans is not None else 0, _p(state), G, K, V, _p(cand_score), _p(cand_beam),
+                                   _p(cand_tok), _stream())
+    _l.check(rc, f"a3v_beam_select(G={G},K={K},V={V})")
+
+
+def beam_advance(cand_score, cand_beam, cand_tok, st, tokens_in, tokens_out, V: int, eos: int, early_stopping: bool, len_div,
+                 pos_cap: int, *, trans=None):
+    """One launch (a3v_beam_advance): the walk over the 2K candidates of every group that is not done.  ``st`` carries the device
+    state (model/beam.py ``BeamState``: cum, alive, state, glen, done, parent, next_tok, pos, base, limit and the pool); the
+    token rows are read from ``tokens_in`` and written to ``tokens_out`` (the caller swaps them every step)."""
+    G, K2 = cand_score.shape
+    K = K2 // 2
+    R = G * K
+    _dev(cand_score, cand_beam, cand_tok, tokens_in, tokens_out, len_div, trans)
+    per_row = ((st.cum, torch.float32), (st.alive, torch.uint8), (st.state, torch.int32), (st.parent, torch.int32),
+               (st.next_tok, torch.int64), (st.pos, torch.int32))
+    per_group = ((st.glen, torch.int32), (st.done, torch.uint8), (st.base, torch.int32), (st.limit, torch.int32),
+                 (st.pool_n, torch.int32), (st.pool_added, torch.int32))
+    pool = ((st.pool_score, torch.float32), (st.pool_cum, torch.float32), (st.pool_len, torch.int32), (st.pool_seq, torch.int32))
+    for group, n in ((per_row, R), (per_group, G), (pool, R)):
+        for t, d in group:
+            assert t.is_cuda and t.dtype == d and t.is_contiguous() and t.numel() == n, (t.dtype, d, t.numel(), n)
+    for t in (tokens_in, tokens_out):
+        assert t.dtype == torch.int64 and tuple(t.shape) == (R, tokens_in.shape[1]) and t.is_contiguous()
+    ld = tokens_in.shape[1]
+    assert tokens_in.data_ptr() != tokens_out.data_ptr()
+    assert st.pool_ids.dtype == torch.int64 and tuple(st.pool_ids.shape) == (G, K, ld) and st.pool_ids.is_contiguous() and st.pool_ids.is_cuda
+    assert len_div.dtype == torch.float32 and len_div.is_contiguous() and len_div.numel() >= 2
+    assert all(t.dtype == d and t.is_contiguous() for t, d in ((cand_score, torch.float32), (cand_beam, torch.int32), (cand_tok, torch.int32)))
+    if trans is not None:
+        _trans_ok(trans, V)
+    rc = _l.load().a3v_beam_advance(_p(cand_score), _p(cand_beam), _p(cand_tok), G, K, int(V), int(eos), int(bool(early_stopping)),
+                                    _p(len_div), len_div.numel(), _p(trans), trans.shape[0] if trans is not None else 0, _p(st.base),
+                                    _p(st.limit), int(pos_cap), _p(st.cum), _p(st.alive), _p(st.state), _p(st.glen), _p(st.done),
+                                    _p(st.parent), _p(st.next_tok), _p(st.pos), _p(tokens_in), _p(tokens_out), ld, _p(st.pool_n),
+                                    _p(st.pool_added), _p(st.pool_score), _p(st.pool_cum), _p(st.pool_len), _p(st.pool_seq),
+                                    _p(st.pool_ids), _stream())
+    _l.check(rc, f"a3v_beam_advance(G={G},K={K},V={V})")
+
+
+def kv_permute_tails(k_caches, vt_caches, parent, tail_lo, pos, tail_max: int, K: int, ptrs=None):
+    """One launch over every layer (a3v_kv_permute_tails): for every cache row r with parent[r] != r the positions
+    [tail_lo[r], pos[r]) of row parent[r] (a row of r's group of ``K`` consecutive rows; the values from before the call) replace
+    the same positions of row r in K [B,Hkv,Smax,hd] and V^T [B,Hkv,hd,Smax].  parent / tail_lo / pos: device int32 [B];
+    ``tail_max`` (host) >= max(pos) - min(tail_lo) over the moved rows of every group.  ``ptrs`` as in ``kv_copy_span`` (returned either way)."""
+    k0 = k_caches[0]
+    B, Hkv, Smax, hd = k0.shape
+    K = int(K)
+    assert 1 <= K <= 8 and B % K == 0, (B, K)
+    for k, v in zip(k_caches, vt_caches):
+        _dev(k, v)
+        assert k.is_contiguous() and v.is_contiguous() and k.dtype == v.dtype == k0.dtype
+        assert tuple(k.shape) == (B, Hkv, Smax, hd) and tuple(v.shape) == (B, Hkv, hd, Smax)
+    _dev(parent, tail_lo, pos)
+    assert all(t.dtype == torch.int32 and t.is_contiguous() and t.numel() == B for t in (parent, tail_lo, pos))
+    if ptrs is None:
+        ptrs = torch.tensor([[t.data_ptr() for t in k_caches], [t.data_ptr() for t in vt_caches]], dtype=torch.int64, device=k0.device)
+    assert ptrs.dtype == torch.int64 and tuple(ptrs.shape) == (2, len(k_caches)) and ptrs.is_contiguous()
+    rc = _l.load().a3v_kv_permute_tails(_p(ptrs[0]), _p(ptrs[1]), len(k_caches), _p(parent), _p(tail_lo), _p(pos), int(tail_max), B // K, K,
+                                        Hkv, hd, Smax, dt(k0), _stream())
+    _l.check(rc, f"a3v_kv_permute_tails(K={K},tail_max={tail_max},hd={hd})")
+    return ptrs
+
+
 def verify_prepare(logits, x, nq, pos, out, *, seen=None, penalty: float = 1.0, trans=None, state=None, lse=None):
     """Lookup decoding, sample and match (a3v_verify_prepare): one pass over the fp32 verify logits [B*Q, V].  ``out`` row b * Q + j =
     the row as the plain loop would prepare it if drafts x[b, 1..j] had been emitted: the repetition penalty over ``seen[b]`` and

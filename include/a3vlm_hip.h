@@ -911,6 +911,60 @@ int a3v_verify_uniforms(const float* uni, int64_t n_uni, const int64_t* row_base
                         int Q, float* u, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Beam search (opt-in; a3v_beam.hip; no reference counterpart; tests/beam_ref.py restates select and advance, bit for bit).
+ * Groups of K = num_beams consecutive cache rows, 1 <= K <= 8: group g of G owns rows [g K, g K + K), R = G K.  Everything per row
+ * and per group lives on the DEVICE; no entry reads anything back.
+ *   per row:   cum[R] fp32 (sum of raw log-probs), alive[R] uint8, state[R] int32 (the automaton state of a3v_constrain_*; a value
+ *              outside [0, n_states) = unconstrained), token rows [R, ld_tok] int64 (the GENERATED ids only), parent[R] / pos[R]
+ *              int32, next_tok[R] int64.
+ *   per group: glen[G] (ids generated so far), limit[G] (ids it may generate), base[G] (cache position of generated id 0: image
+ *              words + prompt length), done[G] uint8, and a pool of at most K finished hypotheses: pool_n[G], pool_added[G] (entries
+ *              ever accepted: the source of pool_seq), pool_score / pool_cum [G, K] fp32, pool_len / pool_seq [G, K] int32,
+ *              pool_ids [G, K, ld_tok] int64 (without the EOS id).  Pool slots are in no order: the host sorts by (score
+ *              descending, seq ascending).
+ * a3v_beam_select: one 1024-thread block per group.  Candidate (beam b, token v) of a row with alive != 0 is allowed when trans is
+ *   NULL, or the row's state is outside [0, n_states), or trans[state, v] >= 0; its score is s = cum[b] + (z[b, v] - lse[b]): two fp32
+ *   operations in that order on the RAW logits [R, V] (row stride ld >= V; rows of any alignment: 16-byte loads of a 16-byte
+ *   aligned row, single elements otherwise -- a3v_logits_prepare's rule).  s == -inf or NaN is never taken.  Output: the best 2K
+ *   candidates of the group, by s descending, then flat index b V + v ascending, into cand_score / cand_beam / cand_tok [G, 2K];
+ *   unfilled slots hold (-inf, -1, -1).  The result depends only on that order, not on the reduction shape.  K V < 2^31.
+ * a3v_beam_advance: one block per group; a group with done != 0 is not touched.  With L = glen[g] and the effective limit
+ *   lim = min(limit[g], ld_tok, n_div - 1, pos_cap - base[g]) (base < 0: 0): L >= lim ends the group at once.  Otherwise the 2K
+ *   candidates are walked in rank order; a slot with a score of -inf / NaN, a beam outside [0, K) or a token outside [0, V) is
+ *   skipped.  An EOS candidate at rank < K enters the pool with score s / len_div[L] (a true fp32 division; len_div[j] =
+ *   fp32(max(j, 1) ** length_penalty), a host table of n_div entries), sum s, length L and the parent's token row; at rank >= K it
+ *   is dropped.  A full pool keeps the best K, a tie keeps the earlier entry.  Any other candidate becomes the next live beam
+ *   j = 0, 1, .. until K are taken: row g K + j gets parent = g K + b (absolute row), next_tok, cum = s, alive = 1, state' =
+ *   trans[state[parent], tok] (an unconstrained parent: its state), pos = base + L (the cache position of the token to embed),
+ *   token row = the parent's L ids plus the token (read from tokens_in, written to tokens_out: the caller swaps the two every step).
+ *   The rows behind the takers are dead: parent = itself, next_tok = 0, cum = -inf, alive = 0, pos = -1.  glen = L + 1.  The group
+ *   is then DONE when no beam is alive; or glen reached lim (first every live beam enters the pool at its sum over len_div[glen],
+ *   in beam order); or the pool is full and early_stopping != 0; or the pool is full and cum[beam 0] / len_div[glen] <= the worst
+ *   pool score.  A done group's rows get parent = itself, next_tok = 0, alive = 0, pos = -1 and done = 1.
+ * a3v_kv_permute_tails: for every row r whose parent[r] != r (a parent outside r's group is read as r), the positions
+ *   [tail_lo[r], pos[r]) (clamped to [0, Smax)) of cache row parent[r] replace the same positions of row r, in K [B,Hkv,Smax,hd] and
+ *   V^T [B,Hkv,hd,Smax] of EVERY layer in one launch (k_ptrs / vt_ptrs as a3v_kv_copy_span; bf16 or fp32; hd and Smax multiples of
+ *   8).  All rows read the values from before the call: a thread owns one 16-byte offset for all K rows of a group, reads the K
+ *   vectors, passes the barrier and writes every row from its parent's copy, so several rows may name one parent and a parent may
+ *   itself be overwritten.  tail_max (host value) sizes the grid: it must be >= max(pos) - min(tail_lo) over the MOVED rows of
+ *   every group (the longest span when all rows of a group share one span, as beam search has it); positions of a group behind
+ *   min(tail_lo) + tail_max are not moved.  16-byte
+ *   stores; V^T vectors that straddle an edge of the span element by element.  Nothing outside the spans is written.  tail_max == 0
+ *   launches nothing. */
+int a3v_beam_select(const float* logits, int64_t ld, const float* lse, const float* cum, const uint8_t* alive, const int16_t* trans,
+                    int n_states, const int32_t* state, int G, int K, int V, float* cand_score, int32_t* cand_beam, int32_t* cand_tok,
+                    void* stream);
+int a3v_beam_advance(const float* cand_score, const int32_t* cand_beam, const int32_t* cand_tok, int G, int K, int V, int eos,
+                     int early_stopping, const float* len_div, int n_div, const int16_t* trans, int n_states, const int32_t* base,
+                     const int32_t* limit, int pos_cap, float* cum, uint8_t* alive, int32_t* state, int32_t* glen, uint8_t* done,
+                     int32_t* parent, int64_t* next_tok, int32_t* pos, const int64_t* tokens_in, int64_t* tokens_out, int64_t ld_tok,
+                     int32_t* pool_n, int32_t* pool_added, float* pool_score, float* pool_cum, int32_t* pool_len, int32_t* pool_seq,
+                     int64_t* pool_ids, void* stream);
+int a3v_kv_permute_tails(const void* const* k_ptrs, const void* const* vt_ptrs, int n_layers, const int32_t* parent,
+                         const int32_t* tail_lo, const int32_t* pos, int tail_max, int G, int K, int Hkv, int hd, int Smax, int dtype,
+                         void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Training (backward) entry points. Reference: autograd through the same modules under
  * autocast(bf16) with fp32 master weights (engine_finetune.py:44-68, main_finetune.py:212-217).
  * Convention: activations and their grads use `act_dtype` (bf16 / f32 parity); the residual
