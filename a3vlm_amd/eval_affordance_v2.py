@@ -135,11 +135,14 @@ def get_args_parser():
                         "so that decoding takes the single-call step (and --quant of eval_affordance_with_quant applies)")
     p.add_argument("--kv_quant", type=str, choices=["fp8"], default=None,
                    help="keep the KV cache in fp8 e4m3 with per-position scales (Transformer.quantize_kv_cache): half the cache memory and half "
-                        "the cache bytes per decode step; independent of --quant, applied after --merge_lora")
+                        "the cache bytes per decode step; independent of --quant, applied after --merge_lora.  With --continuous_rows N "
+                        "it is the fp8 cache of the per-row decode path (quantize_kv_cache('fp8', rows=True)); not with "
+                        "--lookup_decoding or --num_beams")
     p.add_argument("--continuous_rows", type=int, default=0,
                    help="N > 0: answers come from MetaModel.generate_many on N KV-cache rows (every row at its own position, a finished "
                         "row is refilled with the next prompt); the loader then hands over 4 N samples at a time and --batch_size is "
-                        "not used.  0 (default): generate() per batch.  Not with --kv_quant or an unmerged LoRA model")
+                        "not used.  0 (default): generate() per batch.  Not with an unmerged LoRA model; with --kv_quant fp8 the rows "
+                        "decode over the fp8 cache")
     p.add_argument("--repetition_penalty", type=float, default=1.0,
                    help="HF repetition penalty over the prompt text and everything generated so far, applied on the device before "
                         "temperature / top-p (1.0 = off, the default; > 1 discourages loops in long answers)")
@@ -203,6 +206,20 @@ def check_num_beams(args) -> int:
     if float(getattr(args, "repetition_penalty", 1.0)) != 1.0:
         raise SystemExit(f"--num_beams {k} scores beams by raw log-probs: set --repetition_penalty 1.0, or --num_beams 0")
     return k
+
+
+def check_kv_quant(args) -> bool:
+    """True: the fp8 KV cache of the per-row decode path (--kv_quant fp8 with --continuous_rows N).  What has no fp8 form ends the
+    run before the model is built."""
+    if not getattr(args, "kv_quant", None):
+        return False
+    if int(getattr(args, "lookup_decoding", 0) or 0):
+        raise SystemExit(f"--lookup_decoding {args.lookup_decoding} has no fp8 KV-cache form (there is no fp8 verify attention): set "
+                         "--lookup_decoding 0, or drop --kv_quant")
+    if int(getattr(args, "num_beams", 0) or 0):
+        raise SystemExit(f"--num_beams {args.num_beams} has no fp8 KV-cache form (the tail permute of beam search is bf16): set "
+                         "--num_beams 0, or drop --kv_quant")
+    return int(getattr(args, "continuous_rows", 0) or 0) > 0
 
 
 def check_answer_regex(args):
@@ -269,6 +286,7 @@ def main(args):
     num_samples = check_num_samples(args)
     lookup = check_lookup(args)
     answer_regex = check_answer_regex(args)
+    kv_rows = check_kv_quant(args)
     distributed = "RANK" in os.environ and "WORLD_SIZE" in os.environ
     rank, world, local = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("LOCAL_RANK", 0))
     if args.model_parallel_size != 1:
@@ -293,7 +311,7 @@ def main(args):
     if getattr(args, "quant", False):     # eval_affordance_with_quant.py --quant: 4-bit decoder linears + LM head, NF4 or --quant_format mxfp4 (bf16 weights freed)
         model.llma.quantize_decode_weights(getattr(args, "quant_format", "nf4"), prefill=getattr(args, "quant_prefill", False))
     if getattr(args, "kv_quant", None):
-        model.llma.quantize_kv_cache(args.kv_quant)
+        model.llma.quantize_kv_cache(args.kv_quant, rows=kv_rows)
     model.eval()
 
     name = os.path.basename(args.dataset).split(".")[0]

@@ -134,6 +134,12 @@ SIGNATURES = {
     "a3v_attention_decode_rows_splits": (I, [I, I, I]),
     "a3v_attention_decode_rows_shared": (I, [P, P, P, P, P, P, P, I, I, I, I, I, ctypes.POINTER(c_int64), P, P, I, P]),
     "a3v_kv_copy_span": (I, [P, P, I, I, P, I, I, I, I, I, I, I, I, P]),
+    "a3v_rope_kvquant_rows": (I, [P, L, P, L, P, P, P, P, P, P, I, I, I, I, I, P]),
+    "a3v_attention_decode_rows_fp8kv": (I, [P, L, P, P, P, P, P, L, P, I, I, I, I, I, I, P, P, P]),
+    "a3v_attention_decode_rows_fp8kv_shared": (I, [P, L, P, P, P, P, P, L, P, P, P, I, I, I, I, I, I, P, P, P]),
+    "a3v_attention_decode_rows_fp8kv_splits": (I, [I, I, I]),
+    "a3v_kv8_copy_span": (I, [P, P, P, P, I, I, P, I, I, I, I, I, I, I, P]),
+    "a3v_llama_decode_step_rows_kv8_form": (I, [I, I, I, I, I, I, I]),
     "a3v_generate_step_rows": (I, [P, L, P, I, I, P, L, P, P, I, P, P, I, P, P, P, P, P, P]),
     "a3v_llama_decode_step_rows_form": (I, [I, I, I, I, I, I, I]),
     "a3v_rope_kvcache_spans": (I, [P, L, P, L, P, P, P, P, P, I, I, I, I, I, I, I, P]),
@@ -186,6 +192,8 @@ SIGNATURES["a3v_llama_decode_step_rows"] = (I, [ctypes.POINTER(LlamaLayer), I, P
 SIGNATURES["a3v_llama_decode_step_verify"] = (I, [ctypes.POINTER(LlamaLayer), I, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, F, P])
 SIGNATURES["a3v_llama_decode_step_rows_shared"] = (I, [ctypes.POINTER(LlamaLayer), I, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I,
                                                        F, P])
+SIGNATURES["a3v_llama_decode_step_rows_kv8"] = (I, [ctypes.POINTER(LlamaLayer), ctypes.POINTER(Kv8Layer), I, P, P, P, P, P, P, P, P, P, P, P,
+                                                    I, I, I, I, I, I, I, I, F, P])
 
 _lib = None
 

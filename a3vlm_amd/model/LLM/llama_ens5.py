@@ -232,6 +232,7 @@ class Transformer(nn.Module):
         self._cache_shape = None
         self._kv_quant: Optional[str] = None        # quantize_kv_cache: None = bf16 caches, "fp8" = e4m3 caches + per-position scales
         self._kv8: Optional[Dict[str, object]] = None
+        self._kv_rows = False                       # quantize_kv_cache("fp8", rows=True): the fp8 cache of the ragged decode path
         self._ws: Dict[tuple, torch.Tensor] = {}
         self._row_maps: Dict[tuple, tuple] = {}
 
@@ -344,13 +345,32 @@ class Transformer(nn.Module):
         return self._cos_sin
 
     # ------------------------------------------------------------------ KV cache
-    def _allocate_kv_cache(self, bsz: int) -> None:
-        """llama_ens5.py:171-176,533-535 (re-allocated only when the shape changes)."""
+    def _allocate_kv_cache(self, bsz: int, rows: bool = False) -> None:
+        """llama_ens5.py:171-176,533-535 (re-allocated only when the shape changes).  ``rows``: the cache of allocate_rows -- under
+        quantize_kv_cache("fp8", rows=True) a kind of its own (below), else the same cache."""
         smax = (self.args.max_seq_len + 63) // 64 * 64
-        shape = (bsz, self.n_kv_heads, smax, self.head_dim, self._dtype, str(self._device), self._kv_quant)
+        kind = "fp8-rows" if rows and self._kv_quant == "fp8" and self._kv_rows else self._kv_quant
+        shape = (bsz, self.n_kv_heads, smax, self.head_dim, self._dtype, str(self._device), kind)
         if self._cache_shape == shape:
             return
         dev, dtp = self._device, self._dtype
+        if kind == "fp8-rows":
+            # e4m3 caches and scales of bsz rows per layer; the shared bf16 K / V^T pair holds ONE row (prefill_row is a batch-1
+            # forward); no staging pair (a3v_rope_kvquant_rows writes the new position straight into the fp8 cache)
+            if dtp != torch.bfloat16:
+                raise RuntimeError("the fp8 KV cache needs a bf16 model")
+            Hkv, hd, L = self.n_kv_heads, self.head_dim, self.n_layers
+            self._destroy_kv_cache()
+            pair_k = torch.zeros(1, Hkv, smax, hd, dtype=dtp, device=dev)
+            pair_vt = torch.zeros(1, Hkv, hd, smax, dtype=dtp, device=dev)
+            self._kv8 = dict(
+                k_q=[torch.zeros(bsz, Hkv, smax, hd, dtype=torch.uint8, device=dev) for _ in range(L)],
+                vt_q=[torch.zeros(bsz, Hkv, hd, smax, dtype=torch.uint8, device=dev) for _ in range(L)],
+                k_scale=[torch.zeros(bsz, Hkv, smax, dtype=torch.float32, device=dev) for _ in range(L)],
+                v_scale=[torch.zeros(bsz, Hkv, smax, dtype=torch.float32, device=dev) for _ in range(L)])
+            self._k_cache, self._vt_cache = [pair_k] * L, [pair_vt] * L
+            self._cache_shape = shape
+            return
         if self._kv_quant == "fp8":
             # e4m3 caches and per-(batch, kv-head, position) scales per layer; ONE bf16 K / V^T pair at full Smax shared by all layers
             # (the multi-token forward runs unchanged on it, layer after layer) and one single-position staging pair for decode
@@ -379,8 +399,9 @@ class Transformer(nn.Module):
 
     def _destroy_kv_cache(self) -> None:
         self._k_cache, self._vt_cache, self._cache_shape, self._kv8 = [], [], None, None
+        self._layer_tab_key = None         # the step's pointer tables follow the allocation: a later cache of the same shape is another one
 
-    def quantize_kv_cache(self, mode: Optional[str] = "fp8") -> None:
+    def quantize_kv_cache(self, mode: Optional[str] = "fp8", rows: bool = False) -> None:
         """Opt-in fp8 (OCP e4m3fn) KV cache for ``forward_inference`` (format: include/a3vlm_hip.h, "fp8 KV cache"): half the cache
         bytes a decode step reads and half the cache allocation.  ``None`` restores the bf16 cache.  Any allocated cache is dropped
         (the next prefill allocates the new kind).  Independent of ``quantize_decode_weights`` -- either order.
@@ -388,12 +409,23 @@ class Transformer(nn.Module):
         Prefill is bit-identical to the bf16-cache model: every layer runs the unchanged bf16 kernels on one shared bf16 K / V^T pair
         and a3v_kv_quantize_fp8 then moves the layer's new positions into its fp8 cache.  Decode (one token) quantises the new
         position and runs a3v_attention_decode_fp8kv -- inside a3v_llama_decode_step_kv8 where the fused step form exists.  A
-        multi-token continuation dequantises each layer's prefix into the shared pair first.  bf16 models, head_dim 64 or 128."""
+        multi-token continuation dequantises each layer's prefix into the shared pair first.  bf16 models, head_dim 64 or 128.
+
+        ``rows=True`` (with ``"fp8"`` only) also opens the ragged decode path -- ``allocate_rows``, ``prefill_row``,
+        ``forward_inference_rows`` (with or without shared prompt keys), ``share_prefix``, ``generate_many`` -- which ``"fp8"`` alone
+        refuses.  ``allocate_rows(R)`` then makes a cache of its own kind: fp8 caches and scales for R rows, the shared bf16 pair
+        for ONE row (``prefill_row`` is a batch-1 forward; its logits are the bf16-cache model's bit for bit) and no staging pair
+        (a3v_rope_kvquant_rows writes the new position, a3v_attention_decode_rows_fp8kv reads the cache -- inside
+        a3v_llama_decode_step_rows_kv8 where the fused form exists).  ``forward_inference`` / ``generate`` on the same object
+        allocate and behave as under ``"fp8"`` alone.  Lookup decoding and beam search have no fp8 form and are refused."""
         if mode not in (None, "fp8"):
             raise ValueError(f"unknown KV-cache format {mode!r}: only 'fp8' (OCP e4m3fn, per-position scales) or None (bf16) exist")
+        if rows and mode != "fp8":
+            raise ValueError(f"quantize_kv_cache(rows=True) is the ragged form of the fp8 cache: it needs mode 'fp8', not {mode!r}")
         if mode == "fp8" and self.head_dim not in (64, 128):
             raise ValueError(f"the fp8 KV cache needs head_dim 64 or 128, this model has {self.head_dim}")
         self._kv_quant = mode
+        self._kv_rows = bool(rows)
         self._destroy_kv_cache()
         self._layer_tab_key = None
 
@@ -490,8 +522,9 @@ class Transformer(nn.Module):
         self._linear(act, w2, h, residual=h)
 
     def _decoder_layers(self, h: torch.Tensor, B: int, S: int, start_pos: int, rope_pos0: int,
-                        k_caches, vt_caches, causal: bool) -> None:
-        """h [B*S, dim] updated in place through all blocks (llama_ens5.py:237-249)."""
+                        k_caches, vt_caches, causal: bool, kv8=None) -> None:
+        """h [B*S, dim] updated in place through all blocks (llama_ens5.py:237-249).  ``kv8``: the fp8 arrays that take the new
+        positions when they are not the model's whole cache (prefill_row: its views of one cache row)."""
         a = self.args
         H, Hkv, hd, dim = self.n_heads, self.n_kv_heads, self.head_dim, a.dim
         rows = B * S
@@ -506,8 +539,9 @@ class Transformer(nn.Module):
         # fp8 KV cache (quantize_kv_cache): k_caches / vt_caches then hold the ONE shared bf16 pair.  S > 1: the layer runs unchanged on
         # the pair (a continuation dequantises the layer's prefix into it first) and its new positions are quantised afterwards;
         # S == 1: the new position goes through the staging pair into the fp8 cache and the attention reads the fp8 cache.
-        kv8 = self._kv8 if k_caches is self._k_cache else None
-        stage = kv8 is not None and S == 1
+        if kv8 is None and k_caches is self._k_cache:
+            kv8 = self._kv8
+        stage = kv8 is not None and S == 1 and "stage_k" in kv8      # (a rows cache has no staging pair: S == 1 runs as S > 1)
         cpos = 0 if stage else start_pos             # where the qkv epilogue / rope kernel writes in the cache it is handed
 
         def attend(i, kc, vc, strides):
@@ -1001,17 +1035,36 @@ class Transformer(nn.Module):
         return logits.clone()
 
     # ------------------------------------------------------------------ ragged decode (every cache row at its own position)
-    def _ragged_check(self) -> None:
-        """Refusals of the ragged path, raised before anything is launched."""
-        if self._kv_quant == "fp8":
-            raise RuntimeError("ragged decode (prefill_row / forward_inference_rows / generate_many) has no fp8 KV-cache form yet: "
-                               "call quantize_kv_cache(None) for the bf16 cache, or use generate()")
+    def _ragged_check(self, what: Optional[str] = None) -> None:
+        """Refusals of the ragged path, raised before anything is allocated or launched.  ``what``: an entry that exists for the bf16
+        cache alone ("lookup decoding", "forward_verify_rows", "beam_search")."""
+        if self._kv_quant == "fp8" and not self._kv_rows:
+            raise RuntimeError("ragged decode (prefill_row / forward_inference_rows / generate_many) is not open on this fp8 KV cache: "
+                               "call quantize_kv_cache(None) for the bf16 cache, or quantize_kv_cache('fp8', rows=True) for the fp8 "
+                               "cache of the ragged path, or use generate()")
+        if self._kv_quant == "fp8" and what is not None:
+            missing = "a3v_kv_permute_tails has no fp8 form" if what == "beam_search" else "there is no fp8 verify attention"
+            raise RuntimeError(f"{what} is not implemented on the fp8 KV cache ({missing}): call quantize_kv_cache(None) for the bf16 "
+                               "cache" + ("" if what == "beam_search" else ", or use lookup=0"))
+
+    def _cache_rows(self) -> int:
+        """Rows of the allocated cache (0: none).  Under an fp8 rows cache the shared bf16 pair holds one row, the fp8 arrays all."""
+        if self._kv8 is not None:
+            return self._kv8["k_q"][0].shape[0]
+        return self._k_cache[0].shape[0] if self._k_cache else 0
+
+    def _kv8_rows(self) -> Optional[Dict[str, object]]:
+        """The fp8 arrays of a cache made by allocate_rows under quantize_kv_cache("fp8", rows=True); None on a bf16 cache."""
+        if self._kv8 is None:
+            return None
+        assert "stage_k" not in self._kv8, "allocate_rows(batch_rows) first: this fp8 cache is forward_inference's"
+        return self._kv8
 
     def allocate_rows(self, batch_rows: int) -> None:
         """The KV cache of ``batch_rows`` independent rows for prefill_row / forward_inference_rows."""
         self._ragged_check()
         assert 0 < batch_rows <= self.args.max_batch_size, (batch_rows, self.args.max_batch_size)
-        self._allocate_kv_cache(batch_rows)
+        self._allocate_kv_cache(batch_rows, rows=True)
         self._pack(check=True)
 
     @torch.no_grad()
@@ -1022,7 +1075,7 @@ class Transformer(nn.Module):
         self._ragged_check()
         a = self.args
         assert tokens.dim() == 2 and tokens.shape[0] == 1, tuple(tokens.shape)
-        assert self._k_cache and 0 <= row < self._k_cache[0].shape[0], "allocate_rows(batch_rows) first"
+        assert 0 <= row < self._cache_rows(), "allocate_rows(batch_rows) first"
         T = tokens.shape[1]
         W = 0
         if image is not None:
@@ -1036,9 +1089,16 @@ class Transformer(nn.Module):
         if image is not None:
             self.encode_image_into(h, [image], 1, S, qformer_feats, extra_feats, (0,))
         # the batch is the outermost dimension of both caches: one row of them is a contiguous cache of batch 1
-        kc = [k[row:row + 1] for k in self._k_cache]
-        vc = [v[row:row + 1] for v in self._vt_cache]
-        self._decoder_layers(h, 1, S, 0, 0, kc, vc, True)
+        kv8 = self._kv8_rows()
+        if kv8 is not None:
+            # fp8 rows cache: the unchanged bf16 forward on the one-row pair; after each layer a3v_kv_quantize_fp8 moves its positions
+            # into that layer's views of the row
+            views = {f: [t[row:row + 1] for t in kv8[f]] for f in ("k_q", "vt_q", "k_scale", "v_scale")}
+            self._decoder_layers(h, 1, S, 0, 0, list(self._k_cache), list(self._vt_cache), True, kv8=views)
+        else:
+            kc = [k[row:row + 1] for k in self._k_cache]
+            vc = [v[row:row + 1] for v in self._vt_cache]
+            self._decoder_layers(h, 1, S, 0, 0, kc, vc, True)
         xn = self._buf("xn_last", (1, a.dim))
         ops.rmsnorm(h[S - 1:S], self.norm.weight, xn, a.norm_eps)
         logits = torch.empty(1, a.vocab_size, dtype=torch.float32, device=self._device)
@@ -1049,7 +1109,11 @@ class Transformer(nn.Module):
         """One bf16 decode step with row b at cache position pos[b] from one C call (a3v_llama_decode_step_rows; with shared prompt
         keys a3v_llama_decode_step_rows_shared)."""
         bufs = self._decode_step_buffers(B)
-        if src_row is not None:
+        if self._kv8 is not None:          # fp8 rows cache: one entry, the two arrays NULL without shared prompt keys
+            self._llama_layer_table()      # (builds the kv8 table too)
+            sp = (src_row.data_ptr(), shared.data_ptr()) if src_row is not None else (None, None)
+            self._call_step("a3v_llama_decode_step_rows_kv8", h, bufs, (pos.data_ptr(), *sp, pos_max, B), tables=(self._kv8_tab,))
+        elif src_row is not None:
             self._call_step("a3v_llama_decode_step_rows_shared", h, bufs, (pos.data_ptr(), src_row.data_ptr(), shared.data_ptr(), pos_max, B))
         else:
             self._call_step("a3v_llama_decode_step_rows", h, bufs, (pos.data_ptr(), pos_max, B))
@@ -1071,7 +1135,15 @@ class Transformer(nn.Module):
         torch.add(pos, 1, out=sk)                      # keys of row b (idle rows: <= 0)
         ldq = qkv.stride(0)
         path = self._layer_path(h, B, True, ragged=True)
+        kv8 = self._kv8_rows()
         for i in range(self.n_layers):
+            if kv8 is not None:            # fp8 rows cache: a3v_rope_kvquant_rows, then the fp8 rows attention (plain or shared)
+                fp8c = (kv8["k_q"][i], kv8["vt_q"][i], kv8["k_scale"][i], kv8["v_scale"][i])
+                self._layer(i, path, h, (xn, qkv, att, act),
+                            lambda: ops.rope_kvquant_rows(qkv, qkv, *fp8c, cs, pos, B, H, Hkv, hd),
+                            lambda: ops.attention_decode_rows_fp8kv(qkv, *fp8c, att, sk, pos_max + 1, B, H, Hkv, hd, scratch, counters,
+                                                                    src_row, shared))
+                continue
             kc, vc = self._k_cache[i], self._vt_cache[i]
             smax = kc.shape[2]
             strides = (ldq, ldq, hd, Hkv * smax * hd, smax * hd, hd, Hkv * hd * smax, hd * smax, smax, H * hd, H * hd, hd)
@@ -1100,14 +1172,15 @@ class Transformer(nn.Module):
             raise ValueError("forward_inference_rows: src_row and shared are given together, or neither")
         if src_row is not None:
             assert all(t.dtype == torch.int32 and t.numel() == B and t.is_contiguous() and t.is_cuda for t in (src_row, shared))
-        assert self._k_cache and self._k_cache[0].shape[0] == B, "allocate_rows(batch_rows) first; one token per cache row"
+        assert self._cache_rows() == B, "allocate_rows(batch_rows) first; one token per cache row"
         assert next_tok.dtype == torch.int64 and pos.dtype == torch.int32 and pos.numel() == B and pos.is_contiguous()
         assert 0 <= pos_max < min(self._k_cache[0].shape[2], self._cos_sin_cpu.shape[0]), pos_max
         h = self._buf("h", (B, a.dim))
         ops.embed_assemble(next_tok.view(B, 1).contiguous(), self.tok_embeddings.weight, h, B, 1, 0, a.dim)
         w8 = self._step_format_code()
+        form = "a3v_llama_decode_step_rows_form" if self._kv8_rows() is None else "a3v_llama_decode_step_rows_kv8_form"
         fused = (self._dtype == torch.bfloat16 and not getattr(self, "_per_kernel_decode", False) and w8 is not None
-                 and _lib.load().a3v_llama_decode_step_rows_form(B, a.dim, a.n_heads, self.n_kv_heads, self.head_dim, self.ffn, w8) == 2)
+                 and getattr(_lib.load(), form)(B, a.dim, a.n_heads, self.n_kv_heads, self.head_dim, self.ffn, w8) == 2)
         if fused:
             self._decode_step_rows(h, B, pos, pos_max, src_row, shared)
         else:
@@ -1138,7 +1211,7 @@ class Transformer(nn.Module):
         if given); the rows of idle queries are not meaningful.  bf16 and fp32 streams.
         INVARIANT: the step leaves keys at pos[b] .. pos[b] + nq[b] - 1.  Those of rejected drafts lie behind the position the row
         continues from: no later query reads them (each masks at its own key count) and the next step overwrites them."""
-        self._ragged_check()
+        self._ragged_check("forward_verify_rows")
         a = self.args
         B, Q = x.shape
         M = B * Q
@@ -1185,13 +1258,22 @@ class Transformer(nn.Module):
         """Makes the rows ``dst_rows`` siblings of cache row ``src_row``, whose prompt fills positions [0, P) (image words
         included): the keys below the last 64 boundary, P & ~63, stay in the source row alone and are read from there
         (``forward_inference_rows(..., src_row=, shared=)``); the rest of the prompt, [P & ~63, P), is copied into every sibling's
-        own row by one launch over all layers (a3v_kv_copy_span).  Returns P & ~63, the value to put in ``shared[]``."""
+        own row by one launch over all layers (a3v_kv_copy_span; an fp8 rows cache: a3v_kv8_copy_span, bytes and scales).  Returns
+        P & ~63, the value to put in ``shared[]``."""
         self._ragged_check()
-        assert self._k_cache and 0 <= src_row < self._k_cache[0].shape[0], "allocate_rows(batch_rows) first"
+        assert 0 <= src_row < self._cache_rows(), "allocate_rows(batch_rows) first"
         assert 0 <= P <= self._k_cache[0].shape[2], (P, self._k_cache[0].shape[2])
         lo = P & ~63
         dst = dst_rows if isinstance(dst_rows, torch.Tensor) else torch.tensor(list(dst_rows), dtype=torch.int32, device=self._device)
-        if dst.numel() and P > lo:
+        kv8 = self._kv8_rows()
+        if dst.numel() and P > lo and kv8 is not None:
+            arrays = [kv8[f] for f in ("k_q", "vt_q", "k_scale", "v_scale")]
+            key = tuple(t.data_ptr() for ts in arrays for t in ts)
+            ptrs = self._ws.get("kv8_ptrs")
+            if ptrs is None or ptrs[0] != key:             # the device table of base pointers follows the cache allocation
+                ptrs = (key, None)
+            self._ws["kv8_ptrs"] = (key, ops.kv8_copy_span(*arrays, src_row, dst, lo, P, ptrs[1]))
+        elif dst.numel() and P > lo:
             key = tuple(t.data_ptr() for t in self._k_cache) + tuple(t.data_ptr() for t in self._vt_cache)
             ptrs = self._ws.get("kv_ptrs")
             if ptrs is None or ptrs[0] != key:             # the device table of base pointers follows the cache allocation

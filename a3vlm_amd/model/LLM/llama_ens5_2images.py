@@ -33,7 +33,7 @@ class Transformer(_Base):
     def _image_slots(self):
         return [(self.start_img, self.end_img), (self.start_depth_img, self.end_depth_img)]
 
-    def _ragged_check(self) -> None:
+    def _ragged_check(self, what: Optional[str] = None) -> None:
         raise NotImplementedError("ragged decode (prefill_row / forward_inference_rows / generate_many) is not implemented for the "
                                   "two-image plugin: use generate(), which takes the depth images")
 

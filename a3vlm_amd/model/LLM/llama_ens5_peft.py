@@ -89,19 +89,19 @@ class Transformer(base.Transformer):
             raise NotImplementedError("MXFP4 decode weights beside LoRA adapters are not implemented: merge_adapters() first")
         super().quantize_decode_weights(mode, prefill)
 
-    def _ragged_check(self) -> None:
+    def _ragged_check(self, what: Optional[str] = None) -> None:
         if not self._merged:
             # the ragged step has no adapter hooks: it would silently decode with the base weights alone
             raise NotImplementedError("ragged decode (prefill_row / forward_inference_rows / generate_many) is not implemented beside "
                                       "LoRA adapters: merge_adapters() first (MetaModel.merge_lora / --merge_lora), or use generate()")
-        super()._ragged_check()
+        super()._ragged_check(what)
 
-    def quantize_kv_cache(self, mode: Optional[str] = "fp8") -> None:
+    def quantize_kv_cache(self, mode: Optional[str] = "fp8", rows: bool = False) -> None:
         if mode is not None and not self._merged:
             # decode beside adapters runs kernel by kernel with the adapter hooks (no fused step): the fp8 cache is not wired into it
             raise NotImplementedError("the fp8 KV cache is not implemented beside LoRA adapters: merge_adapters() first "
                                       "(MetaModel.merge_lora / --merge_lora), then quantize_kv_cache('fp8')")
-        super().quantize_kv_cache(mode)
+        super().quantize_kv_cache(mode, rows)
 
     def quantize_base_weights(self, mode: str = "nf4") -> None:
         """QLoRA (the reference's ``main_finetune.py --quant``: bf16 model, checkpoint, ``quantize(model, nf4)``, then train what is left

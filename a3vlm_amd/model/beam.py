@@ -130,7 +130,7 @@ def beam_search(model, prompts: List[str], images: Optional[torch.Tensor] = None
     nret = int(num_return_sequences)
     automaton = model.constraint_automaton(constraint)
     llma = model.llma
-    llma._ragged_check()                                      # before anything is allocated or launched
+    llma._ragged_check("beam_search")                         # before anything is allocated or launched
     dev = model._device
     args = llma.args
     N, V, eos = len(prompts), args.vocab_size, model.tokenizer.eos_id

@@ -76,7 +76,7 @@ class MetaModel(nn.Module):
     def from_pretrained(cls, pretrained_path, llama_type: Optional[str] = None, llama_config=None,
                         tokenizer_path: Optional[str] = None, with_visual: bool = False, max_seq_len: int = 4096,
                         mp_group=None, dtype=torch.bfloat16, device="cuda", quant=False, kv_quant: Optional[str] = None,
-                        quant_prefill: bool = False) -> "MetaModel":
+                        quant_prefill: bool = False, kv_rows: bool = False) -> "MetaModel":
         """Build the model a checkpoint folder describes and load it (reference: model/meta.py:88-222).
 
         What is not given is looked up in the LAST folder of ``pretrained_path``: ``llama_type`` in ``meta.json``,
@@ -93,7 +93,8 @@ class MetaModel(nn.Module):
         decode steps of more than 32 rows W4A8 on the images (``prefill=True`` there); with fp8 it is that mode's W8A8 prefill; with
         ``quant="nf4"`` it is refused.
         ``kv_quant="fp8"`` (no reference counterpart) keeps the KV cache of ``generate`` in fp8 e4m3 with per-position scales
-        (``Transformer.quantize_kv_cache``); independent of ``quant``."""
+        (``Transformer.quantize_kv_cache``); independent of ``quant``.  ``kv_rows=True`` (needs ``kv_quant="fp8"``) makes it the fp8
+        cache of the ragged path as well (``quantize_kv_cache("fp8", rows=True)``: ``generate_many`` over fp8 rows)."""
         import os
         import warnings
         from ..checkpoint import load_tensor_parallel_model_list
@@ -105,6 +106,8 @@ class MetaModel(nn.Module):
                              "prefill): NF4 has no quantised-activation form")
         if quant_prefill and not quant:
             raise ValueError("quant_prefill needs quant='mxfp4' (or fp8)")
+        if kv_rows and kv_quant != "fp8":
+            raise ValueError("kv_rows is the ragged form of the fp8 KV cache: it needs kv_quant='fp8'")
         for path in paths:
             if path.startswith("hf://"):
                 raise NotImplementedError(f"{path}: downloading from the hub is not available here; pass a local folder")
@@ -146,7 +149,7 @@ class MetaModel(nn.Module):
         elif quant:
             model.llma.quantize_decode_weights("fp8", prefill=bool(quant_prefill))
         if kv_quant is not None:
-            model.llma.quantize_kv_cache(kv_quant)
+            model.llma.quantize_kv_cache(kv_quant, rows=bool(kv_rows))
         model.eval()
         return model
 
@@ -538,7 +541,7 @@ class MetaModel(nn.Module):
             if int(lookup_ngram) < 1:
                 raise ValueError(f"generate_many: lookup_ngram = {lookup_ngram}; >= 1")
         llma = self.llma
-        llma._ragged_check()                                  # before anything is allocated or launched
+        llma._ragged_check("lookup decoding" if D else None)  # before anything is allocated or launched
         dev = self._device
         N = len(prompts)
         args = llma.args
@@ -749,7 +752,7 @@ class MetaModel(nn.Module):
             raise ValueError(f"generate_many: lookup_ngram = {lookup_ngram}; >= 1")
         automaton = self.constraint_automaton(constraint)
         llma = self.llma
-        llma._ragged_check()                                  # before anything is allocated or launched
+        llma._ragged_check("lookup decoding")                 # before anything is allocated or launched
         dev = self._device
         N = len(prompts)
         args = llma.args

@@ -666,6 +666,76 @@ def kv_copy_span(k_caches, vt_caches, src_row: int, dst_rows, lo: int, hi: int, 
     return ptrs
 
 
+def _kv8_arrays(k_q, vt_q, k_scale, v_scale):
+    """(B, Hkv, Smax, hd) of the four arrays of one layer's fp8 cache, checked."""
+    _dev(k_q, vt_q, k_scale, v_scale)
+    B, Hkv, Smax, hd = k_q.shape
+    assert k_q.dtype == vt_q.dtype == torch.uint8 and k_scale.dtype == v_scale.dtype == torch.float32
+    assert all(t.is_contiguous() for t in (k_q, vt_q, k_scale, v_scale))
+    assert tuple(vt_q.shape) == (B, Hkv, hd, Smax) and tuple(k_scale.shape) == tuple(v_scale.shape) == (B, Hkv, Smax)
+    return B, Hkv, Smax, hd
+
+
+def rope_kvquant_rows(qkv, q_out, k_q, vt_q, k_scale, v_scale, cos_sin, pos, B, H, Hkv, hd):
+    """``rope_kvcache_rows`` into an fp8 cache, one launch: q rotated into q_out, the rotated bf16 k row and the v row quantised per
+    kv-head and written at position pos[b] of row b's own cache (device int32 [B]; outside [0, Smax) = idle row: no cache write,
+    zero q row).  Bit-equal to ``rope_kvcache_rows`` into a bf16 cache followed by ``kv_quantize_fp8`` (S = 1) of that position."""
+    _dev(qkv, q_out, cos_sin, pos)
+    Bc, Hc, Smax, hdc = _kv8_arrays(k_q, vt_q, k_scale, v_scale)
+    assert qkv.dtype == q_out.dtype == torch.bfloat16 and pos.dtype == torch.int32 and pos.is_contiguous() and pos.numel() >= B
+    assert Bc >= B and (Hc, hdc) == (Hkv, hd)
+    rc = _l.load().a3v_rope_kvquant_rows(_p(qkv), qkv.stride(0), _p(q_out), q_out.stride(0), _p(k_q), _p(vt_q), _p(k_scale), _p(v_scale),
+                                         _p(cos_sin), _p(pos), B, H, Hkv, hd, Smax, _stream())
+    _l.check(rc, f"a3v_rope_kvquant_rows(B={B},H={H},Hkv={Hkv},hd={hd})")
+
+
+def attention_decode_rows_fp8kv_splits(B: int, H: int, sk_max: int) -> int:
+    return _l.load().a3v_attention_decode_rows_fp8kv_splits(B, H, sk_max)
+
+
+def attention_decode_rows_fp8kv(q, k_q, vt_q, k_scale, v_scale, out, sk, sk_max: int, B, H, Hkv, hd, scratch, counters,
+                                src_row=None, shared=None):
+    """``attention_decode_fp8kv`` with sk[b] keys for row b (device int32 [B]; <= 0 = idle row, zero output; above sk_max read as
+    sk_max).  scratch: attention_scratch_floats(B, H, hd, sk_max) floats; counters int32 [>= B*H], zero; left zero.
+    ``src_row`` / ``shared`` (both or neither): shared prompt keys as ``attention_decode_rows_shared`` -- below the shared length
+    the K bytes, V^T bytes and both scales of row b are read from cache row src_row[b]; the arrays hold all B rows."""
+    _dev(q, out, sk, scratch, counters, src_row, shared)
+    Bc, Hc, Smax, hdc = _kv8_arrays(k_q, vt_q, k_scale, v_scale)
+    assert q.dtype == out.dtype == torch.bfloat16 and Bc >= B and (Hc, hdc) == (Hkv, hd)
+    assert (src_row is None) == (shared is None)
+    assert all(t is None or (t.dtype == torch.int32 and t.is_contiguous() and t.numel() >= B) for t in (sk, src_row, shared))
+    assert scratch.dtype == torch.float32 and scratch.numel() >= attention_scratch_floats(B, H, hd, sk_max)
+    assert counters.dtype == torch.int32 and counters.numel() >= B * H
+    head = (_p(q), q.stride(0), _p(k_q), _p(vt_q), _p(k_scale), _p(v_scale), _p(out), out.stride(0), _p(sk))
+    tail = (int(sk_max), B, H, Hkv, hd, Smax, _p(scratch), _p(counters), _stream())
+    if src_row is None:
+        rc = _l.load().a3v_attention_decode_rows_fp8kv(*head, *tail)
+    else:
+        rc = _l.load().a3v_attention_decode_rows_fp8kv_shared(*head, _p(src_row), _p(shared), *tail)
+    _l.check(rc, f"a3v_attention_decode_rows_fp8kv(B={B},sk_max={sk_max},H={H},hd={hd},shared={src_row is not None})")
+    return out
+
+
+def kv8_copy_span(k_q, vt_q, k_scale, v_scale, src_row: int, dst_rows, lo: int, hi: int, ptrs=None):
+    """``kv_copy_span`` for an fp8 cache: positions [lo, hi) (0 <= hi - lo < 64) of cache row ``src_row`` -- K bytes, V^T byte runs
+    and both scale runs -- into the rows ``dst_rows`` (device int32; entries outside the cache are skipped) of every layer, one
+    launch.  The four arguments are the per-layer lists.  ``ptrs``: the device int64 [4, layers] table of their base pointers if the
+    caller keeps one (returned either way)."""
+    B, Hkv, Smax, hd = k_q[0].shape
+    assert len(k_q) == len(vt_q) == len(k_scale) == len(v_scale)
+    for arrays in zip(k_q, vt_q, k_scale, v_scale):
+        assert _kv8_arrays(*arrays) == (B, Hkv, Smax, hd)
+    _dev(dst_rows)
+    assert dst_rows.dtype == torch.int32 and dst_rows.is_contiguous()
+    if ptrs is None:
+        ptrs = torch.tensor([[t.data_ptr() for t in ts] for ts in (k_q, vt_q, k_scale, v_scale)], dtype=torch.int64, device=k_q[0].device)
+    assert ptrs.dtype == torch.int64 and tuple(ptrs.shape) == (4, len(k_q)) and ptrs.is_contiguous()
+    rc = _l.load().a3v_kv8_copy_span(_p(ptrs[0]), _p(ptrs[1]), _p(ptrs[2]), _p(ptrs[3]), len(k_q), int(src_row), _p(dst_rows),
+                                     dst_rows.numel(), B, int(lo), int(hi), Hkv, hd, Smax, _stream())
+    _l.check(rc, f"a3v_kv8_copy_span(src={src_row},lo={lo},hi={hi},hd={hd})")
+    return ptrs
+
+
 def generate_step_rows(logits, sampled, tokens, cur, limit, pos_base: int, stop_seq, stop_off, n_stop: int, stopped, stop_pos, live,
                        next_tok, pos):
     """One launch = one step of generate_many's bookkeeping (a3v_generate_step_rows): per row argmax (or the sampled id), the

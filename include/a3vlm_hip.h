@@ -617,7 +617,8 @@ int a3v_llama_decode_step_kv8(const a3v_llama_layer* layers, const a3v_kv8_layer
 /* ---------------------------------------------------------------------------------------
  * Ragged decode (opt-in; no reference counterpart: model/meta.py:413-485 keeps every batch row at one cache position).  Each
  * batch row decodes at its own position; every position array is a DEVICE int32[B].  An idle row (a negative position, or one
- * outside the cache) writes nothing into any cache and its outputs are zeros, never NaN.  bf16 KV cache only.
+ * outside the cache) writes nothing into any cache and its outputs are zeros, never NaN.  These entries take the bf16 KV cache
+ * (the fp8 one: "fp8 KV cache on the ragged decode path" below).
  *
  * a3v_rope_kvcache_rows: a3v_rope_kvcache at S = 1 with start_pos = rope_pos0 = pos[b] per row, one launch, bf16 and fp32, the
  * per-element arithmetic of that entry (a row is bit-equal to the uniform call at its position).  pos[b] outside [0, Smax) is an
@@ -696,6 +697,71 @@ int a3v_llama_decode_step_rows_shared(const a3v_llama_layer* layers, int n_layer
                                       float* attn_scratch, void* skinny_ws, const float* cos_sin, const int32_t* pos,
                                       const int32_t* src_row, const int32_t* shared, int pos_max, int B, int dim, int H, int Hkv,
                                       int hd, int ffn, int Smax, float eps, void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * fp8 KV cache on the ragged decode path (opt-in; a3v_kv8_rows.hip).  The arrays are those of "fp8 KV cache" above (k_q, vt_q,
+ * k_scale, v_scale of one layer; Smax % 64 == 0; every pointer 16-B aligned), the position arrays those of "Ragged decode" (DEVICE
+ * int32[B]; an idle row writes nothing into any cache array and its outputs are zeros, never NaN).  bf16 model, hd 64 or 128:
+ * anything else is A3V_ERR_SHAPE before any launch.
+ *
+ * a3v_rope_kvquant_rows: the per-row RoPE and the quantising cache write in ONE launch.  qkv [B, ldqkv] bf16 as the plain-store qkv
+ * GEMV leaves it (q heads, k heads, v heads).  For a running row (0 <= pos[b] < Smax): q is rotated at pos[b] into q_out (may be
+ * qkv: in place) with a3v_rope_kvcache_rows' arithmetic; k is rotated and rounded to bf16; that bf16 k row and the bf16 v row are
+ * quantised per kv-head with a3v_kv_quantize_fp8's arithmetic (scale = max(amax, 1e-12) / 448, a true division, e4m3 round to
+ * nearest even, saturating) and written at position pos[b] of the row's own cache: hd K bytes, hd single V^T bytes (one per d row,
+ * column pos[b]) and the two scales.  BIT CONTRACT: q_out, the codes and the scales equal a3v_rope_kvcache_rows into a bf16 cache
+ * followed by a3v_kv_quantize_fp8 (S = 1) of that position.  Nothing outside position pos[b] of row b is written.  An idle row
+ * (pos[b] < 0 or >= Smax, bounded in the kernel) writes nothing to any cache array and its q_out row is zeros.
+ *
+ * a3v_attention_decode_rows_fp8kv: a3v_attention_decode_fp8kv over sk[b] keys for row b, 0 < sk[b] <= sk_max <= Smax (sk[b] above
+ * sk_max is read as sk_max; sk[b] <= 0: the row's output is zeros).  The walk, the fp32 products score = (q . kq) k_scale
+ * softmax_scale and p v_scale, and the masks by select are that entry's; the split plan is a3v_attention_decode_plan's at
+ * Sk = sk_max, a key range beyond sk[b] contributes (m, l) = (-inf, 0) and still arrives at the combine.  counters: B*H
+ * zero-initialised ints, required, left zero.  scratch: a3v_attention_scratch_floats(B, H, hd, sk_max) floats.  CONTRACTS: (a) with
+ * one key range a row is bit-equal to a3v_attention_decode_fp8kv at Sk = sk[b]; (b) with every row at sk_max the launch is bit-equal
+ * to the uniform one.  a3v_attention_decode_rows_fp8kv_splits: the number of key ranges of that plan.
+ * a3v_attention_decode_rows_fp8kv_shared: plus src_row / shared of "Shared prompt keys" (the same rule: S_b = min(shared[b], sk[b])
+ * rounded down to 64, src_row outside [0, B) read as b, one level only).  Below S_b all FOUR streams of row b -- K bytes, V^T
+ * bytes, k_scale and v_scale -- come from row src_row[b]; a tile starts at a multiple of 64 and a 16-B V^T load is 16 keys, so
+ * nothing straddles two rows.  (c) The output equals the plain entry on caches into which bytes AND scales of [0, S_b) of row
+ * src_row[b] were copied into row b, bit for bit; positions below S_b of row b's own arrays are never read.  (d) src_row == NULL:
+ * the call IS the plain one.
+ *
+ * a3v_kv8_copy_span: a3v_kv_copy_span for the fp8 cache: positions [lo, hi), 0 <= hi - lo < 64, of cache row src_row into the rows
+ * dst_rows[0..n_dst) (DEVICE int32; entries outside [0, B) or equal to src_row are skipped) of EVERY layer in one launch -- K bytes,
+ * V^T byte runs and both scale runs.  k_ptrs / vt_ptrs / ks_ptrs / vs_ptrs: DEVICE arrays of n_layers base pointers.  Vector stores
+ * where aligned, elements at the edges; nothing outside the span is written.  hi == lo or n_dst == 0 launches nothing.
+ *
+ * a3v_llama_decode_step_rows_kv8: a3v_llama_decode_step_rows[_shared] over the fp8 caches of `kv8` (the k_cache / vt_cache fields
+ * of `layers` are not read).  src_row / shared: both or neither.  Fused form only (a3v_llama_decode_step_rows_kv8_form == 2: bf16,
+ * fp8 or NF4 weight images; else the query says 0, the call returns A3V_ERR_SHAPE with nothing touched and the host runs kernel by
+ * kernel).  SIX launches per layer: the qkv GEMV with the RMSNorm prologue and a plain store, a3v_rope_kvquant_rows on the qkv buffer
+ * in place, the fp8 rows attention over pos[b] + 1 keys (sk_max = pos_max + 1; the kernel adds the one itself), wo, w1|w3, w2.
+ * 17..32 rows run as two chunks; the attention of the chunk at row b0 gets the un-offset bases of all four arrays, the slices at b0
+ * and the row offset, so a sibling in the second chunk may read a leader in the first.  The step equals the per-kernel sequence of
+ * the entries above bit for bit.  Everything the stage's launches would refuse (H % Hkv, the alignment of qkv and of the four arrays
+ * of every layer) is refused by the entry itself, before its first launch.  As in a3v_llama_decode_step_rows, the idle row of the
+ * step is pos[b] < 0: a pos[b] >= Smax (which pos_max < Smax excludes for a caller that keeps pos_max honest) is idle for the write
+ * but is read by the attention as sk_max keys, so that row's output is not zeros; it is the caller's to keep pos[b] <= pos_max. */
+int a3v_rope_kvquant_rows(const void* qkv, int64_t ldqkv, void* q_out, int64_t ldq, void* k_q, void* vt_q, float* k_scale,
+                          float* v_scale, const float* cos_sin, const int32_t* pos, int B, int H, int Hkv, int hd, int Smax,
+                          void* stream);
+int a3v_attention_decode_rows_fp8kv(const void* q, int64_t ldq, const void* k_q, const void* vt_q, const float* k_scale,
+                                    const float* v_scale, void* out, int64_t ldo, const int32_t* sk, int sk_max, int B, int H,
+                                    int Hkv, int hd, int Smax, float* scratch, int* counters, void* stream);
+int a3v_attention_decode_rows_fp8kv_shared(const void* q, int64_t ldq, const void* k_q, const void* vt_q, const float* k_scale,
+                                           const float* v_scale, void* out, int64_t ldo, const int32_t* sk, const int32_t* src_row,
+                                           const int32_t* shared, int sk_max, int B, int H, int Hkv, int hd, int Smax,
+                                           float* scratch, int* counters, void* stream);
+int a3v_attention_decode_rows_fp8kv_splits(int B, int H, int sk_max);
+int a3v_kv8_copy_span(const void* const* k_ptrs, const void* const* vt_ptrs, const void* const* ks_ptrs, const void* const* vs_ptrs,
+                      int n_layers, int src_row, const int32_t* dst_rows, int n_dst, int B, int lo, int hi, int Hkv, int hd,
+                      int Smax, void* stream);
+int a3v_llama_decode_step_rows_kv8(const a3v_llama_layer* layers, const a3v_kv8_layer* kv8, int n_layers, void* h, void* xn,
+                                   void* qkv, void* att, void* act, float* attn_scratch, void* skinny_ws, const float* cos_sin,
+                                   const int32_t* pos, const int32_t* src_row, const int32_t* shared, int pos_max, int B, int dim,
+                                   int H, int Hkv, int hd, int ffn, int Smax, float eps, void* stream);
+int a3v_llama_decode_step_rows_kv8_form(int B, int dim, int H, int Hkv, int hd, int ffn, int w8);
 
 /* ---------------------------------------------------------------------------------------
  * Lookup decoding (opt-in; a3v_spec.hip; no reference counterpart).  One decode step feeds Q = D + 1 query positions per cache row,
