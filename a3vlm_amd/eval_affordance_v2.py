@@ -74,6 +74,8 @@ class VQADataset(torch.utils.data.Dataset):
         # decode_only: the worker hands over the decoded pixels (uint8 HWC); pad / resize / normalise run on the device per batch
         self.transform_val = T_decode_rgb(img_size) if decode_only else T_padded_resize(img_size)
         self.image_root = image_root
+        self.cache_last = False            # --share_image_prefix: records of one image are adjacent, the image is loaded once
+        self._last = (None, None)
 
     def __len__(self):
         return len(self.test)
@@ -82,7 +84,12 @@ class VQADataset(torch.utils.data.Dataset):
         data = self.test[idx]
         path = data["image"]
         local = path if os.path.isfile(path) or not self.image_root else os.path.join(self.image_root, os.path.basename(path))
-        image = self.transform_val(Image.open(local).convert("RGB"))
+        if self.cache_last and self._last[0] == local:
+            image = self._last[1]
+        else:
+            image = self.transform_val(Image.open(local).convert("RGB"))
+            if self.cache_last:
+                self._last = (local, image)
         conv = default_conversation()
         conv.load_qas([[data["conversations"][0]["value"], None]])
         return {"question": conv.get_prompt(), "question_id": idx, "annotation": data["conversations"][1]["value"],
@@ -155,6 +162,12 @@ def get_args_parser():
     p.add_argument("--save_scores", action="store_true", default=False,
                    help="every record gains \"logprob_sum\" and \"logprobs\": the model's own log-probability of the answer's tokens "
                         "(raw logits, temperature 1), a confidence for AP-style evaluation")
+    p.add_argument("--share_image_prefix", action="store_true",
+                   help="several questions about one image pay for its prefill once (MetaModel.generate_many(prefix_sharing=True)): the "
+                        "records are ordered stably so that equal image paths are adjacent, each image is loaded once, questions that "
+                        "share the image and the leading prompt tokens read those keys from one KV-cache row; the output file keeps the "
+                        "record order and format it had.  Needs --continuous_rows >= 2; not with --num_samples > 1, --lookup_decoding, "
+                        "--num_beams or --kv_quant")
     p.add_argument("--num_samples", type=int, default=1,
                    help="N > 1: draw N answers per (image, question) from ONE prefill (MetaModel.generate_many(n=N): the image is "
                         "encoded once and the prompt's keys are stored once) and keep the most confident well-formed box; every record "
@@ -269,6 +282,27 @@ def select_sample(samples) -> int:
     return max(pool, key=lambda k: (samples[k]["logprob_sum"], -k))
 
 
+def check_share_image_prefix(args) -> bool:
+    """--share_image_prefix and what it cannot be combined with: every refusal ends the run here, before the model is built."""
+    if not getattr(args, "share_image_prefix", False):
+        return False
+    if int(getattr(args, "continuous_rows", 0) or 0) < 2:
+        raise SystemExit("--share_image_prefix runs the questions of an image in several KV-cache rows that read one prefix: add "
+                         "--continuous_rows R with R >= 2")
+    if int(getattr(args, "num_samples", 1)) > 1:
+        raise SystemExit(f"--share_image_prefix shares one level only and --num_samples {args.num_samples} already shares the prompt "
+                         "among its samples: use --num_samples 1, or drop --share_image_prefix")
+    if int(getattr(args, "lookup_decoding", 0) or 0):
+        raise SystemExit("--share_image_prefix has no verify step over a shared prefix: set --lookup_decoding 0, or drop --share_image_prefix")
+    if int(getattr(args, "num_beams", 0) or 0):
+        raise SystemExit(f"--share_image_prefix: the beams of --num_beams {args.num_beams} already read their leader's row: set "
+                         "--num_beams 0, or drop --share_image_prefix")
+    if getattr(args, "kv_quant", None):
+        raise SystemExit("--share_image_prefix has no fp8 KV-cache form (no prefill attention reads fp8 keys): drop --kv_quant, or "
+                         "--share_image_prefix")
+    return True
+
+
 def check_num_samples(args) -> int:
     n = int(getattr(args, "num_samples", 1))
     if n < 1:
@@ -287,6 +321,7 @@ def main(args):
     lookup = check_lookup(args)
     answer_regex = check_answer_regex(args)
     kv_rows = check_kv_quant(args)
+    share_prefix = check_share_image_prefix(args)
     distributed = "RANK" in os.environ and "WORLD_SIZE" in os.environ
     rank, world, local = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("LOCAL_RANK", 0))
     if args.model_parallel_size != 1:
@@ -326,6 +361,10 @@ def main(args):
     pre = GpuPaddedResize(args.input_size, dev, torch.float32) if on_gpu else None
     idx = list(shard_range(len(dataset), world, rank))
     rows = getattr(args, "continuous_rows", 0)
+    if share_prefix:       # equal image paths adjacent (stable: the questions of an image keep their order); written back in record order
+        idx.sort(key=lambda k: dataset.test[k]["image"])
+        dataset.cache_last = True
+    order = []
     loader = torch.utils.data.DataLoader(torch.utils.data.Subset(dataset, idx), batch_size=4 * rows if rows > 0 else args.batch_size, shuffle=False,
                                          num_workers=args.num_workers, pin_memory=True, drop_last=False, collate_fn=collate_fn)
     outputs = []
@@ -368,9 +407,11 @@ def main(args):
                     if save_scores:
                         outputs[-1].update(logprob_sum=scs[best]["sum"], logprobs=scs[best]["logprobs"])
                 continue
+            order.extend(qids)
             if rows > 0:           # a chunk of a few batches at a time: the loader's workers stay ahead of the decode
                 answers = model.generate_many(prompts, image, batch_rows=rows, max_gen_len=args.max_gen_len, temperature=args.temperature,
                                               top_p=args.top_p, **controls, **({"lookup": lookup} if lookup else {}),
+                                              **({"prefix_sharing": True, "image_ids": list(paths)} if share_prefix else {}),
                                               **({"lookup_verify": "choice"} if lookup and getattr(args, "lookup_verify", "argmax") == "choice" else {}))
             else:
                 answers = model.generate(prompts, image, max_gen_len=args.max_gen_len, temperature=args.temperature, top_p=args.top_p,
@@ -387,6 +428,8 @@ def main(args):
                     outputs[-1]["accepted_per_step"] = st["accepted"] / max(st["steps"], 1)
                 if sc is not None:     # the scores of the generated tokens (the text above may be cut further by postprocess_answer)
                     outputs[-1].update(logprob_sum=sc["sum"], logprobs=sc["logprobs"])
+    if share_prefix:       # back to the order of the records
+        outputs = [o for _, o in sorted(zip(order, outputs), key=lambda x: x[0])]
     if distributed:
         gathered = [None] * world
         dist.all_gather_object(gathered, outputs)

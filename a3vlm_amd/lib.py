@@ -143,6 +143,9 @@ SIGNATURES = {
     "a3v_generate_step_rows": (I, [P, L, P, I, I, P, L, P, P, I, P, P, I, P, P, P, P, P, P]),
     "a3v_llama_decode_step_rows_form": (I, [I, I, I, I, I, I, I]),
     "a3v_rope_kvcache_spans": (I, [P, L, P, L, P, P, P, P, P, I, I, I, I, I, I, I, P]),
+    "a3v_attention_extend_rows_scratch_floats": (L, [I, I, I, I]),
+    "a3v_attention_extend_rows": (I, [P, P, P, P, P, P, P, P, I, I, I, I, I, I, ctypes.POINTER(c_int64), P, I, P]),
+    "a3v_rope_kvcache_extend": (I, [P, L, P, L, P, P, P, P, P, I, I, I, I, I, I, I, P]),
     "a3v_attention_verify_rows": (I, [P, P, P, P, P, P, I, I, I, I, I, I, ctypes.POINTER(c_int64), P, P, I, P]),
     "a3v_attention_verify_rows_splits": (I, [I, I, I]),
     "a3v_attention_verify_rows_scratch_floats": (L, [I, I, I, I, I]),

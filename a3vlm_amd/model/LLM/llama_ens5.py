@@ -1042,6 +1042,9 @@ class Transformer(nn.Module):
             raise RuntimeError("ragged decode (prefill_row / forward_inference_rows / generate_many) is not open on this fp8 KV cache: "
                                "call quantize_kv_cache(None) for the bf16 cache, or quantize_kv_cache('fp8', rows=True) for the fp8 "
                                "cache of the ragged path, or use generate()")
+        if self._kv_quant == "fp8" and what == "extend_rows":
+            raise RuntimeError("extend_rows (generate_many(prefix_sharing=True)) is not implemented on the fp8 KV cache (no prefill "
+                               "attention reads fp8 keys): call quantize_kv_cache(None) for the bf16 cache, or use prefix_sharing=False")
         if self._kv_quant == "fp8" and what is not None:
             missing = "a3v_kv_permute_tails has no fp8 form" if what == "beam_search" else "there is no fp8 verify attention"
             raise RuntimeError(f"{what} is not implemented on the fp8 KV cache ({missing}): call quantize_kv_cache(None) for the bf16 "
@@ -1252,6 +1255,103 @@ class Transformer(nn.Module):
         ops.rmsnorm(h, self.norm.weight, xn, a.norm_eps)
         logits = out if out is not None else torch.empty(M, a.vocab_size, dtype=torch.float32, device=self._device)
         self._lm_head_last(xn, logits, True)
+        return logits
+
+    @torch.no_grad()
+    def extend_rows(self, rows, tokens, start, src_row=None, shared=None) -> torch.Tensor:
+        """The forward of SUFFIX tokens over keys that are already cached (include/a3vlm_hip.h, "Extend prefill"): cache row
+        ``rows[i]`` takes the ids ``tokens[i]`` (1-D, non-empty) at positions ``start[i]`` .. (image words included) and attends to
+        the keys [0, start[i]) below them -- its own, or with ``src_row[i]`` / ``shared[i]`` (both or neither; host ints) those
+        below shared[i] rounded down to 64 from cache row src_row[i] (``share_prefix``'s rule).  One packed pass over
+        M = sum of the suffix lengths rows: embed, every decoder block with a3v_rope_kvcache_extend + a3v_attention_extend_rows as
+        its attention stage, the final RMSNorm and the LM head on each suffix's last row only.  Returns fp32 logits
+        [len(rows), V] in the order of ``rows``.  The other cache rows are not touched.  bf16 and fp32 streams, the bf16 / fp32
+        KV cache; the weights run as in ``prefill_row``."""
+        if (src_row is None) != (shared is None):
+            raise ValueError("extend_rows: src_row and shared are given together, or neither")
+        self._ragged_check("extend_rows")
+        a = self.args
+        R = self._cache_rows()
+        if R == 0:
+            raise ValueError("extend_rows: allocate_rows(batch_rows) first")
+        smax = min(self._k_cache[0].shape[2], self._cos_sin_cpu.shape[0])
+        rows, start = [int(r) for r in rows], [int(x) for x in start]
+        n = len(rows)
+        if not (n == len(tokens) == len(start)) or n == 0 or len(set(rows)) != n or min(rows) < 0 or max(rows) >= R:
+            raise ValueError(f"extend_rows: rows {rows} must be distinct rows of the {R}-row cache, one suffix and one start each")
+        lens = [int(t.numel()) for t in tokens]
+        for r, ln, st, t in zip(rows, lens, start, tokens):
+            if t.dim() != 1 or ln == 0:
+                raise ValueError(f"extend_rows: row {r} has an empty suffix: every row takes at least one token (a prompt that is all "
+                                 "prefix is cut one token earlier: share P = min(C, len - 1) & ~63)")
+            if st < 0 or st + ln > smax:
+                raise ValueError(f"extend_rows: row {r}: start {st} + {ln} tokens > the cache length {smax}: use a larger max_seq_len "
+                                 "or a shorter prompt")
+        H, Hkv, hd = self.n_heads, self.n_kv_heads, self.head_dim
+        dev = self._device
+        order = sorted(range(n), key=lambda j: rows[j])        # the packing follows the cache rows: q_off is indexed by row
+        q_off, sk, src, shr, last = [0] * (R + 1), [0] * R, list(range(R)), [0] * R, [0] * n
+        o = 0
+        for j in order:
+            r = rows[j]
+            q_off[r], o = o, o + lens[j]
+            sk[r], last[j] = start[j] + lens[j], o - 1
+            if src_row is not None:
+                src[r], shr[r] = int(src_row[j]), int(shared[j])
+        M = o
+        for r in range(R - 1, -1, -1):                         # rows without a suffix: an empty span in front of the next row's
+            if sk[r] == 0:
+                q_off[r] = q_off[r + 1] if r + 1 < R else M
+        q_off[R] = M
+        for r in range(R):                                     # (a row's span ends where the next one starts)
+            assert q_off[r] <= q_off[r + 1]
+        i32 = lambda x: torch.tensor(x, dtype=torch.int32, device=dev)
+        q_off_d, sk_d = i32(q_off), i32(sk)
+        src_d, shr_d = (i32(src), i32(shr)) if src_row is not None else (None, None)
+        nq_max, sk_max = max(lens), max(sk)
+        x = torch.cat([tokens[j].to(device=dev, dtype=torch.long) for j in order]).view(M, 1).contiguous()
+        h = self._buf("h", (M, a.dim))
+        ops.embed_assemble(x, self.tok_embeddings.weight, h, M, 1, 0, a.dim)
+        self._pack()
+        cs = self._cos_sin_dev()
+        xn, qkv, att, act, _ = self._row_buffers(M, False)
+        scratch = None
+        if h.dtype == torch.bfloat16 and hd in (64, 128):
+            scratch = self._buf("extend_scratch", (ops.attention_extend_rows_scratch_floats(R, H, hd, self._k_cache[0].shape[2]),), torch.float32)
+        ldq = qkv.stride(0)
+        path = self._layer_path(h, M, False)
+        if path == "w8a8":
+            if self._weights.version != self._packed_version:
+                raise RuntimeError("parameters changed after quantize_decode_weights(): call it again (or with mode=None)")
+            xq = self._buf("fp8_x", (M, max(a.dim, H * hd)), torch.uint8)
+            aq = self._buf("fp8_act", (M, self.ffn), torch.uint8)
+            sx = self._buf("fp8_sx", (M,), torch.float32)
+        for i, lyr in enumerate(self.layers):
+            kc, vc = self._k_cache[i], self._vt_cache[i]
+            cap = kc.shape[2]
+            strides = (ldq, ldq, hd, Hkv * cap * hd, cap * hd, hd, Hkv * hd * cap, hd * cap, cap, H * hd, H * hd, hd)
+            rope = lambda: ops.rope_kvcache_extend(qkv, qkv, kc, vc, cs, q_off_d, sk_d, nq_max, R, H, Hkv, hd)
+            attend = lambda: ops.attention_extend_rows(qkv, kc, vc, att, q_off_d, sk_d, nq_max, sk_max, R, H, Hkv, hd, strides, scratch,
+                                                       src_d, shr_d)
+            if path == "w8a8":             # W8A8 as _decoder_layers runs it, the qkv product stored plainly (its RoPE epilogue has one
+                # position for all rows) and rotated by the span kernel
+                (wqkv_q, wqkv_s), (wo_q, wo_s), (w13_q, w13_s), (w2_q, w2_s) = self._layer_operands(i, path)
+                ops.quantize_rows_fp8(h, xq[:, :a.dim], sx, lyr.attention_norm.weight, a.norm_eps)
+                ops.gemm_nt_fp8(xq[:, :a.dim], sx, wqkv_q, wqkv_s, qkv)
+                rope()
+                attend()
+                ops.quantize_rows_fp8(att, xq[:, :H * hd], sx)
+                ops.gemm_nt_fp8(xq[:, :H * hd], sx, wo_q, wo_s, h, residual=h)
+                ops.quantize_rows_fp8(h, xq[:, :a.dim], sx, lyr.ffn_norm.weight, a.norm_eps)
+                ops.gemm_nt_fp8(xq[:, :a.dim], sx, w13_q, w13_s, act, epilogue=ops.EPI_SWIGLU)
+                ops.quantize_rows_fp8(act, aq, sx)
+                ops.gemm_nt_fp8(aq, sx, w2_q, w2_s, h, residual=h)
+                continue
+            self._layer(i, path, h, (xn, qkv, att, act), rope, attend)
+        xl = self._buf("xn_last", (n, a.dim))
+        ops.rmsnorm(h, self.norm.weight, xl, a.norm_eps, row_idx=i32(last))
+        logits = torch.empty(n, a.vocab_size, dtype=torch.float32, device=dev)
+        self._lm_head_last(xl, logits, False)
         return logits
 
     def share_prefix(self, src_row: int, dst_rows, P: int) -> int:

@@ -458,7 +458,7 @@ class MetaModel(nn.Module):
                       sample_uniforms: Optional[torch.Tensor] = None, repetition_penalty: float = 1.0,
                       return_logprobs: bool = False, top_k: int = 0, min_p: float = 0.0, n: int = 1,
                       lookup: Optional[int] = None, lookup_ngram: int = 3, lookup_drafter=None, constraint=None,
-                      lookup_verify: str = "argmax"):
+                      lookup_verify: str = "argmax", prefix_sharing: bool = False, image_ids=None):
         """Any number of prompts through ``batch_rows`` KV-cache rows (no reference counterpart; opt-in): every row decodes at its
         own position, and a row whose answer is finished is prefilled with the next prompt while the others keep decoding, so a
         short answer does not hold its row until the longest answer of a batch is done.  Answers come back in input order.
@@ -496,8 +496,18 @@ class MetaModel(nn.Module):
         equals it (``a3v_accept_rows_chosen``): the answers are the plain loop's for the same ``sample_uniforms``.  It lifts the
         refusals of ``lookup`` for ``temperature > 0`` (with ``top_p`` / ``top_k`` / ``min_p``), ``repetition_penalty``,
         ``return_logprobs`` and ``constraint``; ``n > 1`` is still refused (use ``n=1``, or ``lookup=0``).
+        ``prefix_sharing=True`` (opt-in; several questions about one image): prompts that are ADJACENT in the list, carry the same
+        image (``image_ids[i] == image_ids[j]``; without ``image_ids``: the same object of a list of images, or no image at all) and
+        start with the same tokens form a run (``ragged.prefix_groups``).  With C = 1 + image words + common text tokens and
+        P = min(C, shortest member - 1) & ~63, the first P positions are prefilled ONCE, in the row of the run's first member (the
+        image is encoded once, those logits are discarded), every member then runs its own suffix over them in one packed pass
+        (``Transformer.extend_rows``) and decodes with the shared-prefix step.  Members that find no free row wait and are extended
+        over the prefix later; the row that holds it takes no other run's prompt until the last member is done
+        (``ragged.PrefixScheduler``).  Order and format of the results are the plain call's; a run of one, or P == 0, takes the
+        plain path.  One level of sharing only: not with ``n > 1`` (use ``n=1``), ``lookup`` (use ``lookup=0``), ``beam_search`` or
+        the fp8 KV cache (each raises, naming the way out).
         Not for the fp8 KV cache, LoRA models before ``merge_lora()`` or the two-image plugin (each raises, naming the way out)."""
-        from .ragged import GroupScheduler, LookupBound, RowScheduler
+        from .ragged import GroupScheduler, LookupBound, PrefixScheduler, RowScheduler, prefix_groups
         if isinstance(prompts, str):
             raise ValueError(f"{self.__class__}.generate_many expects a LIST of prompts, but str is given")
         controls = genctl.wanted(repetition_penalty, return_logprobs)      # ValueError before any device use
@@ -511,6 +521,15 @@ class MetaModel(nn.Module):
         if n > int(batch_rows):
             raise ValueError(f"generate_many: n = {n} samples per prompt need n cache rows at once: batch_rows = {batch_rows} < n")
         D = int(lookup or 0)
+        if prefix_sharing:                 # refusals of prefix sharing, before any device use
+            if n > 1:
+                raise ValueError(f"generate_many: prefix_sharing shares one level only, n = {n} samples already read their leader's "
+                                 "prompt: use n=1, or prefix_sharing=False")
+            if D:
+                raise ValueError(f"generate_many: prefix_sharing has no verify step over a shared prefix, lookup = {D}: use lookup=0, "
+                                 "or prefix_sharing=False")
+            if image_ids is not None and len(image_ids) != len(prompts):
+                raise ValueError(f"generate_many: image_ids has {len(image_ids)} entries for {len(prompts)} prompts")
         if lookup_verify not in ("argmax", "choice"):
             raise ValueError(f"generate_many: lookup_verify = {lookup_verify!r}; 'argmax' (greedy verification, the default) or 'choice' "
                              "(sample and match)")
@@ -541,7 +560,7 @@ class MetaModel(nn.Module):
             if int(lookup_ngram) < 1:
                 raise ValueError(f"generate_many: lookup_ngram = {lookup_ngram}; >= 1")
         llma = self.llma
-        llma._ragged_check("lookup decoding" if D else None)  # before anything is allocated or launched
+        llma._ragged_check("lookup decoding" if D else "extend_rows" if prefix_sharing else None)  # before anything is allocated or launched
         dev = self._device
         N = len(prompts)
         args = llma.args
@@ -549,6 +568,13 @@ class MetaModel(nn.Module):
         assert 0 < R <= args.max_batch_size, (R, args.max_batch_size)
         mgl = [int(max_gen_len)] * N if isinstance(max_gen_len, int) else [int(x) for x in max_gen_len]
         assert len(mgl) == N, (len(mgl), N)
+        image_keys = list(image_ids) if image_ids is not None else None
+        if isinstance(images, (list, tuple)):          # a list of per-prompt images: the same object is the same image
+            if image_keys is None:
+                image_keys = [id(x) for x in images]
+            images = torch.stack(list(images)) if len(images) else None
+        if image_keys is None:                         # a stacked tensor says nothing about equal rows; no image at all is one image
+            image_keys = list(range(N)) if images is not None else [None] * N
         if images is not None:
             images = images.to(dev)
             assert images.shape[0] == N, (tuple(images.shape), N)
@@ -601,12 +627,17 @@ class MetaModel(nn.Module):
                                     return_logprobs, dev)
         cs = constrain.ConstraintState(automaton, R, args.vocab_size, dev) if automaton is not None else None
         # answers are kept per (prompt, sample) at index i * n + s
-        sched = RowScheduler(lens, limits, R, W) if n == 1 else GroupScheduler(lens, limits, R, W, n)
+        runs = prefix_groups(prompt_tokens, image_keys, W) if prefix_sharing else []
+        share = any(P > 0 for _, P in runs)            # no run of several prompts: the plain call, untouched
+        if share:
+            sched = PrefixScheduler(lens, limits, R, W, runs)
+        else:
+            sched = RowScheduler(lens, limits, R, W) if n == 1 else GroupScheduler(lens, limits, R, W, n)
         ids: List[Optional[List[int]]] = [None] * (N * n)
         lps: List[List[float]] = [[] for _ in range(N * n)]
         llma.allocate_rows(R)
         src_row = shared = None
-        if n > 1:                          # shared prompt keys: row r reads its keys below shared[r] from cache row src_row[r]
+        if n > 1 or share:                 # shared prompt keys: row r reads its keys below shared[r] from cache row src_row[r]
             src_row = torch.arange(R, dtype=torch.int32, device=dev)
             shared = torch.zeros(R, dtype=torch.int32, device=dev)
         sample_of = [0] * R
@@ -657,10 +688,31 @@ class MetaModel(nn.Module):
             decoded = [self.tokenizer.decode(t) for t in ids]
             return (decoded, ids) if return_ids else decoded
         while True:
-            for i, rows in ([(i, [row]) for row, i in sched.refill()] if n == 1 else sched.refill()):
+            if share:                      # prefix sharing: plain refills as below; a run's members extend over the prefix in its leader row
+                admitted = []
+                for lead, P, new, members in sched.refill():
+                    if P == 0:
+                        admitted.append((members[0][1], [lead], True))
+                        src_row[lead], shared[lead] = lead, 0
+                        continue
+                    i0 = members[0][1]
+                    if new:                # the first P positions, once: BOS, the image words, the common text (logits discarded)
+                        t = torch.tensor(prompt_tokens[i0][:P - W], dtype=torch.long, device=dev)
+                        llma.prefill_row(lead, t[None], None if images is None else images[i0:i0 + 1])
+                    rws = [r for r, _ in members]
+                    sfx = [torch.tensor(prompt_tokens[i][P - W:], dtype=torch.long, device=dev) for _, i in members]
+                    lg = llma.extend_rows(rws, sfx, [P] * len(rws), src_row=[lead] * len(rws), shared=[P] * len(rws))
+                    for j, (r, i) in enumerate(members):
+                        logits[r].copy_(lg[j])
+                        src_row[r], shared[r] = lead, P
+                        admitted.append((i, [r], False))
+            else:
+                admitted = [(i, rows, True) for i, rows in ([(i, [row]) for row, i in sched.refill()] if n == 1 else sched.refill())]
+            for i, rows, prefill in admitted:
                 lead = rows[0]
                 t = torch.tensor(prompt_tokens[i], dtype=torch.long, device=dev)
-                logits[lead].copy_(llma.prefill_row(lead, t[None], None if images is None else images[i:i + 1])[0])
+                if prefill:
+                    logits[lead].copy_(llma.prefill_row(lead, t[None], None if images is None else images[i:i + 1])[0])
                 if n > 1:                  # one prefill per group: the siblings start from the leader's logits and read its prefix
                     src_row[lead], shared[lead] = lead, 0
                     sib = torch.tensor(rows[1:], dtype=torch.long, device=dev)
@@ -716,7 +768,7 @@ class MetaModel(nn.Module):
                         sched.release(r)
                     if not sched.occupied():
                         continue                                         # refill (or leave) before another step
-            if n == 1:
+            if n == 1 and not share:
                 llma.forward_inference_rows(next_tok, pos, pos_max, out=logits)
             else:
                 llma.forward_inference_rows(next_tok, pos, pos_max, out=logits, src_row=src_row, shared=shared)
@@ -876,7 +928,8 @@ class MetaModel(nn.Module):
     def beam_search(self, prompts: List[str], images: Optional[torch.Tensor] = None, *, num_beams: int, batch_rows: int,
                     max_gen_len=512, length_penalty: float = 1.0, early_stopping: bool = True, num_return_sequences: int = 1,
                     constraint=None, return_ids: bool = False, return_scores: bool = False, poll_every: int = 4,
-                    additional_stop_symbols: Iterable[str] = (), temperature: float = 0.0, repetition_penalty: float = 1.0, lookup=None):
+                    additional_stop_symbols: Iterable[str] = (), temperature: float = 0.0, repetition_penalty: float = 1.0, lookup=None,
+                    prefix_sharing: bool = False):
         """Beam search over ``batch_rows // num_beams`` prompts at a time (no reference counterpart; opt-in; ``model/beam.py``): the
         most probable answers by the sum of raw log-probs over ``len ** length_penalty``, HF ``num_beams`` semantics
         (``tests/beam_ref.py`` is the contract).  1 <= ``num_beams`` <= 8 consecutive cache rows per prompt, ONE prefill per prompt
@@ -888,7 +941,11 @@ class MetaModel(nn.Module):
         ``{"sum": sum of log-probs, "score": sum / len ** length_penalty}``.  Every step moves the generated keys of re-parented
         beams, which grows linearly with the answer's length: made for the short structured answers of this task.
         ``additional_stop_symbols``, ``temperature > 0``, ``repetition_penalty != 1`` and ``lookup`` are refused, as are the fp8 KV
-        cache, LoRA models before ``merge_lora()`` and the two-image plugin (each raises, naming the way out)."""
+        cache, LoRA models before ``merge_lora()`` and the two-image plugin (each raises, naming the way out), and
+        ``prefix_sharing`` (the beams of a prompt already read their leader's row; sharing goes one level only)."""
+        if prefix_sharing:
+            raise ValueError("beam_search: the beams of a prompt already share their leader's prompt keys and sharing goes one level "
+                             "only: use prefix_sharing=False, or generate_many(prefix_sharing=True) for greedy / sampled answers")
         from . import beam
         return beam.beam_search(self, prompts, images, num_beams=num_beams, batch_rows=batch_rows, max_gen_len=max_gen_len,
                                 length_penalty=length_penalty, early_stopping=early_stopping, num_return_sequences=num_return_sequences,

@@ -198,3 +198,124 @@ class LookupBound:
         for r in run:
             self.bound[r] = min(self.bound[r] + self.Q, self.last[r])
         return pos_max
+
+
+def prefix_groups(prompt_tokens: Sequence[Sequence[int]], image_keys: Sequence[object], pos_base: int = 0) -> List[Tuple[List[int], int]]:
+    """Prefix sharing (``generate_many(..., prefix_sharing=True)``): the input list cut into runs ``(members, P)`` of ADJACENT
+    prompts with the same image key (``image_keys[i] == image_keys[j]``) whose caches start with the same P positions.
+
+    A prompt's cache is [BOS | pos_base image words | text]: with L the longest common token prefix of the run (BOS included) the
+    common cache prefix is C = pos_base + L, and P = min(C, shortest member's cache length - 1) & ~63 -- every member keeps at
+    least one token of its own (its last-position logits start its answer), and P is a multiple of 64 because the attention
+    kernels switch between the prefix row and the own row at 64-key tiles only.  P must also cover BOS and the image words
+    (P >= pos_base + 1 when there is an image: the prefix is prefilled with the image in front, whole), else it counts as 0.
+    A run is extended greedily while its P stays > 0; a run of one, or P == 0, is ``([i], 0)``: today's path."""
+    assert len(prompt_tokens) == len(image_keys)
+
+    def shared_len(members):
+        first = prompt_tokens[members[0]]
+        L = min(len(prompt_tokens[i]) for i in members)
+        for i in members[1:]:
+            t, k = prompt_tokens[i], 0
+            while k < L and t[k] == first[k]:
+                k += 1
+            L = k
+        P = min(pos_base + L, pos_base + min(len(prompt_tokens[i]) for i in members) - 1) & ~63
+        return P if P > 0 and (pos_base == 0 or P >= pos_base + 1) else 0
+
+    out: List[Tuple[List[int], int]] = []
+    i, N = 0, len(prompt_tokens)
+    while i < N:
+        members, P = [i], 0
+        j = i + 1
+        while j < N and image_keys[j] == image_keys[i]:
+            Pj = shared_len(members + [j])
+            if Pj == 0:
+                break
+            members, P = members + [j], Pj
+            j += 1
+        out.append((members, P if len(members) > 1 else 0))
+        i = j
+    return out
+
+
+class PrefixScheduler(RowScheduler):
+    """``RowScheduler`` over the runs of ``prefix_groups``: a run of several prompts stores its common prefix ONCE, in the row its
+    first member is admitted to (the leader row), and every member runs its own suffix over it.
+
+    * ``refill()`` admits prompts in input order, lowest free row first, and returns a list of
+      ``(leader_row, P, new, [(row, prompt), ...])``: ``P == 0`` is a plain refill of one row (``leader_row == row``); otherwise the
+      members listed are extended over the P prefix positions held in ``leader_row``, and ``new`` says that the prefix has to be
+      prefilled there first (the run's first admission).  The first member of a run takes the leader row itself.
+    * Members that find no free row wait; no later prompt overtakes them.  They are admitted when a row frees -- any free row, or
+      the run's own leader row once its current member has finished (its prefix stays where it is).
+    * The leader row is HELD while any member of its run runs or waits: it takes no prompt of another run until the last member
+      has been released (``GroupScheduler``'s rule for the leader of n samples).
+    * ``advance()`` / ``occupied()`` / ``release()`` / ``finished_at_once`` / ``steps`` as in ``RowScheduler``; with runs of one only
+      the assignments are that class's."""
+
+    def __init__(self, prompt_lens: Sequence[int], limits: Sequence[int], batch_rows: int, pos_base: int,
+                 groups: Sequence[Tuple[Sequence[int], int]]):
+        super().__init__(prompt_lens, limits, batch_rows, pos_base)
+        assert [i for members, _ in groups for i in members] == list(range(len(prompt_lens))), "the runs cover the prompts in order"
+        self.group_of: List[int] = [0] * len(prompt_lens)
+        self.groups = [(list(members), int(P)) for members, P in groups]
+        for g, (members, _) in enumerate(self.groups):
+            for i in members:
+                self.group_of[i] = g
+        self.leader_of_group: List[int] = [-1] * len(self.groups)    # the row that holds the run's prefix, -1 before / after
+        self.left: List[int] = [0] * len(self.groups)                 # members of the run not yet released (running or waiting)
+
+    def held(self) -> List[int]:
+        """rows whose prefix a run still needs"""
+        return [r for g, r in enumerate(self.leader_of_group) if r >= 0 and self.left[g] > 0]
+
+    def release(self, row: int) -> int:
+        i = super().release(row)
+        g = self.group_of[i]
+        if self.groups[g][1] > 0:
+            self.left[g] -= 1
+            if self.left[g] == 0:
+                self.leader_of_group[g] = -1
+        return i
+
+    def refill(self):
+        out = []
+        N = len(self.prompt_lens)
+        while True:
+            while self.next_prompt < N and self.limits[self.next_prompt] <= self.prompt_lens[self.next_prompt]:
+                i = self.next_prompt                       # nothing to write: never takes a row, leaves its run at once
+                self.finished_at_once.append(i)
+                self.next_prompt += 1
+                g = self.group_of[i]
+                if self.groups[g][1] > 0:
+                    if i == self.groups[g][0][0]:
+                        self.left[g] = len(self.groups[g][0])
+                    self.left[g] -= 1
+                    if self.left[g] == 0:
+                        self.leader_of_group[g] = -1
+            if self.next_prompt == N:
+                break
+            i = self.next_prompt
+            g = self.group_of[i]
+            members, P = self.groups[g]
+            held = set(self.held())
+            lead = self.leader_of_group[g] if P > 0 else -1
+            free = [r for r, x in enumerate(self.rows) if x is None and (r not in held or r == lead)]
+            if not free:
+                break
+            if P > 0 and i == members[0]:
+                self.left[g] = len(members)
+            new = P > 0 and lead < 0
+            r = free[0]
+            if new:
+                lead = self.leader_of_group[g] = r
+            self.next_prompt += 1
+            self.rows[r] = i
+            self.next_pos[r] = self.pos_base + self.prompt_lens[i]
+            self.generated[r] = 0
+            if P > 0 and out and out[-1][0] == lead and out[-1][1] == P and self.group_of[out[-1][3][0][1]] == g:
+                out[-1][3].append((r, i))                  # one extend for every member admitted together
+            else:
+                out.append((lead if P > 0 else r, P, new, [(r, i)]))
+        return out

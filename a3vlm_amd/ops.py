@@ -770,6 +770,42 @@ def rope_kvcache_spans(qkv, q_out, k_cache, vt_cache, cos_sin, pos, nq, B, Q, H,
     _l.check(rc, f"a3v_rope_kvcache_spans(B={B},Q={Q},H={H},Hkv={Hkv},hd={hd})")
 
 
+def rope_kvcache_extend(qkv, q_out, k_cache, vt_cache, cos_sin, q_off, sk, nq_max: int, B, H, Hkv, hd):
+    """Extend prefill: the packed rows q_off[b] .. q_off[b+1]-1 of qkv are rotated at positions sk[b]-nq[b] .. sk[b]-1 and written
+    there into cache row b (q_off: device int32 [B+1]; sk: device int32 [B], the row's key count after the extend).  Per element
+    ``rope_kvcache`` at B = 1 on the row's slice.  A row without a span, or whose span does not fit, writes nothing."""
+    _dev(qkv, q_out, k_cache, vt_cache, cos_sin, q_off, sk)
+    assert q_off.dtype == sk.dtype == torch.int32 and q_off.is_contiguous() and sk.is_contiguous()
+    assert q_off.numel() >= B + 1 and sk.numel() >= B
+    assert k_cache.is_contiguous() and vt_cache.is_contiguous() and k_cache.shape[0] >= B and k_cache.dtype == vt_cache.dtype == qkv.dtype
+    rc = _l.load().a3v_rope_kvcache_extend(_p(qkv), qkv.stride(0), _p(q_out), q_out.stride(0), _p(k_cache), _p(vt_cache), _p(cos_sin),
+                                           _p(q_off), _p(sk), int(nq_max), B, H, Hkv, hd, k_cache.shape[2], dt(qkv), _stream())
+    _l.check(rc, f"a3v_rope_kvcache_extend(B={B},nq_max={nq_max},H={H},Hkv={Hkv},hd={hd})")
+
+
+def attention_extend_rows_scratch_floats(B: int, H: int, hd: int, sk_max: int) -> int:
+    return _l.load().a3v_attention_extend_rows_scratch_floats(B, H, hd, sk_max)
+
+
+def attention_extend_rows(q, k, vt, out, q_off, sk, nq_max: int, sk_max: int, B, H, Hkv, hd, strides, scratch=None, src_row=None,
+                          shared=None):
+    """Extend prefill: causal attention of packed query spans (rows q_off[b] .. q_off[b+1]-1 of q / out) over per-row caches of
+    sk[b] keys; with ``src_row`` / ``shared`` (both or neither, device int32 [B]) row b reads its keys below min(shared[b], sk[b])
+    rounded down to 64 from cache row src_row[b].  Row b is bit-equal to ``attention`` at B = 1, Sq = nq[b], Sk = sk[b], causal.
+    bf16 at hd 64 / 128 needs scratch (attention_extend_rows_scratch_floats(B, H, hd, sk_max) floats)."""
+    _dev(q, k, vt, out, q_off, sk, src_row, shared, scratch)
+    assert q_off.dtype == sk.dtype == torch.int32 and q_off.is_contiguous() and sk.is_contiguous()
+    assert q_off.numel() >= B + 1 and sk.numel() >= B and k.shape[0] >= B and vt.shape[0] >= B
+    assert (src_row is None) == (shared is None)
+    if src_row is not None:
+        assert all(t.dtype == torch.int32 and t.is_contiguous() and t.numel() >= B for t in (src_row, shared))
+    assert scratch is None or (scratch.dtype == torch.float32 and scratch.numel() >= attention_extend_rows_scratch_floats(B, H, hd, sk_max))
+    rc = _l.load().a3v_attention_extend_rows(_p(q), _p(k), _p(vt), _p(out), _p(q_off), _p(sk), _p(src_row), _p(shared), int(nq_max),
+                                             int(sk_max), B, H, Hkv, hd, _Strides(*strides), _p(scratch), dt(q), _stream())
+    _l.check(rc, f"a3v_attention_extend_rows(B={B},nq_max={nq_max},sk_max={sk_max},H={H},hd={hd})")
+    return out
+
+
 def attention_verify_rows_splits(B: int, H: int, sk_max: int) -> int:
     return _l.load().a3v_attention_verify_rows_splits(B, H, sk_max)
 

@@ -699,6 +699,46 @@ int a3v_llama_decode_step_rows_shared(const a3v_llama_layer* layers, int n_layer
                                       int hd, int ffn, int Smax, float eps, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Extend prefill (opt-in; a3v_extend.hip; no reference counterpart).  The forward of a row's own SUFFIX tokens over keys that are
+ * already cached -- in the row itself or, below a shared length, in another row ("Shared prompt keys" above).  The queries of all
+ * rows are PACKED: row b brings nq[b] = q_off[b+1] - q_off[b] of them, rows q_off[b] .. q_off[b+1]-1 of q / out [M, H*hd]
+ * (q_off: DEVICE int32[B+1], non-decreasing, within [0, M]; the host cannot see it).  sk[b] (DEVICE int32[B]) is the row's key
+ * count AFTER the extend: query j of row b sits at cache position sk[b] - nq[b] + j and sees the keys [0, that position].
+ * These entries take the bf16 / fp32 KV cache; no prefill attention reads fp8 keys.
+ *
+ * a3v_attention_extend_rows: causal attention of the packed queries.  k [B,Hkv,Smax,hd] / vt [B,Hkv,hd,Smax] and the 12 strides
+ * as a3v_attention_decode_rows takes them (strides[1] / [2]: q row / head, [10] / [11]: out row / head, [0] and [9] unused; a V^T
+ * row and a K head bound sk_max).  src_row / shared: the two arrays of a3v_attention_decode_rows_shared with exactly their
+ * meaning and bounding (S_b = min(shared[b], sk[b]) rounded down to 64; a src_row outside [0, B) reads as b; one level only; k / vt
+ * hold all B rows).  Both NULL: the plain form.  One NULL: A3V_ERR_ARG.  nq_max / sk_max (host) size the grid.
+ * Rows: nq[b] <= 0 or sk[b] <= 0 is an IDLE row: it reads nothing and its out rows are NOT written (they are not zeroed either).
+ * nq[b] above nq_max is read as nq_max (the row's first nq_max packed queries), sk[b] above sk_max as sk_max, and a span longer
+ * than its keys as the keys: bounded by the kernels, nothing is read outside q_off's rows or a cache row.
+ * Forms.  bf16 at hd 64 / 128: the walk of a3v_attention's causal prefill kernel per row -- 128-query tiles from the row's first
+ * query, 64-key tiles from position 0, the same LDS-DMA double buffer, MFMA order, lazy rescale and staged O; a key tile starts at
+ * a multiple of 64 and S_b is one, so a tile lies wholly in src_row[b]'s cache or wholly in the row's own (the source is a
+ * wave-uniform choice between two buffer descriptors).  A row with ONE query takes a3v_attention's Sq == 1 route instead (its
+ * two-phase decode kernel and combine under the split plan of B = 1, computed per row on the device): two further launches whose
+ * blocks leave at once for every other row.  scratch: a3v_attention_extend_rows_scratch_floats(B, H, hd, sk_max) floats (bf16 at
+ * hd 64 / 128 only; q, k, vt, out 16-byte aligned, strides multiples of 8).  fp32 (any hd <= 256; also bf16 at other head dims):
+ * one wave per (query, head, row), a3v_attention's generic kernel; scratch unused.
+ * BIT-EQUALITY CONTRACT: (a) plain form: row b's out rows equal a3v_attention(B = 1, Sq = nq[b], Sk = sk[b], causal = 1) on that
+ * row's slice of q and the caches; (b) shared form: equals the plain form on caches into which positions [0, S_b) of row
+ * src_row[b] were copied; (c) src_row == NULL is the plain call; (d) an idle row leaves its out rows untouched.
+ * a3v_rope_kvcache_extend: rotates the packed q in place (q_out may be qkv) and writes k / v^T of row b at positions
+ * sk[b]-nq[b] .. sk[b]-1 of its OWN cache row ([B,Hkv,Smax,hd] / [B,Hkv,hd,Smax] contiguous): per element a3v_rope_kvcache(B = 1,
+ * S = nq[b], start_pos = rope_pos0 = sk[b] - nq[b]) on the row's slice, bit for bit, one launch.  (a3v_rope_kvcache_spans keeps its
+ * contract: at most 8 positions per row in a [B*Q] layout.)  A row with nq[b] <= 0, nq[b] > nq_max, sk[b] < nq[b] or sk[b] > Smax
+ * is idle: nothing of it is written, neither q_out rows nor cache.  Nothing outside the spans is written. */
+int64_t a3v_attention_extend_rows_scratch_floats(int B, int H, int hd, int sk_max);
+int a3v_attention_extend_rows(const void* q, const void* k, const void* vt, void* out, const int32_t* q_off, const int32_t* sk,
+                              const int32_t* src_row, const int32_t* shared, int nq_max, int sk_max, int B, int H, int Hkv, int hd,
+                              const int64_t* strides, float* scratch, int dtype, void* stream);
+int a3v_rope_kvcache_extend(const void* qkv, int64_t ldqkv, void* q_out, int64_t ldq, void* k_cache, void* vt_cache,
+                            const float* cos_sin, const int32_t* q_off, const int32_t* sk, int nq_max, int B, int H, int Hkv, int hd,
+                            int Smax, int dtype, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * fp8 KV cache on the ragged decode path (opt-in; a3v_kv8_rows.hip).  The arrays are those of "fp8 KV cache" above (k_q, vt_q,
  * k_scale, v_scale of one layer; Smax % 64 == 0; every pointer 16-B aligned), the position arrays those of "Ragged decode" (DEVICE
  * int32[B]; an idle row writes nothing into any cache array and its outputs are zeros, never NaN).  bf16 model, hd 64 or 128:
